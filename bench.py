@@ -1,9 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- Langevin steps/s of the MCPC hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set-up, W warm-up calls, K timed learning calls, the outputs of the last
+timed call when --dump-outputs is given, and the JSON line (`value`, `ms_per_step`, `config`, `build_info`).  Everything else below
+-- the inference-only calls, `roofline` (HIP events around every launch during the timed calls), `self_check` and `cpu_baseline`
+-- runs only with --full.
+--dump-outputs DIR: after the timed calls, what the last one returned to its caller, as DIR/<name>.npy (float64 energies, float32
+otherwise): `energies` [T, cols], `param_grads` (the normalised, reduced gradient bucket), `state_layer<l>` (the final latent
+states) and `records_layer<l>` (x every 100 steps); chains are a fixed seeded sample where an array would not fit the 60 MB budget.
 
 One bench "step" = ONE CALL of the hot path in BASELINE.json's configuration (cfg-M of BASELINE.md section 4):
     net 30-256-256-784 ReLU (get_model shape, reference utils/model.py:47-69), Bernoulli read-out,
@@ -15,7 +23,7 @@ One bench "step" = ONE CALL of the hot path in BASELINE.json's configuration (cf
     learning call (the timed `value`): the reference's training=True call (utils/training_evaluation.py:43-56) -- Hebbian
         sums accumulated over the 4000 sampling steps, the normalised parameter-gradient read-out and, for N > 1, the
         single RCCL all-reduce of the 276 146-float gradient bucket.   value = N * K * T / wall   [Langevin steps/s]
-    inference-only call (training=False, no Hebbian sums): K calls timed the same way right after, reported beside it.
+    inference-only call (training=False, no Hebbian sums; --full): K calls timed the same way right after, reported beside it.
 
 Everything in the timed region goes through the C ABI (libmcpc.so); inputs are resident in HBM before the clock starts.
 `roofline` is computed from HIP events the library records on its launch stream (mcpc_set_profiling) during the timed
@@ -141,6 +149,54 @@ def cpu_baseline(batch, budget_s=20.0):
                       f"{torch.get_num_threads()} torch threads (fastest of 8/16/32/64/default on 3-step probes) of {os.cpu_count()} host cpus"}
 
 
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000                # under 64 MB by either reading of "MB"
+DUMP_SEED = 30
+
+
+def dump_outputs(path, res, flat, state):
+    """Write what one call returned to its caller as <path>/<name>.npy, at most DUMP_BUDGET_BYTES in all.
+
+    energies (float64) and the gradient bucket are written whole (energy rows are sampled only past a quarter of the budget); the
+    final states whole while they fit half of what is left, the records in what remains after them.  Where an array must shrink,
+    its chains (rows of the energies) are the first n of one permutation drawn from DUMP_SEED, in ascending order: the same
+    arguments select the same chains in every run and every build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    header = 128                                           # .npy header bytes per file (v1.0: a multiple of 64, <= 128 here)
+
+    def pick(n_total, n):
+        perm = np.random.default_rng(DUMP_SEED).permutation(n_total)
+        return torch.from_numpy(np.sort(perm[:max(1, min(n, n_total))])).to(res.energies.device)
+
+    out = {}
+    en = res.energies.to(torch.float64)
+    row_bytes = en.shape[1] * 8
+    if en.numel() * 8 > DUMP_BUDGET_BYTES // 4:
+        en = en.index_select(0, pick(en.shape[0], (DUMP_BUDGET_BYTES // 4) // row_bytes))
+    out["energies"] = en
+    if flat is not None:
+        out["param_grads"] = flat.to(torch.float32)
+    left = DUMP_BUDGET_BYTES - sum(t.numel() * t.element_size() + header for t in out.values())
+    batch = state[0].shape[0]
+    width = sum(x.shape[1] for x in state)
+    state_chains = batch if batch * width * 4 + header * len(state) <= left // 2 else (left // 2 - header * len(state)) // (width * 4)
+    idx = None if state_chains >= batch else pick(batch, state_chains)
+    for l, x in enumerate(state):
+        out["state_layer%d" % l] = (x if idx is None else x.index_select(0, idx)).to(torch.float32)
+    left = DUMP_BUDGET_BYTES - sum(t.numel() * t.element_size() + header for t in out.values())
+    recs = [(l, r) for l, r in enumerate(res.rec_x) if r is not None and r.numel()]
+    if recs:
+        per_chain = sum(r.shape[0] * r.shape[2] * 4 for _, r in recs)
+        n = (left - header * len(recs)) // per_chain
+        idx = None if n >= batch else pick(batch, n)
+        for l, r in recs:
+            out["records_layer%d" % l] = (r if idx is None else r.index_select(1, idx)).to(torch.float32)
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+    total = sum(os.path.getsize(os.path.join(path, name + ".npy")) for name in out)
+    assert total <= DUMP_BUDGET_BYTES, (total, {k: tuple(v.shape) for k, v in out.items()})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -148,6 +204,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2, help="untimed warm-up calls (of each kind)")
     ap.add_argument("--T", type=int, default=5000, help="Langevin steps per call: T/5 mixing + 4T/5 sampling (BASELINE: 5000)")
     ap.add_argument("--batch", type=int, default=6000, help="chains per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the inference-only calls and report roofline, self_check and cpu_baseline (a plain run times the "
+                         "headline calls only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed call returned as DIR/<name>.npy (at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the inference-only calls (clean PMC passes of the learning call)")
     ap.add_argument("--only-inference", action="store_true", help="time inference-only calls only (clean PMC passes of the inference call)")
@@ -234,12 +295,14 @@ def main():
         return res, flat
 
     def timed(learning, n_calls):
-        """n_calls back-to-back calls between barrier + synchronize on both sides; max over ranks."""
+        """n_calls back-to-back calls between barrier + synchronize on both sides; max over ranks.  With --full the library also
+        brackets every launch of the step kernel with HIP events (the roofline's source)."""
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
-        eng.set_profiling(True)
+        if args.full:
+            eng.set_profiling(True)
         t0 = time.perf_counter()
         for _ in range(n_calls):
             res, flat = one_call(learning)
@@ -249,26 +312,41 @@ def main():
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         eng.sync_check()          # raises if a kernel reported a device-side fault during the timed calls
-        plain = eng.last_step_kernel_ms() + (eng.last_shader_clock_ghz(),)
-        eng.set_profiling(False)
+        plain = None
+        if args.full:
+            plain = eng.last_step_kernel_ms() + (eng.last_shader_clock_ghz(),)
+            eng.set_profiling(False)
         if dist is not None:
             tt = torch.tensor([dt], device=device, dtype=torch.float64)
             all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
-        return dt, res, plain
+        return dt, res, flat, plain
 
+    def dump(res_, flat_):
+        """--dump-outputs: the last timed call's results and the state it left (rank 0's shard; the bucket is the reduced one)."""
+        if args.dump_outputs and rank == 0:
+            state = [torch.empty_like(x) for x in xs]
+            eng.store_state(state)
+            eng.sync_check()
+            dump_outputs(args.dump_outputs, res_, flat_, state)
+
+    # the inference-only calls are the secondary measurement of --full (or the primary one with --only-inference)
+    secondary = args.only_inference or (args.full and not args.no_secondary)
     for _ in range(Wm):
         if not args.only_inference:
             one_call(True)
-        if not args.no_secondary:
+        if secondary:
             one_call(False)
     dt_learn = res = plain_l = None
     if not args.only_inference:
-        dt_learn, res, plain_l = timed(True, K)
+        dt_learn, res, flat_l, plain_l = timed(True, K)
+        dump(res, flat_l)
     dt_inf = plain_i = None
-    if not args.no_secondary or args.only_inference:
-        dt_inf, res_i, plain_i = timed(False, K)
-        res = res if res is not None else res_i
+    if secondary:
+        dt_inf, res_i, _, plain_i = timed(False, K)
+        if res is None:
+            res = res_i
+            dump(res_i, None)
     primary_learning = dt_learn is not None
     dt = dt_learn if primary_learning else dt_inf
 
@@ -282,7 +360,7 @@ def main():
     # the grouping of fp32 partial sums.  What the reference defines for these: pc_trainer.py:853-862 (dF/dtheta summed over
     # accumulate_p_at), :904-914 (normalisation).
     self_check = None
-    if not args.no_self_check:
+    if args.full and not args.no_self_check:
         def replay(engine):
             engine.load_state(xs)
             r_ = engine.run(T, loss_kind=L.LOSS_BERNOULLI, xopt=L.XOPT_SGD, lr=0.03, noise_mode=L.NOISE_PHILOX, noise_var=2.0,
@@ -337,6 +415,8 @@ def main():
         bytes_per_step = 7472.0 * B
 
         def kernel_line(kernel, prof, flops_per_step, note, n_wg, wg_per_launch, mode):
+            if prof is None:                # a plain run: the launches were not bracketed (--full)
+                return None
             ms, n, steps, ghz = prof
             if not n or not steps:
                 return None
@@ -456,7 +536,7 @@ def main():
                                 "a measurement of %d GPUs" % (world, local_rank, world))
         if self_check is not None:
             out["self_check"] = self_check
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(B, args.cpu_budget)
             out["config"]["speedup_vs_cpu_port"] = out["value"] / out["cpu_baseline"]["value"]
         os.write(json_fd, (json.dumps(out) + "\n").encode())

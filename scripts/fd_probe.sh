@@ -8,7 +8,7 @@ for ln in open("gpurun_out/fd3/$tag.out"):
         print("$tag", "learning us/step", round(d["config"]["us_per_langevin_step"],1), "inference us/step", round(d["config"]["inference_only"]["us_per_langevin_step"],1), "mixed us/step", round(m.get("us_per_step",0),1), "plain us/step", round(d["roofline"]["us_per_step"],1))
 PY
 }
-A="--steps 3 --warmup 1 --T 1000 --no-cpu-baseline"
+A="--steps 3 --warmup 1 --T 1000 --no-cpu-baseline --full"
 run base python3 bench.py $A
 run dist python3 bench.py $A --force-dist
 GPU_MAX_HW_QUEUES=8 run dist_q8 python3 bench.py $A --force-dist

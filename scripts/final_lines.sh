@@ -4,7 +4,7 @@
 ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/r06
 mkdir -p $OUT
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench.err
+python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench_line.json 2> $OUT/bench.err
 python3 -c "
 import json; d=json.load(open('$OUT/bench_line.json')); r=d['roofline']; print(d['value'], d['config']['inference_only']['steps_per_s'], r['frac'], r['traffic'], d['build_info']['csrc'])"
 cd /tmp && export TMPDIR=/tmp

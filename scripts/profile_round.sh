@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-end evidence run on an MI355X box (via gpurun, from the repo root):   bash scripts/profile_round.sh <tag>  ->  gpurun_out/<tag>/
 #   pytest.log          the GPU suite
-#   bench_line.json     the driver's command (bench.py --steps 20 --warmup 5)
+#   bench_line.json     the benchmark line with everything it reports (bench.py --steps 20 --warmup 5 --full)
 #   kernel_stats.csv    rocprofv3 --kernel-trace --stats of the same program at --steps 3 --warmup 1 --no-secondary (learning calls only: the
 #                       step kernel has ONE name in every stretch and mode, and roofline.avg_bracket_ms of the line is the average over
 #                       the launches of the timed LEARNING calls -- inference-only calls use longer launches)
@@ -14,7 +14,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 python3 -m pytest tests -m gpu -q > $OUT/pytest.log 2>&1 || { tail -20 $OUT/pytest.log; exit 1; }
 tail -1 $OUT/pytest.log
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench.err
+python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench_line.json 2> $OUT/bench.err
 cat $OUT/bench_line.json
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-secondary --no-cpu-baseline --no-self-check > $OUT/stats_bench.json 2> $OUT/stats.err

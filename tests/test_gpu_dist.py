@@ -123,7 +123,7 @@ def test_bench_multi_rank_code_path_with_one_rank():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--T", "400",
-           "--force-dist", "--no-cpu-baseline"]
+           "--force-dist", "--no-cpu-baseline", "--full"]
     run = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert run.returncode == 0, run.stderr[-2000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.strip()]
@@ -154,7 +154,7 @@ def test_bench_two_ranks_rehearsed_on_gloo():
     T, K = 300, 2
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", str(K), "--warmup", "1", "--T", str(T),
-           "--dist-backend", "gloo", "--no-cpu-baseline"]
+           "--dist-backend", "gloo", "--no-cpu-baseline", "--full"]
     run = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert run.returncode == 0, run.stderr[-3000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.strip().startswith("{")]
