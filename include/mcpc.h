@@ -224,6 +224,18 @@ int mcpc_query(const mcpc_engine* e, int32_t* lds_bytes, int32_t* chains_per_wg,
                int32_t* spill_slots);
 /* Name of the step kernel this engine launches, as it appears in a rocprofv3 kernel trace (static string). */
 const char* mcpc_step_kernel_name(const mcpc_engine* e);
+/* What the last mcpc_run actually launched -- the engine's preference above is not always what serves a run (injected noise, gradients-only
+ * runs and Adam with noise keep the main plan's kernel): the step kernel's name as above; a run that also ran a plain launch beside the round
+ * schedule names both, joined by " + ".  "" before the first run.  Host bookkeeping only: no device work, no synchronisation.  The string
+ * is valid until the next mcpc_run on this engine. */
+const char* mcpc_last_step_kernel_name(const mcpc_engine* e);
+/* What the last Hebbian flush of Linear j >= 1 launched (Linear 0's sums take mcpc_dw0_kernel at the end of every accumulating run):
+ * one "<kernel><<TE>,<RA>[,T]>x<groups>[*<activation groups>]" per launch of the tiled kernels, joined by "+" (heb7: the fp16-piece form
+ * mcpc_heb7_kernel, heb: the fp32-MFMA form mcpc_heb_kernel, T: operands swapped), or "dw tiles=<64 x 64 wave tiles>" for the streaming
+ * mcpc_dw_kernel; then "ksplit=<K-splits> rps=<spilled rows per split>" and the spill layout, "tm" (tile-major) or "rm" (row-major).
+ * E.g. "heb7<17,2>x1+heb7<16,2>x2 ksplit=12 rps=1536 tm".  "" for j = 0, out of range, or before the first flush.  Host bookkeeping
+ * only; valid until the next mcpc_run on this engine. */
+const char* mcpc_last_flush_plan(const mcpc_engine* e, int j);
 
 /* Timing hooks.  While profiling is enabled (mcpc_set_profiling(e, 1); every call of it resets the tallies), mcpc_run
  * brackets every step-kernel launch with HIP events on its stream (a launch of the round schedule advances only the workgroups it

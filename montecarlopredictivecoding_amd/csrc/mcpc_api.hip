@@ -226,6 +226,9 @@ struct mcpc_engine {
     int rr_k = 0, rr_m = 0;
     std::string rr_name;                 // mcpc_step_kernel_name of an engine on the round schedule
     std::string u_rr_name;               // ... when its fused calls run on the unified-wave kernel
+    // diagnostics, host strings set while launching (no device work): what the last mcpc_run and each Linear's last flush launched
+    std::string last_step;                       // mcpc_last_step_kernel_name
+    std::string last_flush[kMaxLatent + 1];      // mcpc_last_flush_plan, per Linear j >= 1
     std::vector<int> rr_count, rr_off;   // per launch of a cycle: workgroups, offset of its [ids][rel] rows in rr_tab
     int* rr_tab = nullptr;
     // profiling
@@ -1395,6 +1398,14 @@ int flush_spill(mcpc_engine* e, int n_slots, int slot0, hipStream_t stream, int 
         const float* E = (j < e->L ? e->spill_e[j] : e->spill_eo) + (size_t)slot0 * e->Bpad * ne;
         const float* A = e->spill_a[j - 1] + (size_t)slot0 * e->Bpad * na;
         const HebPlan h = plan_hebbian(e, ne, na, rows);
+        std::string plan;                                       // mcpc_last_flush_plan: one "kernel<args>x<groups>[*<act groups>]" per launch
+        auto name_launch = [&](const char* kern, int te, int ra, bool sw, int n_mt, int n_nt) {
+            char buf[64];
+            snprintf(buf, sizeof buf, "%s%s<%d,%d%s>x%d", plan.empty() ? "" : "+", kern, te, ra, sw ? ",T" : "", n_mt);
+            plan += buf;
+            if (n_nt > 1) plan += "*" + std::to_string(n_nt);
+        };
+        const char* const heb_name = e->knobs.heb_fp32 ? "heb" : "heb7";
         const int e_id = j < e->L ? kMaxLatent + j : kSpillIdEo;          // (mcpc_kernels.h: spill_id_e / kSpillIdEo)
         float* slab = e->slab + ln.slab_off;
         float* slab_b = slab + (size_t)h.ksplit * ne * na;
@@ -1404,6 +1415,7 @@ int flush_spill(mcpc_engine* e, int n_slots, int slot0, hipStream_t stream, int 
             stream = next_stream((double)ne * na);
             // transposed product: the activations take the E slot, the errors the A slot; slab = [split][na][ne]
             HebArgs a{A, E, slab, slab_b, rows, na, ne, h.rps, 1, 1, h.ksplit, 0, smax + spill_id_a_host(j - 1), smax + e_id};
+            name_launch(heb_name, h.te[0], 2, true, 1, 1);
             int rc = 0;
             if (!e->knobs.heb_fp32) {
                 if (h.te[0] == 1) rc = launch_heb7<1, 2, true>(a, stream);
@@ -1422,6 +1434,8 @@ int flush_spill(mcpc_engine* e, int n_slots, int slot0, hipStream_t stream, int 
                 stream = next_stream((double)h.n_mt[part] * h.te[part] * 16 * na);
                 int rc = 0;
                 const int te = h.te[part];
+                const bool resplit = te == 17 && h.ra == 2 && !e->knobs.heb_fp32 && e->knobs.heb171;        // (named where it launches)
+                if (!resplit) name_launch(heb_name, te, h.ra, false, h.n_mt[part], h.n_nt);
                 if (!e->knobs.heb_fp32) {
                     if (te == 17 && h.ra == 2 && !e->knobs.heb171) rc = launch_heb7<17, 2>(a, stream);
                     else if (te == 17 && h.ra == 2) {
@@ -1429,6 +1443,7 @@ int flush_spill(mcpc_engine* e, int n_slots, int slot0, hipStream_t stream, int 
                         // i.e. twice the activation groups -- this group's 272 error columns are read twice (+6.5 MB per step at cfg-M)
                         HebArgs a1 = a;
                         a1.n_nt = 2 * a.n_nt;
+                        name_launch(heb_name, 17, 1, false, a1.n_mt, a1.n_nt);
                         rc = launch_heb7<17, 1>(a1, stream);
                     }
                     else if (te == 16 && h.ra == 2) rc = launch_heb7<16, 2>(a, stream);
@@ -1450,7 +1465,9 @@ int flush_spill(mcpc_engine* e, int n_slots, int slot0, hipStream_t stream, int 
             stream = next_stream((double)ne * na);
             hipLaunchKernelGGL(mcpc_dw_kernel, dim3((h.wave_tiles + 3) / 4, h.ksplit), dim3(256), 0, stream, E, A, slab, slab_b,
                                rows, ne, na, h.rps);
+            plan = "dw tiles=" + std::to_string(h.wave_tiles);
         }
+        e->last_flush[j] = plan + " ksplit=" + std::to_string(h.ksplit) + " rps=" + std::to_string(h.rps) + (ln.spill_tm ? " tm" : " rm");
         const float sign = j < e->L ? -1.0f : 1.0f;
         jobs.job[jobs.n_jobs++] = ReduceJob{slab, ln.G, ne * na, h.ksplit, sign, h.swapped ? ne : 0, h.swapped ? na : 0};
         jobs.job[jobs.n_jobs++] = ReduceJob{slab_b, ln.Gb, ne, h.ksplit, sign, 0, 0};
@@ -1695,7 +1712,10 @@ int mcpc_run(mcpc_engine* e, const mcpc_run_desc* r, void* stream_) {
 #ifdef MCPC_STAMPS
     rr_ok = false;
 #endif
+    // mcpc_last_step_kernel_name: which forms this run launched (bit 0 plain launch, bit 1 round schedule)
+    unsigned launched = 0;
     auto run_round_cycle = [&](const KParams& base, int t0, int q) -> int {
+        launched |= 2u;
         KParams Q = base;
         Q.t0 = t0; Q.spill_t0 = t0; Q.n_steps = q; Q.rr_q = q;
         const int s0 = t0 - r->t_begin;
@@ -1767,6 +1787,7 @@ int mcpc_run(mcpc_engine* e, const mcpc_run_desc* r, void* stream_) {
             if (rc) return rc;
         } else {
         { const int rc = prof_begin(); if (rc) return rc; }
+        launched |= 1u;
         if (use_u) hipLaunchKernelGGL((mcpc_steps_u_kernel<false>), dim3(e->nwg_live), dim3(kUThreads), e->u.lds_bytes, stream, P);
         else if (e->ws == 2) hipLaunchKernelGGL((mcpc_steps_ws2_kernel<1>), dim3(e->nwg_live), dim3(kWs2Threads), e->lds_bytes, stream, P);
         else hipLaunchKernelGGL((mcpc_steps_kernel<1, 4>), dim3(e->nwg), dim3(256), e->lds_bytes, stream, P);
@@ -1841,6 +1862,15 @@ int mcpc_run(mcpc_engine* e, const mcpc_run_desc* r, void* stream_) {
             }
         }
         t += n;
+    }
+    {
+        std::string name;
+        if (launched & 2u) name = use_u ? e->u_rr_name : e->rr_name;
+        if (launched & 1u) {
+            if (!name.empty()) name += " + ";
+            name += use_u ? "mcpc::mcpc_steps_u_kernel<false>" : e->ws == 2 ? "mcpc::mcpc_steps_ws2_kernel<1, false>" : "mcpc::mcpc_steps_kernel<1, 4>";
+        }
+        e->last_step = name;
     }
     // everything that follows on the caller's stream (dw0, gradient read-out, the next run) sees finished sums
     for (int h = 0; h < kMaxRingParts; ++h)
@@ -1979,6 +2009,15 @@ const char* mcpc_step_kernel_name(const mcpc_engine* e) {
     if (e->rr) return e->rr_name.c_str();
     if (e->ws == 2) return "mcpc::mcpc_steps_ws2_kernel<1, false>";
     return "mcpc::mcpc_steps_kernel<1, 4>";
+}
+
+const char* mcpc_last_step_kernel_name(const mcpc_engine* e) {
+    return e ? e->last_step.c_str() : "";
+}
+
+const char* mcpc_last_flush_plan(const mcpc_engine* e, int j) {
+    if (!e || j < 0 || j >= e->L + (e->has_head ? 1 : 0)) return "";
+    return e->last_flush[j].c_str();
 }
 
 int mcpc_sync_check(mcpc_engine* e, void* stream_) {

@@ -267,6 +267,14 @@ class Engine:
         name = self._lib.mcpc_step_kernel_name(self._h).decode()
         return dict(lds_bytes=a.value, chains_per_wg=b.value, n_workgroups=c.value, spill_slots=d.value, step_kernel=name)
 
+    def last_step_kernel(self) -> str:
+        """The step kernel the last run launched (include/mcpc.h: mcpc_last_step_kernel_name; query()["step_kernel"] is the preference)."""
+        return self._lib.mcpc_last_step_kernel_name(self._h).decode()
+
+    def last_flush_plan(self, j: int) -> str:
+        """What the last Hebbian flush of Linear j >= 1 launched, e.g. 'heb7<17,2>x1+heb7<16,2>x2 ksplit=12 rps=1536 tm' (mcpc_last_flush_plan)."""
+        return self._lib.mcpc_last_flush_plan(self._h, j).decode()
+
     def set_profiling(self, enable: bool):
         L.check(self._lib.mcpc_set_profiling(self._h, 1 if enable else 0))
 
