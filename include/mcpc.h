@@ -86,11 +86,21 @@ typedef struct mcpc_net_desc {
     int64_t spill_budget_bytes;          /* HBM budget for the Hebbian spill ring; 0 = default: room for 384 steps in three parts (17 GB at 6000
                                           * chains of cfg-M's net), at least 6 GiB, at most a quarter of the device's memory */
     const char* tuning;                  /* NULL, or developer overrides of the schedule heuristics as "key=value,key=value"
-                                          * (parsed once by mcpc_create, not kept): ws=0|2|3 step kernel (0: the barrier kernel, the
+                                          * (parsed once by mcpc_create, not kept): ws=0|2|3|4 step kernel (0: the barrier kernel, the
                                           * fallback and the independent form parity checks replay the default against; 2: the in-place
                                           * wave-specialised kernel for every run; 3: the unified-wave kernel for the runs it serves -- fused
                                           * SGD / Adam updates -- or an error when its LDS plan does not fit; default: in-place, with the
-                                          * unified-wave kernel for small networks and for zero-loss calls), u_row / u_gemm0 / u_kb / u_kbt /
+                                          * unified-wave kernel for small networks and for zero-loss calls; 4: the layer-wise kernels
+                                          * mcpc_lw_fwd_kernel + mcpc_lw_bwd_kernel for every run, whatever the widths -- state, activations
+                                          * and errors of all chains in global memory, two launches per step; together with no_lean, no_xl,
+                                          * overlay16, rr or u_*, knobs of the LDS-resident kernels, it is MCPC_EINVAL),
+                                          * wide=1 (the choice stays as without it, and the layer-wise kernels serve the engine ONLY where
+                                          * mcpc_create would otherwise fail with MCPC_ENOMEM because no LDS plan holds the network or its
+                                          * last latent layer is wider than 256 units under a read-out; composes with every other key: a
+                                          * forced ws=0|2|3 whose plan does not fit falls to the layer-wise kernels too.  Without ws=4 or
+                                          * wide=1 such a network is rejected with MCPC_ENOMEM.  On the layer-wise kernels the widths are
+                                          * limited by device memory only -- per chain and unit 12 B of state, activation and error, 8 B of
+                                          * Adam moments, and the Hebbian spill ring; MCPC_MAX_LATENT stays 6), u_row / u_gemm0 / u_kb / u_kbt /
                                           * u_eh / u_eb / u_ef=N (cost model the unified-wave kernel's rows are dealt by),
                                           * no_overlap=1, slot_cap=N, spill_gb=N, ring_parts=N,
                                           * flush_tail=N, flush_streams=1|2, cu_slack=N, dw_ksplit=N, ws_prio=0|1|2, stagger=N, no_lean=1,
@@ -222,7 +232,9 @@ int mcpc_sync_check(mcpc_engine* e, void* stream);
  * mcpc_step_kernel_name), spill slots. */
 int mcpc_query(const mcpc_engine* e, int32_t* lds_bytes, int32_t* chains_per_wg, int32_t* n_workgroups,
                int32_t* spill_slots);
-/* Name of the step kernel this engine launches, as it appears in a rocprofv3 kernel trace (static string). */
+/* Name of the step kernel this engine launches, as it appears in a rocprofv3 kernel trace (static string); an engine on the layer-wise
+ * kernels names the pair of launches a step is, "mcpc::mcpc_lw_fwd_kernel + mcpc::mcpc_lw_bwd_kernel", and mcpc_query reports the forward
+ * kernel's LDS bytes, its chain tile and the workgroups of one forward launch. */
 const char* mcpc_step_kernel_name(const mcpc_engine* e);
 /* What the last mcpc_run actually launched -- the engine's preference above is not always what serves a run (injected noise, gradients-only
  * runs and Adam with noise keep the main plan's kernel): the step kernel's name as above; a run that also ran a plain launch beside the round
@@ -255,6 +267,14 @@ int mcpc_last_shader_clock_ghz(mcpc_engine* e, float* ghz);
  * kernels on gfx950, so the next launch on each CU finds the pattern in whatever LDS it does not write itself.  Used by
  * tests/test_gpu_lds_poison.py to show that no result depends on LDS content the step kernels did not produce. */
 int mcpc_debug_poison_lds(int device, uint32_t word, void* stream);
+
+/* Diagnostic (tests only; no device work): the unit-tile jobs of the two launches a step of the layer-wise kernels is, for a network of
+ * `n_latent` layers of `sizes[l]` units and a read-out of `n_out` (0: none).  Writes up to `cap` (layer, first 16-unit tile) pairs of the
+ * forward launch into fwd (layer n_latent = the read-out) and of the backward launch into bwd, their counts into n_fwd / n_bwd (also when
+ * they exceed cap), and into tile[0..1] the chains and the 16-unit tiles one workgroup covers.  gridDim.y of a launch walks the jobs,
+ * gridDim.x the chain tiles. */
+int mcpc_debug_lw_jobs(int32_t n_latent, const int32_t* sizes, int32_t n_out, int32_t* fwd, int32_t* bwd, int32_t cap,
+                       int32_t* n_fwd, int32_t* n_bwd, int32_t* tile);
 
 #ifdef __cplusplus
 }

@@ -106,6 +106,8 @@ SYMBOLS = {
                                            C.POINTER(C.c_int64)]),
     "mcpc_last_shader_clock_ghz": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mcpc_debug_poison_lds": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p]),
+    "mcpc_debug_lw_jobs": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
 _lib = None

@@ -66,7 +66,9 @@ struct Lin {
 constexpr int kMaxRingParts = 8;
 struct Knobs {
     int ws = -1;              // -1: automatic; 0: barrier kernel; 2: in-place wave-specialised kernel everywhere; 3: insist on the unified-wave
-                              // kernel (mcpc_steps_u.h) for the runs it serves (create fails when its LDS plan does not fit)
+                              // kernel (mcpc_steps_u.h) for the runs it serves (create fails when its LDS plan does not fit); 4: the layer-wise
+                              // kernels (mcpc_steps_lw.h) for every run, whatever the widths
+    int wide = 0;             // 1: a network no LDS plan serves (mcpc_create would fail with MCPC_ENOMEM) runs on the layer-wise kernels instead
     int no_overlap = 0;       // 1: Hebbian flushes run serially on the caller's stream (one ring segment = the whole ring)
     int slot_cap = 384;       // spill-ring slots at most (3 parts of 128 steps)
     int spill_gb = 0;         // > 0: spill budget in GiB (overrides mcpc_net_desc::spill_budget_bytes)
@@ -116,7 +118,7 @@ int parse_tuning(const char* str, Knobs& k) {
         const std::string key = item.substr(0, eq);
         const int val = eq == std::string::npos ? 1 : atoi(item.c_str() + eq + 1);
         struct { const char* name; int* dst; } table[] = {
-            {"ws", &k.ws}, {"no_overlap", &k.no_overlap},
+            {"ws", &k.ws}, {"wide", &k.wide}, {"no_overlap", &k.no_overlap},
             {"slot_cap", &k.slot_cap}, {"spill_gb", &k.spill_gb}, {"cu_slack", &k.cu_slack}, {"ring_parts", &k.ring_parts}, {"flush_tail", &k.flush_tail}, {"flush_streams", &k.flush_streams}, {"dw_ksplit", &k.dw_ksplit},
             {"ws_prio", &k.ws_prio}, {"stagger", &k.stagger}, {"no_lean", &k.no_lean}, {"no_ybits", &k.no_ybits}, {"overlay16", &k.overlay16}, {"heb_fp32", &k.heb_fp32}, {"heb171", &k.heb171}, {"rr", &k.rr}, {"rr_qmax", &k.rr_qmax}, {"no_xl", &k.no_xl},
             {"u_row", &k.u_row}, {"u_gemm0", &k.u_gemm0}, {"u_kb", &k.u_kb}, {"u_kbt", &k.u_kbt}, {"u_eh", &k.u_eh}, {"u_eb", &k.u_eb}, {"u_ef", &k.u_ef}};
@@ -125,7 +127,18 @@ int parse_tuning(const char* str, Knobs& k) {
             if (key == t.name) { *t.dst = val; found = true; }
         if (!found) return fail(MCPC_EINVAL, "unknown tuning key '%s' in mcpc_net_desc::tuning", key.c_str());
     }
-    if (k.ws != -1 && k.ws != 0 && k.ws != 2 && k.ws != 3) return fail(MCPC_EINVAL, "tuning ws=%d: 0 (barrier kernel), 2 (in-place kernel) or 3 (unified-wave kernel)", k.ws);
+    if (k.ws != -1 && k.ws != 0 && k.ws != 2 && k.ws != 3 && k.ws != 4)
+        return fail(MCPC_EINVAL, "tuning ws=%d: 0 (barrier kernel), 2 (in-place kernel), 3 (unified-wave kernel) or 4 (layer-wise kernels)", k.ws);
+    if (k.ws == 4) {
+        // knobs of the LDS-resident kernels have nothing to act on: an incompatible pair is an error of its own, not a silent no-op
+        const Knobs dflt;
+        const struct { const char* name; bool set; } lds_only[] = {
+            {"no_lean", k.no_lean != 0}, {"no_xl", k.no_xl != 0}, {"overlay16", k.overlay16 != 0}, {"rr", k.rr != dflt.rr},
+            {"u_row", k.u_row != dflt.u_row}, {"u_gemm0", k.u_gemm0 != dflt.u_gemm0}, {"u_kb", k.u_kb != dflt.u_kb}, {"u_kbt", k.u_kbt != dflt.u_kbt},
+            {"u_eh", k.u_eh != dflt.u_eh}, {"u_eb", k.u_eb != dflt.u_eb}, {"u_ef", k.u_ef != dflt.u_ef}};
+        for (auto& t : lds_only)
+            if (t.set) return fail(MCPC_EINVAL, "tuning ws=4 (layer-wise kernels) together with %s, a knob of the LDS-resident kernels", t.name);
+    }
     if (k.slot_cap < 2) k.slot_cap = 2;
     if (k.cu_slack < 0) k.cu_slack = 0;
     if (k.ring_parts < 2 || k.ring_parts > kMaxRingParts) return fail(MCPC_EINVAL, "tuning ring_parts=%d: 2..%d", k.ring_parts, kMaxRingParts);
@@ -133,6 +146,9 @@ int parse_tuning(const char* str, Knobs& k) {
 }
 
 }  // namespace
+
+// the pair of launches a step on the layer-wise kernels is (mcpc_step_kernel_name, mcpc_last_step_kernel_name: as a trace shows them)
+static const char* const kLwName = "mcpc::mcpc_lw_fwd_kernel + mcpc::mcpc_lw_bwd_kernel";
 
 // LDS plan and step table of the unified-wave kernel (mcpc_steps_u.h), kept BESIDE the engine's main plan: mcpc_run picks the kernel per
 // run (lean runs: fused SGD update with or without the Philox kick, Adam without noise), everything else stays on the main plan's kernel.
@@ -218,6 +234,13 @@ struct mcpc_engine {
     int lds_spillmax = 0;
     int g_first = -1;               // in-place table: first entry with work for the GEMM waves (build_phases_ws2)
     UPlan u;                        // unified-wave kernel: its own LDS plan and table
+    // layer-wise kernels (mcpc_steps_lw.h): state, activations and errors of all chains in global memory, two launches per step
+    bool lw = false;
+    float* lw_fx[kMaxLatent]{};     // f(x_l) [Bpad][npad_l]
+    float* lw_err[kMaxLatent]{};    // e_l, l >= 1
+    float* lw_err_o = nullptr;      // e_o [Bpad][out_pad]
+    LwJob* lw_jobs = nullptr;       // forward jobs, then backward jobs
+    int lw_nf = 0, lw_nb = 0;       // ... how many of each (= gridDim.y of the two launches)
     int lds_rowexp = 0;             // in-place plan: kRowExpFloats words of row exponents (mcpc_kernels.h: rowexp_track)
     unsigned long long* clk = nullptr;   // profiling: {shader cycles, 100 MHz ticks} of one wave per launch (KParams::clk)
     float* dummy = nullptr;         // 4 KiB of zeros (KParams::dummy)
@@ -280,6 +303,8 @@ int free_all(mcpc_engine* e) {
     auto F = [](auto*& p) { if (p) { (void)hipFree((void*)p); p = nullptr; } };
     for (int l = 0; l < kMaxLatent; ++l) { F(e->x[l]); F(e->m[l]); F(e->v[l]); F(e->spill_a[l]); F(e->spill_e[l]); }
     F(e->e0sum); F(e->mu1); F(e->ypad); F(e->ytile); F(e->ybits); F(e->y_binary); F(e->spill_eo); F(e->slab); F(e->epart); F(e->adam_coef); F(e->phases); F(e->err); F(e->wexp); F(e->spillmax); F(e->clk); F(e->dummy); F(e->u.phases);
+    for (int l = 0; l < kMaxLatent; ++l) { F(e->lw_fx[l]); F(e->lw_err[l]); }
+    F(e->lw_err_o); F(e->lw_jobs);
     for (auto& ln : e->lin) { F(ln.Wf); F(ln.Wb); F(ln.bias_pad); F(ln.G); F(ln.Gb); }
     for (auto& ev : e->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     for (int h = 0; h < kMaxRingParts; ++h) { if (e->ev_steps[h]) (void)hipEventDestroy(e->ev_steps[h]); if (e->ev_flush[h]) (void)hipEventDestroy(e->ev_flush[h]); e->ev_steps[h] = e->ev_flush[h] = nullptr; }
@@ -885,6 +910,81 @@ int build_phases(mcpc_engine* e) {
 
 namespace {
 
+// ---- layer-wise kernels (mcpc_steps_lw.h) ---------------------------------------------------------------------------------------------------
+// The unit-tile jobs of the two launches of a step: gridDim.y of the forward launch walks (Linear j, first unit tile) for every Linear --
+// the read-out is j = L, Linear 0 (no GEMM) included -- in tiles of kLwUnitTiles x 16 units, gridDim.y of the backward launch (latent
+// layer l, first unit tile); gridDim.x is the chain tile.  Every 16-unit tile of every layer is in exactly one job (tests/test_wide_cases.py
+// checks that through mcpc_lw_job_table).
+int lw_job_table(int L, const int* npad, int out_pad, std::vector<LwJob>& fwd, std::vector<LwJob>& bwd) {
+    fwd.clear(); bwd.clear();
+    // widest first: the long GEMMs of a launch start first, the short tiles fill its tail
+    auto tiles_of = [&](int j) { return (j < L ? npad[j] : out_pad) / 16; };
+    auto cost_of = [&](int j) { return j == 0 ? 0 : npad[j - 1]; };
+    std::vector<int> order;
+    for (int j = 0; j <= L; ++j) if (tiles_of(j) > 0) order.push_back(j);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cost_of(a) > cost_of(b); });
+    for (int j : order)
+        for (int ut = 0; ut < tiles_of(j); ut += kLwUnitTiles) fwd.push_back(LwJob{j, ut});
+    auto bcost = [&](int l) { return l + 1 < L ? npad[l + 1] : out_pad; };
+    std::vector<int> border;
+    for (int l = 0; l < L; ++l) border.push_back(l);
+    std::stable_sort(border.begin(), border.end(), [&](int a, int b) { return bcost(a) > bcost(b); });
+    for (int l : border)
+        for (int ut = 0; ut < npad[l] / 16; ut += kLwUnitTiles) bwd.push_back(LwJob{l, ut});
+    return 0;
+}
+
+int setup_lw(mcpc_engine* e) {
+    int rc;
+    for (int l = 0; l < e->L; ++l) {
+        const size_t n = (size_t)e->Bpad * e->npad[l];
+        if ((rc = dmalloc(e->lw_fx[l], n))) return rc;
+        if (l >= 1 && (rc = dmalloc(e->lw_err[l], n))) return rc;
+    }
+    if (e->has_head && (rc = dmalloc(e->lw_err_o, (size_t)e->Bpad * e->out_pad))) return rc;
+    std::vector<LwJob> fwd, bwd;
+    lw_job_table(e->L, e->npad, e->has_head ? e->out_pad : 0, fwd, bwd);
+    e->lw_nf = (int)fwd.size(); e->lw_nb = (int)bwd.size();
+    if (e->lw_nf > 65535 || e->lw_nb > 65535) return fail(MCPC_EINVAL, "layer-wise kernels: more than 65535 unit-tile jobs per launch");
+    fwd.insert(fwd.end(), bwd.begin(), bwd.end());
+    if ((rc = dmalloc(e->lw_jobs, fwd.size()))) return rc;
+    if (hipMemcpy(e->lw_jobs, fwd.data(), fwd.size() * sizeof(LwJob), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(MCPC_EHIP, "hipMemcpy of the layer-wise job table failed");
+    e->nwg_live = (e->Bpad / kLwChains) * e->lw_nf;         // workgroups of the forward launch (mcpc_query; one energy slot each)
+    return 0;
+}
+
+// steps [t0, t0 + n) of a run on the layer-wise kernels: two launches per step on the caller's stream.  `P` carries the segment's spill
+// pointers (spill_t0 = t0); what changes from step to step travels in the launch arguments.
+int launch_lw_steps(mcpc_engine* e, const mcpc_run_desc* r, const KParams& P, int t0, int n, hipStream_t stream) {
+    LwParams Q{};
+    Q.P = P;
+    for (int l = 0; l < e->L; ++l) { Q.fx[l] = e->lw_fx[l]; Q.err[l] = e->lw_err[l]; }
+    Q.err_o = e->lw_err_o;
+    const dim3 gf(e->Bpad / kLwChains, e->lw_nf), gb(e->Bpad / kLwChains, e->lw_nb);
+    for (int t = t0; t < t0 + n; ++t) {
+        const size_t s = (size_t)(t - r->t_begin);
+        Q.t = t;
+        Q.slot = (t >= P.acc_begin && t < P.acc_end) ? t - P.spill_t0 : -1;
+        Q.rec_idx = -1;
+        if (P.rec_count > 0 && t >= P.rec_begin) {
+            const int k = (t - P.rec_begin) / P.rec_stride;
+            if (k < P.rec_count && P.rec_begin + k * P.rec_stride == t) Q.rec_idx = k;
+        }
+        Q.do_energy = (P.energy_mode == MCPC_ENERGY_ALL || (P.energy_mode == MCPC_ENERGY_LAST && t == P.T - 1)) ? 1 : 0;
+        Q.erow = P.energy_mode == MCPC_ENERGY_ALL ? t : 0;
+        Q.P.adam_coef = r->xopt_kind == MCPC_XOPT_ADAM ? e->adam_coef + 2 * s : nullptr;
+        if (r->noise_mode == MCPC_NOISE_EXTERNAL)
+            for (int l = 0; l < e->L; ++l) Q.P.layer[l].ext_noise = r->ext_noise[l] + s * e->d.batch * e->d.sizes[l];
+        Q.jobs = e->lw_jobs;
+        hipLaunchKernelGGL(mcpc_lw_fwd_kernel, gf, dim3(kLwThreads), 0, stream, Q);
+        Q.jobs = e->lw_jobs + e->lw_nf;
+        hipLaunchKernelGGL(mcpc_lw_bwd_kernel, gb, dim3(kLwThreads), 0, stream, Q);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // Round schedule of the in-place kernel for a shard of U 16-chain units on C < U CUs.  One unit per CU is what the kernel is built
 // for (a step is a chain of dependent hand-overs inside ONE workgroup: a second workgroup per CU does not fit the LDS, a launch of
 // U > C workgroups runs as ceil(U / C) hardware rounds, the last one mostly empty).  Instead the units are dealt into k groups and a
@@ -1000,17 +1100,38 @@ int mcpc_create(const mcpc_net_desc* d, mcpc_engine** out) {
     // (a last latent layer of up to 256 units) in both kernels (cap_ws2 = 4 GEMM waves x 4 tiles, cap_bar = 4 waves x 4 tiles).
     const int last_tiles = e->has_head ? e->npad[e->L - 1] / 16 : 0;
     const int cap_ws2 = kWs2Pairs * ws2_nt<1>(), cap_bar = kNT * kWaves;
-    if (last_tiles > std::max(cap_ws2, cap_bar) || (last_tiles > cap_bar && e->ws != 2)) {
+    // The layer-wise kernels (mcpc_steps_lw.h) know neither limit: tuning ws=4 takes them for every run, wide=1 where the checks below fail
+    bool lw = kn.ws == 4;
+    if (!lw && (last_tiles > std::max(cap_ws2, cap_bar) || (last_tiles > cap_bar && e->ws != 2))) {
+        if (kn.wide) lw = true;
+        else {
         delete e;
         return fail(MCPC_ENOMEM, "last latent layer wider than %d units is not supported by the fused read-out (its back-projection is held in register tiles)", (e->ws == 2 ? std::max(cap_ws2, cap_bar) : cap_bar) * 16);
+        }
     }
-    int rc = e->ws == 2 ? plan_lds_ws2(e) : plan_lds(e);
-    if (rc && e->ws == 2 && kn.ws == -1 && last_tiles <= cap_bar) {   // no in-place plan fits: the barrier schedule
-        g_err.clear();
-        e->ws = 0; e->nw = kWaves;
-        rc = plan_lds(e);
+    int rc = 0;
+    if (!lw) {
+        rc = e->ws == 2 ? plan_lds_ws2(e) : plan_lds(e);
+        if (rc && e->ws == 2 && kn.ws == -1 && last_tiles <= cap_bar) {   // no in-place plan fits: the barrier schedule
+            g_err.clear();
+            e->ws = 0; e->nw = kWaves;
+            rc = plan_lds(e);
+        }
+        if (rc == MCPC_ENOMEM && kn.wide) { g_err.clear(); rc = 0; lw = true; }
+        if (rc) { delete e; return rc; }
+        // (a forced unified-wave kernel whose plan does not fit: the same fallback under wide=1, the same failure without it -- below)
+        if (kn.ws == 3 && kn.wide && e->ws == 2) {
+            if (kn.no_lean || kn.no_xl) lw = true;
+            else { (void)plan_lds_u(e); if (!e->u.ok) { g_err.clear(); lw = true; } }
+        }
     }
-    if (rc) { delete e; return rc; }
+    if (lw) {
+        // no LDS plan, no phase table: whole chain tiles of the layer-wise kernels, their static LDS
+        e->lw = true; e->ws = 0; e->nw = kLwWaves; e->u = UPlan{};
+        e->Bpad = (d->batch + kLwChains - 1) / kLwChains * kLwChains;
+        e->nwg = e->Bpad / e->ct;
+        e->lds_bytes = kLwLdsBytes;
+    }
     e->nwg_live = e->ws == 2 ? (d->batch + 15) / 16 : e->nwg;
 
     auto bail = [&](int code) { free_all(e); delete e; return code; };
@@ -1076,7 +1197,8 @@ int mcpc_create(const mcpc_net_desc* d, mcpc_engine** out) {
         e->lin[j].spill_tm = (heb_wide(et, at) || heb_narrow_in(et, at)) && !kn.heb_fp32;
     }
 
-    if ((rc = e->ws == 2 ? build_phases_ws2(e) : build_phases(e))) return bail(rc);
+    if (e->lw) { if ((rc = setup_lw(e))) return bail(rc); }
+    else if ((rc = e->ws == 2 ? build_phases_ws2(e) : build_phases(e))) return bail(rc);
     // the unified-wave kernel beside the in-place kernel, where its plan fits (mcpc_steps_u.h)
     if (e->ws == 2 && (kn.ws == -1 || kn.ws == 3) && !kn.no_lean && !kn.no_xl) {
         (void)plan_lds_u(e);
@@ -1084,7 +1206,7 @@ int mcpc_create(const mcpc_net_desc* d, mcpc_engine** out) {
         e->u.prefer = e->u.ok && (kn.ws == 3 || choose_unified(e));
         if (e->u.on && (rc = build_phases_u(e))) return bail(rc);
     }
-    if (kn.ws == 3 && !e->u.on) return bail(fail(MCPC_ENOMEM, "tuning ws=3: the unified-wave kernel's LDS plan does not fit this network (%d bytes)", e->u.lds_bytes));
+    if (kn.ws == 3 && !e->u.on && !e->lw) return bail(fail(MCPC_ENOMEM, "tuning ws=3: the unified-wave kernel's LDS plan does not fit this network (%d bytes)", e->u.lds_bytes));
     if ((rc = dmalloc(e->err, 1))) return bail(rc);
     if (hipMemset(e->err, 0, sizeof(int)) != hipSuccess) return bail(fail(MCPC_EHIP, "hipMemset failed"));
     if ((rc = dmalloc(e->spillmax, (size_t)kMaxRingParts * kSpillTensors))) return bail(rc);
@@ -1096,7 +1218,7 @@ int mcpc_create(const mcpc_net_desc* d, mcpc_engine** out) {
     if ((rc = dmalloc(e->dummy, 1024))) return bail(rc);
     if (hipMemset(e->dummy, 0, 4096) != hipSuccess) return bail(fail(MCPC_EHIP, "hipMemset failed"));
     const void* kfn = e->ws == 2 ? (const void*)mcpc_steps_ws2_kernel<1> : (const void*)mcpc_steps_kernel<1, 4>;
-    hipError_t herr = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes);
+    hipError_t herr = e->lw ? hipSuccess : hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes);
     if (herr != hipSuccess) return bail(fail(MCPC_EHIP, "hipFuncSetAttribute(%d bytes LDS) failed: %s", e->lds_bytes, hipGetErrorString(herr)));
     if (e->ws == 2 && e->nwg_live > n_cu && kn.rr) {
         if ((rc = setup_rounds(e, n_cu))) return bail(rc);
@@ -1563,7 +1685,7 @@ int mcpc_run(mcpc_engine* e, const mcpc_run_desc* r, void* stream_) {
     const size_t erows = r->energy_mode == MCPC_ENERGY_ALL ? (size_t)r->T : 1;
     // energy partials per step: one slot per workgroup; the in-place kernel indexes them by 16-chain tile (its 32- and 16-chain
     // forms can then serve the same call)
-    const size_t eslots = e->ws == 2 ? (size_t)e->Bpad / 16 : (size_t)e->nwg;
+    const size_t eslots = e->lw ? (size_t)e->nwg_live : e->ws == 2 ? (size_t)e->Bpad / 16 : (size_t)e->nwg;
     if (r->energy_mode != MCPC_ENERGY_NONE && erows > e->epart_rows) {
         if (e->epart) retire(e, e->epart, stream);        // earlier launches may still write it
         e->epart = nullptr;
@@ -1582,6 +1704,12 @@ int mcpc_run(mcpc_engine* e, const mcpc_run_desc* r, void* stream_) {
         hipLaunchKernelGGL(mcpc_mu1_kernel, dim3(grid_for(total)), dim3(256), 0, stream, e->inputs, l0.W, l0.bias, e->mu1,
                            e->d.batch, e->d.n_in, e->d.sizes[0], e->Bpad, e->npad[0]);
     }
+    // layer-wise kernels: f(x_l) of the state the run starts from (the backward launches keep it current from there)
+    if (e->lw)
+        for (int l = 0; l < e->L; ++l) {
+            const size_t total4 = (size_t)e->Bpad * e->npad[l] / 4;
+            hipLaunchKernelGGL(mcpc_lw_act_kernel, dim3(grid_for(total4)), dim3(256), 0, stream, (const float*)e->x[l], e->lw_fx[l], total4, e->d.acts[l]);
+        }
     const bool run_accumulates = acc_b < acc_e && r->t_begin < acc_e && r->t_begin + r->n_steps > acc_b;
     if (run_accumulates) { const int rc = ensure_spill(e, stream); if (rc) return rc; }
     if (r->acc_reset && run_accumulates) {
@@ -1788,7 +1916,8 @@ int mcpc_run(mcpc_engine* e, const mcpc_run_desc* r, void* stream_) {
         } else {
         { const int rc = prof_begin(); if (rc) return rc; }
         launched |= 1u;
-        if (use_u) hipLaunchKernelGGL((mcpc_steps_u_kernel<false>), dim3(e->nwg_live), dim3(kUThreads), e->u.lds_bytes, stream, P);
+        if (e->lw) { const int rc = launch_lw_steps(e, r, P, t, n, stream); if (rc) return rc; }
+        else if (use_u) hipLaunchKernelGGL((mcpc_steps_u_kernel<false>), dim3(e->nwg_live), dim3(kUThreads), e->u.lds_bytes, stream, P);
         else if (e->ws == 2) hipLaunchKernelGGL((mcpc_steps_ws2_kernel<1>), dim3(e->nwg_live), dim3(kWs2Threads), e->lds_bytes, stream, P);
         else hipLaunchKernelGGL((mcpc_steps_kernel<1, 4>), dim3(e->nwg), dim3(256), e->lds_bytes, stream, P);
         { const int rc = prof_end((double)n); if (rc) return rc; }
@@ -1868,7 +1997,7 @@ int mcpc_run(mcpc_engine* e, const mcpc_run_desc* r, void* stream_) {
         if (launched & 2u) name = use_u ? e->u_rr_name : e->rr_name;
         if (launched & 1u) {
             if (!name.empty()) name += " + ";
-            name += use_u ? "mcpc::mcpc_steps_u_kernel<false>" : e->ws == 2 ? "mcpc::mcpc_steps_ws2_kernel<1, false>" : "mcpc::mcpc_steps_kernel<1, 4>";
+            name += e->lw ? kLwName : use_u ? "mcpc::mcpc_steps_u_kernel<false>" : e->ws == 2 ? "mcpc::mcpc_steps_ws2_kernel<1, false>" : "mcpc::mcpc_steps_kernel<1, 4>";
         }
         e->last_step = name;
     }
@@ -1996,7 +2125,7 @@ int mcpc_philox_normals(int device, uint64_t seed, uint64_t step, int layer, uin
 int mcpc_query(const mcpc_engine* e, int32_t* lds_bytes, int32_t* chains_per_wg, int32_t* n_workgroups, int32_t* spill_slots) {
     if (!e) return fail(MCPC_EINVAL, "null engine");
     if (lds_bytes) *lds_bytes = e->lds_bytes;
-    if (chains_per_wg) *chains_per_wg = e->ct;
+    if (chains_per_wg) *chains_per_wg = e->lw ? kLwChains : e->ct;
     if (n_workgroups) *n_workgroups = e->nwg_live;
     if (spill_slots) *spill_slots = e->slots;
     return MCPC_OK;
@@ -2004,6 +2133,7 @@ int mcpc_query(const mcpc_engine* e, int32_t* lds_bytes, int32_t* chains_per_wg,
 
 const char* mcpc_step_kernel_name(const mcpc_engine* e) {
     if (!e) return "";
+    if (e->lw) return kLwName;
     // (an engine that holds the unified-wave kernel's plan runs its fused calls -- what a benchmark times -- on that kernel)
     if (e->u.prefer) return e->rr ? e->u_rr_name.c_str() : "mcpc::mcpc_steps_u_kernel<false>";
     if (e->rr) return e->rr_name.c_str();
@@ -2099,6 +2229,21 @@ int mcpc_debug_poison_lds(int device, uint32_t word, void* stream_) {
     }
     (void)hipFree(seen);
     return rc;
+}
+
+int mcpc_debug_lw_jobs(int32_t n_latent, const int32_t* sizes, int32_t n_out, int32_t* fwd, int32_t* bwd, int32_t cap,
+                       int32_t* n_fwd, int32_t* n_bwd, int32_t* tile) {
+    if (n_latent < 1 || n_latent > kMaxLatent || !sizes || n_out < 0) return fail(MCPC_EINVAL, "bad network");
+    int npad[kMaxLatent];
+    for (int l = 0; l < n_latent; ++l) { if (sizes[l] < 1) return fail(MCPC_EINVAL, "sizes[%d]=%d", l, sizes[l]); npad[l] = pad16(sizes[l]); }
+    std::vector<LwJob> f, b;
+    lw_job_table(n_latent, npad, pad16(n_out), f, b);
+    for (int i = 0; i < (int)f.size() && i < cap && fwd; ++i) { fwd[2 * i] = f[i].layer; fwd[2 * i + 1] = f[i].ut0; }
+    for (int i = 0; i < (int)b.size() && i < cap && bwd; ++i) { bwd[2 * i] = b[i].layer; bwd[2 * i + 1] = b[i].ut0; }
+    if (n_fwd) *n_fwd = (int32_t)f.size();
+    if (n_bwd) *n_bwd = (int32_t)b.size();
+    if (tile) { tile[0] = kLwChains; tile[1] = kLwUnitTiles; }
+    return MCPC_OK;
 }
 
 int mcpc_set_profiling(mcpc_engine* e, int enable) {

@@ -1051,3 +1051,4 @@ __global__ void mcpc_philox_kernel(uint64_t seed, uint64_t step, int layer, uint
 #include "mcpc_steps_ws2.h"
 #include "mcpc_steps_u.h"
 #include "mcpc_hebbian.h"
+#include "mcpc_steps_lw.h"

@@ -1,0 +1,438 @@
+// K1w  Layer-wise step kernels: networks too wide for the LDS plans of K1 / K1u.
+//
+// The state of ALL chains lives in global memory and one Langevin step is TWO launches over (Linear, chain tile, unit tile) output tiles:
+//   mcpc_lw_fwd_kernel   every prediction of the step at once: mu_j = f(x_{j-1}) W_j^T + b_j as a tiled GEMM, epilogue e_j = c_j (x_j - mu_j)
+//                        (read-out: output, loss, e_o = dloss/dout), energy partials, Hebbian spill, trajectory records; errors -> global memory.
+//                        Linear 0's prediction is the constant mu_1 (mcpc_mu1_kernel): its tiles have no GEMM.
+//   mcpc_lw_bwd_kernel   every x update at once: g_l = e_l - f'(x_l) (e_{l+1} W_{l+1}) as a tiled GEMM on the transposed fragments, epilogue = the
+//                        x update of bwd_epilogue (mcpc_kernels.h), in place (an element of x_l is read and written by one thread only), and
+//                        f(x_l) of the new state for the next forward launch.
+// Given x_t all predictions are independent of each other, and given the errors all back-projections are: the two launch boundaries are the
+// only synchronisation (no grid barrier, no spin-wait, no cooperative launch).
+//
+// Tile: one workgroup of 4 waves = 64 chains x 128 units; a wave owns 2 unit tiles x 4 chain tiles of 16 x 16 (8 accumulators).  Per
+// 32-deep k-block the 64 x 32 block of the B operand (activations / errors: fp32 rows in global memory) is read ONCE per workgroup, scaled
+// by its chain row's power of two and split into the two fp16 planes by the thread that loaded it (split8: the PS form of b_planes), and
+// handed to all four waves through a double-buffered LDS block of 2 x 64 x 36 floats; the weight fragments of mcpc_pack_kernel stream
+// L2 -> registers.  Arithmetic of mcpc_gemm_f16.h, unchanged: per row one exponent from the row's own maximum (a pre-pass of the
+// workgroup over its 64 rows), three MFMAs per product ([a_m b_m,] a_m b_h, a_h b_m, a_h b_h; four for K <= 64), k-blocks ascending in one
+// fp32 accumulator per tile, un-scaled at the end.  Lanes whose eight k values lie beyond a k range that is not a multiple of 32 stage
+// zeros and load nothing (global rows are npad wide: what lies behind them is the next chain's row).
+#pragma once
+
+namespace mcpc {
+
+constexpr int kLwChains = 64;                       // chains per workgroup
+constexpr int kLwCTT = kLwChains / 16;              // chain tiles per wave
+constexpr int kLwWaves = 4;
+constexpr int kLwThreads = kLwWaves * 64;
+constexpr int kLwUTW = 2;                           // unit tiles per wave
+constexpr int kLwUnitTiles = kLwWaves * kLwUTW;     // unit tiles per workgroup (128 units)
+constexpr int kLwLd = kKB + 4;                      // floats per chain row of a staged k-block
+constexpr int kLwStageFloats = 2 * kLwChains * kLwLd;
+constexpr int kLwLdsBytes = (kLwStageFloats + kLwChains + kLwWaves + 2) * 4;     // staging, row exponents, energy partials, spill maxima
+
+struct LwJob { int layer; int ut0; };               // forward: Linear j (layer L = the read-out); backward: latent layer l; first unit tile
+
+struct LwParams {
+    KParams P;                     // what the LDS-resident kernels take: layers, read-out, optimiser, noise, records (LDS offsets unused)
+    float* fx[kMaxLatent];         // f(x_l)   [Bpad][npad_l]: written by the backward launch, B operand of the forward launch
+    float* err[kMaxLatent];        // e_l      [Bpad][npad_l], l >= 1: written by the forward launch, B operand of the backward launch
+    float* err_o;                  // e_o      [Bpad][out_pad]
+    const LwJob* jobs;             // [gridDim.y]
+    int t;                         // step of the call
+    int slot;                      // spill slot of this step (-1: the step does not accumulate)
+    int rec_idx;                   // record index of this step (-1: not recorded)
+    int do_energy, erow;           // energies of this step go to row erow of the partial table
+};
+
+__device__ __forceinline__ LwJob lw_load_job(const LwJob* tbl, int i) {
+    typedef __attribute__((address_space(4))) const int cint;
+    cint* w = (cint*)(tbl + i);
+    LwJob j; j.layer = w[0]; j.ut0 = w[1];
+    return j;
+}
+
+// acc[i][ct] = sum_k W[tile i][k] B[chain0 + 16 ct + c][k] (fp32), un-scaled.  All 256 threads take part (staging, barriers) whatever nt.
+//   A, voff: fragment base and this lane's byte offset of block 0 of the wave's tiles;  Bg: rows [Bpad][ldb], kw valid columns
+template <bool MM>
+__device__ __forceinline__ void lw_gemm(f32x4 (&acc)[kLwUTW][kLwCTT], const gu32x4* __restrict__ A, const uint32_t (&voff)[kLwUTW], int nkb, int kw,
+                                        const float* __restrict__ Bg, int ldb, int chain0, int a_exp, float* stage, int* sexp, int tid, int lane) {
+    const int srow = tid >> 2, sg = tid & 3;                  // staging: this thread's chain row and 8-float group of every k-block
+    const float* const brow = Bg + (size_t)(chain0 + srow) * ldb + 8 * sg;
+    const int last = nkb - 1;
+    const bool tail_ok = (uint32_t)(kKB * last + 8 * sg) < (uint32_t)kw;       // does this group of the LAST block lie inside the row?
+    // the row's exponent: largest |value| of the row (gemm_row_exp: the same maximum, the same field)
+    float mx = 0.f;
+#pragma unroll 4
+    for (int kb = 0; kb < nkb; ++kb) {
+        if (kb < last || tail_ok) {
+            const f32x4 a = ld4(brow + kb * kKB), b = ld4(brow + kb * kKB + 4);
+            mx = absmax4(absmax4(mx, a), b);
+        }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
+    const int b_exp = scale_exp_for_max(mx);
+    if (sg == 0) sexp[srow] = b_exp;
+    const float bscale = pow2i(b_exp);
+    const f32x4 z4 = splat(0.f);
+    f32x4 s0, s1;                                             // the staged values of the NEXT block, in flight
+#define LW_STAGE_LOAD(k_)                                                                           \
+    do {                                                                                            \
+        const int kc_ = (k_) < last ? (k_) : last;                                                  \
+        const bool ok_ = kc_ < last || tail_ok;                                                     \
+        const float* const src_ = ok_ ? brow + kc_ * kKB : Bg;                                      \
+        const f32x4 v0_ = ld4(src_), v1_ = ld4(src_ + 4);                                           \
+        s0 = ok_ ? v0_ : z4; s1 = ok_ ? v1_ : z4;                                                   \
+    } while (0)
+#define LW_STAGE_WRITE(buf_)                                                                        \
+    do {                                                                                            \
+        const frag_t f_ = split8(s0, s1, bscale);                                                   \
+        float* const dst_ = stage + (buf_) * (kLwChains * kLwLd) + srow * kLwLd + 8 * sg;           \
+        *reinterpret_cast<u32x4*>(dst_) = f_.h; *reinterpret_cast<u32x4*>(dst_ + 4) = f_.m;         \
+    } while (0)
+    const char __attribute__((address_space(1)))* const Ab = (const char __attribute__((address_space(1)))*)A;
+    frag_t fa[kLwUTW];
+#pragma unroll
+    for (int i = 0; i < kLwUTW; ++i) { fa[i].h = *(const gu32x4*)(Ab + voff[i]); fa[i].m = *(const gu32x4*)(Ab + voff[i] + 1024u); }
+    LW_STAGE_LOAD(0);
+    LW_STAGE_WRITE(0);
+    LW_STAGE_LOAD(1);
+    __syncthreads();
+    const int c = lane & 15, g = lane >> 4;
+    const float* const rd = stage + c * kLwLd + 8 * g;
+    for (int k = 0; k < nkb; ++k) {
+        // the fragments of block k + 1 (the last block re-reads itself: never conditional)
+        const int kn = k < last ? k + 1 : last;
+        const char __attribute__((address_space(1)))* const Ak = Ab + (size_t)kn * (kFragBlock * 16u);
+        frag_t fn[kLwUTW];
+#pragma unroll
+        for (int i = 0; i < kLwUTW; ++i) { fn[i].h = *(const gu32x4*)(Ak + voff[i]); fn[i].m = *(const gu32x4*)(Ak + voff[i] + 1024u); }
+        frag_t bs[kLwCTT];
+        const float* const rk = rd + (k & 1) * (kLwChains * kLwLd);
+#pragma unroll
+        for (int ct = 0; ct < kLwCTT; ++ct) bs[ct] = b_planes<true>(ld4(rk + 16 * ct * kLwLd), ld4(rk + 16 * ct * kLwLd + 4), 0.f);
+        // per accumulator the products of gemm_fixed in its order: small terms first
+#define LW_M(ap_, bp_)                                                                              \
+        _Pragma("unroll") for (int ct = 0; ct < kLwCTT; ++ct)                                       \
+            _Pragma("unroll") for (int i = 0; i < kLwUTW; ++i) acc[i][ct] = mfma4(fa[i].ap_, bs[ct].bp_, acc[i][ct])
+        if constexpr (MM) { LW_M(m, m); }
+        LW_M(m, h); LW_M(h, m); LW_M(h, h);
+#undef LW_M
+        if (k < last) {
+            LW_STAGE_WRITE((k + 1) & 1);
+            LW_STAGE_LOAD(k + 2);
+        }
+        __syncthreads();              // block k + 1 is staged; every wave is through with the buffer block k + 2 will take
+#pragma unroll
+        for (int i = 0; i < kLwUTW; ++i) fa[i] = fn[i];
+    }
+#undef LW_STAGE_LOAD
+#undef LW_STAGE_WRITE
+    // un-scale: the lane's chains are the rows whose exponents the staging threads published (gemm_unscale)
+#pragma unroll
+    for (int ct = 0; ct < kLwCTT; ++ct) {
+        const float un = pow2i(-a_exp) * pow2i(-sexp[16 * ct + c]);
+#pragma unroll
+        for (int i = 0; i < kLwUTW; ++i) acc[i][ct] = acc[i][ct] * un;
+    }
+}
+
+// the wave's tiles of a job and the GEMM over them (nkb == 0: no GEMM, the accumulators stay zero)
+__device__ __forceinline__ void lw_job_gemm(f32x4 (&acc)[kLwUTW][kLwCTT], const void* A, int a_tile_stride, int utw, int ntiles, int nkb, int kw,
+                                            const float* Bg, int chain0, int a_exp, float* stage, int* sexp, int tid, int lane) {
+#pragma unroll
+    for (int i = 0; i < kLwUTW; ++i)
+#pragma unroll
+        for (int ct = 0; ct < kLwCTT; ++ct) acc[i][ct] = splat(0.f);
+    if (nkb <= 0) return;
+    uint32_t voff[kLwUTW];
+#pragma unroll
+    for (int i = 0; i < kLwUTW; ++i) {
+        const int ut = utw + i < ntiles ? utw + i : ntiles - 1;          // tiles beyond the layer re-read its last tile (never used)
+        voff[i] = (uint32_t)(ut * a_tile_stride + lane) * 16u;
+    }
+    if (nkb <= kShortK) lw_gemm<true>(acc, (const gu32x4*)A, voff, nkb, kw, Bg, kw, chain0, a_exp, stage, sexp, tid, lane);
+    else lw_gemm<false>(acc, (const gu32x4*)A, voff, nkb, kw, Bg, kw, chain0, a_exp, stage, sexp, tid, lane);
+}
+
+// ---- forward epilogues (fwd_epilogue / headf_epilogue of mcpc_kernels.h with the errors in global memory) ----------------------------------
+template <int ACT>
+__device__ __forceinline__ float lw_fwd_latent(const LwParams& Q, int l, int utw, int nt, int chain0, int lane, const f32x4 (&acc)[kLwUTW][kLwCTT],
+                                               float& amx, float& emx) {
+    const KParams& P = Q.P;
+    const KLayer& Ly = P.layer[l];
+    const int c = lane & 15, q = lane >> 4;
+    const int npad = Ly.npad, n = Ly.n, B = P.B, Bpad = P.Bpad, slot = Q.slot;
+    const float ecoef = Ly.ecoef;
+    float* const eg = Q.err[l];
+    float* const rec = (Q.rec_idx >= 0 && Ly.rec != nullptr) ? Ly.rec + (size_t)Q.rec_idx * B * n : nullptr;
+    float esum = 0.f;
+#pragma unroll
+    for (int i = 0; i < kLwUTW; ++i) {
+        if (i >= nt) continue;
+        const int u0 = 16 * (utw + i) + 4 * q;
+        // (l == 0: the prediction is the constant mu_1 row; l >= 1: GEMM + bias)
+        const f32x4 bias = l > 0 ? ld4(Ly.bias + u0) : splat(0.f);
+#pragma unroll
+        for (int ct = 0; ct < kLwCTT; ++ct) {
+            const int chain = chain0 + 16 * ct + c;
+            const bool live = chain < B;
+            const size_t row = (size_t)chain * npad + u0;
+            const f32x4 x = ld4(Ly.x + row);
+            const f32x4 mub = l > 0 ? bias : ld4(P.mu1 + row);
+            const f32x4 d = x - (acc[i][ct] + mub);               // x - mu
+            const f32x4 e = d * ecoef;
+            if (l > 0) st4(eg + row, e);
+            if (slot >= 0) {
+                const f32x4 z = splat(0.f);
+                f32x4 fx;
+                fx.x = actf<ACT>(x.x); fx.y = actf<ACT>(x.y); fx.z = actf<ACT>(x.z); fx.w = actf<ACT>(x.w);
+                const size_t srow = (size_t)slot * Bpad + chain;
+                st4s(Ly.spill_a + spill_offset(Ly.spill_a_tm, srow, u0, npad), live ? fx : z);
+                amx = absmax4(amx, live ? fx : z);
+                if (l > 0) {
+                    st4s(Ly.spill_e + spill_offset(Ly.spill_e_tm, srow, u0, npad), live ? e : z);
+                    emx = absmax4(emx, live ? e : z);
+                } else if (live) {        // Linear 0 sees a constant input: only sum_t e_1 is needed
+                    float* sp = Ly.spill_e + row;
+                    st4(sp, ld4(sp) + e);
+                }
+            }
+            if (rec != nullptr && live) st_unpadded(rec, chain, n, u0, x);
+            const f32x4 dd = d * d;
+            esum += live ? 0.5f * ecoef * (dd.x + dd.y + dd.z + dd.w) : 0.0f;
+        }
+    }
+    return esum;
+}
+
+__device__ __forceinline__ float lw_fwd_head(const LwParams& Q, int utw, int nt, int chain0, int lane, const f32x4 (&acc)[kLwUTW][kLwCTT], float& omx) {
+    const KParams& P = Q.P;
+    const KHead& H = P.head;
+    const int c = lane & 15, q = lane >> 4;
+    const int npad = H.npad, n = H.n, B = P.B, Bpad = P.Bpad, mask_start = H.mask_start, kind = H.loss_kind, slot = Q.slot;
+    const float inv_var = H.inv_var;
+    const bool do_energy = Q.do_energy != 0;
+    float* const rec = (Q.rec_idx >= 0 && H.rec_out != nullptr) ? H.rec_out + (size_t)Q.rec_idx * B * n : nullptr;
+    float lsum = 0.f;
+#pragma unroll
+    for (int i = 0; i < kLwUTW; ++i) {
+        if (i >= nt) continue;
+        const int u0 = 16 * (utw + i) + 4 * q;
+        const f32x4 bias = ld4(H.bias + u0);
+#pragma unroll
+        for (int ct = 0; ct < kLwCTT; ++ct) {
+            const int chain = chain0 + 16 * ct + c;
+            const bool live = chain < B;
+            const size_t row = (size_t)chain * npad + u0;
+            const f32x4 o = acc[i][ct] + bias;
+            f32x4 e = splat(0.f);
+            if (kind != MCPC_LOSS_NONE) {
+                const f32x4 y = ld4(H.y + row);
+                const float ov[4] = {o.x, o.y, o.z, o.w}, yv[4] = {y.x, y.y, y.z, y.w};
+                float ev[4];
+                if (kind == MCPC_LOSS_GAUSSIAN) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const bool on = live && (u0 + r) >= mask_start && (u0 + r) < n;
+                        const float dlt = ov[r] - yv[r];
+                        ev[r] = on ? inv_var * dlt : 0.f;
+                        lsum += on ? 0.5f * inv_var * dlt * dlt : 0.f;
+                    }
+                } else if (do_energy) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const bool on = live && (u0 + r) >= mask_start && (u0 + r) < n;
+                        float sg, bc;
+                        sigmoid_bce_f(ov[r], yv[r], sg, bc);
+                        ev[r] = on ? sg - yv[r] : 0.f;
+                        lsum += on ? bc : 0.f;
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const bool on = live && (u0 + r) >= mask_start && (u0 + r) < n;
+                        ev[r] = on ? sigmoid_f(ov[r]) - yv[r] : 0.f;
+                    }
+                }
+                e.x = ev[0]; e.y = ev[1]; e.z = ev[2]; e.w = ev[3];
+            }
+            st4(Q.err_o + row, e);
+            if (slot >= 0) { st4s(H.spill_e + spill_offset(H.spill_tm, (size_t)slot * Bpad + chain, u0, npad), e); omx = absmax4(omx, e); }
+            if (rec != nullptr && live) st_unpadded(rec, chain, n, u0, o);
+        }
+    }
+    return lsum;
+}
+
+__global__ __launch_bounds__(kLwThreads) void mcpc_lw_fwd_kernel(const LwParams Q) {
+    __shared__ __attribute__((aligned(16))) float stage[kLwStageFloats];
+    __shared__ int sexp[kLwChains];
+    __shared__ float sred[kLwWaves];
+    __shared__ unsigned smax[2];
+    const KParams& P = Q.P;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const LwJob job = lw_load_job(Q.jobs, blockIdx.y);
+    const int j = job.layer, L = P.L;
+    const bool head = j == L;
+    const int chain0 = blockIdx.x * kLwChains;
+    const int utw = job.ut0 + kLwUTW * wave;
+    const int ntiles = head ? P.head.ntiles : P.layer[j].ntiles;
+    int nt = ntiles - utw;
+    nt = nt < 0 ? 0 : (nt > kLwUTW ? kLwUTW : nt);
+    if (tid < 2) smax[tid] = 0u;
+    // the GEMM: Linear j over f(x_{j-1}) (none for j == 0)
+    f32x4 acc[kLwUTW][kLwCTT];
+    const int kw = j > 0 ? P.layer[j - 1].npad : 0, nkb = (kw + kKB - 1) / kKB;
+    const void* const A = j == 0 ? nullptr : (head ? (const void*)P.head.Wf : (const void*)P.layer[j].Wf);
+    lw_job_gemm(acc, A, nkb * kFragBlock, utw, ntiles, nkb, kw, j > 0 ? Q.fx[j - 1] : nullptr, chain0, j > 0 ? load_wexp(P.wexp, j) : 0,
+                stage, sexp, tid, lane);
+    float esum = 0.f, mx0 = 0.f, mx1 = 0.f;
+    if (head) {
+        esum = lw_fwd_head(Q, utw, nt, chain0, lane, acc, mx1);
+    } else {
+        const int act = P.layer[j].act;
+        if (act == MCPC_ACT_RELU) esum = lw_fwd_latent<MCPC_ACT_RELU>(Q, j, utw, nt, chain0, lane, acc, mx0, mx1);
+        else if (act == MCPC_ACT_TANH) esum = lw_fwd_latent<MCPC_ACT_TANH>(Q, j, utw, nt, chain0, lane, acc, mx0, mx1);
+        else esum = lw_fwd_latent<MCPC_ACT_IDENTITY>(Q, j, utw, nt, chain0, lane, acc, mx0, mx1);
+    }
+    const bool spills = Q.slot >= 0 && P.spillmax != nullptr;
+    if (Q.do_energy) { esum = wave_sum(esum); if (lane == 0) sred[wave] = esum; }
+    __syncthreads();                  // (smax is zero for every wave from here on; sred is complete behind the next barrier)
+    if (spills) {
+        mx0 = wave_max(mx0); mx1 = wave_max(mx1);
+        if (lane == 0) { atomicMax(&smax[0], __float_as_uint(mx0)); atomicMax(&smax[1], __float_as_uint(mx1)); }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        if (Q.do_energy) {
+            // one slot per workgroup of this launch: its own Linear's column, zeros in the others (mcpc_energy_reduce_kernel sums the slots)
+            double v = 0.0;
+#pragma unroll
+            for (int w = 0; w < kLwWaves; ++w) v += (double)sred[w];
+            const size_t wg = (size_t)blockIdx.y * gridDim.x + blockIdx.x, nwg = (size_t)gridDim.x * gridDim.y;
+            double* const o = P.epart + ((size_t)Q.erow * nwg + wg) * (kMaxLatent + 1);
+            const int col = head ? kMaxLatent : j;
+#pragma unroll
+            for (int k = 0; k <= kMaxLatent; ++k) o[k] = k == col ? v : 0.0;
+        }
+        if (spills) {
+            // order-free: integer maxima of bit patterns (non-negative floats order like them)
+            if (head) { if (smax[1]) atomicMax(P.spillmax + kSpillIdEo, smax[1]); }
+            else {
+                if (smax[0]) atomicMax(P.spillmax + spill_id_a(j), smax[0]);
+                if (j > 0 && smax[1]) atomicMax(P.spillmax + spill_id_e(j), smax[1]);
+            }
+        }
+    }
+}
+
+// ---- backward epilogue: the x update of bwd_epilogue<MODE 0> on global rows, f(x_new) for the next forward launch -----------------------------
+template <int ACT>
+__device__ __forceinline__ void lw_bwd_update(const LwParams& Q, int l, float sign, int utw, int nt, int chain0, int lane,
+                                              const f32x4 (&acc)[kLwUTW][kLwCTT]) {
+    const KParams& P = Q.P;
+    const KLayer& Ly = P.layer[l];
+    const int c = lane & 15, q = lane >> 4;
+    const int npad = Ly.npad, n = Ly.n, B = P.B;
+    const float lr = P.lr, nscale = P.noise_scale, ecoef = Ly.ecoef;
+    const uint64_t seed = P.seed, step = P.step_base + (uint64_t)Q.t, chain_base = P.chain_base;
+    const float* const eg = Q.err[l];
+#pragma unroll
+    for (int i = 0; i < kLwUTW; ++i) {
+        if (i >= nt) continue;
+        const int u0 = 16 * (utw + i) + 4 * q;
+#pragma unroll
+        for (int ct = 0; ct < kLwCTT; ++ct) {
+            const int chain = chain0 + 16 * ct + c;
+            const bool live = chain < B;
+            const size_t row = (size_t)chain * npad + u0;
+            const f32x4 x = ld4(Ly.x + row), back = acc[i][ct];
+            const f32x4 e = l > 0 ? ld4(eg + row) : (x - ld4(P.mu1 + row)) * ecoef;
+            f32x4 g;
+            g.x = e.x + sign * actd<ACT>(x.x, actf<ACT>(x.x)) * back.x;
+            g.y = e.y + sign * actd<ACT>(x.y, actf<ACT>(x.y)) * back.y;
+            g.z = e.z + sign * actd<ACT>(x.z, actf<ACT>(x.z)) * back.z;
+            g.w = e.w + sign * actd<ACT>(x.w, actf<ACT>(x.w)) * back.w;
+            if (!P.update_x) {          // gradients only: x and f(x) stay
+                if (live && Ly.xgrad != nullptr) st_unpadded(Ly.xgrad, chain, n, u0, g);
+                continue;
+            }
+            f32x4 xn;
+            if (P.xopt == MCPC_XOPT_SGD) {
+                xn = x - g * lr;
+            } else {
+                // torch.optim.Adam single-tensor path (adam_x, mcpc_device.h); the moments are tile-major (tile_major_offset)
+                const size_t mrow = tile_major_offset(chain, u0, npad);
+                f32x4 m = ld4s(Ly.m + mrow), v = ld4s(Ly.v + mrow);
+                m.x = adam_m(m.x, g.x, P.omb1); m.y = adam_m(m.y, g.y, P.omb1); m.z = adam_m(m.z, g.z, P.omb1); m.w = adam_m(m.w, g.w, P.omb1);
+                v.x = adam_v(v.x, g.x, P.beta2, P.omb2); v.y = adam_v(v.y, g.y, P.beta2, P.omb2); v.z = adam_v(v.z, g.z, P.beta2, P.omb2); v.w = adam_v(v.w, g.w, P.beta2, P.omb2);
+                st4s(Ly.m + mrow, m);
+                st4s(Ly.v + mrow, v);
+                const float nss = P.adam_coef[0], bc2s = P.adam_coef[1], eps = P.eps;      // (the host passes this step's pair)
+                xn.x = adam_x(x.x, m.x, v.x, nss, bc2s, eps);
+                xn.y = adam_x(x.y, m.y, v.y, nss, bc2s, eps);
+                xn.z = adam_x(x.z, m.z, v.z, nss, bc2s, eps);
+                xn.w = adam_x(x.w, m.w, v.w, nss, bc2s, eps);
+            }
+            if (P.noise_mode == MCPC_NOISE_PHILOX) {
+                xn = xn + normals4(seed, step, (uint32_t)l, (uint32_t)(chain_base + (uint64_t)chain), (uint32_t)(u0 >> 2)) * nscale;
+            } else if (P.noise_mode == MCPC_NOISE_EXTERNAL && live) {
+                xn = xn + ld_unpadded(Ly.ext_noise, chain, n, u0) * nscale;                // (the host passes this step's image)
+            }
+            // padded units stay exactly zero (their gradient is zero; only the noise must be masked)
+            if (u0 + 0 >= n) xn.x = 0.f;
+            if (u0 + 1 >= n) xn.y = 0.f;
+            if (u0 + 2 >= n) xn.z = 0.f;
+            if (u0 + 3 >= n) xn.w = 0.f;
+            st4(Ly.x + row, xn);
+            f32x4 fx;
+            fx.x = actf<ACT>(xn.x); fx.y = actf<ACT>(xn.y); fx.z = actf<ACT>(xn.z); fx.w = actf<ACT>(xn.w);
+            st4(Q.fx[l] + row, fx);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kLwThreads) void mcpc_lw_bwd_kernel(const LwParams Q) {
+    __shared__ __attribute__((aligned(16))) float stage[kLwStageFloats];
+    __shared__ int sexp[kLwChains];
+    const KParams& P = Q.P;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const LwJob job = lw_load_job(Q.jobs, blockIdx.y);
+    const int l = job.layer, L = P.L;
+    const int chain0 = blockIdx.x * kLwChains;
+    const int utw = job.ut0 + kLwUTW * wave;
+    const int ntiles = P.layer[l].ntiles;
+    int nt = ntiles - utw;
+    nt = nt < 0 ? 0 : (nt > kLwUTW ? kLwUTW : nt);
+    // the back-projection: e_{l+1} W_{l+1} (the read-out's error for the last latent layer; none without a read-out)
+    const bool last = l == L - 1;
+    const bool has_gemm = !last || P.has_head;
+    const int kw = !has_gemm ? 0 : (last ? P.head.npad : P.layer[l + 1].npad), nkb = (kw + kKB - 1) / kKB;
+    const void* const A = !has_gemm ? nullptr : (last ? (const void*)P.head.Wb : (const void*)P.layer[l + 1].Wb);
+    const float* const Bg = !has_gemm ? nullptr : (last ? Q.err_o : Q.err[l + 1]);
+    const float sign = !has_gemm ? 0.0f : (last ? 1.0f : -1.0f);
+    f32x4 acc[kLwUTW][kLwCTT];
+    lw_job_gemm(acc, A, nkb * kFragBlock, utw, ntiles, nkb, kw, Bg, chain0, has_gemm ? load_wexp(P.wexp, l + 1) : 0, stage, sexp, tid, lane);
+    const int act = P.layer[l].act;
+    if (act == MCPC_ACT_RELU) lw_bwd_update<MCPC_ACT_RELU>(Q, l, sign, utw, nt, chain0, lane, acc);
+    else if (act == MCPC_ACT_TANH) lw_bwd_update<MCPC_ACT_TANH>(Q, l, sign, utw, nt, chain0, lane, acc);
+    else lw_bwd_update<MCPC_ACT_IDENTITY>(Q, l, sign, utw, nt, chain0, lane, acc);
+}
+
+// f(x_l) of the state a run starts from (mcpc_load_state may have replaced it since the last run): one launch per layer and run; from
+// there on the backward launches keep it current
+__global__ void mcpc_lw_act_kernel(const float* __restrict__ x, float* __restrict__ fx, size_t total4, int act) {
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total4; idx += (size_t)gridDim.x * blockDim.x) {
+        const f32x4 v = ld4(x + 4 * idx);
+        f32x4 f;
+        f.x = act_f(act, v.x); f.y = act_f(act, v.y); f.z = act_f(act, v.z); f.w = act_f(act, v.w);
+        st4(fx + 4 * idx, f);
+    }
+}
+
+}  // namespace mcpc

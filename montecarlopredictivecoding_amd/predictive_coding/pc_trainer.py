@@ -60,6 +60,10 @@ _PHILOX_STEPS = [0]
 # cache is a small LRU: every distinct (shape, batch) -- e.g. the ragged last batch of a data loader -- owns device
 # memory, evicted engines are closed.
 _ENGINES = collections.OrderedDict()
+_MCPC_ENOMEM = -3          # include/mcpc.h: the configuration does not fit the device (LDS / HBM)
+# what the layer-wise kernels cost where both forms run (scripts/wide_nets.py)
+_WIDE_COST = ("Where both forms run, a step on them takes about 1.4 to 2.4 times as long as on the LDS-resident kernels "
+              "(cfg-M's net at 6000 chains: 1.4-1.6; 20-128-128 -> 784 at 256 chains: 2.2-2.4, measured on an MI355X).")
 _ENGINE_CACHE_SIZE = 8
 
 
@@ -566,7 +570,17 @@ class PCTrainer(object):
         key = (net.key(B, device), os.environ.get("MCPC_TUNING"))
         eng = _ENGINES.get(key)
         if eng is None:
-            eng = Engine(net.sizes, net.acts, net.n_in, net.n_out, B, device=device, ecoef=net.ecoef)
+            try:
+                eng = Engine(net.sizes, net.acts, net.n_in, net.n_out, B, device=device, ecoef=net.ecoef)
+                eng._wide_reason = None
+            except L.MCPCError as exc:
+                if exc.code != _MCPC_ENOMEM:
+                    raise
+                # no LDS plan holds this network: the layer-wise kernels (state of all chains in global memory, two launches per step)
+                # serve it -- whatever MCPC_TUNING pins keeps governing the LDS kernels wherever those serve
+                tuning = ",".join(s for s in (os.environ.get("MCPC_TUNING"), "wide=1") if s)
+                eng = Engine(net.sizes, net.acts, net.n_in, net.n_out, B, device=device, ecoef=net.ecoef, tuning=tuning)
+                eng._wide_reason = str(exc)
             eng._bound_sig = None
             _ENGINES[key] = eng
             while len(_ENGINES) > _ENGINE_CACHE_SIZE:
@@ -574,6 +588,12 @@ class PCTrainer(object):
                 old.close()
         else:
             _ENGINES.move_to_end(key)
+        if getattr(eng, "_wide_reason", None) and not getattr(self, "_wide_announced", False):
+            self._wide_announced = True         # leaving the fast path is loud, once per trainer
+            warnings.warn(
+                "In PCTrainer.train_on_batch, the network does not fit the LDS-resident step kernels ({}): the call runs on the "
+                "layer-wise kernels (mcpc_lw_fwd_kernel + mcpc_lw_bwd_kernel: state, activations and errors of all chains in "
+                "global memory, two launches per step).  {}".format(eng._wide_reason, _WIDE_COST), category=RuntimeWarning)
         return eng
 
     def _announce_staging(self, plan):
