@@ -222,6 +222,28 @@ int mcpc_comm_destroy(mcpc_engine* e);
 int mcpc_philox_normals(int device, uint64_t seed, uint64_t step, int layer, uint64_t chain_base,
                         int batch, int n_units, float* out, int raw, void* stream);
 
+/* Streaming first and second moments of recorded steps: what a Langevin call is consumed as (the reference reduces the recorded steps in
+ * torch: get_representations(rep_type="expectation"), utils/model.py:150-156; the histograms and means of figure_2.py / figure_3.py).
+ * A host reduces the record ring of a sliced call on the device, between the slices of mcpc_run, instead of keeping the trajectory.
+ */
+#define MCPC_MOM_IDENTITY 0
+#define MCPC_MOM_SIGMOID  1   /* g = the read-out's own sigmoid_f (csrc/mcpc_device.h): the Bernoulli mean the step kernels use */
+
+/* For i < row_elems, with r_k = rec + (int64)(first + k*stride) * row_elems, k = 0..n-1 in ascending order:
+ *   sum[i]   = (accumulate ? sum[i]   : 0) + g(r_0[i]) + g(r_1[i]) + ...        (fp64, added in exactly this order)
+ *   sumsq[i] = (accumulate ? sumsq[i] : 0) + g(r_0[i])^2 + ...                   (sumsq may be NULL)
+ * rec is a record buffer as mcpc_run writes it ([records][batch][width] fp32, row_elems = batch*width).  Stateless,
+ * asynchronous on `stream`, no engine needed (like mcpc_philox_normals).
+ * One thread owns an output element and walks the records with fp64 accumulators in registers: no atomics, no split of the record
+ * axis, so the result depends neither on the launch shape nor on how the caller chunks the records (0..36 in one call, or 1 + 5 + 31
+ * with accumulate = 1, give the same bits), and with MCPC_MOM_IDENTITY both sums are bitwise a sequential fp64 loop on the host (the
+ * square of an fp32 value is exact in fp64).  n = 0 zeroes the accumulators when accumulate = 0 and does nothing otherwise.
+ * MCPC_EINVAL: sum NULL, rec NULL with n > 0, row_elems < 1, stride < 1, first < 0, n < 0, unknown transform.  All offsets are 64-bit.
+ * 16-B loads per lane when row_elems % 4 == 0 and rec, sum, sumsq are 16-B aligned; a scalar form otherwise.  The accumulators are
+ * read and written once per call (16 B per element, 32 with sumsq): long chunks amortise them. */
+int mcpc_moments_accumulate(int device, const float* rec, int64_t row_elems, int32_t first, int32_t stride, int32_t n,
+                            int32_t transform, double* sum, double* sumsq, int accumulate, void* stream);
+
 /* Synchronise `stream` and report device-side faults of the runs issued so far (the wave-specialised step kernel
  * bounds every intra-workgroup wait; a wait that runs out is recorded instead of hanging the GPU).
  * Returns MCPC_ESTATE if the last results must not be used.  The only host-synchronising call besides create/destroy. */

@@ -17,6 +17,7 @@ LOSS_NONE, LOSS_GAUSSIAN, LOSS_BERNOULLI = 0, 1, 2
 XOPT_SGD, XOPT_ADAM = 0, 1
 NOISE_NONE, NOISE_PHILOX, NOISE_EXTERNAL = 0, 1, 2
 ENERGY_NONE, ENERGY_LAST, ENERGY_ALL = 0, 1, 2
+MOM_IDENTITY, MOM_SIGMOID = 0, 1
 
 # MCPC_LIB: developer override to load a diagnostic build (e.g. libmcpc_stamps.so) or a `make variant` A/B library; a library that
 # reports exp=1 (built with a timing-experiment switch: wrong results on purpose) is refused unless MCPC_ALLOW_EXP=1
@@ -95,6 +96,8 @@ SYMBOLS = {
     "mcpc_comm_destroy": (C.c_int, [C.c_void_p]),
     "mcpc_philox_normals": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_int,
                                       C.c_void_p, C.c_int, C.c_void_p]),
+    "mcpc_moments_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "mcpc_query": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                              C.POINTER(C.c_int32)]),
     "mcpc_step_kernel_name": (C.c_char_p, [C.c_void_p]),

@@ -15,6 +15,7 @@
 
 #include "mcpc_build.h"
 #include "mcpc_kernels.h"
+#include "mcpc_moments.h"
 
 using namespace mcpc;
 
@@ -2118,6 +2119,29 @@ int mcpc_philox_normals(int device, uint64_t seed, uint64_t step, int layer, uin
     const size_t total = (size_t)batch * ((n_units + 3) / 4);
     hipLaunchKernelGGL(mcpc_philox_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream_, seed, step, layer, chain_base,
                        batch, n_units, out, raw);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+int mcpc_moments_accumulate(int device, const float* rec, int64_t row_elems, int32_t first, int32_t stride, int32_t n, int32_t transform,
+                            double* sum, double* sumsq, int accumulate, void* stream_) {
+    if (!sum) return fail(MCPC_EINVAL, "moments: sum is null");
+    if (row_elems < 1) return fail(MCPC_EINVAL, "moments: row_elems=%lld, must be at least 1", (long long)row_elems);
+    if (stride < 1) return fail(MCPC_EINVAL, "moments: stride=%d, must be at least 1", stride);
+    if (first < 0) return fail(MCPC_EINVAL, "moments: first=%d, must not be negative", first);
+    if (n < 0) return fail(MCPC_EINVAL, "moments: n=%d, must not be negative", n);
+    if (transform != MCPC_MOM_IDENTITY && transform != MCPC_MOM_SIGMOID) return fail(MCPC_EINVAL, "moments: unknown transform %d", transform);
+    if (n > 0 && !rec) return fail(MCPC_EINVAL, "moments: rec is null with n=%d", n);
+    if (n == 0 && accumulate) return MCPC_OK;                     // nothing to add
+    HIP_TRY(hipSetDevice(device));
+    // all offsets in 64 bits: (first + k * stride) * row_elems passes 2^31 elements at the shapes the step kernels are built for
+    const float* r0 = n > 0 ? rec + (int64_t)first * row_elems : rec;
+    const int64_t row_step = (int64_t)stride * row_elems;
+    const uintptr_t align = (uintptr_t)r0 | (uintptr_t)sum | (uintptr_t)sumsq;
+    if (row_elems % 4 == 0 && align % 16 == 0)
+        mom_dispatch<4>(transform, r0, row_elems, row_step, n, sum, sumsq, accumulate, (hipStream_t)stream_);
+    else
+        mom_dispatch<1>(transform, r0, row_elems, row_step, n, sum, sumsq, accumulate, (hipStream_t)stream_);
     HIP_TRY(hipGetLastError());
     return MCPC_OK;
 }

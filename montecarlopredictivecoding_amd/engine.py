@@ -306,3 +306,41 @@ def philox_normals(seed, step, layer, chain_base, batch, n_units, device, raw=Fa
     L.check(lib.mcpc_philox_normals(device.index or 0, seed, step, layer, chain_base, batch, n_units,
                                     _ptr(out), 1 if raw else 0, stream))
     return out.view(torch.int32) if raw else out
+
+
+_MOM_TRANSFORMS = {None: L.MOM_IDENTITY, "identity": L.MOM_IDENTITY, "sigmoid": L.MOM_SIGMOID,
+                   L.MOM_IDENTITY: L.MOM_IDENTITY, L.MOM_SIGMOID: L.MOM_SIGMOID}
+
+
+def moments_accumulate(rec, first, stride, n, sum, sumsq=None, transform="identity", accumulate=True):
+    """Add records ``rec[first + k * stride]``, k < n, and their squares to the fp64 accumulators ``sum`` / ``sumsq`` on the device
+    (include/mcpc.h: mcpc_moments_accumulate), in ascending order of k, one thread per element: the sums are bitwise those of a
+    sequential fp64 loop, however the records are chunked over calls.  ``rec``: contiguous fp32 ``[records, ...]`` as an engine run
+    records it; ``sum`` / ``sumsq``: contiguous fp64 of ``rec[0].numel()`` elements (``sumsq`` may be None).  ``transform``:
+    "identity", or "sigmoid" for the read-out's Bernoulli mean.  ``accumulate=False`` overwrites.  On the current torch stream."""
+    lib = L.load()
+    if transform not in _MOM_TRANSFORMS:
+        raise ValueError(f"transform: expected 'identity' or 'sigmoid', got {transform!r}")
+    if not isinstance(rec, torch.Tensor) or rec.dim() < 1:
+        raise TypeError("rec: expected a torch.Tensor [records, ...]")
+    device = rec.device
+    if device.type != "cuda":
+        raise ValueError(f"rec: expected a tensor on a HIP device, got {device}")
+    _check_tensor(rec, rec.shape, device, "rec")
+    row = 1
+    for d in rec.shape[1:]:
+        row *= int(d)
+    first, stride, n = int(first), int(stride), int(n)
+    if n > 0 and first >= 0 and stride >= 1 and first + (n - 1) * stride >= rec.shape[0]:
+        raise ValueError(f"rec holds {rec.shape[0]} records, the last one asked for is {first + (n - 1) * stride}")
+    for t, name in ((sum, "sum"), (sumsq, "sumsq")):
+        if t is None and name == "sumsq":
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a torch.Tensor, got {type(t)}")
+        if t.numel() != row:
+            raise ValueError(f"{name}: expected {row} elements (one per element of a record), got {t.numel()}")
+        _check_tensor(t, t.shape, device, name, torch.float64)
+    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    L.check(lib.mcpc_moments_accumulate(device.index or 0, _ptr(rec), row, first, stride, n, _MOM_TRANSFORMS[transform],
+                                        _ptr(sum), _ptr(sumsq), 1 if accumulate else 0, stream))

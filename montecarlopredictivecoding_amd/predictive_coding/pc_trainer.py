@@ -223,6 +223,15 @@ class PCTrainer(object):
         # 10 000 steps x all latents to the host, pc_trainer.py:440-445,772-774)
         self.mcpc_record_chunk_bytes = 1 << 30
         self.last_record_slices = 0
+        # posterior moments of a fused call, accumulated on the device (moments.py): None = off, or
+        # dict(begin=0, stride=1, layers=(), outputs=None | "identity" | "sigmoid", variance=True); the call then leaves a
+        # moments.Moments in mcpc_last_moments.  The records are reduced out of a two-buffer device ring whose halves hold at most
+        # mcpc_moments_chunk_bytes each, on the call's own stream (mcpc_moments_side_stream = True reduces one
+        # half on a side stream while the next slice fills the other).
+        self.mcpc_moments = None
+        self.mcpc_last_moments = None
+        self.mcpc_moments_chunk_bytes = 1 << 30
+        self.mcpc_moments_side_stream = False
 
     # ---- getters & setters (reference :268-461) -------------------------------------------------------
     def get_T(self) -> int:
@@ -438,6 +447,12 @@ class PCTrainer(object):
         plan, why_not_fused = self._plan(inputs, loss_fn, loss_fn_kwargs, is_unwrap_inputs, is_optimize_inputs,
                                          callback_after_backward, callback_after_t, callback_after_t_kwargs,
                                          backward_kwargs, is_clear_energy_after_use, is_return_batchelement_loss)
+        if self.mcpc_moments is not None:
+            from .. import moments as _moments
+            if plan is None:
+                raise NotImplementedError("mcpc_moments is set, and this call runs on the generic torch loop ({}): posterior moments are "
+                                          "accumulated by the fused HIP loop only".format(why_not_fused))
+            plan["moments"] = _moments.validate_spec(self.mcpc_moments, self._T, len(plan["net"].sizes), plan["net"].n_out)
         if plan is None:
             # outside what the kernels express: the package's generic torch loop (generic_loop.py), loudly, on the device the model
             # lives on ("must work, need not be fast").  It is no way around a missing GPU: without a visible HIP device
@@ -472,6 +487,9 @@ class PCTrainer(object):
             # call is replayed step-wise with the trainer's own persistent torch optimizer
             plan["mode"] = "stepwise"
             plan["why_stepwise"] = "Adam state of optimizer_x carried over from the previous call"
+        if plan["mode"] != "fused" and self.mcpc_moments is not None:
+            raise NotImplementedError("mcpc_moments is set, and this call runs step by step ({}): posterior moments are accumulated by "
+                                      "the fused HIP loop only".format(plan["why_stepwise"]))
         if plan["mode"] == "fused":
             self.last_call_mode = "fused"
             with _few_cpu_threads(plan["staged"]):
@@ -802,9 +820,15 @@ class PCTrainer(object):
             energy_mode=L.ENERGY_ALL if is_return_results_every_t else L.ENERGY_LAST)
         host_step_bytes = 4 * plan["B"] * sum(n for n, on in zip(net.sizes, rec_layers) if on)
         self.last_record_slices = 0
-        if any(rec_layers) and n_rec == T and T * host_step_bytes > self.mcpc_record_chunk_bytes:
-            res = self._run_fused_sliced(eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes,
-                                         is_return_outputs and net.n_out > 0)
+        mom = plan.get("moments")
+        if mom is not None:
+            # posterior moments: the call runs as slices whatever its size, and the records moments ask for are reduced on the device
+            res, self.mcpc_last_moments = self._run_fused_sliced(
+                eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, is_return_outputs and net.n_out > 0,
+                every_t=is_return_results_every_t, mom=mom)
+        elif any(rec_layers) and n_rec == T and T * host_step_bytes > self.mcpc_record_chunk_bytes:
+            res, _ = self._run_fused_sliced(eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes,
+                                            is_return_outputs and net.n_out > 0)
         else:
             res = eng.run(T, acc_reset=acc_reset, rec_begin=rec_begin, rec_stride=1, rec_count=n_rec if any_rec else 0,
                           rec_x=rec_layers, rec_out=is_return_outputs and net.n_out > 0, **run_kw)
@@ -829,46 +853,121 @@ class PCTrainer(object):
         return self._collect_results(plan, res, T, is_return_results_every_t, is_return_outputs,
                                      is_return_representations, is_return_xs, loss_fn)
 
-    def _run_fused_sliced(self, eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, rec_out):
-        """A call whose every-step trajectory would not fit the record budget on the device: the same T steps as slices of
-        one `mcpc_run` each (slicing does not change a bit of the trajectories, tests/test_gpu_fullsize.py), the latent
-        records of a slice go to one half of a two-buffer device ring and are copied to pinned host memory on a side stream
-        while the next slice computes.  Outputs stay on the device, as in the reference (live tensors, pc_trainer.py:733,770)."""
-        from ..engine import RunResult
+    def _run_fused_sliced(self, eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, rec_out, every_t=True, mom=None):
+        """A call whose every-step trajectory would not fit the record budget on the device, or whose records feed `mcpc_moments`:
+        the same T steps as slices of one `mcpc_run` each (slicing does not change a bit of the trajectories,
+        tests/test_gpu_fullsize.py).  The latent records of a slice go to one half of a two-buffer device ring.  Records the caller's
+        keywords ask for (`rec_layers`, `rec_out`) are copied to pinned host memory on a side stream while the next slice computes;
+        outputs stay on the device, as in the reference (live tensors, pc_trainer.py:733,770).  Records `mom` (a validated
+        `mcpc_moments`) asks for are reduced on the device by `moments_accumulate` after each slice, out of the same ring rows, and
+        are neither copied nor kept unless the caller asked too.  With `every_t` false the caller gets the last step's records and
+        energies only, as from an unsliced call.  Returns (RunResult, Moments or None)."""
+        from ..engine import RunResult, moments_accumulate
         dev, B = plan["device"], plan["B"]
-        S = max(1, min(T, self.mcpc_record_chunk_bytes // max(2 * host_step_bytes, 1)))
-        host = [torch.empty(T, B, n, dtype=torch.float32, pin_memory=True) if on else None for n, on in zip(net.sizes, rec_layers)]
-        ring = [[torch.empty(S, B, n, dtype=torch.float32, device=dev) if on else None for n, on in zip(net.sizes, rec_layers)]
-                for _ in range(2)]
-        out_full = torch.empty(T, B, net.n_out, dtype=torch.float32, device=dev) if rec_out else None
-        energies = torch.zeros(T, L.ENERGY_COLS, dtype=torch.float64, device=dev)
-        main, side = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
-        drained = [None, None]                              # event: the copy out of this half of the ring has finished
-        acc_b = run_kw["acc_begin"]
-        run_kw = dict(run_kw, energy_mode=L.ENERGY_ALL)
-        n_slices = 0
-        for t0 in range(0, T, S):
+        nl = len(net.sizes)
+        mom_layers = [mom is not None and l in mom.layers for l in range(nl)]
+        mom_out = mom is not None and mom.outputs is not None
+        ring_layers = [a or b_ for a, b_ in zip(rec_layers, mom_layers)]
+        out_direct = rec_out and every_t                     # every step's outputs are kept anyway: slices write them in place
+        ring_out = (rec_out or mom_out) and not out_direct
+        S = T
+        if any(rec_layers) and every_t:
+            S = min(S, self.mcpc_record_chunk_bytes // max(2 * host_step_bytes, 1))
+        if mom is not None:
+            # one half of the ring is a chunk of at most mcpc_moments_chunk_bytes
+            step_bytes = 4 * B * (sum(n for n, on in zip(net.sizes, ring_layers) if on) + (net.n_out if ring_out or mom_out else 0))
+            S = min(S, self.mcpc_moments_chunk_bytes // max(step_bytes, 1))
+        S = max(1, S)
+        # A slice boundary inside the window that accumulates parameter gradients would regroup their fp32 sums (one Hebbian flush and
+        # one fold of Linear 0's sum per run; tests/test_gpu_widening.py).  A call with moments must leave param.grad bitwise as
+        # without them, so it keeps that window in ONE slice: the ring is then as long as the window, whatever the chunk budget says.
+        keep = (run_kw["acc_begin"], run_kw["acc_end"]) if mom is not None and run_kw["acc_end"] > run_kw["acc_begin"] else None
+        bounds, t0 = [], 0
+        while t0 < T:
             n = min(S, T - t0)
+            if keep is not None and keep[0] < t0 + n < keep[1]:              # it would end inside the window
+                n = keep[0] - t0 if t0 < keep[0] else keep[1] - t0
+            bounds.append((t0, n))
+            t0 += n
+        S = max(n for _, n in bounds)
+        rows = T if every_t else 1
+        host = [torch.empty(rows, B, n, dtype=torch.float32, pin_memory=True) if on else None for n, on in zip(net.sizes, rec_layers)]
+        ring = [[torch.empty(S, B, n, dtype=torch.float32, device=dev) if on else None for n, on in zip(net.sizes, ring_layers)]
+                for _ in range(2)]
+        ring_o = [torch.empty(S, B, net.n_out, dtype=torch.float32, device=dev) if ring_out else None for _ in range(2)]
+        out_full = torch.empty(rows, B, net.n_out, dtype=torch.float32, device=dev) if rec_out else None
+        energies = torch.zeros(rows, L.ENERGY_COLS, dtype=torch.float64, device=dev)
+        acc = None
+        if mom is not None:
+            def zeros(n):
+                return torch.zeros(B, n, dtype=torch.float64, device=dev)
+            acc = dict(x_sum=[zeros(n) if on else None for n, on in zip(net.sizes, mom_layers)],
+                       x_sumsq=[zeros(n) if on and mom.variance else None for n, on in zip(net.sizes, mom_layers)],
+                       out_sum=zeros(net.n_out) if mom_out else None,
+                       out_sumsq=zeros(net.n_out) if mom_out and mom.variance else None)
+        main, side = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+        drained = [None, None]                              # event: the side stream has finished with this half of the ring
+        acc_b = run_kw["acc_begin"]
+        run_kw = dict(run_kw, energy_mode=L.ENERGY_ALL if every_t else L.ENERGY_LAST)
+        reduce_on_side = mom is not None and self.mcpc_moments_side_stream
+
+        def reduce(t0, n, half):
+            first, cnt = mom.chunk(t0, n)
+            if cnt == 0:
+                return
+            for l in range(nl):
+                if mom_layers[l]:
+                    moments_accumulate(ring[half][l], first, mom.stride, cnt, acc["x_sum"][l], acc["x_sumsq"][l], accumulate=True)
+            if mom_out:
+                src = out_full[t0:t0 + n] if out_direct else ring_o[half]
+                moments_accumulate(src, first, mom.stride, cnt, acc["out_sum"], acc["out_sumsq"], transform=mom.outputs,
+                                   accumulate=True)
+
+        n_slices = 0
+        for t0, n in bounds:
             half = n_slices & 1
+            last = t0 + n == T
             if drained[half] is not None:
                 main.wait_event(drained[half])
             eng.run(T, t_begin=t0, n_steps=n, adam_step0=t0, energies_out=energies,
                     acc_reset=acc_reset and (t0 <= acc_b < t0 + n),
-                    rec_begin=t0, rec_stride=1, rec_count=n, rec_x=rec_layers, rec_x_bufs=ring[half],
-                    rec_out=rec_out, rec_out_buf=None if out_full is None else out_full[t0:t0 + n], **run_kw)
-            filled = torch.cuda.Event()
-            filled.record(main)
-            side.wait_event(filled)
-            with torch.cuda.stream(side):
-                for h, d in zip(host, ring[half]):
-                    if h is not None:
-                        h[t0:t0 + n].copy_(d[:n], non_blocking=True)
-                drained[half] = torch.cuda.Event()
-                drained[half].record(side)
+                    rec_begin=t0, rec_stride=1, rec_count=n, rec_x=ring_layers, rec_x_bufs=ring[half],
+                    rec_out=out_direct or ring_out,
+                    rec_out_buf=out_full[t0:t0 + n] if out_direct else ring_o[half], **run_kw)
+            if mom is not None and not reduce_on_side:
+                reduce(t0, n, half)
+            if ring_out and rec_out and last:
+                out_full[0].copy_(ring_o[half][n - 1])       # (not every_t: the last step's outputs)
+            to_host = any(rec_layers) and (every_t or last)
+            if to_host or reduce_on_side:
+                filled = torch.cuda.Event()
+                filled.record(main)
+                side.wait_event(filled)
+                with torch.cuda.stream(side):
+                    if reduce_on_side:
+                        reduce(t0, n, half)
+                    if to_host:
+                        for h, d in zip(host, ring[half]):
+                            if h is not None:
+                                if every_t:
+                                    h[t0:t0 + n].copy_(d[:n], non_blocking=True)
+                                else:
+                                    h[0].copy_(d[n - 1], non_blocking=True)
+                    drained[half] = torch.cuda.Event()
+                    drained[half].record(side)
             n_slices += 1
         side.synchronize()
         self.last_record_slices = n_slices
-        return RunResult(energies=energies, rec_x=host, rec_out=out_full)
+        result = None
+        if mom is not None:
+            from ..moments import Moments
+            md = plan["model_device"]
+
+            def back(t):
+                return None if t is None else t.to(md)
+            result = Moments(n=mom.n, x_sum=[back(t) for t in acc["x_sum"]], x_sumsq=[back(t) for t in acc["x_sumsq"]],
+                             out_sum=back(acc["out_sum"]), out_sumsq=back(acc["out_sumsq"]))
+        return RunResult(energies=energies, rec_x=host, rec_out=out_full), result
 
     # ---- step-wise path -------------------------------------------------------------------------------------
     def _run_stepwise(self, plan, inputs, loss_fn, is_sample_x_at_batch_start, is_reset_optimizer_x_at_batch_start,

@@ -160,3 +160,40 @@ def get_representations(gen_pc, config, trainers, loader, rep_type="MAP", use_cu
             reps.append(kept.reshape(-1, traj.shape[2]))
             labels.append(label.repeat(n))
     return TensorDataset(torch.cat(reps, dim=0), torch.cat(labels, dim=0))
+
+
+def get_posterior_expectation(gen_pc, config, trainers, loader, use_cuda=False, with_variance=False):
+    """The ``TensorDataset`` of ``get_representations(..., rep_type="expectation")`` -- MAP call with ``trainers[0]``, then an MCPC call
+    with ``trainers[1]`` started from the MAP state, mean of x_1 over all T steps -- with the mean accumulated on the device by the
+    call itself (``PCTrainer.mcpc_moments``, fp64 sums): no trajectory is recorded to the host or kept.  ``with_variance`` adds a third
+    tensor, the per-unit posterior variance (unbiased, over the same T steps)."""
+    from torch.utils.data import TensorDataset
+    if len(trainers) != 2:
+        raise NotImplementedError
+    device = next(gen_pc.parameters()).device
+    input_size = len(gen_pc[0].bias)
+    pc_trainer, mcpc_trainer = trainers
+    means, variances, labels = [], [], []
+    saved = mcpc_trainer.mcpc_moments
+    mcpc_trainer.mcpc_moments = dict(begin=0, stride=1, layers=(0,), outputs=None, variance=bool(with_variance))
+    try:
+        for data, label in loader:
+            pseudo_input = torch.zeros(data.shape[0], input_size, device=device)
+            data, label = data.to(device), label.to(device)
+            kw = dict(inputs=pseudo_input, loss_fn=config["loss_fn"],
+                      loss_fn_kwargs={"_target": data, "_var": config["input_var"]},
+                      is_log_progress=False, is_return_results_every_t=False, is_checking_after_callback_after_t=False)
+            pc_trainer.train_on_batch(**kw)
+            mcpc_trainer.train_on_batch(callback_after_t=random_step, callback_after_t_kwargs={"_pc_trainer": mcpc_trainer},
+                                        is_sample_x_at_batch_start=False, **kw)
+            m = mcpc_trainer.mcpc_last_moments
+            means.append(m.x_mean[0])
+            if with_variance:
+                variances.append(m.x_var[0])
+            labels.append(label)
+    finally:
+        mcpc_trainer.mcpc_moments = saved
+    tensors = [torch.cat(means, dim=0), torch.cat(labels, dim=0)]
+    if with_variance:
+        tensors.append(torch.cat(variances, dim=0))
+    return TensorDataset(*tensors)

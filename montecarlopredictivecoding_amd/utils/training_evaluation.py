@@ -113,6 +113,40 @@ def get_mse_rec(gen_pc, config, dataloader, use_cuda):
     return mse / n_data
 
 
+def get_mse_rec_posterior(gen_pc, config, dataloader, use_cuda):
+    """Masked-reconstruction error of the posterior-predictive mean: ``get_mse_rec``'s protocol (infer from the bottom half of each
+    image under the masked loss, score the top half), with the reconstruction E[output | bottom half] over the ``sampling`` steps that
+    follow ``mixing`` steps of an MCPC call started from the MAP state.  The mean is accumulated on the device by the call itself
+    (``PCTrainer.mcpc_moments``): the Bernoulli mean sigmoid(logits), thresholded at 0.5, for ``bernoulli_fn``; the read-out itself
+    for ``fe_fn``."""
+    import torch
+    from ..utils.model import bernoulli_fn, bernoulli_fn_mask, fe_fn, fe_fn_mask, random_step
+    loss_fn = {fe_fn: fe_fn_mask, bernoulli_fn: bernoulli_fn_mask}[config["loss_fn"]]
+    is_bernoulli = config["loss_fn"] is bernoulli_fn
+    gen_pc.train()
+    device = next(gen_pc.parameters()).device
+    pc_trainer = get_pc_trainer(gen_pc, config, training=False, is_mcpc=True)
+    mcpc_trainer = get_mcpc_trainer(gen_pc, config, training=False)
+    mcpc_trainer.mcpc_moments = dict(begin=config["mixing"], stride=1, layers=(), outputs="sigmoid" if is_bernoulli else "identity",
+                                     variance=False)
+    mse, n_data = 0.0, 0
+    for data, _ in dataloader:
+        data = data.to(device)
+        pseudo_input = torch.zeros(data.shape[0], config["input_size"], device=device)
+        kw = dict(inputs=pseudo_input, loss_fn=loss_fn, loss_fn_kwargs={"_target": data, "_var": config["input_var"]},
+                  is_log_progress=False, is_return_results_every_t=False, is_checking_after_callback_after_t=False)
+        pc_trainer.train_on_batch(**kw)
+        mcpc_trainer.train_on_batch(callback_after_t=random_step, callback_after_t_kwargs={"_pc_trainer": mcpc_trainer},
+                                    is_sample_x_at_batch_start=False, **kw)
+        img = mcpc_trainer.mcpc_last_moments.out_mean
+        if is_bernoulli:
+            img = (img > 0.5).type_as(img)
+        half = round(data.shape[1] / 2)
+        mse += float(((img[:, :-half] - data[:, :-half]) ** 2).mean(1).sum())
+        n_data += data.shape[0]
+    return mse / n_data
+
+
 def marginal_likelihood_from_logits(logits, dataloader):
     """log (1/S) sum_s p(y | o_s), averaged over the data, for read-out logits o_s [S, n0] (clamped to +-20 as the reference
     does, training_evaluation.py:177) -- the likelihood core of get_marginal_likelihood as a function of the prior samples.
