@@ -298,6 +298,18 @@ int mcpc_debug_poison_lds(int device, uint32_t word, void* stream);
 int mcpc_debug_lw_jobs(int32_t n_latent, const int32_t* sizes, int32_t n_out, int32_t* fwd, int32_t* bwd, int32_t cap,
                        int32_t* n_fwd, int32_t* n_bwd, int32_t* tile);
 
+/* Diagnostic (tests only; no device work, no device needed): everything mcpc_create would decide for `desc` on a device of `n_cu` compute
+ * units and `total_mem` bytes of memory (read only when desc->spill_budget_bytes <= 0; 0 = unknown), as one JSON object: "form"
+ * (in-place | barrier | layer-wise), "kernel" (mcpc_step_kernel_name), "Bpad", "workgroups" and "chains_per_wg" (mcpc_query), "npad",
+ * "out_pad", "slots" / "half_slots" of the spill ring, "spill_tm" per Linear; "main" and "unified"."plan", the LDS plan and step table
+ * of the main form and of the unified-wave kernel ("unified" also says whether the plan fits, is held and is preferred): "lds_bytes",
+ * "regions" as [name, layer | -1, float offset, floats], "xl", "chunk" / "ring" / "overlay" of the in-place plan, and "table", one row
+ * of numbers per entry in the order "fields" names (every KPhase field but the weight pointer; the unified table holds "rows" rows of
+ * "n_phases" entries, one per wave); "lw", the layer-wise job table (forward jobs, then backward jobs); "rounds", the round schedule
+ * with the [unit, rel] pairs of every launch of a cycle.  desc->device is ignored.  Writes at most cap - 1 characters and a NUL into
+ * out, and the size the whole text needs (NUL included) into *needed.  Fails as mcpc_create would: same codes, same messages. */
+int mcpc_debug_plan(const mcpc_net_desc* desc, int32_t n_cu, int64_t total_mem, char* out, int64_t cap, int64_t* needed);
+
 #ifdef __cplusplus
 }
 #endif

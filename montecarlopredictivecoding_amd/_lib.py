@@ -111,6 +111,7 @@ SYMBOLS = {
     "mcpc_debug_poison_lds": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p]),
     "mcpc_debug_lw_jobs": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mcpc_debug_plan": (C.c_int, [C.POINTER(NetDesc), C.c_int32, C.c_int64, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
 }
 
 _lib = None

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer tool (round 6): calibrate the cost model the unified-wave kernel's rows are dealt by (csrc/mcpc_api.hip: build_phases_u; tuning
+"""Developer tool (round 6): calibrate the cost model the unified-wave kernel's rows are dealt by (csrc/mcpc_plan.h: build_phases_u; tuning
 knobs u_row, u_gemm0, u_kb, u_kbt, u_eh, u_eb, u_ef) by measurement: us per step of MCPC / MAP / learning calls on the reference's net at
 batch 256 for a grid of model parameters.    python3 scripts/u_cost_search.py [T]"""
 import itertools

@@ -1,4 +1,4 @@
-"""The round schedule (csrc/mcpc_api.hip: setup_rounds / run_round_cycle): a shard of more 16-chain units than CUs runs as k launches
+"""The round schedule (csrc/mcpc_plan.h: plan_rounds, csrc/mcpc_api.hip: run_round_cycle): a shard of more 16-chain units than CUs runs as k launches
 per cycle, every unit in m of them, instead of ceil(U / CUs) hardware rounds.
 
 Chains are independent and every schedule runs the same per-chain arithmetic, so against
@@ -22,7 +22,7 @@ BARRIER = "ws=0"
 
 
 def _plan(units, n_cu=256):
-    """Mirror of setup_rounds: per k <= 16 the largest m whose launches of m consecutive groups fit the CUs; the smallest k within
+    """Mirror of plan_rounds: per k <= 16 the largest m whose launches of m consecutive groups fit the CUs; the smallest k within
     3 % of the best k / m."""
     fit = {}
     for k in range(2, 17):

@@ -1,5 +1,5 @@
-"""Host logic of the round schedule (csrc/mcpc_api.hip: setup_rounds), mirrored in Python and checked for the properties the kernel
-launches rely on -- no GPU needed.
+"""Host logic of the round schedule (csrc/mcpc_plan.h: plan_rounds), mirrored in Python and checked for the properties the kernel
+launches rely on, and the mirror checked against what the library plans (mcpc_debug_plan) -- no GPU needed.
 
 A shard of U 16-chain units on C < U CUs runs cycles of k launches of q steps; launch i holds groups i .. i+m-1 (mod k) of the k
 groups the units are dealt into.  What must hold for ANY (U, C):
@@ -12,6 +12,10 @@ groups the units are dealt into.  What must hold for ANY (U, C):
 import math
 
 import pytest
+
+from tests.plan_util import plan as library_plan
+
+SHARD_SIZES = lambda n_cu: list(range(n_cu + 1, 3 * n_cu + 2)) + [5 * n_cu + 3, 12 * n_cu - 1, 16 * n_cu, 16 * n_cu + 1, 40 * n_cu + 7]
 
 
 def plan(units, n_cu=256):
@@ -32,7 +36,7 @@ def plan(units, n_cu=256):
 
 
 def tables(units, k, m):
-    """Per launch of a cycle: [(unit, rel)], as setup_rounds builds them."""
+    """Per launch of a cycle: [(unit, rel)], as plan_rounds builds them."""
     done = [0] * k
     out = []
     for i in range(k):
@@ -55,7 +59,7 @@ def test_known_cases():
 
 @pytest.mark.parametrize("n_cu", [256, 304, 64])
 def test_cycle_properties_for_every_shard_size(n_cu):
-    for units in list(range(n_cu + 1, 3 * n_cu + 2)) + [5 * n_cu + 3, 12 * n_cu - 1, 16 * n_cu, 16 * n_cu + 1, 40 * n_cu + 7]:
+    for units in SHARD_SIZES(n_cu):
         k, m = plan(units, n_cu)
         assert 1 <= m < k or (m == 1 and k >= 2)
         launches = tables(units, k, m)
@@ -74,3 +78,14 @@ def test_cycle_properties_for_every_shard_size(n_cu):
                    default=None)
         if best is not None:
             assert k / m <= 1.03 * best + 1e-9, (units, k, m, best)
+
+
+@pytest.mark.parametrize("n_cu", [256, 304, 64])
+def test_the_library_plans_what_the_model_plans(n_cu):
+    """(k, m) and the per-launch (unit, rel) tables of plan_rounds itself, for a net of 16-wide layers at `units` 16-chain units:
+    the properties above then hold for the code that runs."""
+    for units in SHARD_SIZES(n_cu):
+        r = library_plan(sizes=[16, 16], n_out=16, batch=16 * units, n_cu=n_cu)["rounds"]
+        k, m = plan(units, n_cu)
+        assert (r["on"], r["k"], r["m"]) == (1, k, m), (units, r["k"], r["m"], k, m)
+        assert [[tuple(row) for row in rows] for rows in r["launches"]] == tables(units, k, m), units
