@@ -19,12 +19,19 @@
  *
  * Threading: one engine per (device, stream); an engine is not re-entrant.  All launches are
  * asynchronous on the given stream; the calls that wait for the device are mcpc_create / mcpc_destroy,
- * mcpc_sync_check and the two profiling getters.  mcpc_run does not wait for the stream, with two
+ * mcpc_sync_check and the two profiling getters.  mcpc_run does not wait for the stream, with three
  * bounded exceptions: a run with MCPC_XOPT_ADAM uploads its bias-correction table from one of two pinned
  * staging buffers and waits (hipEventSynchronize) for the upload issued two Adam runs earlier if that
  * has still not executed; and the first run that accumulates Hebbian sums allocates the spill ring
- * (hipMalloc).  Device buffers that have to grow (per-step tables, energy partials; geometrically) are
- * replaced, the old ones retired behind an event and freed by a later run once that event has completed.
+ * (hipMalloc); and the first run after an mcpc_bind_target that could take a specialised instantiation
+ * of the in-place step kernel (fused SGD + Philox kick or Adam without noise, all-ReLU network,
+ * Bernoulli loss, engine on the in-place kernel; not under tuning spec=0) and has at least spec_wait
+ * steps (tuning, default 0: every such run) waits (hipEventSynchronize) for the three flag words that bind copied to
+ * the host behind its kernels -- i.e. until the stream has executed everything queued up to and
+ * including the bind.  A shorter run only polls that copy (hipEventQuery) and keeps the generic kernel
+ * until it has landed.
+ * Device buffers that have to grow (per-step tables, energy partials; geometrically) are replaced, the
+ * old ones retired behind an event and freed by a later run once that event has completed.
  * The library reads no environment variables.
  */
 #ifndef MCPC_H
@@ -107,8 +114,10 @@ typedef struct mcpc_net_desc {
                                           * no_ybits=1, overlay16=1, heb_fp32=1 (the Hebbian GEMM on the fp32 MFMA instead of its fp16
                                           * form), rr=0 (shards of more 16-chain units than CUs as ONE launch in hardware rounds instead of
                                           * the round schedule), rr_qmax=N (most steps per launch of the round schedule), no_xl=1 (state and
-                                          * per-step constants of a workgroup's chains in global memory instead of LDS).  Unknown keys are
-                                          * an error.  Used by A/B runs and by the tests that pin the kernel forms against each other. */
+                                          * per-step constants of a workgroup's chains in global memory instead of LDS), spec=0 (every launch
+                                          * of the in-place kernel on its generic instantiation, never a specialised one), spec_wait=N
+                                          * (runs of fewer than N steps do not wait for the host copy of the target's flags: Threading,
+                                          * above).  Unknown keys are an error.  Used by A/B runs and by the tests that pin the kernel forms against each other. */
 } mcpc_net_desc;
 
 /* One train_on_batch call (or a slice of it).  Steps are numbered 0..T-1 inside the call. */
@@ -174,7 +183,11 @@ int mcpc_bind_params(mcpc_engine* e, int j, const float* W, const float* bias);
 int mcpc_params_changed(mcpc_engine* e, void* stream);
 
 /* Pseudo-input [batch][n_in] (NULL = zeros, the reference's usual call) and target [batch][n_out].
- * Replaces: `inputs`, loss_fn_kwargs['_target'] of train_on_batch, pc_trainer.py:500-524. */
+ * Replaces: `inputs`, loss_fn_kwargs['_target'] of train_on_batch, pc_trainer.py:500-524.
+ * mcpc_bind_target never waits.  On an engine that may take a specialised instantiation of the
+ * in-place kernel it also queues a 12-byte copy of what its kernels found (target exactly 0/1, target
+ * inside [-1, 2]) to pinned host memory, and an event behind it; the next candidate mcpc_run waits
+ * for, or polls, that event (Threading, above). */
 int mcpc_bind_inputs(mcpc_engine* e, const float* inputs, void* stream);
 int mcpc_bind_target(mcpc_engine* e, const float* target, void* stream);
 
@@ -188,7 +201,9 @@ int mcpc_store_state(mcpc_engine* e, float* const* x, void* stream);
  * calls the way the reference does when neither reset flag of train_on_batch is set (pc_trainer.py:742-752). */
 int mcpc_store_adam_state(mcpc_engine* e, float* const* m, float* const* v, void* stream);
 
-/* The hot loop: n_steps iterations of pc_trainer.py:712-981 (+ random_step) on every chain. */
+/* The hot loop: n_steps iterations of pc_trainer.py:712-981 (+ random_step) on every chain.
+ * Asynchronous but for the bounded host waits listed under Threading (Adam table upload, first
+ * spill-ring allocation, the bound target's flags once per bind). */
 int mcpc_run(mcpc_engine* e, const mcpc_run_desc* run, void* stream);
 
 /* Un-normalised parameter-gradient sums of Linear j accumulated by mcpc_run:
@@ -246,7 +261,8 @@ int mcpc_moments_accumulate(int device, const float* rec, int64_t row_elems, int
 
 /* Synchronise `stream` and report device-side faults of the runs issued so far (the wave-specialised step kernel
  * bounds every intra-workgroup wait; a wait that runs out is recorded instead of hanging the GPU).
- * Returns MCPC_ESTATE if the last results must not be used.  The only host-synchronising call besides create/destroy. */
+ * Returns MCPC_ESTATE if the last results must not be used.  The only call besides create/destroy that
+ * synchronises the whole stream on every call (mcpc_run's bounded waits: Threading, above). */
 int mcpc_sync_check(mcpc_engine* e, void* stream);
 
 /* Introspection for benchmarks / DESIGN.md: bytes of LDS per workgroup, chains per workgroup, workgroups of the shard (units
@@ -260,7 +276,9 @@ int mcpc_query(const mcpc_engine* e, int32_t* lds_bytes, int32_t* chains_per_wg,
 const char* mcpc_step_kernel_name(const mcpc_engine* e);
 /* What the last mcpc_run actually launched -- the engine's preference above is not always what serves a run (injected noise, gradients-only
  * runs and Adam with noise keep the main plan's kernel): the step kernel's name as above; a run that also ran a plain launch beside the round
- * schedule names both, joined by " + ".  "" before the first run.  Host bookkeeping only: no device work, no synchronisation.  The string
+ * schedule names both, joined by " + ".  Launches of the in-place kernel that took one of its specialised instantiations (a trace shows them
+ * as mcpc::mcpc_steps_ws2_spec_kernel<...>) are named behind the form they belong to, as " [mcpc_steps_ws2_spec_kernel: hot, hot+spill]"; a
+ * run on the generic instantiation alone carries no such tag.  "" before the first run.  Host bookkeeping only: no device work, no synchronisation.  The string
  * is valid until the next mcpc_run on this engine. */
 const char* mcpc_last_step_kernel_name(const mcpc_engine* e);
 /* What the last Hebbian flush of Linear j >= 1 launched (Linear 0's sums take mcpc_dw0_kernel at the end of every accumulating run):

@@ -42,6 +42,11 @@ struct mcpc_engine : EnginePlan {
     int* y_binary = nullptr;        // device flag: the bound target is exactly 0/1 everywhere
     int ywords = 0;
     bool target_bound = false;
+    // host copy of the three flag words (target_flags_on_host): requested by mcpc_bind_target behind its kernels; engines that may take a
+    // specialised instantiation of the in-place kernel only
+    int* y_flags_host = nullptr;    // pinned
+    hipEvent_t y_flags_ev = nullptr;
+    bool y_flags_pending = false;
     const float* inputs = nullptr;
     // Hebbian spill ring (EnginePlan::slots in parts of half_slots): the flush of one part runs on `aux` while the step kernel fills another
     hipStream_t aux = nullptr;
@@ -142,6 +147,8 @@ int free_all(mcpc_engine* e) {
     if (e->spacer) { (void)hipStreamDestroy(e->spacer); e->spacer = nullptr; }
     if (e->ev_fork) { (void)hipEventDestroy(e->ev_fork); e->ev_fork = nullptr; }
     if (e->ev_join) { (void)hipEventDestroy(e->ev_join); e->ev_join = nullptr; }
+    if (e->y_flags_ev) { (void)hipEventDestroy(e->y_flags_ev); e->y_flags_ev = nullptr; }
+    if (e->y_flags_host) { (void)hipHostFree(e->y_flags_host); e->y_flags_host = nullptr; }
     F(e->rr_tab);
     for (auto& q : e->retired) { (void)hipFree(q.p); if (q.ev) (void)hipEventDestroy(q.ev); }
     e->retired.clear();
@@ -220,7 +227,8 @@ int upload_table(mcpc_engine* e, StepPlan& p) {
 hipError_t allow_lds(const void* fn, int bytes) { return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
 int upload_rounds(mcpc_engine* e) {
     if (const int rc = upload(e->rr_tab, e->rr_host, "the round-schedule tables")) return rc;
-    if (allow_lds((const void*)mcpc_steps_ws2_kernel<1, true>, e->main.lds_bytes) != hipSuccess) return fail(MCPC_EHIP, "hipFuncSetAttribute failed for the round schedule");
+    for (const Ws2SpecEntry& sp : kWs2Specs)
+        if (sp.fn[1] && allow_lds(sp.fn[1], e->main.lds_bytes) != hipSuccess) return fail(MCPC_EHIP, "hipFuncSetAttribute failed for the round schedule");
     return 0;
 }
 
@@ -315,6 +323,12 @@ int mcpc_create(const mcpc_net_desc* d, mcpc_engine** out) {
         if ((rc = zeroed(e->ypad, (size_t)e->Bpad * e->out_pad)) || (rc = dmalloc(e->ytile, (size_t)e->Bpad * e->out_pad))) return bail(rc);
         e->ywords = (e->out_pad + 31) / 32;
         if ((rc = dmalloc(e->ybits, (size_t)e->Bpad * e->ywords)) || (rc = zeroed(e->y_binary, 3))) return bail(rc);   // [1] stays 0; [2]: target in [-1, 2]
+        // (only an engine whose lean runs stay on the in-place kernel can take one of its specialised instantiations: ws2_spec_candidate)
+        if (e->ws == 2 && !e->lw && !e->u.prefer && e->knobs.spec) {
+            if (hipHostMalloc((void**)&e->y_flags_host, 3 * sizeof(int), hipHostMallocDefault) != hipSuccess || hipEventCreateWithFlags(&e->y_flags_ev, hipEventDisableTiming) != hipSuccess)
+                return bail(fail(MCPC_EHIP, "pinned copy of the target flags: allocation failed"));
+            e->y_flags_host[0] = e->y_flags_host[1] = e->y_flags_host[2] = 0;
+        }
     }
     // gradient sums and packed weights of every Linear
     const int nlin = e->L + (e->has_head ? 1 : 0);
@@ -348,7 +362,9 @@ int mcpc_create(const mcpc_net_desc* d, mcpc_engine** out) {
         return bail(rc);
     // every kernel the engine may launch is allowed its plan's LDS
     const void* kfn = e->ws == 2 ? (const void*)mcpc_steps_ws2_kernel<1> : (const void*)mcpc_steps_kernel<1, 4>;
-    const hipError_t herr = e->lw ? hipSuccess : allow_lds(kfn, e->main.lds_bytes);
+    hipError_t herr = e->lw ? hipSuccess : allow_lds(kfn, e->main.lds_bytes);
+    for (int i = WS2_SPEC_GENERIC + 1; i < WS2_SPEC_COUNT && herr == hipSuccess && e->ws == 2 && !e->lw; ++i)      // (the in-place kernel's specialised instantiations)
+        if (kWs2Specs[i].fn[0]) herr = allow_lds(kWs2Specs[i].fn[0], e->main.lds_bytes);
     if (herr != hipSuccess) return bail(fail(MCPC_EHIP, "hipFuncSetAttribute(%d bytes LDS) failed: %s", e->main.lds_bytes, hipGetErrorString(herr)));
     if (e->rr && (rc = upload_rounds(e))) return bail(rc);
     if (e->u.on && (allow_lds((const void*)mcpc_steps_u_kernel<false>, e->u.plan.lds_bytes) != hipSuccess ||
@@ -419,6 +435,14 @@ int mcpc_bind_target(mcpc_engine* e, const float* target, void* stream_) {
     hipLaunchKernelGGL(mcpc_pack_target_bits_kernel, dim3(grid_for((size_t)e->Bpad * e->ywords)), dim3(256), 0, (hipStream_t)stream_,
                        e->ypad, e->ybits, e->y_binary, e->Bpad, e->out_pad, e->ywords);
     HIP_TRY(hipGetLastError());
+    // what the kernels found goes to the host as well: a run chooses its instantiation of the in-place kernel from it (ws2_select_mode)
+    // (engines that can take a specialised instantiation only.  A copy still on its way from an earlier bind is simply followed by this
+    // one, in stream order, and the event re-recorded behind it: whoever asks waits for, or looks at, the latest.  No host wait here.)
+    if (e->y_flags_host && e->y_flags_ev) {
+        HIP_TRY(hipMemcpyAsync(e->y_flags_host, e->y_binary, 3 * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream_));
+        HIP_TRY(hipEventRecord(e->y_flags_ev, (hipStream_t)stream_));
+        e->y_flags_pending = true;
+    }
     e->target_bound = true;
     return MCPC_OK;
 }
@@ -923,6 +947,61 @@ KParams run_params(const mcpc_engine* e, const mcpc_run_desc* r, const StepPlan&
     return P;
 }
 
+// Which instantiation of the in-place kernel a launch of this run takes (mcpc_steps_ws2.h: kWs2Specs).  A specialised mode fixes at compile
+// time what the generic kernel decides per workgroup from KParams, so it is chosen only when EVERY workgroup of the launch decides
+// that way -- the tests below are the body's own (mcpc_steps_ws2_body.inc: upd_mode, lean, xl, rowexp, ybin, y_bounded, slot), on the
+// host's copies of the same values.  What differs per lane (the padding chains of a last unit: LeanLane::livem) is data, not mode.
+//   lean for every workgroup: only units that hold a chain of the batch are launched (nwg_live; the round schedule deals those units)
+// ws2_spec_candidate: what holds for every launch of a run, whatever the bound target is.
+bool ws2_spec_candidate(const mcpc_engine* e, const KParams& P) {
+#ifdef MCPC_EXP_NOLEAN
+    return false;
+#endif
+    if (!e->y_flags_host || e->ws != 2 || e->lw) return false;                                                        // (tuning spec=0, another kernel form: never allocated)
+    const bool kick = P.update_x && P.xopt == MCPC_XOPT_SGD && P.noise_mode == MCPC_NOISE_PHILOX;                     // UPD: lean SGD + Philox kick,
+    const bool map = P.update_x && P.xopt == MCPC_XOPT_ADAM && P.noise_mode == MCPC_NOISE_NONE;                       // or lean Adam (the MAP warm-up)
+    if (!kick && !map) return false;
+    if (!P.lean_ok || !P.xl) return false;                                                                            // lean, XL (and with them ROWEXP)
+    for (int l = 0; l < e->L; ++l)
+        if (P.layer[l].act != MCPC_ACT_RELU) return false;                                                            // ACT
+    return P.has_head && P.head.loss_kind == MCPC_LOSS_BERNOULLI && e->target_bound;                                  // HEAD, as far as the run descriptor tells
+}
+
+// HEAD needs what only the device knows when mcpc_bind_target returns: that the target is 0/1 everywhere and bounded.  The bind copies the
+// three flag words to pinned host memory behind its kernels; a candidate run asks here, once.  `hot` comes back true when the words
+// have landed and say so.  A run of at least `spec_wait` steps (default 0: every candidate run) WAITS for the copy (hipEventSynchronize on the bind's event: the host
+// blocks until the stream has executed the bind, the GPU then idles for one launch latency -- with a target bound in front of every
+// call, calls of 4 to 1000 steps end 3-7 % sooner than on the parent, and no sooner than on it without the wait, because the copy has never
+// landed when the next run is queued: profiles/spec_modes.txt section 7); a shorter run only looks (hipEventQuery) and keeps the generic
+// kernel while the copy is still on its way.
+int target_flags_on_host(mcpc_engine* e, const KParams& P, int run_steps, bool& hot) {
+    hot = false;
+    if (e->y_flags_pending) {
+        if (run_steps >= e->knobs.spec_wait) {
+            HIP_TRY(hipEventSynchronize(e->y_flags_ev));
+        } else {
+            const hipError_t q = hipEventQuery(e->y_flags_ev);
+            if (q == hipErrorNotReady) return 0;
+            HIP_TRY(q);
+        }
+        e->y_flags_pending = false;
+    }
+    const int* const yf = e->y_flags_host;       // [0] 0/1 everywhere, [1] never set (tuning no_ybits reads it), [2] inside [-1, 2]
+    hot = yf[P.head.y_binary - e->y_binary] != 0 && yf[2] != 0;
+    return 0;
+}
+
+// `hot`: the run is a candidate and its target's flags hold.  `accumulating`: mcpc_run cuts its launches at the accumulation window, so
+// every step of a launch lies on one side of it.  `mix`: a launch of the round schedule.
+int ws2_select_mode(const KParams& P, bool hot, bool accumulating, bool mix) {
+    if (!hot) return WS2_SPEC_GENERIC;
+    const bool map = P.xopt == MCPC_XOPT_ADAM;
+    if (map && accumulating) return WS2_SPEC_GENERIC;
+    if (accumulating && !P.spill_sys) return WS2_SPEC_GENERIC;                       // (a spill that stays in the L2: no instantiation of its own)
+    const int spec = map ? WS2_SPEC_MAP : !accumulating ? WS2_SPEC_HOT : WS2_SPEC_HOT_SPILL;          // SPILL
+    return kWs2Specs[spec].fn[mix ? 1 : 0] ? spec : WS2_SPEC_GENERIC;
+}
+
 #ifdef MCPC_STAMPS
 // diagnostic build: where the waves of the launch that just ran steps [t, t + n) spent their cycles (waits for the stream)
 int report_stamps(mcpc_engine* e, bool use_u, int t, int n, hipStream_t stream) {
@@ -1034,7 +1113,18 @@ int mcpc_run(mcpc_engine* e, const mcpc_run_desc* r, void* stream_) {
 #endif
     // mcpc_last_step_kernel_name: which forms this run launched (bit 0 plain launch, bit 1 round schedule)
     unsigned launched = 0;
-    auto run_round_cycle = [&](const KParams& base, int t0, int q) -> int {
+    unsigned specs_rr = 0, specs_plain = 0;               // ... and which instantiations of the in-place kernel (bit = Ws2Spec)
+    bool hot = false;                                     // (a run on the unified-wave kernel never asks: no wait, no query)
+    if (!use_u && ws2_spec_candidate(e, P))
+        if (const int rc = target_flags_on_host(e, P, r->n_steps, hot)) return rc;
+    auto launch_ws2 = [&](KParams& K, bool mix, int nblocks, bool accumulating) -> int {
+        const int spec = ws2_select_mode(K, hot, accumulating, mix);
+        (mix ? specs_rr : specs_plain) |= 1u << spec;
+        void* args[] = {&K};
+        HIP_TRY(hipLaunchKernel(kWs2Specs[spec].fn[mix ? 1 : 0], dim3(nblocks), dim3(kWs2Threads), args, sp.lds_bytes, stream));
+        return 0;
+    };
+    auto run_round_cycle = [&](const KParams& base, int t0, int q, bool accumulating) -> int {
         launched |= 2u;
         KParams Q = base;
         set_window(e, r, Q, t0, q);
@@ -1043,7 +1133,7 @@ int mcpc_run(mcpc_engine* e, const mcpc_run_desc* r, void* stream_) {
             Q.wg_list = e->rr_tab + e->rr_off[i]; Q.wg_rel = Q.wg_list + e->rr_count[i];
             { const int rc = prof_begin(); if (rc) return rc; }
             if (use_u) hipLaunchKernelGGL((mcpc_steps_u_kernel<true>), dim3(e->rr_count[i]), dim3(kUThreads), sp.lds_bytes, stream, Q);
-            else hipLaunchKernelGGL((mcpc_steps_ws2_kernel<1, true>), dim3(e->rr_count[i]), dim3(kWs2Threads), sp.lds_bytes, stream, Q);
+            else if (const int rc = launch_ws2(Q, true, e->rr_count[i], accumulating)) return rc;
             { const int rc = prof_end((double)q * e->rr_count[i] / e->nwg_live); if (rc) return rc; }
         }
         HIP_TRY(hipGetLastError());
@@ -1072,7 +1162,7 @@ int mcpc_run(mcpc_engine* e, const mcpc_run_desc* r, void* stream_) {
             // whole cycles, longest launches first; fewer than rr_m steps left run as one plain launch (hardware rounds)
             while (n >= e->rr_m) {
                 const int q = std::min(std::max(1, e->knobs.rr_qmax), n / e->rr_m);
-                const int rc = run_round_cycle(P, t, q);
+                const int rc = run_round_cycle(P, t, q, false);
                 if (rc) return rc;
                 t += q * e->rr_m; n -= q * e->rr_m;
             }
@@ -1097,14 +1187,14 @@ int mcpc_run(mcpc_engine* e, const mcpc_run_desc* r, void* stream_) {
             P.spillmax = nullptr;
         }
         if (rr_q >= 1) {
-            const int rc = run_round_cycle(P, t, rr_q);
+            const int rc = run_round_cycle(P, t, rr_q, in_acc);
             if (rc) return rc;
         } else {
             { const int rc = prof_begin(); if (rc) return rc; }
             launched |= 1u;
             if (e->lw) { const int rc = launch_lw_steps(e, r, P, t, n, stream); if (rc) return rc; }
             else if (use_u) hipLaunchKernelGGL((mcpc_steps_u_kernel<false>), dim3(e->nwg_live), dim3(kUThreads), sp.lds_bytes, stream, P);
-            else if (e->ws == 2) hipLaunchKernelGGL((mcpc_steps_ws2_kernel<1>), dim3(e->nwg_live), dim3(kWs2Threads), sp.lds_bytes, stream, P);
+            else if (e->ws == 2) { const int rc = launch_ws2(P, false, e->nwg_live, in_acc); if (rc) return rc; }
             else hipLaunchKernelGGL((mcpc_steps_kernel<1, 4>), dim3(e->nwg), dim3(256), sp.lds_bytes, stream, P);
             { const int rc = prof_end((double)n); if (rc) return rc; }
         }
@@ -1130,11 +1220,19 @@ int mcpc_run(mcpc_engine* e, const mcpc_run_desc* r, void* stream_) {
         t += n;
     }
     {
+        // (a run on the generic instantiation alone reads as it always did; specialised launches are named behind the form they belong to)
+        auto spec_tag = [](unsigned specs) -> std::string {
+            if (!(specs & ~(1u << WS2_SPEC_GENERIC))) return "";
+            std::string tag;
+            for (int i = 0; i < WS2_SPEC_COUNT; ++i)
+                if (specs & (1u << i)) tag += (tag.empty() ? "" : ", ") + std::string(kWs2Specs[i].tag);
+            return " [mcpc_steps_ws2_spec_kernel: " + tag + "]";
+        };
         std::string name;
-        if (launched & 2u) name = use_u ? e->u_rr_name : e->rr_name;
+        if (launched & 2u) name = (use_u ? e->u_rr_name : e->rr_name) + spec_tag(specs_rr);
         if (launched & 1u) {
             if (!name.empty()) name += " + ";
-            name += plain_kernel_name(*e, use_u);
+            name += plain_kernel_name(*e, use_u) + spec_tag(specs_plain);
         }
         e->last_step = name;
     }

@@ -80,6 +80,11 @@ struct Knobs {
     int rr_qmax = 100;        // round schedule: most steps per launch in stretches without Hebbian accumulation
     int heb171 = 0;           // 1: the 17-tile group of a read-out on <17, 1> with twice the activation groups instead of <17, 2> (A/B)
     int heb_fp32 = 0;         // 1: the tiled Hebbian GEMM runs on the fp32 MFMA (mcpc_heb_kernel) instead of the fp16x6 form (A/B, parity tests)
+    int spec = 1;             // 0: every launch of the in-place kernel takes its generic instantiation, never a specialised one (A/B, parity tests)
+    int spec_wait = 0;        // a run of at least this many steps waits for the host copy of the bound target's flags (mcpc_api.hip:
+                              // target_flags_on_host); a shorter one specialises only if the copy has landed.  0, every candidate run
+                              // waits: with a target bound in front of every call that won at every length from 4 steps up, and runs
+                              // that only polled were 2 % behind the parent (profiles/spec_modes.txt section 7)
     // unified-wave kernel: the cost model its rows are dealt by (build_phases_u) -- developer knobs for its calibration.  The defaults started
     // from in-kernel stamps (shader cycles: 2000 / 1200 / 330 / 68 / 1000 / 1300 / 500) and were then moved by a grid search on the step time
     // itself (scripts/u_cost_search.py, profiles/r06_small_net.txt: 16.9 -> 16.1 us per MCPC step at batch 256): what the model has to get
@@ -110,7 +115,7 @@ inline int parse_tuning(const char* str, Knobs& k) {
         struct { const char* name; int* dst; } table[] = {
             {"ws", &k.ws}, {"wide", &k.wide}, {"no_overlap", &k.no_overlap},
             {"slot_cap", &k.slot_cap}, {"spill_gb", &k.spill_gb}, {"cu_slack", &k.cu_slack}, {"ring_parts", &k.ring_parts}, {"flush_tail", &k.flush_tail}, {"flush_streams", &k.flush_streams}, {"dw_ksplit", &k.dw_ksplit},
-            {"ws_prio", &k.ws_prio}, {"stagger", &k.stagger}, {"no_lean", &k.no_lean}, {"no_ybits", &k.no_ybits}, {"overlay16", &k.overlay16}, {"heb_fp32", &k.heb_fp32}, {"heb171", &k.heb171}, {"rr", &k.rr}, {"rr_qmax", &k.rr_qmax}, {"no_xl", &k.no_xl},
+            {"ws_prio", &k.ws_prio}, {"stagger", &k.stagger}, {"no_lean", &k.no_lean}, {"no_ybits", &k.no_ybits}, {"overlay16", &k.overlay16}, {"heb_fp32", &k.heb_fp32}, {"heb171", &k.heb171}, {"rr", &k.rr}, {"rr_qmax", &k.rr_qmax}, {"no_xl", &k.no_xl}, {"spec", &k.spec}, {"spec_wait", &k.spec_wait},
             {"u_row", &k.u_row}, {"u_gemm0", &k.u_gemm0}, {"u_kb", &k.u_kb}, {"u_kbt", &k.u_kbt}, {"u_eh", &k.u_eh}, {"u_eb", &k.u_eb}, {"u_ef", &k.u_ef}};
         bool found = false;
         for (auto& t : table)

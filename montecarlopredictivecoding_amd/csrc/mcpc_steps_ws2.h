@@ -257,14 +257,42 @@ __device__ __forceinline__ float ws2_headf_epilogue(const KParams& P, const KPha
 // MIX: the launch is one launch of a round-schedule cycle (setup_rounds, mcpc_api.hip) -- workgroups take their unit and the steps it
 // has already done from per-launch lists (KParams::wg_list / wg_rel).
 // (The body is a textual include: wrapped into a device function and inlined, the SAME code compiled about 1 % slower.)
-template <int CTT, bool MIX = false>
-__global__ __launch_bounds__(kWs2Threads, MCPC_WS2_WAVES_PER_EU) void mcpc_steps_ws2_kernel(const KParams P) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-#define WS2_BLOCK blockIdx.x
-#define WS2_NBLOCKS gridDim.x
-#include "mcpc_steps_ws2_body.inc"
-#undef WS2_BLOCK
-#undef WS2_NBLOCKS
-}
+// One definition serves every instantiation (mcpc_steps_ws2_kernel.inc: launch bounds, LDS declaration, the body's macros), included
+// once per kernel name with WS2_KERNEL_TEMPLATE / WS2_KERNEL_NAME / WS2_MODE set.
+// The GENERIC kernel: every decision of a launch is a run-time value of KParams (WS2_MODE = Ws2Generic).
+#define WS2_KERNEL_TEMPLATE template <int CTT, bool MIX = false>
+#define WS2_KERNEL_NAME mcpc_steps_ws2_kernel
+#define WS2_MODE Ws2Generic
+#include "mcpc_steps_ws2_kernel.inc"
+// The same body with the launch's decisions fixed at compile time (MODE: a Ws2Mode, mcpc_ws2_lean.h): the branches, the live ranges of
+// the paths not taken and the SGPR spills they cause are gone; the floating-point operations and their order are the generic kernel's.
+// A kernel of its own name, so that a trace tells the instantiations apart and the generic kernel's two symbols stay what they were.
+// The instantiations the library holds are listed ONCE, in kWs2Specs below; ws2_select_mode (mcpc_api.hip) picks one per launch.
+#define WS2_KERNEL_TEMPLATE template <class MODE, int CTT, bool MIX = false>
+#define WS2_KERNEL_NAME mcpc_steps_ws2_spec_kernel
+#define WS2_MODE MODE
+#include "mcpc_steps_ws2_kernel.inc"
+
+// The hot set: what every script of the reference runs per step on a ReLU network with a Bernoulli read-out -- lean SGD with the fused
+// Philox kick, state and constants in LDS, row words, a bit-packed 0/1 target -- apart by whether the launch accumulates (its spill
+// stores then go out at system scope).
+template <int SPILL> using Ws2HotMode = Ws2Mode<WS2_UPD_SGD_PHILOX, 1, 1, SPILL, WS2_HEAD_BERNOULLI_BITS, MCPC_ACT_RELU>;
+// The MAP warm-up of the same networks: Adam on x without noise, nothing accumulated.
+using Ws2MapMode = Ws2Mode<WS2_UPD_ADAM, 1, 1, WS2_SPILL_OFF, WS2_HEAD_BERNOULLI_BITS, MCPC_ACT_RELU>;
+enum Ws2Spec { WS2_SPEC_GENERIC = 0, WS2_SPEC_HOT, WS2_SPEC_HOT_SPILL, WS2_SPEC_MAP, WS2_SPEC_COUNT };
+struct Ws2SpecEntry { const void* fn[2]; const char* tag; };      // fn[MIX]; tag: what mcpc_last_step_kernel_name adds to the generic kernel's name
+#ifndef MCPC_EXP_NOLEAN
+static const Ws2SpecEntry kWs2Specs[WS2_SPEC_COUNT] = {
+    {{(const void*)mcpc_steps_ws2_kernel<1, false>, (const void*)mcpc_steps_ws2_kernel<1, true>}, "generic"},
+    {{(const void*)mcpc_steps_ws2_spec_kernel<Ws2HotMode<WS2_SPILL_OFF>, 1, false>, (const void*)mcpc_steps_ws2_spec_kernel<Ws2HotMode<WS2_SPILL_OFF>, 1, true>}, "hot"},
+    {{(const void*)mcpc_steps_ws2_spec_kernel<Ws2HotMode<WS2_SPILL_SYS>, 1, false>, (const void*)mcpc_steps_ws2_spec_kernel<Ws2HotMode<WS2_SPILL_SYS>, 1, true>}, "hot+spill"},
+    // (a spill that stays in the L2 -- a small shard, a narrow network: KParams::spill_sys == 0 -- keeps the generic kernel: the in-place
+    // kernel serves such shards only under tuning ws=2, and no measurement asked for an instantiation of their own)
+    {{(const void*)mcpc_steps_ws2_spec_kernel<Ws2MapMode, 1, false>, (const void*)mcpc_steps_ws2_spec_kernel<Ws2MapMode, 1, true>}, "map"},
+};
+#else       // (timing build without the lean epilogues: the generic kernel everywhere)
+static const Ws2SpecEntry kWs2Specs[WS2_SPEC_COUNT] = {
+    {{(const void*)mcpc_steps_ws2_kernel<1, false>, (const void*)mcpc_steps_ws2_kernel<1, true>}, "generic"}, {{nullptr, nullptr}, ""}, {{nullptr, nullptr}, ""}, {{nullptr, nullptr}, ""}};
+#endif
 
 }  // namespace mcpc

@@ -1,6 +1,8 @@
 // Body of a workgroup of the in-place wave-specialised step kernel: included as the body of mcpc_steps_ws2_kernel (WS2_BLOCK =
 // blockIdx.x: the kernels of the plain schedule compile exactly as they did as stand-alone kernels) and twice inside
-// mcpc_steps_ws2_mixed_kernel (one block per workgroup form).  Expects: CTT, MIX, P, lds, WS2_BLOCK, WS2_NBLOCKS.
+// mcpc_steps_ws2_mixed_kernel (one block per workgroup form).  Expects: CTT, MIX, P, lds, WS2_BLOCK, WS2_NBLOCKS, and WS2_MODE: the
+// launch's compile-time mode (mcpc_ws2_lean.h: Ws2Mode) -- a field other than kModeDyn replaces the run-time test below by its value.
+    using M = WS2_MODE;
     constexpr int NW = kWs2Pairs, NTW = ws2_nt<CTT>();
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -21,26 +23,27 @@
     for (int i = tid; i < P.lds_floats / 4; i += kWs2Threads) st4(lds + 4 * i, splat(0.f));
     __syncthreads();
     if (tid < 2 * kWs2Pairs) reinterpret_cast<int*>(sync)[tid] = 0;
-    const int upd_mode = (P.update_x && P.xopt == MCPC_XOPT_SGD)
+    const int upd_mode = M::UPD != kModeDyn ? (M::UPD == WS2_UPD_SGD_PHILOX ? 2 : (M::UPD == WS2_UPD_SGD ? 1 : 0))
+                         : (P.update_x && P.xopt == MCPC_XOPT_SGD)
                              ? (P.noise_mode == MCPC_NOISE_PHILOX ? 2 : (P.noise_mode == MCPC_NOISE_NONE ? 1 : 0)) : 0;
     // lean epilogues (mcpc_ws2_lean.h): fused SGD update (or Adam without noise: the MAP warm-up), every chain of the
     // workgroup inside the batch, 32-bit offsets fit
-    const bool lean_adam = P.update_x && P.xopt == MCPC_XOPT_ADAM && P.noise_mode == MCPC_NOISE_NONE;
-    const bool lean = (upd_mode != 0 || lean_adam) && chain0 < P.B && P.lean_ok;       // (padding chains of a last workgroup: LeanLane::livem)
+    const bool lean_adam = M::UPD != kModeDyn ? M::UPD == WS2_UPD_ADAM : P.update_x && P.xopt == MCPC_XOPT_ADAM && P.noise_mode == MCPC_NOISE_NONE;
+    const bool lean = M::UPD != kModeDyn || ((upd_mode != 0 || lean_adam) && chain0 < P.B && P.lean_ok);       // (padding chains of a last workgroup: LeanLane::livem)
     // the lean epilogues of a plan with the room keep the state (and what else they read every step) in LDS for the whole launch
-    const bool xl = CTT == 1 && lean && P.xl != 0;
+    const bool xl = M::XL != kModeDyn ? M::XL != 0 : CTT == 1 && lean && P.xl != 0;
     // lean epilogues keep the exponent of every B row they write (mcpc_kernels.h: rowexp_track): the GEMM waves then scan no row
 #ifdef MCPC_EXP_NOLEAN
     const bool rowexp = false;
 #else
-    const bool rowexp = CTT == 1 && lean;
+    const bool rowexp = M::ROWEXP != kModeDyn ? M::ROWEXP != 0 : CTT == 1 && lean;
 #endif
     float* const rx = rowexp ? lds + P.lds_rowexp : nullptr;
     // f(x_l) of the state the launch starts from; afterwards the x updates keep FX_l current
     for (int l = 0; l < L; ++l) {
         const KLayer& Ly = P.layer[l];
-        if (Ly.act == MCPC_ACT_RELU) ws2_fill_fx<MCPC_ACT_RELU>(Ly, lds, chain0, tid, 16 * CTT, xl, rx, rowexp_fx(l));
-        else if (Ly.act == MCPC_ACT_TANH) ws2_fill_fx<MCPC_ACT_TANH>(Ly, lds, chain0, tid, 16 * CTT, xl, rx, rowexp_fx(l));
+        if (M::act(Ly.act) == MCPC_ACT_RELU) ws2_fill_fx<MCPC_ACT_RELU>(Ly, lds, chain0, tid, 16 * CTT, xl, rx, rowexp_fx(l));
+        else if (M::act(Ly.act) == MCPC_ACT_TANH) ws2_fill_fx<MCPC_ACT_TANH>(Ly, lds, chain0, tid, 16 * CTT, xl, rx, rowexp_fx(l));
         else ws2_fill_fx<MCPC_ACT_IDENTITY>(Ly, lds, chain0, tid, 16 * CTT, xl, rx, rowexp_fx(l));
     }
     if (xl) ws2_fill_constants(P, lds, chain0, tid, 16 * CTT);
@@ -57,7 +60,7 @@
         // next-entry requests, progress counter -- for FWD_0, the energy entry or an x update without a back-projection bought nothing.
         int p = P.g_first;
         if (p < 0) return;                     // (no GEMM anywhere: a single latent layer without a read-out)
-        const bool y_bounded = P.has_head && *P.head.y_bounded != 0;      // (headb_fixed_exp: the bound target lies in [-1, 2])
+        const bool y_bounded = M::HEAD != kModeDyn ? M::HEAD == WS2_HEAD_BERNOULLI_BITS : P.has_head && *P.head.y_bounded != 0;      // (headb_fixed_exp: the bound target lies in [-1, 2])
         KPhase ph_next = load_phase(P.phases, p);
         int nt_next, aoff[NTW];
         frag_t pre0[NTW];
@@ -107,7 +110,7 @@
                     if (is_headb) {
                         if (nt > 0 MCPC_EXP_GEMM_GATE) {
                             // the chunks of the read-out add up in accb, in scaled units
-                            const int hb_exp = headb_fixed_exp(P.head.loss_kind, y_bounded);        // (wave-uniform: a constant for a bounded read-out error)
+                            const int hb_exp = headb_fixed_exp(M::loss_kind(P.head), y_bounded);        // (wave-uniform: a constant for a bounded read-out error)
                             const bool hb_word = hb_exp == kScaleAuto && rowexp && ph.b_row >= 0;
                             const int fixed_b = hb_word ? rowexp_read(rx, ph.b_row, c) : hb_exp;
                             GemmScale gs{load_wexp(P.wexp, ph.a_lin), GS_ACCUM, fixed_b, accb_run,
@@ -200,21 +203,22 @@
         LL.livem[ct] = live ? ~0u : 0u;
     }
     // 0/1 targets are read bit-packed (a wave-uniform flag the library set when the target was bound)
-    const bool ybin = lean && P.has_head && *P.head.y_binary != 0;
+    const bool ybin = M::HEAD != kModeDyn ? M::HEAD == WS2_HEAD_BERNOULLI_BITS : lean && P.has_head && *P.head.y_binary != 0;
     // sum_t e_1 of this launch in registers (lean path, top layer of at most one tile per wave, rot == 0 for FWD entries)
     const bool e0_in_regs = lean && P.layer[0].ntiles <= NW;
     bool e0_dirty = false;
     f32x4 e0acc[CTT];
 #pragma unroll
     for (int ct = 0; ct < CTT; ++ct) e0acc[ct] = splat(0.f);
-    if (e0_in_regs && t_first + P.n_steps > P.acc_begin && t_first < P.acc_end) lean_load_e0<CTT>(P, k, LL, e0acc);   // (a launch that accumulates)
+    if (e0_in_regs && (M::SPILL != kModeDyn ? M::SPILL != WS2_SPILL_OFF : t_first + P.n_steps > P.acc_begin && t_first < P.acc_end)) lean_load_e0<CTT>(P, k, LL, e0acc);   // (a launch that accumulates)
     STAMP_DECL
     for (int s = 0; s < P.n_steps; ++s) {
         const int t = t_first + s;
         const int s_tab = MIX ? t - P.t0 : s;          // index into per-step tables (Adam coefficients, external noise): they start at P.t0
         const int base = s * n_ent;
         const bool do_energy = (P.energy_mode == MCPC_ENERGY_ALL) || (P.energy_mode == MCPC_ENERGY_LAST && t == P.T - 1);
-        const int slot = (t >= P.acc_begin && t < P.acc_end) ? (t - P.spill_t0) : -1;
+        // (a specialised launch lies on one side of the accumulation window with every step: ws2_select_mode)
+        const int slot = M::SPILL == WS2_SPILL_OFF ? -1 : (M::SPILL != kModeDyn || (t >= P.acc_begin && t < P.acc_end)) ? (t - P.spill_t0) : -1;
         int rec_idx = -1;
         if (P.rec_count > 0 && t >= P.rec_begin) {
             const int kk = (t - P.rec_begin) / P.rec_stride;
@@ -264,7 +268,7 @@
             nt = nt < 0 ? 0 : (nt > NTW ? NTW : nt);
 #ifndef MCPC_EXP_NOLEAN
             if (lean) {
-                const int act = P.layer[ph.layer].act;
+                const int act = M::act(P.layer[ph.layer].act);
                 const int* const pg = &sync->prog_g[k];
                 const int need = base + p + 1;
 #ifdef MCPC_STAMPS_ENTRY       // (diagnostic build: the wait for the partner's block apart from the epilogue's own time)
@@ -279,18 +283,18 @@
 #endif
                 if (ph.type == PH_FWD) {
                     float esum;
-                    if (ph.layer == 0 && slot >= 0) e0_dirty = true;
+                    if (ph.layer == 0 && M::spills(slot)) e0_dirty = true;
                     if constexpr (CTT == 1) {
                         if (xl) {
-                            if (act == MCPC_ACT_RELU) esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_RELU, true>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
-                            else if (act == MCPC_ACT_TANH) esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_TANH, true>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
-                            else esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, true>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
+                            if (act == MCPC_ACT_RELU) esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_RELU, true, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
+                            else if (act == MCPC_ACT_TANH) esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_TANH, true, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
+                            else esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, true, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
                         }
                     }
                     if (!xl) {
-                    if (act == MCPC_ACT_RELU) esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_RELU>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
-                    else if (act == MCPC_ACT_TANH) esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_TANH>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
-                    else esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_IDENTITY>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
+                    if (act == MCPC_ACT_RELU) esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_RELU, false, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
+                    else if (act == MCPC_ACT_TANH) esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_TANH, false, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
+                    else esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, false, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
                     }
                     if (do_energy) { esum = wave_sum(esum); if (lane == ph.layer) en_acc += esum; }
                 } else if (ph.type == PH_HEADF) {
@@ -298,12 +302,12 @@
                     bool done = false;
                     if constexpr (CTT == 1) {
                         if (xl) {
-                            if (ybin) lsum = lean_headf<CTT, NW, NTW, true, true>(P, ph, lds, nt, kk, LL, slot, rec_idx, do_energy, pg, need, P.err, dead, true, rx);
-                            else lsum = lean_headf<CTT, NW, NTW, true, false>(P, ph, lds, nt, kk, LL, slot, rec_idx, do_energy, pg, need, P.err, dead, false, rx);
+                            if (ybin) lsum = lean_headf<CTT, NW, NTW, true, true, false, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, do_energy, pg, need, P.err, dead, true, rx);
+                            else lsum = lean_headf<CTT, NW, NTW, true, false, false, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, do_energy, pg, need, P.err, dead, false, rx);
                             done = true;
                         }
                     }
-                    if (!done) lsum = lean_headf<CTT, NW, NTW>(P, ph, lds, nt, kk, LL, slot, rec_idx, do_energy, pg, need, P.err, dead, ybin, rx);
+                    if (!done) lsum = lean_headf<CTT, NW, NTW, false, false, false, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, do_energy, pg, need, P.err, dead, ybin, rx);
                     if (do_energy) { lsum = wave_sum(lsum); if (lane == kMaxLatent) en_acc += lsum; }
                 } else if (ph.type == PH_BWD) {
                     bool done = false;
@@ -311,33 +315,33 @@
                         if (xl) {
                             done = true;
                             if (lean_adam) {
-                                if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, false, true, true>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
-                                else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, false, true, true>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
-                                else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, false, true, true>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
+                                if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, false, true, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
+                                else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, false, true, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
+                                else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, false, true, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
                             } else if (upd_mode == 2) {
-                                if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, true, false, true>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
-                                else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, true, false, true>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
-                                else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, true, false, true>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
+                                if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, true, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
+                                else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, true, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
+                                else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, true, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
                             } else {
-                                if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, false, false, true>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
-                                else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, false, false, true>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
-                                else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, false, false, true>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
+                                if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, false, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
+                                else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, false, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
+                                else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, false, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
                             }
                         }
                     }
                     if (done) {
                     } else if (lean_adam) {
-                        if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, false, true>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
-                        else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, false, true>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
-                        else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, false, true>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
+                        if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, false, true, false, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
+                        else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, false, true, false, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
+                        else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, false, true, false, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
                     } else if (upd_mode == 2) {
-                        if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, true>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
-                        else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, true>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
-                        else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, true>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
+                        if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, true, false, false, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
+                        else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, true, false, false, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
+                        else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, true, false, false, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
                     } else {
-                        if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, false>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
-                        else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, false>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
-                        else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, false>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
+                        if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, false, false, false, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
+                        else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, false, false, false, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
+                        else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, false, false, false, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
                     }
                 }
                 if (lane == 0) ws_publish(&sync->prog_e[k], base + p + 1);
@@ -405,7 +409,7 @@
     if constexpr (CTT == 1) {
         if (xl) lean_store_x<CTT, NW>(P, lds, k, LL);          // the state of this wave's tiles goes back to global memory
     }
-    spill_max_publish(P.spillmax, lds + P.lds_spillmax, lane);  // what this workgroup spilled at most, per tensor (every E wave, when it is through)
+    if constexpr (M::SPILL != WS2_SPILL_OFF) spill_max_publish(P.spillmax, lds + P.lds_spillmax, lane);  // what this workgroup spilled at most, per tensor (every E wave, when it is through)
     if (clk_wave && lane == 0) {
         atomicAdd(P.clk, __builtin_amdgcn_s_memtime() - clk_c0);
         atomicAdd(P.clk + 1, __builtin_amdgcn_s_memrealtime() - clk_w0);

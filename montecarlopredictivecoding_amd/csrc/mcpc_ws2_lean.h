@@ -73,6 +73,33 @@ __device__ __forceinline__ void spill_st4(float* base, uint32_t image_bytes, uin
 #endif
 }
 
+// ---- compile-time run mode of the in-place step kernel (mcpc_steps_ws2.h) -------------------------------------------------------------
+// What a launch decides once -- optimizer and noise, XL, row words, whether it accumulates, the read-out's loss and target form, the
+// activations -- is a run-time value of KParams in the generic kernel, re-tested in every workgroup, table entry and tile loop; the
+// compiler keeps the union of all paths alive (294 spilled SGPRs).  A field of Ws2Mode fixes one such decision at
+// compile time; kModeDyn leaves it to the run-time test, which then compiles to exactly the generic kernel's code for that decision.
+// ws2_select_mode (mcpc_api.hip) returns a specialised mode only when every launched workgroup would have decided the same.
+constexpr int kModeDyn = -1;
+enum { WS2_UPD_SGD = 1, WS2_UPD_SGD_PHILOX = 2, WS2_UPD_ADAM = 3 };     // lean epilogues with the fused update: SGD, SGD + Philox kick, Adam without noise
+enum { WS2_SPILL_OFF = 0, WS2_SPILL_SYS = 1 };                          // no step of the launch accumulates / every step does, its stores at system scope
+enum { WS2_HEAD_NONE = 0, WS2_HEAD_BERNOULLI_BITS = 1 };                // no loss / Bernoulli read-out whose 0/1 target is read bit-packed (bounded: headb_fixed_exp)
+template <int UPD_ = kModeDyn, int XL_ = kModeDyn, int ROWEXP_ = kModeDyn, int SPILL_ = kModeDyn, int HEAD_ = kModeDyn, int ACT_ = kModeDyn>
+struct Ws2Mode {
+    static constexpr int UPD = UPD_, XL = XL_, ROWEXP = ROWEXP_, SPILL = SPILL_, HEAD = HEAD_, ACT = ACT_;      // ACT: the activation of every latent layer
+    static constexpr bool generic = UPD == kModeDyn && XL == kModeDyn && ROWEXP == kModeDyn && SPILL == kModeDyn && HEAD == kModeDyn && ACT == kModeDyn;
+    static_assert(XL == kModeDyn || UPD != kModeDyn, "XL is a property of the lean epilogues");
+    static_assert(ROWEXP == kModeDyn || UPD != kModeDyn, "row words are kept by the lean epilogues");
+    // `slot` of a step (>= 0: the step spills into that ring slot)
+    static __device__ __forceinline__ bool spills(int slot) { if constexpr (SPILL == kModeDyn) return slot >= 0; else return SPILL != WS2_SPILL_OFF; }
+    static __device__ __forceinline__ bool spill_sys(const KParams& P) { if constexpr (SPILL == kModeDyn) return P.spill_sys != 0; else return SPILL == WS2_SPILL_SYS; }
+    static __device__ __forceinline__ int loss_kind(const KHead& H) {
+        if constexpr (HEAD == kModeDyn) return H.loss_kind; else return HEAD == WS2_HEAD_BERNOULLI_BITS ? MCPC_LOSS_BERNOULLI : MCPC_LOSS_NONE;
+    }
+    static __device__ __forceinline__ int act(int a) { if constexpr (ACT == kModeDyn) return a; else return ACT; }
+    static __device__ __forceinline__ bool has_rx(const float* rx) { if constexpr (ROWEXP == kModeDyn) return rx != nullptr; else return ROWEXP != 0; }
+};
+using Ws2Generic = Ws2Mode<>;
+
 // per-lane constants of an E wave, fixed for the launch
 template <int CTT>
 struct LeanLane {
@@ -102,7 +129,7 @@ template <int ACT> __device__ __forceinline__ f32x4 act4(f32x4 x) {
 // instead of a global read-modify-write in every step.
 // REG (unified-wave kernel, mcpc_steps_u.h): the wave computed the block itself -- it arrives in registers (racc[i][ct], zeros when the entry has
 // no GEMM), nothing is waited for and nothing is read from out_lds.
-template <int CTT, int NW, int NTW, int ACT, bool XL = false, bool REG = false>
+template <int CTT, int NW, int NTW, int ACT, bool XL = false, bool REG = false, class M = Ws2Generic>
 __device__ __forceinline__ float lean_fwd(const KParams& P, const KPhase& ph, float* lds, int nt, int kk, const LeanLane<CTT>& L,
                                           int slot, int rec_idx, const int* prog_g, int need, int* err, int& dead,
                                           f32x4 (&e0acc)[CTT], bool e0_in_regs, float* rx = nullptr, unsigned row_gen = 0u,
@@ -169,11 +196,11 @@ __device__ __forceinline__ float lean_fwd(const KParams& P, const KPhase& ph, fl
     }
     const float ecoef = Ly.ecoef;
     char* const e_lds = reinterpret_cast<char*>(lds + Ly.lds_e);
-    float* const spill_a = slot >= 0 ? Ly.spill_a + (size_t)slot * P.Bpad * Ly.npad : nullptr;
-    float* const spill_e = slot >= 0 ? (l > 0 ? Ly.spill_e + (size_t)slot * P.Bpad * Ly.npad : Ly.spill_e) : nullptr;
+    float* const spill_a = M::spills(slot) ? Ly.spill_a + (size_t)slot * P.Bpad * Ly.npad : nullptr;
+    float* const spill_e = M::spills(slot) ? (l > 0 ? Ly.spill_e + (size_t)slot * P.Bpad * Ly.npad : Ly.spill_e) : nullptr;
     float* const rec = (rec_idx >= 0 && Ly.rec != nullptr) ? Ly.rec + (size_t)rec_idx * P.B * Ly.n : nullptr;
     const uint32_t img_bytes = (uint32_t)P.Bpad * npad4;               // one [Bpad][npad] image (lean_ok: < 4 GiB)
-    const bool sys = P.spill_sys != 0;
+    const bool sys = M::spill_sys(P);
     float esum = 0.f;
     float amx = 0.f, emx = 0.f;            // largest |value| this call spills of A_l / E_l (mcpc_kernels.h: spill_track)
     float rmx = 0.f;                       // largest |value| this lane writes of its chain's E_l row (rowexp_track)
@@ -188,7 +215,7 @@ __device__ __forceinline__ float lean_fwd(const KParams& P, const KPhase& ph, fl
             const f32x4 d = x - (av[i][ct] + bv[i][ct]);                  // x - mu
             const f32x4 e = d * ecoef;
             if (l > 0) { *reinterpret_cast<f32x4*>(e_lds + lrowb[ct] + tb) = e; rmx = absmax4(rmx, e); }
-            if (slot >= 0) {
+            if (M::spills(slot)) {
 #ifdef MCPC_EXP_SPILL_LINEAR      // timing experiment only (rows permuted inside the workgroup's block): one contiguous KiB per store
                 const uint32_t sb = mul24(L.chain[ct] - (uint32_t)L.c, npad4) + 1024u * (uint32_t)tile + 16u * (uint32_t)(L.c + 16 * L.q);
 #else
@@ -207,11 +234,11 @@ __device__ __forceinline__ float lean_fwd(const KParams& P, const KPhase& ph, fl
             esum += L.livem[ct] ? 0.5f * ecoef * (dd.x + dd.y + dd.z + dd.w) : 0.f;          // (a select, not a product: whatever a padding chain holds)
         }
     }
-    if (slot >= 0) {
+    if (M::spills(slot)) {
         spill_track(lds + P.lds_spillmax, spill_id_a(l), amx, L.c + 16 * L.q);
         if (l > 0) spill_track(lds + P.lds_spillmax, spill_id_e(l), emx, L.c + 16 * L.q);
     }
-    if (CTT == 1 && rx != nullptr && ph.o_row >= 0) rowexp_track(rx, ph.o_row, L.c, rmx, row_gen);
+    if (CTT == 1 && M::has_rx(rx) && ph.o_row >= 0) rowexp_track(rx, ph.o_row, L.c, rmx, row_gen);
     return esum;
 }
 
@@ -260,7 +287,7 @@ __device__ __forceinline__ void lean_store_x(const KParams& P, const float* lds,
 // in front of the wait for the partner's block -- the generic epilogue loads them behind it, one L2/HBM round trip exposed
 // per x update -- and the arithmetic is the generic epilogue's, operation for operation (s_tab: row of the bias-correction
 // table).
-template <int CTT, int NW, int NTW, int ACT, bool NOISE, bool ADAM = false, bool XL = false, bool REG = false>
+template <int CTT, int NW, int NTW, int ACT, bool NOISE, bool ADAM = false, bool XL = false, bool REG = false, class M = Ws2Generic>
 __device__ __forceinline__ void lean_bwd(const KParams& P, const KPhase& ph, float* lds, int nt, int kk, const LeanLane<CTT>& L,
                                          int t, const int* prog_g, int need, int* err, int& dead, int s_tab = 0, float* rx = nullptr,
                                          unsigned row_gen = 0u, const f32x4 (*racc)[CTT] = nullptr) {
@@ -398,14 +425,14 @@ __device__ __forceinline__ void lean_bwd(const KParams& P, const KPhase& ph, flo
             rmx = absmax4(rmx, fxn);
         }
     }
-    if (CTT == 1 && rx != nullptr && ph.o_row >= 0) rowexp_track(rx, ph.o_row, L.c, rmx, row_gen);
+    if (CTT == 1 && M::has_rx(rx) && ph.o_row >= 0) rowexp_track(rx, ph.o_row, L.c, rmx, row_gen);
 }
 
 // ---- HEADF entry (read-out chunk): out = acc + bias, e_o = dL/dout -> ring slot (LDS), loss, spills, output records -----
 // XL: bias from LDS; YB (with XL only): the target is 0/1, its words come from LDS and no fp32 target is requested -- a compile-time
 // choice, so that the 0/1 case holds no global load at all (see the note on loads under an `if` below).
 // YWG (with XL, YB, REG): the target words were requested from global memory by the caller, in front of the row's GEMM (ywreg[i])
-template <int CTT, int NW, int NTW, bool XL = false, bool YB = false, bool REG = false, bool YWG = false>
+template <int CTT, int NW, int NTW, bool XL = false, bool YB = false, bool REG = false, bool YWG = false, class M = Ws2Generic>
 __device__ __forceinline__ float lean_headf(const KParams& P, const KPhase& ph, float* lds, int nt, int kk, const LeanLane<CTT>& L,
                                             int slot, int rec_idx, bool do_energy, const int* prog_g, int need, int* err, int& dead,
                                             bool ybin, float* rx = nullptr, const f32x4 (*racc)[CTT] = nullptr, unsigned row_gen = 0u,
@@ -415,7 +442,7 @@ __device__ __forceinline__ float lean_headf(const KParams& P, const KPhase& ph, 
     const KHead& H = P.head;
     // unified-wave kernel: a Bernoulli read-out's error goes to LDS as planes (see below; headf_planes is the GEMM side's test too)
     const bool planes = REG && planes_ok;
-    const int kind = H.loss_kind, n = H.n, mask_start = H.mask_start;
+    const int kind = M::loss_kind(H), n = H.n, mask_start = H.mask_start;
     const uint32_t npad4 = 4u * (uint32_t)H.npad;
     uint32_t rowb[CTT], orowb[CTT];
 #pragma unroll
@@ -486,7 +513,7 @@ __device__ __forceinline__ float lean_headf(const KParams& P, const KPhase& ph, 
         }
     }
     const float inv_var = H.inv_var;
-    float* const spill = slot >= 0 ? H.spill_e + (size_t)slot * P.Bpad * H.npad : nullptr;
+    float* const spill = M::spills(slot) ? H.spill_e + (size_t)slot * P.Bpad * H.npad : nullptr;
     float* const rec = (rec_idx >= 0 && H.rec_out != nullptr) ? H.rec_out + (size_t)rec_idx * P.B * H.n : nullptr;
     float lsum = 0.f;
     float omx = 0.f;                       // largest |value| this call spills of E_o
@@ -561,22 +588,22 @@ __device__ __forceinline__ float lean_headf(const KParams& P, const KPhase& ph, 
             }
             rmx = absmax4(rmx, e);
 #ifdef MCPC_EXP_SPILL_LINEAR
-            if (slot >= 0) spill_st4(spill, (uint32_t)P.Bpad * npad4, mul24(L.chain[ct] - (uint32_t)L.c, npad4) + 1024u * (uint32_t)tile + 16u * (uint32_t)(L.c + 16 * L.q), mask4(e, L.livem[ct]), P.spill_sys != 0);
+            if (M::spills(slot)) spill_st4(spill, (uint32_t)P.Bpad * npad4, mul24(L.chain[ct] - (uint32_t)L.c, npad4) + 1024u * (uint32_t)tile + 16u * (uint32_t)(L.c + 16 * L.q), mask4(e, L.livem[ct]), M::spill_sys(P));
 #else
-            if (slot >= 0) {
+            if (M::spills(slot)) {
                 spill_st4(spill, (uint32_t)P.Bpad * npad4,
                           H.spill_tm ? mul24(L.chain[ct] - (uint32_t)L.c, npad4) + 1024u * (uint32_t)tile + 16u * (uint32_t)(L.c + 16 * L.q) : rowb[ct] + tb,
-                          mask4(e, L.livem[ct]), P.spill_sys != 0);
+                          mask4(e, L.livem[ct]), M::spill_sys(P));
                 omx = absmax4(omx, mask4(e, L.livem[ct]));
             }
 #endif
             if (rec != nullptr && L.livem[ct]) st_unpadded(rec, (int)L.chain[ct], H.n, 16 * tile + 4 * L.q, o);
         }
     }
-    if (slot >= 0) spill_track(lds + P.lds_spillmax, kSpillIdEo, omx, L.c + 16 * L.q);
+    if (M::spills(slot)) spill_track(lds + P.lds_spillmax, kSpillIdEo, omx, L.c + 16 * L.q);
     // (a ring slot is reused inside a step: its generation is the entry, `need` = entries completed so far)
     // (the unified-wave kernel keeps the whole e_o row in LDS: its chunks of one step combine under the step's generation)
-    if (CTT == 1 && rx != nullptr && ph.o_row >= 0) rowexp_track(rx, ph.o_row, L.c, rmx, REG ? row_gen : (unsigned)need);
+    if (CTT == 1 && M::has_rx(rx) && ph.o_row >= 0) rowexp_track(rx, ph.o_row, L.c, rmx, REG ? row_gen : (unsigned)need);
     return lsum;
 }
 
