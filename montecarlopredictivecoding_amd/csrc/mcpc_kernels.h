@@ -10,6 +10,7 @@
 #pragma once
 #include "mcpc_device.h"
 #include "../../include/mcpc.h"
+#include "mcpc_step_math.h"
 
 namespace mcpc {
 
@@ -334,17 +335,6 @@ __device__ __forceinline__ unsigned long long mcpc_stamp() {
 #define STAMP_T(b, ty) do {} while (0)
 #endif
 
-template <int ACT> __device__ __forceinline__ float actf(float x) {
-    if constexpr (ACT == MCPC_ACT_RELU) return fmaxf(x, 0.0f);
-    else if constexpr (ACT == MCPC_ACT_TANH) return tanh_f(x);
-    else return x;
-}
-template <int ACT> __device__ __forceinline__ float actd(float x, float fx) {
-    if constexpr (ACT == MCPC_ACT_RELU) return x > 0.0f ? 1.0f : 0.0f;
-    else if constexpr (ACT == MCPC_ACT_TANH) return 1.0f - fx * fx;
-    else return 1.0f;
-}
-
 // ---- FWD epilogue: prediction errors, energies, activations to LDS, spills, trajectory records -------
 template <int CTT, int NW, int NTW, int ACT, bool WRITE_FX = true>
 __device__ __forceinline__ float fwd_epilogue(const KParams& P, const KPhase& ph, float* lds, int nt, int wave, int lane,
@@ -375,10 +365,9 @@ __device__ __forceinline__ float fwd_epilogue(const KParams& P, const KPhase& ph
             const int cl = 16 * ct + c, chain = chain0 + cl;
             const bool live = chain < B;
             const f32x4 x = xa[ct];
-            const f32x4 d = x - (a[ct] + xb[ct]);                 // x - mu
-            const f32x4 e = d * ecoef;
-            f32x4 fx;
-            fx.x = actf<ACT>(x.x); fx.y = actf<ACT>(x.y); fx.z = actf<ACT>(x.z); fx.w = actf<ACT>(x.w);
+            f32x4 d;                                              // x - mu
+            const f32x4 e = pc_error4(x, a[ct] + xb[ct], ecoef, d);
+            const f32x4 fx = act4<ACT>(x);
             if constexpr (WRITE_FX) st4(fx_lds + cl * ld + u0, fx);   // in-place variant: FX_l is written by the x update
             if (l > 0) st4(e_lds + cl * ld + u0, e);
             if (slot >= 0) {
@@ -395,8 +384,7 @@ __device__ __forceinline__ float fwd_epilogue(const KParams& P, const KPhase& ph
                 }
             }
             if (rec != nullptr && live) st_unpadded(rec, chain, n, u0, x);
-            const f32x4 dd = d * d;
-            esum += live ? 0.5f * ecoef * (dd.x + dd.y + dd.z + dd.w) : 0.0f;
+            esum += live ? pc_energy4(d, ecoef) : 0.0f;
         }
     }
     if (slot >= 0) {
@@ -438,33 +426,7 @@ __device__ __forceinline__ float headf_epilogue(const KParams& P, const KPhase& 
             f32x4 e = splat(0.f);
             if (kind != MCPC_LOSS_NONE) {
                 const f32x4 y = xa[ct];
-                const float ov[4] = {o.x, o.y, o.z, o.w}, yv[4] = {y.x, y.y, y.z, y.w};
-                float ev[4];
-                if (kind == MCPC_LOSS_GAUSSIAN) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const bool on = live && (u0 + r) >= mask_start && (u0 + r) < n;
-                        const float dlt = ov[r] - yv[r];
-                        ev[r] = on ? inv_var * dlt : 0.f;
-                        lsum += on ? 0.5f * inv_var * dlt * dlt : 0.f;
-                    }
-                } else if (do_energy) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const bool on = live && (u0 + r) >= mask_start && (u0 + r) < n;
-                        float sg, bc;
-                        sigmoid_bce_f(ov[r], yv[r], sg, bc);
-                        ev[r] = on ? sg - yv[r] : 0.f;
-                        lsum += on ? bc : 0.f;
-                    }
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const bool on = live && (u0 + r) >= mask_start && (u0 + r) < n;
-                        ev[r] = on ? sigmoid_f(ov[r]) - yv[r] : 0.f;
-                    }
-                }
-                e.x = ev[0]; e.y = ev[1]; e.z = ev[2]; e.w = ev[3];
+                MCPC_READOUT_LOSS4(e, o, y, kind, do_energy, inv_var, lsum, live && (u0 + r) >= mask_start && (u0 + r) < n, true);
             }
             st4(eo_lds + cl * ld + (u0 - 16 * ph.tile0), e);
             if (slot >= 0) { st4s(spill + spill_offset(H.spill_tm, (size_t)slot * Bpad + chain, u0, npad), e); omx = absmax4(omx, e); }
@@ -502,38 +464,25 @@ __device__ __forceinline__ void bwd_epilogue(const KParams& P, const KPhase& ph,
             const int chain = chain0 + 16 * ct + c;
             const size_t row = (size_t)chain * npad + u0;
             const f32x4 x = xa[ct], e = xb[ct], back = a[ct];
-            f32x4 g;
-            g.x = e.x + sign * actd<ACT>(x.x, actf<ACT>(x.x)) * back.x;
-            g.y = e.y + sign * actd<ACT>(x.y, actf<ACT>(x.y)) * back.y;
-            g.z = e.z + sign * actd<ACT>(x.z, actf<ACT>(x.z)) * back.z;
-            g.w = e.w + sign * actd<ACT>(x.w, actf<ACT>(x.w)) * back.w;
+            const f32x4 g = x_grad4<ACT>(x, e, back, sign);
             f32x4 xn;
             if constexpr (MODE == 0) {
                 const bool live = chain < B;
                 if (!P.update_x) {
                     if (live && Ly.xgrad != nullptr) st_unpadded(Ly.xgrad, chain, n, u0, g);
-                    if constexpr (FXOUT) {      // x stays: put f(x) back where the back-projection was handed over
-                        f32x4 fx;
-                        fx.x = actf<ACT>(x.x); fx.y = actf<ACT>(x.y); fx.z = actf<ACT>(x.z); fx.w = actf<ACT>(x.w);
-                        st4(lds + Ly.lds_a + (16 * ct + c) * Ly.ld + u0, fx);
-                    }
+                    // x stays: put f(x) back where the back-projection was handed over
+                    if constexpr (FXOUT) st4(lds + Ly.lds_a + (16 * ct + c) * Ly.ld + u0, act4<ACT>(x));
                     continue;
                 }
                 if (P.xopt == MCPC_XOPT_SGD) {
                     xn = x - g * lr;
                 } else {
-                    // torch.optim.Adam single-tensor path: lerp_, mul_/addcmul_, sqrt/bias2 + eps, addcdiv_ (adam_x, mcpc_device.h)
                     const size_t mrow = tile_major_offset(chain, u0, npad);      // (tile-major: see tile_major_offset)
                     f32x4 m = ld4s(Ly.m + mrow), v = ld4s(Ly.v + mrow);
-                    m.x = adam_m(m.x, g.x, P.omb1); m.y = adam_m(m.y, g.y, P.omb1); m.z = adam_m(m.z, g.z, P.omb1); m.w = adam_m(m.w, g.w, P.omb1);
-                    v.x = adam_v(v.x, g.x, P.beta2, P.omb2); v.y = adam_v(v.y, g.y, P.beta2, P.omb2); v.z = adam_v(v.z, g.z, P.beta2, P.omb2); v.w = adam_v(v.w, g.w, P.beta2, P.omb2);
+                    adam_moments4(m, v, g, P.omb1, P.beta2, P.omb2);
                     st4s(Ly.m + mrow, m);
                     st4s(Ly.v + mrow, v);
-                    const float nss = P.adam_coef[2 * s], bc2s = P.adam_coef[2 * s + 1], eps = P.eps;
-                    xn.x = adam_x(x.x, m.x, v.x, nss, bc2s, eps);
-                    xn.y = adam_x(x.y, m.y, v.y, nss, bc2s, eps);
-                    xn.z = adam_x(x.z, m.z, v.z, nss, bc2s, eps);
-                    xn.w = adam_x(x.w, m.w, v.w, nss, bc2s, eps);
+                    xn = adam_x4(x, m, v, P.adam_coef[2 * s], P.adam_coef[2 * s + 1], P.eps);
                 }
                 if (P.noise_mode == MCPC_NOISE_PHILOX) {
                     xn = xn + normals4(seed, step, (uint32_t)l, (uint32_t)(chain_base + (uint64_t)chain), (uint32_t)(u0 >> 2)) * nscale;
@@ -545,17 +494,10 @@ __device__ __forceinline__ void bwd_epilogue(const KParams& P, const KPhase& ph,
                 if constexpr (MODE == 2)
                     xn = xn + normals4(seed, step, (uint32_t)l, (uint32_t)(chain_base + (uint64_t)chain), (uint32_t)(u0 >> 2)) * nscale;
             }
-            // padded units stay exactly zero (their gradient is zero; only the noise must be masked)
-            if (u0 + 0 >= n) xn.x = 0.f;
-            if (u0 + 1 >= n) xn.y = 0.f;
-            if (u0 + 2 >= n) xn.z = 0.f;
-            if (u0 + 3 >= n) xn.w = 0.f;
+            zero_padded4(xn, u0, n);
             st4s(xptr + row, xn);
-            if constexpr (FXOUT) {              // in-place variant: the next step's GEMMs read f(x_new) from FX_l
-                f32x4 fx;
-                fx.x = actf<ACT>(xn.x); fx.y = actf<ACT>(xn.y); fx.z = actf<ACT>(xn.z); fx.w = actf<ACT>(xn.w);
-                st4(lds + Ly.lds_a + (16 * ct + c) * Ly.ld + u0, fx);
-            }
+            // in-place variant: the next step's GEMMs read f(x_new) from FX_l
+            if constexpr (FXOUT) st4(lds + Ly.lds_a + (16 * ct + c) * Ly.ld + u0, act4<ACT>(xn));
         }
     }
 }

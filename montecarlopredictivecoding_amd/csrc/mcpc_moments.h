@@ -15,7 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mcpc_device.h"
+#include "mcpc_step_math.h"
 
 namespace mcpc {
 
@@ -28,7 +28,7 @@ template <> struct MomVec<4> { using type = float4; };
 
 template <int kXf>
 __device__ __forceinline__ float mom_transform(float v) {
-    if constexpr (kXf == 1) return sigmoid_f(v);
+    if constexpr (kXf == 1) return bernoulli_mean(v);
     else return v;
 }
 

@@ -5,7 +5,7 @@
 //                        (read-out: output, loss, e_o = dloss/dout), energy partials, Hebbian spill, trajectory records; errors -> global memory.
 //                        Linear 0's prediction is the constant mu_1 (mcpc_mu1_kernel): its tiles have no GEMM.
 //   mcpc_lw_bwd_kernel   every x update at once: g_l = e_l - f'(x_l) (e_{l+1} W_{l+1}) as a tiled GEMM on the transposed fragments, epilogue = the
-//                        x update of bwd_epilogue (mcpc_kernels.h), in place (an element of x_l is read and written by one thread only), and
+//                        x update with every optimiser and noise mode behind uniform branches, in place (an element of x_l is read and written by one thread only), and
 //                        f(x_l) of the new state for the next forward launch.
 // Given x_t all predictions are independent of each other, and given the errors all back-projections are: the two launch boundaries are the
 // only synchronisation (no grid barrier, no spin-wait, no cooperative launch).
@@ -157,7 +157,7 @@ __device__ __forceinline__ void lw_job_gemm(f32x4 (&acc)[kLwUTW][kLwCTT], const 
     else lw_gemm<false>(acc, (const gu32x4*)A, voff, nkb, kw, Bg, kw, chain0, a_exp, stage, sexp, tid, lane);
 }
 
-// ---- forward epilogues (fwd_epilogue / headf_epilogue of mcpc_kernels.h with the errors in global memory) ----------------------------------
+// ---- forward epilogues: prediction errors and the read-out's loss error go to global memory ------------------------------------------------
 template <int ACT>
 __device__ __forceinline__ float lw_fwd_latent(const LwParams& Q, int l, int utw, int nt, int chain0, int lane, const f32x4 (&acc)[kLwUTW][kLwCTT],
                                                float& amx, float& emx) {
@@ -182,13 +182,12 @@ __device__ __forceinline__ float lw_fwd_latent(const LwParams& Q, int l, int utw
             const size_t row = (size_t)chain * npad + u0;
             const f32x4 x = ld4(Ly.x + row);
             const f32x4 mub = l > 0 ? bias : ld4(P.mu1 + row);
-            const f32x4 d = x - (acc[i][ct] + mub);               // x - mu
-            const f32x4 e = d * ecoef;
+            f32x4 d;                                              // x - mu
+            const f32x4 e = pc_error4(x, acc[i][ct] + mub, ecoef, d);
             if (l > 0) st4(eg + row, e);
             if (slot >= 0) {
                 const f32x4 z = splat(0.f);
-                f32x4 fx;
-                fx.x = actf<ACT>(x.x); fx.y = actf<ACT>(x.y); fx.z = actf<ACT>(x.z); fx.w = actf<ACT>(x.w);
+                const f32x4 fx = act4<ACT>(x);
                 const size_t srow = (size_t)slot * Bpad + chain;
                 st4s(Ly.spill_a + spill_offset(Ly.spill_a_tm, srow, u0, npad), live ? fx : z);
                 amx = absmax4(amx, live ? fx : z);
@@ -201,8 +200,7 @@ __device__ __forceinline__ float lw_fwd_latent(const LwParams& Q, int l, int utw
                 }
             }
             if (rec != nullptr && live) st_unpadded(rec, chain, n, u0, x);
-            const f32x4 dd = d * d;
-            esum += live ? 0.5f * ecoef * (dd.x + dd.y + dd.z + dd.w) : 0.0f;
+            esum += live ? pc_energy4(d, ecoef) : 0.0f;
         }
     }
     return esum;
@@ -231,33 +229,7 @@ __device__ __forceinline__ float lw_fwd_head(const LwParams& Q, int utw, int nt,
             f32x4 e = splat(0.f);
             if (kind != MCPC_LOSS_NONE) {
                 const f32x4 y = ld4(H.y + row);
-                const float ov[4] = {o.x, o.y, o.z, o.w}, yv[4] = {y.x, y.y, y.z, y.w};
-                float ev[4];
-                if (kind == MCPC_LOSS_GAUSSIAN) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const bool on = live && (u0 + r) >= mask_start && (u0 + r) < n;
-                        const float dlt = ov[r] - yv[r];
-                        ev[r] = on ? inv_var * dlt : 0.f;
-                        lsum += on ? 0.5f * inv_var * dlt * dlt : 0.f;
-                    }
-                } else if (do_energy) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const bool on = live && (u0 + r) >= mask_start && (u0 + r) < n;
-                        float sg, bc;
-                        sigmoid_bce_f(ov[r], yv[r], sg, bc);
-                        ev[r] = on ? sg - yv[r] : 0.f;
-                        lsum += on ? bc : 0.f;
-                    }
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const bool on = live && (u0 + r) >= mask_start && (u0 + r) < n;
-                        ev[r] = on ? sigmoid_f(ov[r]) - yv[r] : 0.f;
-                    }
-                }
-                e.x = ev[0]; e.y = ev[1]; e.z = ev[2]; e.w = ev[3];
+                MCPC_READOUT_LOSS4(e, o, y, kind, do_energy, inv_var, lsum, live && (u0 + r) >= mask_start && (u0 + r) < n, true);
             }
             st4(Q.err_o + row, e);
             if (slot >= 0) { st4s(H.spill_e + spill_offset(H.spill_tm, (size_t)slot * Bpad + chain, u0, npad), e); omx = absmax4(omx, e); }
@@ -330,7 +302,7 @@ __global__ __launch_bounds__(kLwThreads) void mcpc_lw_fwd_kernel(const LwParams 
     }
 }
 
-// ---- backward epilogue: the x update of bwd_epilogue<MODE 0> on global rows, f(x_new) for the next forward launch -----------------------------
+// ---- backward epilogue: the x update on global rows (every optimiser and noise mode), f(x_new) for the next forward launch -------- -----------------------------
 template <int ACT>
 __device__ __forceinline__ void lw_bwd_update(const LwParams& Q, int l, float sign, int utw, int nt, int chain0, int lane,
                                               const f32x4 (&acc)[kLwUTW][kLwCTT]) {
@@ -352,11 +324,7 @@ __device__ __forceinline__ void lw_bwd_update(const LwParams& Q, int l, float si
             const size_t row = (size_t)chain * npad + u0;
             const f32x4 x = ld4(Ly.x + row), back = acc[i][ct];
             const f32x4 e = l > 0 ? ld4(eg + row) : (x - ld4(P.mu1 + row)) * ecoef;
-            f32x4 g;
-            g.x = e.x + sign * actd<ACT>(x.x, actf<ACT>(x.x)) * back.x;
-            g.y = e.y + sign * actd<ACT>(x.y, actf<ACT>(x.y)) * back.y;
-            g.z = e.z + sign * actd<ACT>(x.z, actf<ACT>(x.z)) * back.z;
-            g.w = e.w + sign * actd<ACT>(x.w, actf<ACT>(x.w)) * back.w;
+            const f32x4 g = x_grad4<ACT>(x, e, back, sign);
             if (!P.update_x) {          // gradients only: x and f(x) stay
                 if (live && Ly.xgrad != nullptr) st_unpadded(Ly.xgrad, chain, n, u0, g);
                 continue;
@@ -365,33 +333,21 @@ __device__ __forceinline__ void lw_bwd_update(const LwParams& Q, int l, float si
             if (P.xopt == MCPC_XOPT_SGD) {
                 xn = x - g * lr;
             } else {
-                // torch.optim.Adam single-tensor path (adam_x, mcpc_device.h); the moments are tile-major (tile_major_offset)
-                const size_t mrow = tile_major_offset(chain, u0, npad);
+                const size_t mrow = tile_major_offset(chain, u0, npad);                    // (the moments are tile-major)
                 f32x4 m = ld4s(Ly.m + mrow), v = ld4s(Ly.v + mrow);
-                m.x = adam_m(m.x, g.x, P.omb1); m.y = adam_m(m.y, g.y, P.omb1); m.z = adam_m(m.z, g.z, P.omb1); m.w = adam_m(m.w, g.w, P.omb1);
-                v.x = adam_v(v.x, g.x, P.beta2, P.omb2); v.y = adam_v(v.y, g.y, P.beta2, P.omb2); v.z = adam_v(v.z, g.z, P.beta2, P.omb2); v.w = adam_v(v.w, g.w, P.beta2, P.omb2);
+                adam_moments4(m, v, g, P.omb1, P.beta2, P.omb2);
                 st4s(Ly.m + mrow, m);
                 st4s(Ly.v + mrow, v);
-                const float nss = P.adam_coef[0], bc2s = P.adam_coef[1], eps = P.eps;      // (the host passes this step's pair)
-                xn.x = adam_x(x.x, m.x, v.x, nss, bc2s, eps);
-                xn.y = adam_x(x.y, m.y, v.y, nss, bc2s, eps);
-                xn.z = adam_x(x.z, m.z, v.z, nss, bc2s, eps);
-                xn.w = adam_x(x.w, m.w, v.w, nss, bc2s, eps);
+                xn = adam_x4(x, m, v, P.adam_coef[0], P.adam_coef[1], P.eps);              // (the host passes this step's pair)
             }
             if (P.noise_mode == MCPC_NOISE_PHILOX) {
                 xn = xn + normals4(seed, step, (uint32_t)l, (uint32_t)(chain_base + (uint64_t)chain), (uint32_t)(u0 >> 2)) * nscale;
             } else if (P.noise_mode == MCPC_NOISE_EXTERNAL && live) {
                 xn = xn + ld_unpadded(Ly.ext_noise, chain, n, u0) * nscale;                // (the host passes this step's image)
             }
-            // padded units stay exactly zero (their gradient is zero; only the noise must be masked)
-            if (u0 + 0 >= n) xn.x = 0.f;
-            if (u0 + 1 >= n) xn.y = 0.f;
-            if (u0 + 2 >= n) xn.z = 0.f;
-            if (u0 + 3 >= n) xn.w = 0.f;
+            zero_padded4(xn, u0, n);
             st4(Ly.x + row, xn);
-            f32x4 fx;
-            fx.x = actf<ACT>(xn.x); fx.y = actf<ACT>(xn.y); fx.z = actf<ACT>(xn.z); fx.w = actf<ACT>(xn.w);
-            st4(Q.fx[l] + row, fx);
+            st4(Q.fx[l] + row, act4<ACT>(xn));
         }
     }
 }

@@ -141,8 +141,7 @@ __device__ __forceinline__ void ws2_fill_fx(const KLayer& Ly, float* lds, int ch
     for (int idx = tid; idx < ct_rows * qpr; idx += kWs2Threads) {
         const int r = idx / qpr, u0 = 4 * (idx - r * qpr);
         const f32x4 x = ld4s(Ly.x + (size_t)(chain0 + r) * Ly.npad + u0);
-        f32x4 fx;
-        fx.x = actf<ACT>(x.x); fx.y = actf<ACT>(x.y); fx.z = actf<ACT>(x.z); fx.w = actf<ACT>(x.w);
+        const f32x4 fx = act4<ACT>(x);
         st4(lds + Ly.lds_a + r * Ly.ld + u0, fx);
         if (keep_x) st4(lds + Ly.lds_x + r * Ly.ld + u0, x);
         // generation 0 of the row's exponent word (mcpc_kernels.h: rowexp_track; the words were zeroed with the plan)
@@ -189,7 +188,7 @@ __device__ __forceinline__ float* vreg(float* s) {
     return (float*)(((uint64_t)hi << 32) | lo);
 }
 
-// HEADF epilogue of the E waves: arithmetic of headf_epilogue (mcpc_kernels.h), uniforms in VGPRs
+// HEADF epilogue of the E waves: headf_epilogue (mcpc_kernels.h) with its uniforms in VGPRs
 template <int CTT, int NW, int NTW>
 __device__ __forceinline__ float ws2_headf_epilogue(const KParams& P, const KPhase& ph, float* lds, int nt, int wave, int lane,
                                                     int chain0, const f32x4 (&acc)[NTW][CTT], const f32x4 (&pa)[NTW][CTT],
@@ -217,33 +216,7 @@ __device__ __forceinline__ float ws2_headf_epilogue(const KParams& P, const KPha
             f32x4 e = splat(0.f);
             if (kind != MCPC_LOSS_NONE) {
                 const f32x4 y = pa[i][ct];
-                const float ov[4] = {o.x, o.y, o.z, o.w}, yv[4] = {y.x, y.y, y.z, y.w};
-                float ev[4];
-                if (kind == MCPC_LOSS_GAUSSIAN) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const bool on = live && (u0 + r) >= mask_start && (u0 + r) < n;
-                        const float dlt = ov[r] - yv[r];
-                        ev[r] = on ? inv_var * dlt : 0.f;
-                        lsum += on ? 0.5f * inv_var * dlt * dlt : 0.f;
-                    }
-                } else if (do_energy) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const bool on = live && (u0 + r) >= mask_start && (u0 + r) < n;
-                        float sg, bc;
-                        sigmoid_bce_f(ov[r], yv[r], sg, bc);
-                        ev[r] = on ? sg - yv[r] : 0.f;
-                        lsum += on ? bc : 0.f;
-                    }
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const bool on = live && (u0 + r) >= mask_start && (u0 + r) < n;
-                        ev[r] = on ? sigmoid_f(ov[r]) - yv[r] : 0.f;
-                    }
-                }
-                e.x = ev[0]; e.y = ev[1]; e.z = ev[2]; e.w = ev[3];
+                MCPC_READOUT_LOSS4(e, o, y, kind, do_energy, inv_var, lsum, live && (u0 + r) >= mask_start && (u0 + r) < n, true);
             }
             st4(lds + eo_off + cl * ld + (u0 - tile0x16), e);
             if (slot >= 0) { st4s(spill + spill_offset(spill_tm, (size_t)chain, u0, npad), e); omx = absmax4(omx, e); }

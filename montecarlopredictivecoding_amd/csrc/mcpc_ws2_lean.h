@@ -14,7 +14,7 @@
 //     (LeanLane::livem) -- until round 3 such a workgroup took the generic epilogues and every launch waited for it (+17 %
 //     per step at 7000 chains);
 //   * three loads per slot whatever the entry type   -> each entry type requests exactly its operands.
-// The arithmetic per element is the generic epilogue's, operation for operation: trajectories stay bitwise those of the
+// The arithmetic per element is mcpc_step_math.h's, like the generic epilogues': trajectories stay bitwise those of the
 // other kernel forms and schedules (tests/test_gpu_fullsize.py, tests/test_gpu_rounds.py; bench.py self_check).
 //
 // XL (KParams::xl, 16-chain plans whose LDS has the room -- 45 KB more at cfg-M): the state rows x_l of the workgroup's chains, the
@@ -116,11 +116,6 @@ __device__ __forceinline__ f32x4 mask4(f32x4 v, uint32_t m) {
 }
 
 // tiles of this wave in an entry: tile(i) = tile0 + kk + NW i, i < nt
-template <int ACT> __device__ __forceinline__ f32x4 act4(f32x4 x) {
-    f32x4 r;
-    r.x = actf<ACT>(x.x); r.y = actf<ACT>(x.y); r.z = actf<ACT>(x.z); r.w = actf<ACT>(x.w);
-    return r;
-}
 
 // ---- FWD entry (layer l): e_l = c_l (x_l - mu_l), energies, E_l -> LDS, Hebbian spills ------------------------------
 // mu_l = acc (from G, in LDS at out_lds) + bias for l >= 1; the constant mu_1 row for l == 0 (no GEMM).
@@ -212,8 +207,8 @@ __device__ __forceinline__ float lean_fwd(const KParams& P, const KPhase& ph, fl
 #pragma unroll
         for (int ct = 0; ct < CTT; ++ct) {
             const f32x4 x = xv[i][ct];
-            const f32x4 d = x - (av[i][ct] + bv[i][ct]);                  // x - mu
-            const f32x4 e = d * ecoef;
+            f32x4 d;                                                      // x - mu
+            const f32x4 e = pc_error4(x, av[i][ct] + bv[i][ct], ecoef, d);
             if (l > 0) { *reinterpret_cast<f32x4*>(e_lds + lrowb[ct] + tb) = e; rmx = absmax4(rmx, e); }
             if (M::spills(slot)) {
 #ifdef MCPC_EXP_SPILL_LINEAR      // timing experiment only (rows permuted inside the workgroup's block): one contiguous KiB per store
@@ -230,8 +225,7 @@ __device__ __forceinline__ float lean_fwd(const KParams& P, const KPhase& ph, fl
                 else gst4s(spill_e, rowb[ct] + tb, gld4s(spill_e, rowb[ct] + tb) + e);   // Linear 0: only sum_t e_1 is needed
             }
             if (rec != nullptr && L.livem[ct]) st_unpadded(rec, (int)L.chain[ct], Ly.n, 16 * tile + 4 * L.q, x);
-            const f32x4 dd = d * d;
-            esum += L.livem[ct] ? 0.5f * ecoef * (dd.x + dd.y + dd.z + dd.w) : 0.f;          // (a select, not a product: whatever a padding chain holds)
+            esum += L.livem[ct] ? pc_energy4(d, ecoef) : 0.f;                  // (a select, not a product: whatever a padding chain holds)
         }
     }
     if (M::spills(slot)) {
@@ -285,8 +279,7 @@ __device__ __forceinline__ void lean_store_x(const KParams& P, const float* lds,
 // back = acc from G (GEMM over E_{l+1}, or the read-out back-projection handed over in registers); none for sign == 0.
 // ADAM (the MAP warm-up, torch.optim.Adam on x without noise): the moments m, v of the wave's tiles are requested with x,
 // in front of the wait for the partner's block -- the generic epilogue loads them behind it, one L2/HBM round trip exposed
-// per x update -- and the arithmetic is the generic epilogue's, operation for operation (s_tab: row of the bias-correction
-// table).
+// per x update (s_tab: row of the bias-correction table).
 template <int CTT, int NW, int NTW, int ACT, bool NOISE, bool ADAM = false, bool XL = false, bool REG = false, class M = Ws2Generic>
 __device__ __forceinline__ void lean_bwd(const KParams& P, const KPhase& ph, float* lds, int nt, int kk, const LeanLane<CTT>& L,
                                          int t, const int* prog_g, int need, int* err, int& dead, int s_tab = 0, float* rx = nullptr,
@@ -382,37 +375,21 @@ __device__ __forceinline__ void lean_bwd(const KParams& P, const KPhase& ph, flo
             } else {
                 e = ev[i][ct];
             }
-            f32x4 g;
-            g.x = e.x + sign * actd<ACT>(x.x, actf<ACT>(x.x)) * back.x;
-            g.y = e.y + sign * actd<ACT>(x.y, actf<ACT>(x.y)) * back.y;
-            g.z = e.z + sign * actd<ACT>(x.z, actf<ACT>(x.z)) * back.z;
-            g.w = e.w + sign * actd<ACT>(x.w, actf<ACT>(x.w)) * back.w;
+            const f32x4 g = x_grad4<ACT>(x, e, back, sign);
             f32x4 xn;
             if constexpr (ADAM) {
-                // torch.optim.Adam single-tensor path: lerp_, mul_/addcmul_, sqrt/bias2 + eps, addcdiv_ (adam_x, mcpc_device.h)
                 f32x4 m = mv[i][ct], v = vv[i][ct];
-                m.x = adam_m(m.x, g.x, P.omb1); m.y = adam_m(m.y, g.y, P.omb1); m.z = adam_m(m.z, g.z, P.omb1); m.w = adam_m(m.w, g.w, P.omb1);
-                v.x = adam_v(v.x, g.x, P.beta2, P.omb2); v.y = adam_v(v.y, g.y, P.beta2, P.omb2); v.z = adam_v(v.z, g.z, P.beta2, P.omb2); v.w = adam_v(v.w, g.w, P.beta2, P.omb2);
+                adam_moments4(m, v, g, P.omb1, P.beta2, P.omb2);
                 const uint32_t mb = (mul24(L.chain[ct] >> 4, (uint32_t)Ly.ntiles) + (uint32_t)tile) * 1024u + 16u * (uint32_t)(L.c + 16 * L.q);
                 gst4s(Ly.m, mb, m);
                 gst4s(Ly.v, mb, v);
-                const float nss = P.adam_coef[2 * s_tab], bc2s = P.adam_coef[2 * s_tab + 1], eps = P.eps;
-                xn.x = adam_x(x.x, m.x, v.x, nss, bc2s, eps);
-                xn.y = adam_x(x.y, m.y, v.y, nss, bc2s, eps);
-                xn.z = adam_x(x.z, m.z, v.z, nss, bc2s, eps);
-                xn.w = adam_x(x.w, m.w, v.w, nss, bc2s, eps);
+                xn = adam_x4(x, m, v, P.adam_coef[2 * s_tab], P.adam_coef[2 * s_tab + 1], P.eps);
             } else {
                 xn = x - g * lr;
             }
             if constexpr (NOISE)
                 xn = xn + normals4(seed, step, (uint32_t)l, (uint32_t)(chain_base + (uint64_t)L.chain[ct]), (uint32_t)(4 * tile + L.q)) * nscale;
-            if (pad_tile) {       // padded units stay exactly zero (their gradient is zero; only the noise must be masked)
-                const int u0 = 16 * tile + 4 * L.q;
-                if (u0 + 0 >= n) xn.x = 0.f;
-                if (u0 + 1 >= n) xn.y = 0.f;
-                if (u0 + 2 >= n) xn.z = 0.f;
-                if (u0 + 3 >= n) xn.w = 0.f;
-            }
+            if (pad_tile) zero_padded4(xn, 16 * tile + 4 * L.q, n);
             if constexpr (XL) {
                 *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(lds + Ly.lds_x) + lrowb[ct] + tb) = xn;
             } else {
@@ -534,42 +511,17 @@ __device__ __forceinline__ float lean_headf(const KParams& P, const KPhase& ph, 
                     const uint32_t nib = yw[i][ct] >> (16u * (uint32_t)(tile & 1) + 4u * (uint32_t)L.q);
                     y.x = (float)(nib & 1u); y.y = (float)((nib >> 1) & 1u); y.z = (float)((nib >> 2) & 1u); y.w = (float)((nib >> 3) & 1u);
                 }
+                // a padding chain's error is computed like any chain's; only its share of the loss is dropped (livem)
                 const float ov[4] = {o.x, o.y, o.z, o.w}, yy[4] = {y.x, y.y, y.z, y.w};
                 float ev[4];
                 const int u0 = 16 * tile + 4 * L.q;
                 if (kind == MCPC_LOSS_GAUSSIAN) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const bool on = inside || ((u0 + r) >= mask_start && (u0 + r) < n);
-                        const float dlt = ov[r] - yy[r];
-                        ev[r] = on ? inv_var * dlt : 0.f;
-                        lsum += (on && L.livem[ct]) ? 0.5f * inv_var * dlt * dlt : 0.f;
-                    }
-                } else if (do_energy) {
-                    if (inside) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            float sg, bc;
-                            sigmoid_bce_f(ov[r], yy[r], sg, bc);
-                            ev[r] = sg - yy[r];
-                            lsum += L.livem[ct] ? bc : 0.f;
-                        }
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const bool on = (u0 + r) >= mask_start && (u0 + r) < n;
-                            float sg, bc;
-                            sigmoid_bce_f(ov[r], yy[r], sg, bc);
-                            ev[r] = on ? sg - yy[r] : 0.f;
-                            lsum += (on && L.livem[ct]) ? bc : 0.f;
-                        }
-                    }
+                    MCPC_LOSS_GAUSSIAN4(ev, ov, yy, inv_var, lsum, inside || ((u0 + r) >= mask_start && (u0 + r) < n), L.livem[ct])
+                } else if (do_energy) {       // (a tile whose every unit counts: a wave-uniform branch instead of a select per unit)
+                    if (inside) { MCPC_LOSS_BERNOULLI_ENERGY4(ev, ov, yy, lsum, true, L.livem[ct]) }
+                    else { MCPC_LOSS_BERNOULLI_ENERGY4(ev, ov, yy, lsum, (u0 + r) >= mask_start && (u0 + r) < n, L.livem[ct]) }
                 } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const bool on = inside || ((u0 + r) >= mask_start && (u0 + r) < n);
-                        ev[r] = on ? sigmoid_f(ov[r]) - yy[r] : 0.f;
-                    }
+                    MCPC_LOSS_BERNOULLI_GRAD4(ev, ov, yy, inside || ((u0 + r) >= mask_start && (u0 + r) < n))
                 }
                 e.x = ev[0]; e.y = ev[1]; e.z = ev[2]; e.w = ev[3];
             }
