@@ -259,6 +259,27 @@ int mcpc_philox_normals(int device, uint64_t seed, uint64_t step, int layer, uin
 int mcpc_moments_accumulate(int device, const float* rec, int64_t row_elems, int32_t first, int32_t stride, int32_t n,
                             int32_t transform, double* sum, double* sumsq, int accumulate, void* stream);
 
+/* Per-chain energies of recorded states, evaluated on the device (the reference has them per datapoint: is_return_batchelement_loss,
+ * PCLayer(is_keep_energy_per_datapoint=True), get_energies(is_per_datapoint=True); pc_trainer.py:776-836, pc_layer.py:250-262).
+ * A ROW is one chain at one recorded step.  x_rec[l], l < n_latent: [n_rec][batch][n_l] fp32, as mcpc_run writes rec_x[l] (n_rec = 1
+ * with plain [batch][n_l] states evaluates a current state).  For row r = k * batch + chain the library forms the forward pass
+ * mu_j = f(x_{j-1}) W_j^T + b_j on the engine's packed weights -- the step kernels' own GEMM and per-element arithmetic: a prediction is
+ * bitwise theirs -- with mu_1 from `inputs` ([batch][n_in], NULL = zeros; the inputs bound with mcpc_bind_inputs are not consulted) and the
+ * target row of the chain as bound with mcpc_bind_target, and writes
+ *   out[r][0] = the read-out loss of the row (loss_kind / loss_var / mask_start as in mcpc_run_desc; 0 for MCPC_LOSS_NONE),
+ *   out[r][1 + l] = E_{l+1} = c_l * 0.5 * |x_l - mu_l|^2 (unused columns 0),   out[r][MCPC_MAX_LATENT + 1] = their sum plus the loss.
+ * Summed over the chains of record k this is the row mcpc_run writes into energies_out for the step that recorded k.
+ * Every sum has one fixed order that holds the row's own values only (fp32 over the four units a lane holds and the unit tiles of its
+ * wave, fp64 from there: lanes, waves, unit-tile jobs, layers): a row's result does not depend on the other rows, on n_rec, or on
+ * max_rows.  The records are processed in chunks of max_rows rows (0 = default 16384; rounded up to a multiple of 64) through scratch
+ * the engine allocates on the first call and enlarges when a later call asks for a longer chunk: 8 B per row and padded unit, plus 8 B
+ * per row and 128-unit job.  The engine's state, sums and bound pointers are not touched.  Works on every engine form (the weight
+ * fragments are the same).  Asynchronous on `stream` but for those allocations.
+ * MCPC_EINVAL: null engine / x_rec / x_rec[l] / out, n_rec < 0, max_rows < 0, unknown loss_kind, a loss without a read-out, loss_var
+ * <= 0, mask_start outside 0..n_out-1.  MCPC_ESTATE: parameters not bound, a loss without a bound target.  Nothing is launched then. */
+int mcpc_chain_energies(mcpc_engine* e, const float* inputs, const float* const* x_rec, int32_t n_rec, int32_t loss_kind,
+                        double loss_var, int32_t mask_start, double* out, int32_t max_rows, void* stream);
+
 /* Synchronise `stream` and report device-side faults of the runs issued so far (the wave-specialised step kernel
  * bounds every intra-workgroup wait; a wait that runs out is recorded instead of hanging the GPU).
  * Returns MCPC_ESTATE if the last results must not be used.  The only call besides create/destroy that
@@ -315,6 +336,13 @@ int mcpc_debug_poison_lds(int device, uint32_t word, void* stream);
  * gridDim.x the chain tiles. */
 int mcpc_debug_lw_jobs(int32_t n_latent, const int32_t* sizes, int32_t n_out, int32_t* fwd, int32_t* bwd, int32_t cap,
                        int32_t* n_fwd, int32_t* n_bwd, int32_t* tile);
+
+/* Diagnostic (tests only; no device work): the job table of mcpc_chain_energies for a network as in mcpc_debug_lw_jobs.  Writes up to
+ * `cap` (Linear, first 16-unit tile) pairs into jobs (Linear n_latent = the read-out), their count into n_jobs (also when it exceeds
+ * cap), into n_head how many of them, at the front, belong to the read-out (a call without a loss launches the rest only), and into
+ * tile[0..1] the rows and the 16-unit tiles one workgroup covers.  The jobs of one Linear are contiguous, first tile ascending. */
+int mcpc_debug_chain_energy_jobs(int32_t n_latent, const int32_t* sizes, int32_t n_out, int32_t* jobs, int32_t cap, int32_t* n_jobs,
+                                 int32_t* n_head, int32_t* tile);
 
 /* Diagnostic (tests only; no device work, no device needed): everything mcpc_create would decide for `desc` on a device of `n_cu` compute
  * units and `total_mem` bytes of memory (read only when desc->spill_budget_bytes <= 0; 0 = unknown), as one JSON object: "form"

@@ -98,6 +98,8 @@ SYMBOLS = {
                                       C.c_void_p, C.c_int, C.c_void_p]),
     "mcpc_moments_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "mcpc_chain_energies": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_int32,
+                                      C.c_void_p, C.c_int32, C.c_void_p]),
     "mcpc_query": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                              C.POINTER(C.c_int32)]),
     "mcpc_step_kernel_name": (C.c_char_p, [C.c_void_p]),
@@ -111,6 +113,8 @@ SYMBOLS = {
     "mcpc_debug_poison_lds": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p]),
     "mcpc_debug_lw_jobs": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mcpc_debug_chain_energy_jobs": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mcpc_debug_plan": (C.c_int, [C.POINTER(NetDesc), C.c_int32, C.c_int64, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
 }
 

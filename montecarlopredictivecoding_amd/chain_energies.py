@@ -1,0 +1,80 @@
+"""Per-chain energies of a Langevin call: the request (``PCTrainer.mcpc_chain_energies``) and the result
+(``PCTrainer.mcpc_last_chain_energies``, ``PCTrainer.mcpc_state_energies``).
+
+The reference reports energies per datapoint behind ``is_return_batchelement_loss``, ``PCLayer(is_keep_energy_per_datapoint=True)`` and
+``get_energies(is_per_datapoint=True)``; here a fused call evaluates them on the device out of its record ring
+(csrc/mcpc_chain_energy.h) and the trajectory is never materialised.  This module holds no device code: validation of the request,
+which steps are evaluated, and the split of the library's ``[n, B, L + 2]`` table into the three tensors a caller reads.
+"""
+from dataclasses import dataclass
+from typing import List
+
+import torch
+
+_KEYS = ("begin", "stride")
+
+
+def sample_steps(begin: int, T: int, stride: int) -> range:
+    """The steps of a call of T steps whose states are evaluated."""
+    return range(begin, T, stride)
+
+
+@dataclass(frozen=True)
+class ChainEnergySpec:
+    """A validated ``mcpc_chain_energies`` request for a call of ``T`` steps."""
+    begin: int
+    stride: int
+    T: int
+
+    @property
+    def steps(self) -> List[int]:
+        return list(sample_steps(self.begin, self.T, self.stride))
+
+    @property
+    def n(self) -> int:
+        return len(sample_steps(self.begin, self.T, self.stride))
+
+    def chunk(self, t0: int, n_steps: int):
+        """(first, count): the evaluated steps among t0 .. t0 + n_steps - 1 are rows first, first + stride, ... of a chunk that holds
+        one record per step from t0 on."""
+        f = self.begin if t0 <= self.begin else self.begin + -(-(t0 - self.begin) // self.stride) * self.stride
+        return f - t0, len(range(f, min(t0 + n_steps, self.T), self.stride))
+
+
+def validate_spec(spec, T: int) -> ChainEnergySpec:
+    """``PCTrainer.mcpc_chain_energies`` -> ChainEnergySpec, or ValueError: not a dict, unknown keys, ``begin`` outside [0, T),
+    ``stride`` < 1.  Defaults: begin=0, stride=1."""
+    if not isinstance(spec, dict):
+        raise ValueError(f"mcpc_chain_energies: expected a dict or None, got {type(spec).__name__}")
+    unknown = sorted(k for k in spec if k not in _KEYS)
+    if unknown:
+        raise ValueError(f"mcpc_chain_energies: unknown keys {unknown}; known: {list(_KEYS)}")
+    begin, stride = spec.get("begin", 0), spec.get("stride", 1)
+    for name, v in (("begin", begin), ("stride", stride)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"mcpc_chain_energies: {name} must be an int, got {v!r}")
+    if not 0 <= begin < T:
+        raise ValueError(f"mcpc_chain_energies: begin={begin} outside [0, T={T})")
+    if stride < 1:
+        raise ValueError(f"mcpc_chain_energies: stride={stride}, must be at least 1")
+    return ChainEnergySpec(begin=begin, stride=stride, T=T)
+
+
+@dataclass
+class ChainEnergies:
+    """Energies of ``n`` states of ``B`` chains, fp64, on the model's device.  ``steps[k]`` is the step of the call whose forward saw
+    state k (empty for ``mcpc_state_energies``).  ``loss [n, B]``, ``energy [n, B, L]`` (divided by the trainer's
+    ``energy_coefficient``, as ``results["energy"]`` is), ``overall [n, B]``: summed over the chains they are the call's own results at
+    those steps.  A staged (CPU) model gets them on the CPU; a sharded trainer sees its local chains only, in local order."""
+    steps: List[int]
+    loss: torch.Tensor
+    energy: torch.Tensor
+    overall: torch.Tensor
+
+
+def from_table(table: torch.Tensor, n_layers: int, energy_coefficient: float, steps, device) -> ChainEnergies:
+    """The library's ``[n, B, L_max + 2]`` table (loss, E_1.., overall) -> ChainEnergies on ``device``."""
+    table = table.to(device)
+    return ChainEnergies(steps=list(steps), loss=table[:, :, 0].contiguous(),
+                         energy=(table[:, :, 1:1 + n_layers] / energy_coefficient).contiguous(),
+                         overall=table[:, :, -1].contiguous())

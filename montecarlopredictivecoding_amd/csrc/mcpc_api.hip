@@ -15,6 +15,7 @@
 #include "mcpc_kernels.h"
 #include "mcpc_moments.h"
 #include "mcpc_plan.h"
+#include "mcpc_chain_energy.h"
 
 using namespace mcpc;
 
@@ -85,6 +86,16 @@ struct mcpc_engine : EnginePlan {
     unsigned long long* clk = nullptr;   // profiling: {shader cycles, 100 MHz ticks} of one wave per launch (KParams::clk)
     float* dummy = nullptr;         // 4 KiB of zeros (KParams::dummy)
     int* rr_tab = nullptr;          // device copy of rr_host (round schedule)
+    // per-chain energies (mcpc_chain_energy.h): the evaluator's own scratch, allocated by the first mcpc_chain_energies and grown by a
+    // call that asks for a larger chunk (the old buffers are retired, like every buffer launches in the stream may still use)
+    float* ce_x[kMaxLatent]{};      // x_l    [ce_rows][npad_l]
+    float* ce_fx[kMaxLatent]{};     // f(x_l) [ce_rows][npad_l]
+    float* ce_mu1 = nullptr;        // mu_1 of the call's inputs [Bpad][npad_0]
+    double* ce_part = nullptr;      // [job][ce_rows]
+    LwJob* ce_jobs = nullptr;       // device copy of the job table (ce_job_table)
+    int ce_njobs = 0, ce_nhead = 0;
+    CeFinish ce_finish{};
+    int ce_rows = 0;                // rows the scratch holds (a multiple of kLwChains)
     // diagnostics, host strings set while launching (no device work): what the last mcpc_run and each Linear's last flush launched
     std::string last_step;                       // mcpc_last_step_kernel_name
     std::string last_flush[kMaxLatent + 1];      // mcpc_last_flush_plan, per Linear j >= 1
@@ -139,6 +150,8 @@ int free_all(mcpc_engine* e) {
     F(e->e0sum); F(e->mu1); F(e->ypad); F(e->ytile); F(e->ybits); F(e->y_binary); F(e->spill_eo); F(e->slab); F(e->epart); F(e->adam_coef); F(e->main.dev); F(e->err); F(e->wexp); F(e->spillmax); F(e->clk); F(e->dummy); F(e->u.plan.dev);
     for (int l = 0; l < kMaxLatent; ++l) { F(e->lw_fx[l]); F(e->lw_err[l]); }
     F(e->lw_err_o); F(e->lw_jobs);
+    for (int l = 0; l < kMaxLatent; ++l) { F(e->ce_x[l]); F(e->ce_fx[l]); }
+    F(e->ce_mu1); F(e->ce_part); F(e->ce_jobs);
     for (auto& ln : e->lin) { F(ln.Wf); F(ln.Wb); F(ln.bias_pad); F(ln.G); F(ln.Gb); }
     for (auto& ev : e->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     for (int h = 0; h < kMaxRingParts; ++h) { if (e->ev_steps[h]) (void)hipEventDestroy(e->ev_steps[h]); if (e->ev_flush[h]) (void)hipEventDestroy(e->ev_flush[h]); e->ev_steps[h] = e->ev_flush[h] = nullptr; }
@@ -1380,6 +1393,95 @@ int mcpc_moments_accumulate(int device, const float* rec, int64_t row_elems, int
     return MCPC_OK;
 }
 
+int mcpc_chain_energies(mcpc_engine* e, const float* inputs, const float* const* x_rec, int32_t n_rec, int32_t loss_kind, double loss_var,
+                        int32_t mask_start, double* out, int32_t max_rows, void* stream_) {
+    if (!e) return fail(MCPC_EINVAL, "chain energies: null engine");
+    if (!x_rec) return fail(MCPC_EINVAL, "chain energies: x_rec is null");
+    if (!out) return fail(MCPC_EINVAL, "chain energies: out is null");
+    if (n_rec < 0) return fail(MCPC_EINVAL, "chain energies: n_rec=%d, must not be negative", n_rec);
+    if (max_rows < 0) return fail(MCPC_EINVAL, "chain energies: max_rows=%d, must not be negative (0 = default)", max_rows);
+    for (int l = 0; l < e->L; ++l)
+        if (!x_rec[l]) return fail(MCPC_EINVAL, "chain energies: x_rec[%d] is null", l);
+    const bool with_loss = loss_kind != MCPC_LOSS_NONE;
+    const int nlin = e->L + (e->has_head ? 1 : 0);
+    for (int j = 0; j < nlin; ++j)
+        if (!e->lin[j].bound) return fail(MCPC_ESTATE, "chain energies: Linear %d has no bound parameters (mcpc_bind_params + mcpc_params_changed first)", j);
+    if (loss_kind < 0 || loss_kind > 2) return fail(MCPC_EINVAL, "chain energies: loss_kind=%d", loss_kind);
+    if (loss_kind != MCPC_LOSS_NONE) {
+        if (!e->has_head) return fail(MCPC_EINVAL, "chain energies: a loss needs a read-out Linear (n_out > 0)");
+        if (!e->target_bound) return fail(MCPC_ESTATE, "chain energies: loss requested but no target bound");
+        if (loss_kind == MCPC_LOSS_GAUSSIAN && !(loss_var > 0.0)) return fail(MCPC_EINVAL, "chain energies: loss_var must be positive");
+        if (mask_start < 0 || mask_start >= e->d.n_out)
+            return fail(MCPC_EINVAL, "chain energies: mask_start=%d outside 0..%d", mask_start, e->d.n_out - 1);
+    }
+    const int64_t R = (int64_t)n_rec * e->d.batch;
+    if (R == 0) return MCPC_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(e->d.device));
+    // the chunk: a multiple of the 64-row tile, no longer than the call
+    const int64_t want = max_rows > 0 ? max_rows : kCeDefaultRows;
+    const int chunk = (int)(std::min<int64_t>((want + kLwChains - 1) / kLwChains, (R + kLwChains - 1) / kLwChains) * kLwChains);
+    if (!e->ce_jobs) {
+        std::vector<LwJob> jobs;
+        ce_job_table(e->L, e->npad, e->has_head ? e->out_pad : 0, jobs, e->ce_nhead, e->ce_finish);
+        if (jobs.size() > 65535) return fail(MCPC_EINVAL, "chain energies: more than 65535 unit-tile jobs");
+        if (const int rc = upload(e->ce_jobs, jobs, "the chain-energy job table")) return rc;
+        e->ce_njobs = (int)jobs.size();
+        if (const int rc = dmalloc(e->ce_mu1, (size_t)e->Bpad * e->npad[0])) return rc;
+    }
+    if (chunk > e->ce_rows) {
+        for (int l = 0; l < e->L; ++l) {
+            if (e->ce_x[l]) retire(e, e->ce_x[l], stream);
+            if (e->ce_fx[l]) retire(e, e->ce_fx[l], stream);
+            e->ce_x[l] = e->ce_fx[l] = nullptr;
+        }
+        if (e->ce_part) retire(e, e->ce_part, stream);
+        e->ce_part = nullptr;
+        e->ce_rows = 0;
+        for (int l = 0; l < e->L; ++l) {
+            int rc;
+            if ((rc = dmalloc(e->ce_x[l], (size_t)chunk * e->npad[l])) || (rc = dmalloc(e->ce_fx[l], (size_t)chunk * e->npad[l]))) return rc;
+        }
+        if (const int rc = dmalloc(e->ce_part, (size_t)e->ce_njobs * chunk)) return rc;
+        e->ce_rows = chunk;
+    }
+    free_completed_retired(e);
+    // mu_1 of THESE inputs (the step kernels' own kernel: the same bits)
+    {
+        const Lin& l0 = e->lin[0];
+        const size_t total = (size_t)e->Bpad * e->npad[0];
+        hipLaunchKernelGGL(mcpc_mu1_kernel, dim3(grid_for(total)), dim3(256), 0, stream, inputs, l0.W, l0.bias, e->ce_mu1,
+                           e->d.batch, e->d.n_in, e->d.sizes[0], e->Bpad, e->npad[0]);
+    }
+    CeParams Q{};
+    for (int l = 0; l < e->L; ++l) { Q.x[l] = e->ce_x[l]; Q.fx[l] = e->ce_fx[l]; Q.npad[l] = e->npad[l]; Q.ecoef[l] = e->d.ecoef[l]; }
+    for (int j = 1; j < nlin; ++j) { Q.Wf[j] = e->lin[j].Wf; Q.bias[j] = e->lin[j].bias_pad; }
+    Q.npad[e->L] = e->has_head ? e->out_pad : 0;
+    Q.mu1 = e->ce_mu1; Q.y = e->ypad; Q.wexp = e->wexp; Q.part = e->ce_part;
+    Q.job0 = with_loss ? 0 : e->ce_nhead;
+    Q.jobs = e->ce_jobs + Q.job0;
+    Q.L = e->L; Q.B = e->d.batch; Q.n_out = e->d.n_out; Q.chunk = chunk;
+    Q.loss_kind = loss_kind; Q.mask_start = with_loss ? mask_start : 0;
+    Q.inv_var = loss_kind == MCPC_LOSS_GAUSSIAN ? (float)(1.0 / loss_var) : 1.0f;
+    const int njobs = e->ce_njobs - Q.job0;
+    for (int64_t r0 = 0; r0 < R; r0 += chunk) {
+        const int rows = (int)std::min<int64_t>(chunk, R - r0);
+        const int padded = (rows + kLwChains - 1) / kLwChains * kLwChains;          // tiles of this chunk that hold a row
+        for (int l = 0; l < e->L; ++l) {
+            const size_t total4 = (size_t)padded * e->npad[l] / 4;
+            hipLaunchKernelGGL(mcpc_ce_prep_kernel, dim3(grid_for(total4)), dim3(256), 0, stream, x_rec[l] + (size_t)r0 * e->d.sizes[l],
+                               e->ce_x[l], e->ce_fx[l], rows, padded, e->d.sizes[l], e->npad[l], e->d.acts[l]);
+        }
+        Q.rows = rows;
+        Q.row_base = (int)(r0 % e->d.batch);
+        hipLaunchKernelGGL(mcpc_ce_kernel, dim3(padded / kLwChains, njobs), dim3(kLwThreads), 0, stream, Q);
+        hipLaunchKernelGGL(mcpc_ce_finish_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, (const double*)e->ce_part, out, e->ce_finish,
+                           e->L, with_loss ? 1 : 0, rows, chunk, (size_t)r0);
+    }
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
 int mcpc_query(const mcpc_engine* e, int32_t* lds_bytes, int32_t* chains_per_wg, int32_t* n_workgroups, int32_t* spill_slots) {
     if (!e) return fail(MCPC_EINVAL, "null engine");
     if (lds_bytes) *lds_bytes = e->main.lds_bytes;
@@ -1492,6 +1594,22 @@ int mcpc_debug_lw_jobs(int32_t n_latent, const int32_t* sizes, int32_t n_out, in
     for (int i = 0; i < (int)b.size() && i < cap && bwd; ++i) { bwd[2 * i] = b[i].layer; bwd[2 * i + 1] = b[i].ut0; }
     if (n_fwd) *n_fwd = (int32_t)f.size();
     if (n_bwd) *n_bwd = (int32_t)b.size();
+    if (tile) { tile[0] = kLwChains; tile[1] = kLwUnitTiles; }
+    return MCPC_OK;
+}
+
+int mcpc_debug_chain_energy_jobs(int32_t n_latent, const int32_t* sizes, int32_t n_out, int32_t* jobs, int32_t cap, int32_t* n_jobs,
+                                 int32_t* n_head, int32_t* tile) {
+    if (n_latent < 1 || n_latent > kMaxLatent || !sizes || n_out < 0) return fail(MCPC_EINVAL, "bad network");
+    int npad[kMaxLatent];
+    for (int l = 0; l < n_latent; ++l) { if (sizes[l] < 1) return fail(MCPC_EINVAL, "sizes[%d]=%d", l, sizes[l]); npad[l] = pad16(sizes[l]); }
+    std::vector<LwJob> t;
+    int nh = 0;
+    CeFinish F;
+    ce_job_table(n_latent, npad, pad16(n_out), t, nh, F);
+    for (int i = 0; i < (int)t.size() && i < cap && jobs; ++i) { jobs[2 * i] = t[i].layer; jobs[2 * i + 1] = t[i].ut0; }
+    if (n_jobs) *n_jobs = (int32_t)t.size();
+    if (n_head) *n_head = nh;
     if (tile) { tile[0] = kLwChains; tile[1] = kLwUnitTiles; }
     return MCPC_OK;
 }

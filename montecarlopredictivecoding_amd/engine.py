@@ -214,6 +214,33 @@ class Engine:
         self._keep["run"] = keep
         return res
 
+    # ---- per-chain energies ------------------------------------------------------------------------
+    def chain_energies(self, inputs: Optional[torch.Tensor], x_rec: Sequence[torch.Tensor], *, loss_kind=L.LOSS_NONE, loss_var=1.0,
+                       mask_start=0, out: Optional[torch.Tensor] = None, max_rows: int = 0) -> torch.Tensor:
+        """Loss, layer energies and overall of every chain at every recorded step (include/mcpc.h: mcpc_chain_energies).
+
+        ``x_rec[l]``: contiguous fp32 ``[n_rec, batch, n_l]`` as a run records it, or ``[batch, n_l]`` for one state.  ``inputs``:
+        ``[batch, n_in]`` or None (zeros).  The target is the one bound with ``bind_target``.  Returns (or fills ``out``) fp64
+        ``[n_rec, batch, ENERGY_COLS]``: column 0 the loss, 1..L the layer energies, the last one overall.  ``max_rows``: rows per
+        scratch chunk (0 = the library's default); the result does not depend on it.  On the current torch stream."""
+        if len(x_rec) != self.L:
+            raise ValueError(f"x_rec: expected one tensor per latent layer ({self.L}), got {len(x_rec)}")
+        if inputs is not None:
+            _check_tensor(inputs, (self.batch, self.n_in), self.device, "inputs")
+        n_rec = 1 if x_rec[0].dim() == 2 else int(x_rec[0].shape[0])
+        arr = (C.c_void_p * self.L)()
+        for l, t in enumerate(x_rec):
+            shape = (self.batch, self.sizes[l]) if t.dim() == 2 else (n_rec, self.batch, self.sizes[l])
+            _check_tensor(t, shape, self.device, f"x_rec[{l}]")
+            arr[l] = t.data_ptr()
+        if out is None:
+            out = torch.empty(n_rec, self.batch, L.ENERGY_COLS, dtype=torch.float64, device=self.device)
+        else:
+            _check_tensor(out, (n_rec, self.batch, L.ENERGY_COLS), self.device, "out", torch.float64)
+        L.check(self._lib.mcpc_chain_energies(self._h, _ptr(inputs), arr, n_rec, loss_kind, loss_var, mask_start, _ptr(out),
+                                              int(max_rows), self._stream()))
+        return out
+
     # ---- parameter gradients ---------------------------------------------------------------------
     def read_param_grads(self, j: int, dW: torch.Tensor, db: Optional[torch.Tensor], scale=1.0, accumulate=False):
         n_out, n_in = self.lin_shape(j)

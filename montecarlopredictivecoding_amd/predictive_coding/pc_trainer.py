@@ -232,6 +232,12 @@ class PCTrainer(object):
         self.mcpc_last_moments = None
         self.mcpc_moments_chunk_bytes = 1 << 30
         self.mcpc_moments_side_stream = False
+        # per-chain energies of a fused call, evaluated on the device out of the same ring (chain_energies.py): None = off, or
+        # dict(begin=0, stride=1).  A fused call then leaves chain_energies.ChainEnergies in mcpc_last_chain_energies; composes with
+        # mcpc_moments (one ring serves both).  mcpc_chain_energies_max_rows: rows per scratch chunk of the evaluator (0 = its default).
+        self.mcpc_chain_energies = None
+        self.mcpc_last_chain_energies = None
+        self.mcpc_chain_energies_max_rows = 0
 
     # ---- getters & setters (reference :268-461) -------------------------------------------------------
     def get_T(self) -> int:
@@ -453,6 +459,12 @@ class PCTrainer(object):
                 raise NotImplementedError("mcpc_moments is set, and this call runs on the generic torch loop ({}): posterior moments are "
                                           "accumulated by the fused HIP loop only".format(why_not_fused))
             plan["moments"] = _moments.validate_spec(self.mcpc_moments, self._T, len(plan["net"].sizes), plan["net"].n_out)
+        if self.mcpc_chain_energies is not None:
+            from .. import chain_energies as _chain_energies
+            if plan is None:
+                raise NotImplementedError("mcpc_chain_energies is set, and this call runs on the generic torch loop ({}): per-chain energies "
+                                          "are evaluated out of the fused HIP loop's record ring only".format(why_not_fused))
+            plan["chain_energies"] = _chain_energies.validate_spec(self.mcpc_chain_energies, self._T)
         if plan is None:
             # outside what the kernels express: the package's generic torch loop (generic_loop.py), loudly, on the device the model
             # lives on ("must work, need not be fast").  It is no way around a missing GPU: without a visible HIP device
@@ -490,6 +502,9 @@ class PCTrainer(object):
         if plan["mode"] != "fused" and self.mcpc_moments is not None:
             raise NotImplementedError("mcpc_moments is set, and this call runs step by step ({}): posterior moments are accumulated by "
                                       "the fused HIP loop only".format(plan["why_stepwise"]))
+        if plan["mode"] != "fused" and self.mcpc_chain_energies is not None:
+            raise NotImplementedError("mcpc_chain_energies is set, and this call runs step by step ({}): per-chain energies are "
+                                      "evaluated out of the fused HIP loop's record ring only".format(plan["why_stepwise"]))
         if plan["mode"] == "fused":
             self.last_call_mode = "fused"
             with _few_cpu_threads(plan["staged"]):
@@ -820,15 +835,21 @@ class PCTrainer(object):
             energy_mode=L.ENERGY_ALL if is_return_results_every_t else L.ENERGY_LAST)
         host_step_bytes = 4 * plan["B"] * sum(n for n, on in zip(net.sizes, rec_layers) if on)
         self.last_record_slices = 0
-        mom = plan.get("moments")
-        if mom is not None:
-            # posterior moments: the call runs as slices whatever its size, and the records moments ask for are reduced on the device
-            res, self.mcpc_last_moments = self._run_fused_sliced(
+        mom, ce = plan.get("moments"), plan.get("chain_energies")
+        if mom is not None or ce is not None:
+            # posterior moments / per-chain energies: the call runs as slices whatever its size, and the records they ask for are
+            # reduced on the device
+            ce_inputs = None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous())
+            res, last_mom, last_ce = self._run_fused_sliced(
                 eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, is_return_outputs and net.n_out > 0,
-                every_t=is_return_results_every_t, mom=mom)
+                every_t=is_return_results_every_t, mom=mom, ce=ce, ce_inputs=ce_inputs)
+            if mom is not None:
+                self.mcpc_last_moments = last_mom
+            if ce is not None:
+                self.mcpc_last_chain_energies = last_ce
         elif any(rec_layers) and n_rec == T and T * host_step_bytes > self.mcpc_record_chunk_bytes:
-            res, _ = self._run_fused_sliced(eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes,
-                                            is_return_outputs and net.n_out > 0)
+            res, _, _ = self._run_fused_sliced(eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes,
+                                               is_return_outputs and net.n_out > 0)
         else:
             res = eng.run(T, acc_reset=acc_reset, rec_begin=rec_begin, rec_stride=1, rec_count=n_rec if any_rec else 0,
                           rec_x=rec_layers, rec_out=is_return_outputs and net.n_out > 0, **run_kw)
@@ -853,7 +874,8 @@ class PCTrainer(object):
         return self._collect_results(plan, res, T, is_return_results_every_t, is_return_outputs,
                                      is_return_representations, is_return_xs, loss_fn)
 
-    def _run_fused_sliced(self, eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, rec_out, every_t=True, mom=None):
+    def _run_fused_sliced(self, eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, rec_out, every_t=True, mom=None,
+                          ce=None, ce_inputs=None):
         """A call whose every-step trajectory would not fit the record budget on the device, or whose records feed `mcpc_moments`:
         the same T steps as slices of one `mcpc_run` each (slicing does not change a bit of the trajectories,
         tests/test_gpu_fullsize.py).  The latent records of a slice go to one half of a two-buffer device ring.  Records the caller's
@@ -861,19 +883,22 @@ class PCTrainer(object):
         outputs stay on the device, as in the reference (live tensors, pc_trainer.py:733,770).  Records `mom` (a validated
         `mcpc_moments`) asks for are reduced on the device by `moments_accumulate` after each slice, out of the same ring rows, and
         are neither copied nor kept unless the caller asked too.  With `every_t` false the caller gets the last step's records and
-        energies only, as from an unsliced call.  Returns (RunResult, Moments or None)."""
+        energies only, as from an unsliced call.  With `ce` (a validated `mcpc_chain_energies`) every latent layer goes through the
+        ring and `Engine.chain_energies` evaluates the steps asked for out of its rows after each slice, on the call's own stream,
+        under the slicing rules of `mom`.  Returns (RunResult, Moments or None, ChainEnergies or None)."""
         from ..engine import RunResult, moments_accumulate
         dev, B = plan["device"], plan["B"]
         nl = len(net.sizes)
         mom_layers = [mom is not None and l in mom.layers for l in range(nl)]
         mom_out = mom is not None and mom.outputs is not None
-        ring_layers = [a or b_ for a, b_ in zip(rec_layers, mom_layers)]
+        ring_layers = [a or b_ or ce is not None for a, b_ in zip(rec_layers, mom_layers)]
+        reduced = mom is not None or ce is not None
         out_direct = rec_out and every_t                     # every step's outputs are kept anyway: slices write them in place
         ring_out = (rec_out or mom_out) and not out_direct
         S = T
         if any(rec_layers) and every_t:
             S = min(S, self.mcpc_record_chunk_bytes // max(2 * host_step_bytes, 1))
-        if mom is not None:
+        if reduced:
             # one half of the ring is a chunk of at most mcpc_moments_chunk_bytes
             step_bytes = 4 * B * (sum(n for n, on in zip(net.sizes, ring_layers) if on) + (net.n_out if ring_out or mom_out else 0))
             S = min(S, self.mcpc_moments_chunk_bytes // max(step_bytes, 1))
@@ -881,7 +906,7 @@ class PCTrainer(object):
         # A slice boundary inside the window that accumulates parameter gradients would regroup their fp32 sums (one Hebbian flush and
         # one fold of Linear 0's sum per run; tests/test_gpu_widening.py).  A call with moments must leave param.grad bitwise as
         # without them, so it keeps that window in ONE slice: the ring is then as long as the window, whatever the chunk budget says.
-        keep = (run_kw["acc_begin"], run_kw["acc_end"]) if mom is not None and run_kw["acc_end"] > run_kw["acc_begin"] else None
+        keep = (run_kw["acc_begin"], run_kw["acc_end"]) if reduced and run_kw["acc_end"] > run_kw["acc_begin"] else None
         bounds, t0 = [], 0
         while t0 < T:
             n = min(S, T - t0)
@@ -923,6 +948,22 @@ class PCTrainer(object):
                 moments_accumulate(src, first, mom.stride, cnt, acc["out_sum"], acc["out_sumsq"], transform=mom.outputs,
                                    accumulate=True)
 
+        ce_table = torch.empty(ce.n, B, L.ENERGY_COLS, dtype=torch.float64, device=dev) if ce is not None else None
+        ce_kw = dict(loss_kind=run_kw["loss_kind"], loss_var=run_kw["loss_var"], mask_start=run_kw["mask_start"],
+                     max_rows=self.mcpc_chain_energies_max_rows)
+
+        def evaluate(t0, n, half):
+            first, cnt = ce.chunk(t0, n)
+            if cnt == 0:
+                return
+            k0 = (t0 + first - ce.begin) // ce.stride                # index of the slice's first evaluated step among all of them
+            if ce.stride == 1:
+                eng.chain_energies(ce_inputs, [r_[first:first + cnt] for r_ in ring[half]], out=ce_table[k0:k0 + cnt], **ce_kw)
+            else:
+                for k in range(cnt):
+                    row = first + k * ce.stride
+                    eng.chain_energies(ce_inputs, [r_[row:row + 1] for r_ in ring[half]], out=ce_table[k0 + k:k0 + k + 1], **ce_kw)
+
         n_slices = 0
         for t0, n in bounds:
             half = n_slices & 1
@@ -936,6 +977,8 @@ class PCTrainer(object):
                     rec_out_buf=out_full[t0:t0 + n] if out_direct else ring_o[half], **run_kw)
             if mom is not None and not reduce_on_side:
                 reduce(t0, n, half)
+            if ce is not None:
+                evaluate(t0, n, half)
             if ring_out and rec_out and last:
                 out_full[0].copy_(ring_o[half][n - 1])       # (not every_t: the last step's outputs)
             to_host = any(rec_layers) and (every_t or last)
@@ -967,7 +1010,43 @@ class PCTrainer(object):
                 return None if t is None else t.to(md)
             result = Moments(n=mom.n, x_sum=[back(t) for t in acc["x_sum"]], x_sumsq=[back(t) for t in acc["x_sumsq"]],
                              out_sum=back(acc["out_sum"]), out_sumsq=back(acc["out_sumsq"]))
-        return RunResult(energies=energies, rec_x=host, rec_out=out_full), result
+        ce_result = None
+        if ce is not None:
+            from ..chain_energies import from_table
+            ce_result = from_table(ce_table, nl, self._energy_coefficient, ce.steps, plan["model_device"])
+        return RunResult(energies=energies, rec_x=host, rec_out=out_full), result, ce_result
+
+    def mcpc_state_energies(self, inputs, loss_fn: typing.Callable = None, loss_fn_kwargs: dict = {}):
+        """Loss, layer energies and overall of every chain for the CURRENT x of the PCLayers -- what a MAP call leaves -- evaluated on
+        the device (Engine.chain_energies; no step is run, no state or gradient changes).  Returns chain_energies.ChainEnergies with
+        n = 1: ``loss [1, B]``, ``energy [1, B, L]``, ``overall [1, B]``, fp64 on the model's device.  ``inputs``, ``loss_fn`` and
+        ``loss_fn_kwargs`` as in train_on_batch; a model or loss the fused loop does not express raises NotImplementedError."""
+        from ..chain_energies import from_table
+        plan, why = self._plan(inputs, loss_fn, loss_fn_kwargs, False, False, None, None, {}, {}, False, False)
+        if plan is None:
+            raise NotImplementedError("mcpc_state_energies: outside what the HIP engine expresses ({})".format(why))
+        net, loss = plan["net"], plan["loss"]
+        xs = []
+        for l, layer in enumerate(net.pc_layers):
+            x = layer.get_x()
+            if x is None or tuple(x.shape) != (plan["B"], net.sizes[l]) or x.dtype != torch.float32:
+                raise RuntimeError("mcpc_state_energies: PCLayer {} holds no float32 x of shape {}; run a call first".format(
+                    l, (plan["B"], net.sizes[l])))
+            xs.append(x)
+        eng = self._engine_for(plan)
+        with _few_cpu_threads(plan["staged"]):
+            self._sync_params(eng, net, plan=plan)
+            if loss.target is not None:
+                tgt = loss.target
+                if tgt.dtype != torch.float32 or not tgt.is_contiguous() or tgt.device != plan["device"]:
+                    tgt = tgt.to(device=plan["device"], dtype=torch.float32).contiguous()
+                eng.bind_target(tgt)
+            table = eng.chain_energies(None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous()),
+                                       [self._on_engine(plan, x.data.contiguous()) for x in xs],
+                                       loss_kind=loss.kind, loss_var=loss.var, mask_start=loss.mask_start,
+                                       max_rows=self.mcpc_chain_energies_max_rows)
+            eng.sync_check()
+        return from_table(table, len(net.sizes), self._energy_coefficient, [], plan["model_device"])
 
     # ---- step-wise path -------------------------------------------------------------------------------------
     def _run_stepwise(self, plan, inputs, loss_fn, is_sample_x_at_batch_start, is_reset_optimizer_x_at_batch_start,

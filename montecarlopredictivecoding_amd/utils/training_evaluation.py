@@ -147,6 +147,25 @@ def get_mse_rec_posterior(gen_pc, config, dataloader, use_cuda):
     return mse / n_data
 
 
+def get_map_free_energy(gen_pc, config, dataloader, use_cuda):
+    """Free energy of every datum at its MAP state: ``get_mse_rec``'s protocol (one MAP call per batch from a zero pseudo-input) under
+    the UNMASKED loss of the config, then ``overall`` per chain -- read-out loss plus layer energies of the state the call left --
+    evaluated on the device (``PCTrainer.mcpc_state_energies``).  Returns one fp64 ``[N]`` tensor on the model's device, in the
+    loader's order."""
+    import torch
+    gen_pc.train()
+    device = next(gen_pc.parameters()).device
+    pc_trainer = get_pc_trainer(gen_pc, config, training=False, is_mcpc=True)
+    out = []
+    for data, _ in dataloader:
+        data = data.to(device)
+        pseudo_input = torch.zeros(data.shape[0], config["input_size"], device=device)
+        kw = dict(inputs=pseudo_input, loss_fn=config["loss_fn"], loss_fn_kwargs={"_target": data, "_var": config["input_var"]})
+        pc_trainer.train_on_batch(is_log_progress=False, is_return_results_every_t=False, is_checking_after_callback_after_t=False, **kw)
+        out.append(pc_trainer.mcpc_state_energies(**kw).overall[0])
+    return torch.cat(out)
+
+
 def marginal_likelihood_from_logits(logits, dataloader):
     """log (1/S) sum_s p(y | o_s), averaged over the data, for read-out logits o_s [S, n0] (clamped to +-20 as the reference
     does, training_evaluation.py:177) -- the likelihood core of get_marginal_likelihood as a function of the prior samples.
