@@ -259,6 +259,33 @@ int mcpc_philox_normals(int device, uint64_t seed, uint64_t step, int layer, uin
 int mcpc_moments_accumulate(int device, const float* rec, int64_t row_elems, int32_t first, int32_t stride, int32_t n,
                             int32_t transform, double* sum, double* sumsq, int accumulate, void* stream);
 
+/* Streaming second moments BETWEEN units of recorded steps: fp64 sums of outer products, the raw material of a posterior covariance
+ * within a layer and across layers (csrc/mcpc_cov.h).  The column space is the concatenation, in order, of n_blocks record buffers
+ * (1..MCPC_MAX_LATENT + 1): rec[j] is contiguous fp32 [records][B][widths[j]] as mcpc_run writes rec_x[l] / rec_out, transforms[j] is
+ * MCPC_MOM_IDENTITY or MCPC_MOM_SIGMOID (transforms NULL = all identity), D = widths[0] + ... .  With v_k(c) the D transformed values of
+ * chain c in record first + k*stride, k = 0..n-1 (exactly the records mcpc_moments_accumulate takes):
+ *   pool = 0:  outer[c][i][j] = (accumulate ? outer[c][i][j] : 0) + sum_k v_k(c)[i] * v_k(c)[j]            outer: [B][D][D] fp64
+ *   pool = 1:  outer[i][j]    = (accumulate ? outer[i][j]    : 0) + sum_k sum_c v_k(c)[i] * v_k(c)[j]      outer: [D][D] fp64
+ * The full matrix is written, both triangles, and outer[i][j] is bitwise outer[j][i] (accumulate = 1 adds the same value to both; they
+ * stay bitwise equal where they were).  The first-order sums are mcpc_moments_accumulate's, called for the same blocks.
+ * The products are exact in fp64 (fp32 inputs) and run on the fp64 MFMA; only the additions round.  Two runs of the same call give the
+ * same bits: the decomposition depends on B and the widths alone and no sum is ordered by the hardware's scheduling (no atomics).  UNLIKE
+ * mcpc_moments_accumulate the result is NOT bitwise invariant under how the records are chunked over calls (an MFMA adds four products in
+ * an order of its own, and each call rounds once more into outer), nor is the diagonal bitwise that call's sumsq; both agree per entry
+ * within (R + G + 2) * 2^-52 * sum |v[i] v[j]|, R = the rows contracted (n, times B when pooled), G = the pooled groups (0 for pool = 0).
+ * pool = 1 needs a workspace of mcpc_cov_workspace_bytes(B, widths, n_blocks, 1) bytes (device memory, 8-B aligned, contents
+ * irrelevant before and after; [groups][Dpad][Dpad] fp64 partials that a second kernel adds in ascending group order); pool = 0 needs
+ * none (0 bytes, workspace may be NULL).  The library allocates nothing.  Stateless, asynchronous on `stream`, all offsets 64-bit.
+ * n = 0 reads nothing: it zeroes outer when accumulate = 0 and does nothing otherwise.
+ * mcpc_cov_workspace_bytes returns -1 (and a message in mcpc_last_error) for arguments mcpc_cov_accumulate would refuse.
+ * MCPC_EINVAL: n_blocks outside 1..MCPC_MAX_LATENT + 1, widths NULL, a width < 1, B < 1, pool not 0 or 1, outer NULL, stride < 1,
+ * first < 0, n < 0, an unknown transform, rec or a rec[j] NULL with n > 0, workspace NULL or too small with pool = 1 and n > 0, more
+ * than 32768 padded columns, 2^26 or more jobs (chain groups x blocks of 4 x 4 tile pairs: one launch holds them all). */
+int64_t mcpc_cov_workspace_bytes(int32_t B, const int32_t* widths, int32_t n_blocks, int32_t pool);
+int mcpc_cov_accumulate(int device, const float* const* rec, const int32_t* widths, const int32_t* transforms, int32_t n_blocks,
+                        int32_t B, int32_t first, int32_t stride, int32_t n, int32_t pool, double* outer, int accumulate,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Per-chain energies of recorded states, evaluated on the device (the reference has them per datapoint: is_return_batchelement_loss,
  * PCLayer(is_keep_energy_per_datapoint=True), get_energies(is_per_datapoint=True); pc_trainer.py:776-836, pc_layer.py:250-262).
  * A ROW is one chain at one recorded step.  x_rec[l], l < n_latent: [n_rec][batch][n_l] fp32, as mcpc_run writes rec_x[l] (n_rec = 1

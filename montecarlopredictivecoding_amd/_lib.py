@@ -98,6 +98,10 @@ SYMBOLS = {
                                       C.c_void_p, C.c_int, C.c_void_p]),
     "mcpc_moments_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "mcpc_cov_workspace_bytes": (C.c_int64, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32]),
+    "mcpc_cov_accumulate": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                      C.c_void_p]),
     "mcpc_chain_energies": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_int32,
                                       C.c_void_p, C.c_int32, C.c_void_p]),
     "mcpc_query": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),

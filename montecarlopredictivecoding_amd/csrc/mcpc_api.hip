@@ -14,6 +14,7 @@
 #include "mcpc_build.h"
 #include "mcpc_kernels.h"
 #include "mcpc_moments.h"
+#include "mcpc_cov.h"
 #include "mcpc_plan.h"
 #include "mcpc_chain_energy.h"
 
@@ -383,6 +384,11 @@ int mcpc_create(const mcpc_net_desc* d, mcpc_engine** out) {
     if (e->u.on && (allow_lds((const void*)mcpc_steps_u_kernel<false>, e->u.plan.lds_bytes) != hipSuccess ||
                     allow_lds((const void*)mcpc_steps_u_kernel<true>, e->u.plan.lds_bytes) != hipSuccess))
         return bail(fail(MCPC_EHIP, "hipFuncSetAttribute failed for the unified-wave kernel (%d bytes LDS)", e->u.plan.lds_bytes));
+    // The zero fills above are hipMemset on the NULL stream, which the caller's stream does not wait for when it is a non-blocking one
+    // (every stream torch creates is): without this wait the first mcpc_params_changed on such a stream can be overtaken by the fill of
+    // `wexp`, and the step kernels then read exponent 0 under weights packed with another one
+    // (tests/test_gpu_engine.py::test_two_engines_on_two_streams_run_concurrently: E_2 of 1.9e11 for 441).
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return bail(fail(MCPC_EHIP, "the zero fills of the engine's buffers failed"));
     *out = e;
     return MCPC_OK;
 }
@@ -1389,6 +1395,91 @@ int mcpc_moments_accumulate(int device, const float* rec, int64_t row_elems, int
         mom_dispatch<4>(transform, r0, row_elems, row_step, n, sum, sumsq, accumulate, (hipStream_t)stream_);
     else
         mom_dispatch<1>(transform, r0, row_elems, row_step, n, sum, sumsq, accumulate, (hipStream_t)stream_);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+// shared argument checks of the two covariance entry points; fills the plan
+static int cov_check_shape(int32_t B, const int32_t* widths, int32_t n_blocks, int32_t pool, CovPlan& plan) {
+    if (n_blocks < 1 || n_blocks > kCovMaxBlocks) return fail(MCPC_EINVAL, "cov: n_blocks=%d outside 1..%d", n_blocks, kCovMaxBlocks);
+    if (!widths) return fail(MCPC_EINVAL, "cov: widths is null");
+    if (B < 1) return fail(MCPC_EINVAL, "cov: B=%d, must be at least 1", B);
+    if (pool != 0 && pool != 1) return fail(MCPC_EINVAL, "cov: pool=%d, must be 0 or 1", pool);
+    int64_t D = 0;
+    for (int b = 0; b < n_blocks; ++b) {
+        if (widths[b] < 1) return fail(MCPC_EINVAL, "cov: widths[%d]=%d, must be at least 1", b, widths[b]);
+        D += (widths[b] + 15) / 16 * 16;
+    }
+    if (D > 32768) return fail(MCPC_EINVAL, "cov: %lld padded columns, at most 32768", (long long)D);
+    plan = cov_plan(B, widths, n_blocks, pool);
+    // one workgroup of 64 lanes per job, and a grid holds fewer than 2^32 threads
+    if ((int64_t)plan.groups * plan.npairs >= (1LL << 26))
+        return fail(MCPC_EINVAL, "cov: %lld jobs (chain groups x blocks of tile pairs), a launch holds fewer than %lld", (long long)plan.groups * plan.npairs, 1LL << 26);
+    return MCPC_OK;
+}
+
+int64_t mcpc_cov_workspace_bytes(int32_t B, const int32_t* widths, int32_t n_blocks, int32_t pool) {
+    CovPlan plan;
+    if (cov_check_shape(B, widths, n_blocks, pool, plan)) return -1;
+    return pool ? (int64_t)plan.groups * plan.Dpad * plan.Dpad * (int64_t)sizeof(double) : 0;
+}
+
+int mcpc_cov_accumulate(int device, const float* const* rec, const int32_t* widths, const int32_t* transforms, int32_t n_blocks, int32_t B,
+                        int32_t first, int32_t stride, int32_t n, int32_t pool, double* outer, int accumulate, void* workspace,
+                        int64_t workspace_bytes, void* stream_) {
+    CovPlan plan;
+    if (const int rc = cov_check_shape(B, widths, n_blocks, pool, plan)) return rc;
+    if (!outer) return fail(MCPC_EINVAL, "cov: outer is null");
+    if (stride < 1) return fail(MCPC_EINVAL, "cov: stride=%d, must be at least 1", stride);
+    if (first < 0) return fail(MCPC_EINVAL, "cov: first=%d, must not be negative", first);
+    if (n < 0) return fail(MCPC_EINVAL, "cov: n=%d, must not be negative", n);
+    bool any_sig = false;
+    for (int b = 0; b < n_blocks; ++b) {
+        const int32_t xf = transforms ? transforms[b] : MCPC_MOM_IDENTITY;
+        if (xf != MCPC_MOM_IDENTITY && xf != MCPC_MOM_SIGMOID) return fail(MCPC_EINVAL, "cov: unknown transform %d of block %d", xf, b);
+        any_sig = any_sig || xf == MCPC_MOM_SIGMOID;
+    }
+    if (n > 0) {
+        if (!rec) return fail(MCPC_EINVAL, "cov: rec is null with n=%d", n);
+        for (int b = 0; b < n_blocks; ++b)
+            if (!rec[b]) return fail(MCPC_EINVAL, "cov: rec[%d] is null with n=%d", b, n);
+    }
+    const int64_t need = pool ? (int64_t)plan.groups * plan.Dpad * plan.Dpad * (int64_t)sizeof(double) : 0;
+    if (n > 0 && pool) {
+        if (!workspace) return fail(MCPC_EINVAL, "cov: workspace is null with pool=1 (mcpc_cov_workspace_bytes: %lld bytes)", (long long)need);
+        if (workspace_bytes < need)
+            return fail(MCPC_EINVAL, "cov: workspace of %lld bytes is too small, %lld needed", (long long)workspace_bytes, (long long)need);
+    }
+    if (n == 0 && accumulate) return MCPC_OK;                     // nothing to add
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(device));
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(outer, 0, (size_t)(pool ? 1 : B) * plan.D * plan.D * sizeof(double), stream));
+        return MCPC_OK;
+    }
+    CovParams P{};
+    int32_t tile = 0, col = 0;
+    for (int b = 0; b <= kCovMaxBlocks; ++b) {
+        P.tile0[b] = tile; P.col0[b] = col;
+        if (b < n_blocks) {
+            P.rec[b] = rec[b]; P.width[b] = widths[b]; P.xf[b] = transforms ? transforms[b] : MCPC_MOM_IDENTITY;
+            tile += (widths[b] + 15) / 16; col += widths[b];
+        }
+    }
+    P.n_blocks = n_blocks; P.NT = plan.NT; P.NB = plan.NB; P.npairs = plan.npairs; P.D = plan.D; P.Dpad = plan.Dpad;
+    P.B = B; P.first = first; P.stride = stride; P.n = n; P.gs = plan.gs; P.accumulate = accumulate ? 1 : 0;
+    P.out = pool ? (double*)workspace : outer;
+    const dim3 grid((unsigned)((int64_t)plan.groups * plan.npairs)), block(64);
+    if (pool) {
+        if (any_sig) hipLaunchKernelGGL((mcpc_cov_kernel<true, true>), grid, block, 0, stream, P);
+        else hipLaunchKernelGGL((mcpc_cov_kernel<true, false>), grid, block, 0, stream, P);
+        const int64_t total = (int64_t)plan.D * plan.D;
+        hipLaunchKernelGGL(mcpc_cov_finish_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 2048)), dim3(256), 0, stream, P,
+                           (const double*)workspace, plan.groups, outer);
+    } else {
+        if (any_sig) hipLaunchKernelGGL((mcpc_cov_kernel<false, true>), grid, block, 0, stream, P);
+        else hipLaunchKernelGGL((mcpc_cov_kernel<false, false>), grid, block, 0, stream, P);
+    }
     HIP_TRY(hipGetLastError());
     return MCPC_OK;
 }

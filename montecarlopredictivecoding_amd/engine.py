@@ -371,3 +371,77 @@ def moments_accumulate(rec, first, stride, n, sum, sumsq=None, transform="identi
     stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     L.check(lib.mcpc_moments_accumulate(device.index or 0, _ptr(rec), row, first, stride, n, _MOM_TRANSFORMS[transform],
                                         _ptr(sum), _ptr(sumsq), 1 if accumulate else 0, stream))
+
+
+def cov_workspace_bytes(B, widths, pool=True) -> int:
+    """Bytes of device workspace ``cov_accumulate`` needs for ``B`` chains and blocks of these widths (0 unless pooled)."""
+    lib = L.load()
+    w = (C.c_int32 * len(widths))(*[int(x) for x in widths])
+    need = lib.mcpc_cov_workspace_bytes(int(B), w, len(widths), 1 if pool else 0)
+    if need < 0:
+        L.check(need)
+    return need
+
+
+def cov_accumulate(recs, first, stride, n, outer, transforms=None, pool=False, accumulate=True, workspace=None):
+    """Add the outer products ``v v^T`` of records ``first + k * stride``, k < n, to the fp64 accumulator ``outer`` on the device
+    (include/mcpc.h: mcpc_cov_accumulate; the fp64 MFMA).  ``recs``: a sequence of contiguous fp32 ``[records, B, w_j]`` buffers as an
+    engine run records them; ``v`` is the concatenation of a chain's rows in that order, ``D = sum w_j``.  ``outer``: contiguous fp64
+    ``[B, D, D]``, or ``[D, D]`` with ``pool=True`` (summed over the chains too).  ``transforms``: per block "identity" or "sigmoid"
+    (None = all identity).  ``accumulate=False`` overwrites.  ``workspace`` (pooled only): a contiguous device tensor of at least
+    ``cov_workspace_bytes(B, widths)`` bytes, 8-B aligned; None allocates one for this call.  Both triangles are written and bitwise
+    equal; two runs give the same bits; chunking the records over calls differently does not (within the bound of DESIGN.md section
+    4).  On the current torch stream."""
+    lib = L.load()
+    if isinstance(recs, torch.Tensor) or not len(recs):
+        raise TypeError("recs: expected a non-empty sequence of torch.Tensor [records, B, width]")
+    recs = list(recs)
+    if len(recs) > L.MAX_LATENT + 1:
+        raise ValueError(f"recs: {len(recs)} blocks, at most {L.MAX_LATENT + 1}")
+    transforms = [None] * len(recs) if transforms is None else list(transforms)
+    if len(transforms) != len(recs):
+        raise ValueError(f"transforms: expected one per block ({len(recs)}), got {len(transforms)}")
+    for t in transforms:
+        if t not in _MOM_TRANSFORMS:
+            raise ValueError(f"transforms: expected 'identity' or 'sigmoid', got {t!r}")
+    for j, r in enumerate(recs):
+        if not isinstance(r, torch.Tensor) or r.dim() != 3:
+            raise TypeError(f"recs[{j}]: expected a torch.Tensor [records, B, width]")
+    device = recs[0].device
+    if device.type != "cuda":
+        raise ValueError(f"recs[0]: expected a tensor on a HIP device, got {device}")
+    R, B = int(recs[0].shape[0]), int(recs[0].shape[1])
+    for j, r in enumerate(recs):
+        _check_tensor(r, (R, B, r.shape[2]), device, f"recs[{j}]")
+    widths = [int(r.shape[2]) for r in recs]
+    D = sum(widths)
+    first, stride, n = int(first), int(stride), int(n)
+    if n > 0 and first >= 0 and stride >= 1 and first + (n - 1) * stride >= R:
+        raise ValueError(f"recs hold {R} records, the last one asked for is {first + (n - 1) * stride}")
+    if not isinstance(outer, torch.Tensor):
+        raise TypeError(f"outer: expected a torch.Tensor, got {type(outer)}")
+    _check_tensor(outer, (D, D) if pool else (B, D, D), device, "outer", torch.float64)
+    w = (C.c_int32 * len(recs))(*widths)
+    need = lib.mcpc_cov_workspace_bytes(B, w, len(recs), 1 if pool else 0)
+    if need < 0:
+        L.check(need)
+    ws_bytes = 0
+    if pool:
+        if workspace is None:
+            workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+        if not isinstance(workspace, torch.Tensor):
+            raise TypeError(f"workspace: expected a torch.Tensor, got {type(workspace)}")
+        if workspace.device != device:
+            raise ValueError(f"workspace: expected device {device}, got {workspace.device}")
+        if not workspace.is_contiguous():
+            raise ValueError("workspace: tensor must be contiguous")
+        if workspace.data_ptr() % 8:
+            raise ValueError("workspace: must be 8-byte aligned")
+        ws_bytes = workspace.numel() * workspace.element_size()
+        if ws_bytes < need:
+            raise ValueError(f"workspace: {ws_bytes} bytes, cov_workspace_bytes asks for {need}")
+    ptrs = (C.c_void_p * len(recs))(*[r.data_ptr() for r in recs])
+    xf = (C.c_int32 * len(recs))(*[_MOM_TRANSFORMS[t] for t in transforms])
+    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    L.check(lib.mcpc_cov_accumulate(device.index or 0, ptrs, w, xf, len(recs), B, first, stride, n, 1 if pool else 0, _ptr(outer),
+                                    1 if accumulate else 0, _ptr(workspace) if pool else None, ws_bytes, stream))

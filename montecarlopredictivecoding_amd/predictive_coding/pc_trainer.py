@@ -238,6 +238,15 @@ class PCTrainer(object):
         self.mcpc_chain_energies = None
         self.mcpc_last_chain_energies = None
         self.mcpc_chain_energies_max_rows = 0
+        # posterior covariances of a fused call, accumulated on the device out of the same ring (covariance.py): None = off, or
+        # dict(begin=0, stride=1, layers=all, outputs=None | "identity" | "sigmoid", pool=None | "chains").  A fused call then leaves
+        # covariance.Covariance in mcpc_last_covariance; composes with mcpc_moments and mcpc_chain_energies (one ring serves all
+        # three).  A request whose RESULT (the fp64 outer products and first-order sums) would take more than mcpc_covariance_max_bytes
+        # is refused; the pooled form holds beside it the per-chain first-order sums (8 B per chain and column) and the kernel's
+        # workspace (engine.cov_workspace_bytes) while the call runs.
+        self.mcpc_covariance = None
+        self.mcpc_last_covariance = None
+        self.mcpc_covariance_max_bytes = 2 << 30
 
     # ---- getters & setters (reference :268-461) -------------------------------------------------------
     def get_T(self) -> int:
@@ -465,6 +474,13 @@ class PCTrainer(object):
                 raise NotImplementedError("mcpc_chain_energies is set, and this call runs on the generic torch loop ({}): per-chain energies "
                                           "are evaluated out of the fused HIP loop's record ring only".format(why_not_fused))
             plan["chain_energies"] = _chain_energies.validate_spec(self.mcpc_chain_energies, self._T)
+        if self.mcpc_covariance is not None:
+            from .. import covariance as _covariance
+            if plan is None:
+                raise NotImplementedError("mcpc_covariance is set, and this call runs on the generic torch loop ({}): posterior covariances "
+                                          "are accumulated by the fused HIP loop only".format(why_not_fused))
+            plan["covariance"] = _covariance.validate_spec(self.mcpc_covariance, self._T, len(plan["net"].sizes), plan["net"].n_out,
+                                                           plan["net"].sizes, plan["B"], self.mcpc_covariance_max_bytes)
         if plan is None:
             # outside what the kernels express: the package's generic torch loop (generic_loop.py), loudly, on the device the model
             # lives on ("must work, need not be fast").  It is no way around a missing GPU: without a visible HIP device
@@ -505,6 +521,9 @@ class PCTrainer(object):
         if plan["mode"] != "fused" and self.mcpc_chain_energies is not None:
             raise NotImplementedError("mcpc_chain_energies is set, and this call runs step by step ({}): per-chain energies are "
                                       "evaluated out of the fused HIP loop's record ring only".format(plan["why_stepwise"]))
+        if plan["mode"] != "fused" and self.mcpc_covariance is not None:
+            raise NotImplementedError("mcpc_covariance is set, and this call runs step by step ({}): posterior covariances are "
+                                      "accumulated by the fused HIP loop only".format(plan["why_stepwise"]))
         if plan["mode"] == "fused":
             self.last_call_mode = "fused"
             with _few_cpu_threads(plan["staged"]):
@@ -835,14 +854,14 @@ class PCTrainer(object):
             energy_mode=L.ENERGY_ALL if is_return_results_every_t else L.ENERGY_LAST)
         host_step_bytes = 4 * plan["B"] * sum(n for n, on in zip(net.sizes, rec_layers) if on)
         self.last_record_slices = 0
-        mom, ce = plan.get("moments"), plan.get("chain_energies")
-        if mom is not None or ce is not None:
-            # posterior moments / per-chain energies: the call runs as slices whatever its size, and the records they ask for are
-            # reduced on the device
+        mom, ce, cov = plan.get("moments"), plan.get("chain_energies"), plan.get("covariance")
+        if mom is not None or ce is not None or cov is not None:
+            # posterior moments / per-chain energies / covariances: the call runs as slices whatever its size, and the records they
+            # ask for are reduced on the device
             ce_inputs = None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous())
             res, last_mom, last_ce = self._run_fused_sliced(
                 eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, is_return_outputs and net.n_out > 0,
-                every_t=is_return_results_every_t, mom=mom, ce=ce, ce_inputs=ce_inputs)
+                every_t=is_return_results_every_t, mom=mom, ce=ce, ce_inputs=ce_inputs, cov=cov)
             if mom is not None:
                 self.mcpc_last_moments = last_mom
             if ce is not None:
@@ -875,7 +894,7 @@ class PCTrainer(object):
                                      is_return_representations, is_return_xs, loss_fn)
 
     def _run_fused_sliced(self, eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, rec_out, every_t=True, mom=None,
-                          ce=None, ce_inputs=None):
+                          ce=None, ce_inputs=None, cov=None):
         """A call whose every-step trajectory would not fit the record budget on the device, or whose records feed `mcpc_moments`:
         the same T steps as slices of one `mcpc_run` each (slicing does not change a bit of the trajectories,
         tests/test_gpu_fullsize.py).  The latent records of a slice go to one half of a two-buffer device ring.  Records the caller's
@@ -885,22 +904,26 @@ class PCTrainer(object):
         are neither copied nor kept unless the caller asked too.  With `every_t` false the caller gets the last step's records and
         energies only, as from an unsliced call.  With `ce` (a validated `mcpc_chain_energies`) every latent layer goes through the
         ring and `Engine.chain_energies` evaluates the steps asked for out of its rows after each slice, on the call's own stream,
-        under the slicing rules of `mom`.  Returns (RunResult, Moments or None, ChainEnergies or None)."""
-        from ..engine import RunResult, moments_accumulate
+        under the slicing rules of `mom`.  With `cov` (a validated `mcpc_covariance`) its layers and read-out go through the ring too
+        and `cov_accumulate` / `moments_accumulate` add their outer products and sums after each slice, on the call's own stream, under
+        the same rules; the result is left in `mcpc_last_covariance`.  Returns (RunResult, Moments or None, ChainEnergies or None)."""
+        from ..engine import RunResult, moments_accumulate, cov_accumulate, cov_workspace_bytes
         dev, B = plan["device"], plan["B"]
         nl = len(net.sizes)
         mom_layers = [mom is not None and l in mom.layers for l in range(nl)]
         mom_out = mom is not None and mom.outputs is not None
-        ring_layers = [a or b_ or ce is not None for a, b_ in zip(rec_layers, mom_layers)]
-        reduced = mom is not None or ce is not None
+        cov_layers = [cov is not None and l in cov.layers for l in range(nl)]
+        cov_out = cov is not None and cov.outputs is not None
+        ring_layers = [a or b_ or c_ or ce is not None for a, b_, c_ in zip(rec_layers, mom_layers, cov_layers)]
+        reduced = mom is not None or ce is not None or cov is not None
         out_direct = rec_out and every_t                     # every step's outputs are kept anyway: slices write them in place
-        ring_out = (rec_out or mom_out) and not out_direct
+        ring_out = (rec_out or mom_out or cov_out) and not out_direct
         S = T
         if any(rec_layers) and every_t:
             S = min(S, self.mcpc_record_chunk_bytes // max(2 * host_step_bytes, 1))
         if reduced:
             # one half of the ring is a chunk of at most mcpc_moments_chunk_bytes
-            step_bytes = 4 * B * (sum(n for n, on in zip(net.sizes, ring_layers) if on) + (net.n_out if ring_out or mom_out else 0))
+            step_bytes = 4 * B * (sum(n for n, on in zip(net.sizes, ring_layers) if on) + (net.n_out if ring_out or mom_out or cov_out else 0))
             S = min(S, self.mcpc_moments_chunk_bytes // max(step_bytes, 1))
         S = max(1, S)
         # A slice boundary inside the window that accumulates parameter gradients would regroup their fp32 sums (one Hebbian flush and
@@ -948,6 +971,29 @@ class PCTrainer(object):
                 moments_accumulate(src, first, mom.stride, cnt, acc["out_sum"], acc["out_sumsq"], transform=mom.outputs,
                                    accumulate=True)
 
+        cov_acc = None
+        if cov is not None:
+            D = cov.D
+            cov_widths = [w for _, _, w in cov.columns]
+            cov_xf = ["identity"] * len(cov.layers) + ([cov.outputs] if cov_out else [])
+            cov_acc = dict(outer=torch.zeros(*((D, D) if cov.pooled else (B, D, D)), dtype=torch.float64, device=dev),
+                           # the first-order sums of a block, contiguous for moments_accumulate; gathered into `sum` at the end
+                           part=[torch.zeros(B, w, dtype=torch.float64, device=dev) for w in cov_widths],
+                           ws=torch.empty(max(cov_workspace_bytes(B, cov_widths), 8), dtype=torch.uint8, device=dev)
+                           if cov.pooled else None)
+
+        def reduce_cov(t0, n, half):
+            first, cnt = cov.chunk(t0, n)
+            if cnt == 0:
+                return
+            blocks = [ring[half][l] for l in cov.layers]
+            if cov_out:
+                blocks.append(out_full[t0:t0 + n] if out_direct else ring_o[half])
+            for blk, part, xf in zip(blocks, cov_acc["part"], cov_xf):
+                moments_accumulate(blk, first, cov.stride, cnt, part, None, transform=xf, accumulate=True)
+            cov_accumulate(blocks, first, cov.stride, cnt, cov_acc["outer"], transforms=cov_xf, pool=cov.pooled, accumulate=True,
+                           workspace=cov_acc["ws"])
+
         ce_table = torch.empty(ce.n, B, L.ENERGY_COLS, dtype=torch.float64, device=dev) if ce is not None else None
         ce_kw = dict(loss_kind=run_kw["loss_kind"], loss_var=run_kw["loss_var"], mask_start=run_kw["mask_start"],
                      max_rows=self.mcpc_chain_energies_max_rows)
@@ -979,6 +1025,8 @@ class PCTrainer(object):
                 reduce(t0, n, half)
             if ce is not None:
                 evaluate(t0, n, half)
+            if cov is not None:
+                reduce_cov(t0, n, half)
             if ring_out and rec_out and last:
                 out_full[0].copy_(ring_o[half][n - 1])       # (not every_t: the last step's outputs)
             to_host = any(rec_layers) and (every_t or last)
@@ -1014,6 +1062,13 @@ class PCTrainer(object):
         if ce is not None:
             from ..chain_energies import from_table
             ce_result = from_table(ce_table, nl, self._energy_coefficient, ce.steps, plan["model_device"])
+        if cov is not None:
+            from ..covariance import Covariance
+            s = torch.cat(cov_acc["part"], dim=1)
+            if cov.pooled:
+                s = s.sum(dim=0)
+            self.mcpc_last_covariance = Covariance(n=cov.n, B=B, pooled=cov.pooled, columns=list(cov.columns),
+                                                   sum=s.to(plan["model_device"]), outer=cov_acc["outer"].to(plan["model_device"]))
         return RunResult(energies=energies, rec_x=host, rec_out=out_full), result, ce_result
 
     def mcpc_state_energies(self, inputs, loss_fn: typing.Callable = None, loss_fn_kwargs: dict = {}):

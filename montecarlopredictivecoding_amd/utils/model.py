@@ -197,3 +197,41 @@ def get_posterior_expectation(gen_pc, config, trainers, loader, use_cuda=False, 
     if with_variance:
         tensors.append(torch.cat(variances, dim=0))
     return TensorDataset(*tensors)
+
+
+def get_posterior_covariance(gen_pc, config, trainers, loader, layers=(0,), pool=None):
+    """Posterior means and covariances of the latent units, per batch of ``loader``: MAP call with ``trainers[0]``, then an MCPC call
+    with ``trainers[1]`` started from the MAP state (the protocol of ``get_posterior_expectation``), over the steps from
+    ``config["mixing"]`` on, accumulated on the device by the call itself (``PCTrainer.mcpc_covariance``, fp64 sums on the fp64 MFMA):
+    no trajectory is recorded.  ``layers``: the PC layers whose units are the columns; ``pool``: None for one matrix per datum, "chains"
+    for one per batch.  Returns ``(means, covariances, labels)``: per datum ``[N, D]`` / ``[N, D, D]`` fp64 and ``[N]``; pooled, one
+    ``[D]`` / ``[D, D]`` per batch stacked into ``[batches, D]`` / ``[batches, D, D]``, and the labels of all data."""
+    if len(trainers) != 2:
+        raise NotImplementedError
+    device = next(gen_pc.parameters()).device
+    input_size = len(gen_pc[0].bias)
+    pc_trainer, mcpc_trainer = trainers
+    means, covs, labels = [], [], []
+    saved = mcpc_trainer.mcpc_covariance
+    mcpc_trainer.mcpc_covariance = dict(begin=int(config["mixing"]), stride=1, layers=tuple(layers), outputs=None, pool=pool)
+    try:
+        for data, label in loader:
+            pseudo_input = torch.zeros(data.shape[0], input_size, device=device)
+            data, label = data.to(device), label.to(device)
+            kw = dict(inputs=pseudo_input, loss_fn=config["loss_fn"],
+                      loss_fn_kwargs={"_target": data, "_var": config["input_var"]},
+                      is_log_progress=False, is_return_results_every_t=False, is_checking_after_callback_after_t=False)
+            pc_trainer.train_on_batch(**kw)
+            mcpc_trainer.train_on_batch(callback_after_t=random_step, callback_after_t_kwargs={"_pc_trainer": mcpc_trainer},
+                                        is_sample_x_at_batch_start=False, **kw)
+            c = mcpc_trainer.mcpc_last_covariance
+            if pool is None:
+                means.append(c.mean)
+                covs.append(c.cov(ddof=1))
+            else:
+                means.append(c.mean.unsqueeze(0))
+                covs.append(c.cov(ddof=1).unsqueeze(0))
+            labels.append(label)
+    finally:
+        mcpc_trainer.mcpc_covariance = saved
+    return torch.cat(means, dim=0), torch.cat(covs, dim=0), torch.cat(labels, dim=0)
