@@ -56,7 +56,11 @@ __device__ __forceinline__ f32x4 normals4(uint64_t seed, uint64_t step, uint32_t
 
 // ---- activations (reference utils/model.py:49-52: nn.ReLU / nn.Tanh; none for the linear toys) --
 __device__ __forceinline__ float tanh_f(float x) {
-    // tanh(x) = 1 - 2/(exp(2x)+1); exp via v_exp_f32 (2^x).  |err| ~ 1e-7 absolute.
+    // tanh(x) = 1 - 2/(exp(2x)+1); exp via v_exp_f32 (2^x).  With u = 2^-24 and t = tanh(x):
+    //     |err| <= (1 - t) ((1 + t) / 2 (2 + 4 |x|) + 3) u + u |t|:  4 u = 2.4e-7 at 0, 7 u = 4.2e-7 towards -1, u towards +1
+    // (1 ulp for v_exp_f32 and v_rcp_f32, the rounding of the argument 2.885 x, of e + 1 and of the last subtraction).  ABSOLUTE: near 0
+    // the relative error is unbounded.  Exactly +-1 at +-Inf and wherever 2^(2.885 x) overflows (x > 44.4).  Derived, and compared with
+    // fp64 element by element, in tests/test_gpu_special_values.py.
     const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);   // exp(2x)
     return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
 }
@@ -92,12 +96,16 @@ __device__ __forceinline__ float sigmoid_f(float o) {
 // BCEWithLogits element: max(o,0) - o*y + log1p(exp(-|o|))
 __device__ __forceinline__ float bce_logits_f(float o, float y) {
     const float e = __builtin_amdgcn_exp2f(-fabsf(o) * 1.4426950408889634f);
-    // log1p(e), e in (0,1]: log2(1+e)*ln2 via v_log_f32 (absolute error ~1e-7 per element)
+    // log1p(e), e in (0,1]: log2(1+e)*ln2 via v_log_f32: the bound of sigmoid_bce_f below
     return fmaxf(o, 0.0f) - o * y + 0.6931471805599453f * __builtin_amdgcn_logf(1.0f + e);
 }
 
 // sigmoid(o) and the BCE-with-logits term from ONE exp: with e = exp(-|o|),
 //   sigmoid(o) = (o >= 0 ? 1 : e) / (1 + e),   bce = max(o,0) - o*y + log(1 + e)
+// With u = 2^-24 (1 ulp for v_exp_f32, v_log_f32, v_rcp_f32; derivation and element-by-element comparison with fp64:
+// tests/test_gpu_special_values.py):
+//   |sig error| <= 4.3 u sig = 2.6e-7 sig for o >= 0, (7 + 3 |o|) u sig for o < 0 (the argument's rounding moves e by 2 u |o| e);
+//   |bce error| <= 4 u log(1 + e) + 2.1 u + u (|o y| + |max(o,0) - o y| + |bce|) -- absolute where 1 + e rounds to 1 (|o| >= 17).
 __device__ __forceinline__ void sigmoid_bce_f(float o, float y, float& sig, float& bce) {
     const float e = __builtin_amdgcn_exp2f(-fabsf(o) * 1.4426950408889634f);
     const float r = __builtin_amdgcn_rcpf(1.0f + e);
