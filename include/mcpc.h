@@ -383,6 +383,19 @@ int mcpc_debug_chain_energy_jobs(int32_t n_latent, const int32_t* sizes, int32_t
  * out, and the size the whole text needs (NUL included) into *needed.  Fails as mcpc_create would: same codes, same messages. */
 int mcpc_debug_plan(const mcpc_net_desc* desc, int32_t n_cu, int64_t total_mem, char* out, int64_t cap, int64_t* needed);
 
+/* Diagnostic (tests only; no device work, no device needed): the schedule mcpc_run would issue for `run` on the engine mcpc_debug_plan
+ * describes, as one JSON object.  Only the fields of `run` that shape the schedule are read -- T, t_begin, n_steps (checked as mcpc_run
+ * checks them), acc_begin, acc_end, update_x, xopt_kind, noise_mode, loss_kind -- and its pointers may be null.  "unified": the run is
+ * served by the unified-wave kernel; "accumulates": a step of it lies in the accumulation window; "lean_ok"; "overlap": its Hebbian
+ * flushes run beside the next segment, through a spill ring of "n_parts" parts, else serially; "items", one row of numbers per item in
+ * the order "fields" names: steps [t0, t0 + n) as one plain launch (q = 0) or as one cycle of the round schedule (rr_k launches of q
+ * steps, n = rr_m q), "acc" when they lie in the window -- then the item spills into slots [slot0, slot0 + n) of the ring, part "part",
+ * and "flush" says that a flush of those n slots follows it; "flushes", one entry per flushing item: "rows" = n x Bpad and per Linear
+ * j >= 1, in the order "flush_fields" names, the K-splits and rows per split of that flush and the bound of the splits that sizes the
+ * Linear's slabs (that of a flush of a whole ring part).  out / cap / needed and the failures as for mcpc_debug_plan. */
+int mcpc_debug_run_plan(const mcpc_net_desc* desc, int32_t n_cu, int64_t total_mem, const mcpc_run_desc* run, char* out, int64_t cap,
+                        int64_t* needed);
+
 #ifdef __cplusplus
 }
 #endif

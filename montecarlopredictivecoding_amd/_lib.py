@@ -120,6 +120,8 @@ SYMBOLS = {
     "mcpc_debug_chain_energy_jobs": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                                C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mcpc_debug_plan": (C.c_int, [C.POINTER(NetDesc), C.c_int32, C.c_int64, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "mcpc_debug_run_plan": (C.c_int, [C.POINTER(NetDesc), C.c_int32, C.c_int64, C.POINTER(RunDesc), C.c_char_p, C.c_int64,
+                                      C.POINTER(C.c_int64)]),
 }
 
 _lib = None

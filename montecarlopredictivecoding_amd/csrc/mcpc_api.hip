@@ -97,6 +97,7 @@ struct mcpc_engine : EnginePlan {
     int ce_njobs = 0, ce_nhead = 0;
     CeFinish ce_finish{};
     int ce_rows = 0;                // rows the scratch holds (a multiple of kLwChains)
+    RunPlan run_plan;               // the schedule of the last mcpc_run (plan_run); kept for its storage: no allocation per run
     // diagnostics, host strings set while launching (no device work): what the last mcpc_run and each Linear's last flush launched
     std::string last_step;                       // mcpc_last_step_kernel_name
     std::string last_flush[kMaxLatent + 1];      // mcpc_last_flush_plan, per Linear j >= 1
@@ -511,66 +512,6 @@ int mcpc_store_adam_state(mcpc_engine* e, float* const* m, float* const* v, void
 
 namespace {
 
-// How the Hebbian sums of Linear j are computed for `rows` spilled rows: the LDS-tiled kernel (mcpc_hebbian.h) for wide
-// Linears -- as one or two launches whose error-tile groups cover the output exactly (49 tiles = 17 + 16 + 16) -- the same
-// kernel with the operands swapped for a wide Linear with a narrow input (256 x 32: the narrow side takes the TE slot),
-// and the register-streaming kernel for whatever is left (few output tiles: HBM-bound whatever the tiling).
-struct HebPlan {
-    bool tiled = false, swapped = false;
-    int ra = 0;                                    // activation tiles per wave (TA = 8 ra)
-    int te[2] = {0, 0}, n_mt[2] = {0, 0};          // up to two launches: error tiles per group, number of groups
-    int n_nt = 1;
-    int wave_tiles = 0;                            // streaming kernel: 64 x 64 wave tiles
-    int ksplit = 1, rps = 0;
-    int ksplit_cap = 1;                            // upper bound of ksplit that never decreases with `rows`: sizes the slabs
-};
-
-HebPlan plan_hebbian(const mcpc_engine* e, int ne, int na, int rows) {
-    HebPlan h;
-    const int et = ne / 16, at = na / 16;
-    const bool wide = heb_wide(et, at);
-    const bool narrow_in = heb_narrow_in(et, at);       // e.g. 256 x 32
-    h.tiled = wide || narrow_in;
-    h.swapped = narrow_in;
-    if (wide) {
-        h.ra = at >= 16 ? 2 : 1;
-        h.n_nt = at / (8 * h.ra);
-        if (et <= 8) { h.te[0] = 8; h.n_mt[0] = 1; }
-        else if (et <= 16) { h.te[0] = 16; h.n_mt[0] = 1; }
-        else {
-            // et = 17 b + 16 a exactly when b = et mod 16 groups of 17 fit; otherwise groups of 17 with a ragged last one
-            const int b17 = et % 16, a16 = (et - 17 * b17) / 16;
-            if (et - 17 * b17 >= 0) { h.te[0] = 17; h.n_mt[0] = b17; h.te[1] = 16; h.n_mt[1] = a16; }
-            else { h.te[0] = 17; h.n_mt[0] = (et + 16) / 17; }
-            if (h.n_mt[0] == 0) { h.te[0] = h.te[1]; h.n_mt[0] = h.n_mt[1]; h.te[1] = 0; h.n_mt[1] = 0; }
-        }
-    } else if (narrow_in) {
-        h.ra = 2; h.n_nt = 1; h.te[0] = at; h.n_mt[0] = 1;          // E slot = activations (at tiles), A slot = errors (16 tiles)
-    }
-    if (h.tiled) {
-        // ~48 stages of 32 rows per workgroup (0.3 ms at cfg-M): short enough that the step kernel's next segment never
-        // waits long for CUs, long enough that the slab traffic stays at a few percent of the spill's
-        int want = e->knobs.dw_ksplit > 0 ? e->knobs.dw_ksplit : std::max(1, rows / (48 * kHebKB));
-        // a small flush (the reference's batch of 256: 25 600 rows, 16 splits) would run 16-48 workgroups of 48 stages on an idle chip,
-        // 0.10-0.17 ms per Linear: with at least 8 stages per workgroup, split until the launch has about a workgroup per CU
-        if (e->knobs.dw_ksplit <= 0) {
-            const int cols = std::max(1, (h.n_mt[0] + h.n_mt[1]) * h.n_nt);
-            want = std::max(want, std::min(rows / (8 * kHebKB), (256 + cols - 1) / cols));
-        }
-        want = std::min(want, std::max(1, rows / kHebKB));
-        h.ksplit_cap = want;
-        h.rps = ((rows + want - 1) / want + kHebKB - 1) / kHebKB * kHebKB;
-        h.ksplit = (rows + h.rps - 1) / h.rps;
-    } else {
-        h.wave_tiles = ((ne + 63) / 64) * ((na + 63) / 64);
-        int ksplit = std::max(1, std::min(4096 / h.wave_tiles, rows / 64));
-        h.ksplit_cap = ksplit;
-        h.rps = ((rows + ksplit - 1) / ksplit + 15) / 16 * 16;
-        h.ksplit = (rows + h.rps - 1) / h.rps;
-    }
-    return h;
-}
-
 template <int TE, int RA, bool SW = false>
 int launch_heb(const HebArgs& a, hipStream_t stream) {
     constexpr int lds_bytes = 2 * kHebKB * (heb_lds_stride(16 * TE) + heb_lds_stride(16 * 8 * RA)) * (int)sizeof(float);
@@ -652,7 +593,7 @@ int ensure_spill(mcpc_engine* e, hipStream_t stream) {
     size_t total = 0;
     for (int j = 1; j < nlin; ++j) {
         Lin& ln = e->lin[j];
-        const HebPlan h = plan_hebbian(e, ln.out_pad, ln.in_pad, max_rows);
+        const HebPlan h = plan_hebbian(e->knobs, ln.out_pad, ln.in_pad, max_rows);
         ln.slab_off = total;
         ln.slab_floats = (size_t)h.ksplit_cap * ((size_t)ln.out_pad * ln.in_pad + ln.out_pad);
         total += ln.slab_floats;
@@ -688,7 +629,7 @@ int flush_spill(mcpc_engine* e, int n_slots, int slot0, hipStream_t stream, int 
         const int ne = ln.out_pad, na = ln.in_pad;
         const float* E = (j < e->L ? e->spill_e[j] : e->spill_eo) + (size_t)slot0 * e->Bpad * ne;
         const float* A = e->spill_a[j - 1] + (size_t)slot0 * e->Bpad * na;
-        const HebPlan h = plan_hebbian(e, ne, na, rows);
+        const HebPlan h = plan_hebbian(e->knobs, ne, na, rows);
         std::string plan;                                       // mcpc_last_flush_plan: one "kernel<args>x<groups>[*<act groups>]" per launch
         auto name_launch = [&](const char* kern, int te, int ra, bool sw, int n_mt, int n_nt) {
             char buf[64];
@@ -780,8 +721,7 @@ int check_run(const mcpc_engine* e, const mcpc_run_desc* r) {
     const int nlin = e->L + (e->has_head ? 1 : 0);
     for (int j = 0; j < nlin; ++j)
         if (!e->lin[j].bound) return fail(MCPC_ESTATE, "Linear %d has no bound parameters (mcpc_bind_params + mcpc_params_changed first)", j);
-    if (r->T < 1 || r->t_begin < 0 || r->n_steps < 1 || r->t_begin + r->n_steps > r->T)
-        return fail(MCPC_EINVAL, "bad step range: T=%d t_begin=%d n_steps=%d", r->T, r->t_begin, r->n_steps);
+    if (const int rc = check_step_range(*r)) return rc;
     if (r->loss_kind < 0 || r->loss_kind > 2) return fail(MCPC_EINVAL, "loss_kind=%d", r->loss_kind);
     if (r->loss_kind != MCPC_LOSS_NONE) {
         if (!e->has_head) return fail(MCPC_EINVAL, "a loss needs a read-out Linear (n_out > 0)");
@@ -806,9 +746,6 @@ int check_run(const mcpc_engine* e, const mcpc_run_desc* r) {
     if (r->rec_count < 0 || (r->rec_count > 0 && r->rec_stride < 1)) return fail(MCPC_EINVAL, "bad record schedule");
     return 0;
 }
-
-// energy partials per step: one slot per workgroup; the in-place kernel indexes them by 16-chain tile
-size_t energy_slots(const mcpc_engine* e) { return e->lw ? (size_t)e->nwg_live : e->ws == 2 ? (size_t)e->Bpad / 16 : (size_t)e->nwg; }
 
 // The per-run device tables, in stream order: Adam's bias corrections, room for the energy partials, mu_1, the layer-wise kernels'
 // f(x_l), the spill ring of a run that accumulates (`run_accumulates`) and its cleared sums.
@@ -853,7 +790,7 @@ int prepare_run(mcpc_engine* e, const mcpc_run_desc* r, bool run_accumulates, hi
                 HIP_TRY(hipMemsetAsync(e->v[l], 0, (size_t)e->Bpad * e->npad[l] * 4, stream));
             }
     }
-    const size_t erows = r->energy_mode == MCPC_ENERGY_ALL ? (size_t)r->T : 1, eslots = energy_slots(e);
+    const size_t erows = r->energy_mode == MCPC_ENERGY_ALL ? (size_t)r->T : 1, eslots = energy_slots(*e);
     if (r->energy_mode != MCPC_ENERGY_NONE && erows > e->epart_rows) {
         if (e->epart) retire(e, e->epart, stream);        // earlier launches may still write it
         e->epart = nullptr;
@@ -888,21 +825,6 @@ int prepare_run(mcpc_engine* e, const mcpc_run_desc* r, bool run_accumulates, hi
         HIP_TRY(hipMemsetAsync(e->e0sum, 0, (size_t)e->Bpad * e->npad[0] * 4, stream));
     }
     return 0;
-}
-
-// the lean epilogues address every [Bpad][npad] image with 32-bit lane offsets (KParams::lean_ok)
-bool lean_ok(const mcpc_engine* e) {
-    int widest = e->out_pad;
-    for (int l = 0; l < e->L; ++l) widest = std::max(widest, e->npad[l]);
-    return e->Bpad < (1 << 24) && (uint64_t)e->Bpad * (uint64_t)widest * 4u < (1ull << 32) && !e->knobs.no_lean;
-}
-
-// The unified-wave kernel (mcpc_steps_u.h) serves the lean runs of an engine that holds its plan: fused SGD update with or without
-// the Philox kick, Adam without noise.  Everything else -- gradients-only runs, injected noise -- keeps the main plan's kernel.
-bool use_unified(const mcpc_engine* e, const mcpc_run_desc* r) {
-    return e->u.on && (e->u.prefer || (e->has_head && r->loss_kind == MCPC_LOSS_NONE)) && e->ws == 2 && r->update_x && lean_ok(e) &&
-           ((r->xopt_kind == MCPC_XOPT_SGD && r->noise_mode != MCPC_NOISE_EXTERNAL) ||
-            (r->xopt_kind == MCPC_XOPT_ADAM && r->noise_mode == MCPC_NOISE_NONE));
 }
 
 // The kernel parameters of a run on the kernel form whose plan is `sp`: everything but the launch window (set_window) and the spill
@@ -942,7 +864,7 @@ KParams run_params(const mcpc_engine* e, const mcpc_run_desc* r, const StepPlan&
         H.lds_eo = sp.lds_eo; H.ld = sp.head_ld;
         H.lds_bias = sp.lds_hbias; H.lds_yw = sp.lds_yw;
     }
-    P.mu1 = e->mu1; P.epart = e->epart; P.epart_slots = (int)energy_slots(e);
+    P.mu1 = e->mu1; P.epart = e->epart; P.epart_slots = (int)energy_slots(*e);
     P.phases = sp.dev; P.n_phases = sp.n_phases; P.wexp = e->wexp; P.spillmax = nullptr; P.lds_spillmax = sp.lds_spillmax; P.lds_rowexp = sp.lds_rowexp; P.g_first = sp.g_first;
     P.stagger_cycles = e->knobs.stagger;
     P.L = e->L; P.has_head = e->has_head; P.B = e->d.batch; P.Bpad = e->Bpad; P.T = r->T;
@@ -958,7 +880,7 @@ KParams run_params(const mcpc_engine* e, const mcpc_run_desc* r, const StepPlan&
     P.lds_red = sp.lds_red;
     P.lds_ws_sync = sp.lds_ws_sync;
     P.ws_prio = e->knobs.ws_prio;
-    P.lean_ok = lean_ok(e);
+    P.lean_ok = lean_ok(*e);
     P.err = e->err; P.dummy = e->dummy; P.lds_floats = sp.lds_bytes / 4; P.lds_zero = sp.lds_zero;
     P.clk = e->profiling ? e->clk : nullptr;
     P.xl = sp.xl ? 1 : 0;
@@ -1073,6 +995,102 @@ int report_stamps(mcpc_engine* e, bool use_u, int t, int n, hipStream_t stream) 
 }
 #endif
 
+// What the executor of a run (mcpc_run) carries from launch to launch
+struct RunCtx {
+    mcpc_engine* e;
+    const mcpc_run_desc* r;
+    hipStream_t stream;
+    const StepPlan& sp;             // the plan of the kernel form that serves the run
+    bool use_u;                     // ... the unified-wave kernel's
+    bool hot = false;               // the in-place kernel may take a specialised instantiation (ws2_spec_candidate, target_flags_on_host)
+    bool bracket_open = false;
+    // mcpc_last_step_kernel_name: which forms this run launched (bit 0 plain launch, bit 1 round schedule)
+    unsigned launched = 0;
+    unsigned specs_rr = 0, specs_plain = 0;               // ... and which instantiations of the in-place kernel (bit = Ws2Spec)
+};
+
+// HIP events around every launch of the step kernel (at most kMaxProfBrackets since profiling was switched on: a caller that
+// leaves it on forever stops collecting, it does not accumulate HIP events without bound)
+constexpr size_t kMaxProfBrackets = 1 << 16;
+int prof_begin(RunCtx& c) {
+    mcpc_engine* e = c.e;
+    c.bracket_open = false;
+    if (!e->profiling) return 0;
+    if (e->events_used >= kMaxProfBrackets) return 0;
+    c.bracket_open = true;
+    if (e->events_used == e->events.size()) {
+        hipEvent_t a, b;
+        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return fail(MCPC_EHIP, "hipEventCreate failed");
+        e->events.emplace_back(a, b);
+    }
+    return hipEventRecord(e->events[e->events_used].first, c.stream) == hipSuccess ? 0 : fail(MCPC_EHIP, "hipEventRecord failed");
+}
+int prof_end(RunCtx& c, double steps) {
+    mcpc_engine* e = c.e;
+    if (!e->profiling || !c.bracket_open) return 0;
+    if (hipEventRecord(e->events[e->events_used].second, c.stream) != hipSuccess) return fail(MCPC_EHIP, "hipEventRecord failed");
+    ++e->events_used; e->prof_steps += steps;
+    return 0;
+}
+
+int launch_ws2(RunCtx& c, KParams& K, bool mix, int nblocks, bool accumulating) {
+    const int spec = ws2_select_mode(K, c.hot, accumulating, mix);
+    (mix ? c.specs_rr : c.specs_plain) |= 1u << spec;
+    void* args[] = {&K};
+    HIP_TRY(hipLaunchKernel(kWs2Specs[spec].fn[mix ? 1 : 0], dim3(nblocks), dim3(kWs2Threads), args, c.sp.lds_bytes, c.stream));
+    return 0;
+}
+
+// one cycle of the round schedule (plan_rounds): rr_k launches of q steps, every unit in rr_m of them; afterwards every
+// unit is at t0 + rr_m q.  `base` carries the spill pointers of the ring part in a Hebbian segment.
+int run_round_cycle(RunCtx& c, const KParams& base, int t0, int q, bool accumulating) {
+    mcpc_engine* e = c.e;
+    c.launched |= 2u;
+    KParams Q = base;
+    set_window(e, c.r, Q, t0, q);
+    Q.spill_t0 = t0; Q.rr_q = q;
+    for (int i = 0; i < e->rr_k; ++i) {
+        Q.wg_list = e->rr_tab + e->rr_off[i]; Q.wg_rel = Q.wg_list + e->rr_count[i];
+        if (const int rc = prof_begin(c)) return rc;
+        if (c.use_u) hipLaunchKernelGGL((mcpc_steps_u_kernel<true>), dim3(e->rr_count[i]), dim3(kUThreads), c.sp.lds_bytes, c.stream, Q);
+        else if (const int rc = launch_ws2(c, Q, true, e->rr_count[i], accumulating)) return rc;
+        if (const int rc = prof_end(c, (double)q * e->rr_count[i] / e->nwg_live)) return rc;
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// one plain launch of steps [t0, t0 + n) on the form that serves the run; `P` holds the launch window
+int run_plain(RunCtx& c, KParams& P, int t0, int n, bool accumulating) {
+    mcpc_engine* e = c.e;
+    if (const int rc = prof_begin(c)) return rc;
+    c.launched |= 1u;
+    if (e->lw) { if (const int rc = launch_lw_steps(e, c.r, P, t0, n, c.stream)) return rc; }
+    else if (c.use_u) hipLaunchKernelGGL((mcpc_steps_u_kernel<false>), dim3(e->nwg_live), dim3(kUThreads), c.sp.lds_bytes, c.stream, P);
+    else if (e->ws == 2) { if (const int rc = launch_ws2(c, P, false, e->nwg_live, accumulating)) return rc; }
+    else hipLaunchKernelGGL((mcpc_steps_kernel<1, 4>), dim3(e->nwg), dim3(256), c.sp.lds_bytes, c.stream, P);
+    return prof_end(c, (double)n);
+}
+
+// mcpc_last_step_kernel_name of the run
+std::string last_step_name(const RunCtx& c) {
+    // (a run on the generic instantiation alone reads as it always did; specialised launches are named behind the form they belong to)
+    auto spec_tag = [](unsigned specs) -> std::string {
+        if (!(specs & ~(1u << WS2_SPEC_GENERIC))) return "";
+        std::string tag;
+        for (int i = 0; i < WS2_SPEC_COUNT; ++i)
+            if (specs & (1u << i)) tag += (tag.empty() ? "" : ", ") + std::string(kWs2Specs[i].tag);
+        return " [mcpc_steps_ws2_spec_kernel: " + tag + "]";
+    };
+    std::string name;
+    if (c.launched & 2u) name = (c.use_u ? c.e->u_rr_name : c.e->rr_name) + spec_tag(c.specs_rr);
+    if (c.launched & 1u) {
+        if (!name.empty()) name += " + ";
+        name += plain_kernel_name(*c.e, c.use_u) + spec_tag(c.specs_plain);
+    }
+    return name;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1082,179 +1100,61 @@ int mcpc_run(mcpc_engine* e, const mcpc_run_desc* r, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(e->d.device));
     if (const int rc = check_run(e, r)) return rc;
-    const int acc_b = std::max(r->acc_begin, 0), acc_e = std::min(r->acc_end, r->T);
     if (!e->retired.empty()) free_completed_retired(e);
-    const bool run_accumulates = acc_b < acc_e && r->t_begin < acc_e && r->t_begin + r->n_steps > acc_b;
+    // the schedule (mcpc_plan.h: no device work), then what it needs on the device
+    RunPlan& plan = e->run_plan;
+    plan_run(*e, *r, MCPC_STAMPS_BUILD != 0, plan);
+    const bool run_accumulates = plan.accumulates, overlap = plan.overlap;
     if (const int rc = prepare_run(e, r, run_accumulates, stream)) return rc;
-    const size_t eslots = energy_slots(e);
-    const bool use_u = use_unified(e, r);
-    const StepPlan& sp = use_u ? e->u.plan : e->main;
-    KParams P = run_params(e, r, sp);
+    const size_t eslots = energy_slots(*e);
+    const int end = r->t_begin + r->n_steps;
+    RunCtx c{e, r, stream, plan.unified ? e->u.plan : e->main, plan.unified};
+    KParams P = run_params(e, r, c.sp);
 #ifdef MCPC_STAMPS
     if (!e->dbg) { int rc = dmalloc(e->dbg, (size_t)e->nwg * 2 * kMaxWaves * 16); if (rc) return rc; }
     P.dbg = e->dbg;
 #endif
+    // (a run on the unified-wave kernel never asks: no wait, no query)
+    if (!c.use_u && ws2_spec_candidate(e, P))
+        if (const int rc = target_flags_on_host(e, P, r->n_steps, c.hot)) return rc;
 
-    // ---- step segments: non-accumulating stretches run as one persistent launch; accumulating
-    //      stretches are cut at the spill ring's capacity and followed by a Hebbian flush ----------
-    int t = r->t_begin;
-    const int end = r->t_begin + r->n_steps;
-    const bool overlap = e->aux != nullptr;
-    int half = 0;                                         // part of the ring the next accumulating segment spills into
-    const int n_parts = std::max(1, e->slots / std::max(1, e->half_slots));
-    // HIP events around every launch of the step kernel (at most kMaxProfBrackets since profiling was switched on: a caller that
-    // leaves it on forever stops collecting, it does not accumulate HIP events without bound)
-    constexpr size_t kMaxProfBrackets = 1 << 16;
-    bool bracket_open = false;
-    auto prof_begin = [&]() -> int {
-        bracket_open = false;
-        if (!e->profiling) return 0;
-        if (e->events_used >= kMaxProfBrackets) return 0;
-        bracket_open = true;
-        if (e->events_used == e->events.size()) {
-            hipEvent_t a, b;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return fail(MCPC_EHIP, "hipEventCreate failed");
-            e->events.emplace_back(a, b);
-        }
-        return hipEventRecord(e->events[e->events_used].first, stream) == hipSuccess ? 0 : fail(MCPC_EHIP, "hipEventRecord failed");
-    };
-    auto prof_end = [&](double steps) -> int {
-        if (!e->profiling || !bracket_open) return 0;
-        if (hipEventRecord(e->events[e->events_used].second, stream) != hipSuccess) return fail(MCPC_EHIP, "hipEventRecord failed");
-        ++e->events_used; e->prof_steps += steps;
-        return 0;
-    };
-    // one cycle of the round schedule (plan_rounds): rr_k launches of q steps, every unit in rr_m of them; afterwards every
-    // unit is at t0 + rr_m q.  `base` carries the spill pointers of the ring part in a Hebbian segment.
-    bool rr_ok = e->rr && r->update_x;
-#ifdef MCPC_STAMPS
-    rr_ok = false;
-#endif
-    // mcpc_last_step_kernel_name: which forms this run launched (bit 0 plain launch, bit 1 round schedule)
-    unsigned launched = 0;
-    unsigned specs_rr = 0, specs_plain = 0;               // ... and which instantiations of the in-place kernel (bit = Ws2Spec)
-    bool hot = false;                                     // (a run on the unified-wave kernel never asks: no wait, no query)
-    if (!use_u && ws2_spec_candidate(e, P))
-        if (const int rc = target_flags_on_host(e, P, r->n_steps, hot)) return rc;
-    auto launch_ws2 = [&](KParams& K, bool mix, int nblocks, bool accumulating) -> int {
-        const int spec = ws2_select_mode(K, hot, accumulating, mix);
-        (mix ? specs_rr : specs_plain) |= 1u << spec;
-        void* args[] = {&K};
-        HIP_TRY(hipLaunchKernel(kWs2Specs[spec].fn[mix ? 1 : 0], dim3(nblocks), dim3(kWs2Threads), args, sp.lds_bytes, stream));
-        return 0;
-    };
-    auto run_round_cycle = [&](const KParams& base, int t0, int q, bool accumulating) -> int {
-        launched |= 2u;
-        KParams Q = base;
-        set_window(e, r, Q, t0, q);
-        Q.spill_t0 = t0; Q.rr_q = q;
-        for (int i = 0; i < e->rr_k; ++i) {
-            Q.wg_list = e->rr_tab + e->rr_off[i]; Q.wg_rel = Q.wg_list + e->rr_count[i];
-            { const int rc = prof_begin(); if (rc) return rc; }
-            if (use_u) hipLaunchKernelGGL((mcpc_steps_u_kernel<true>), dim3(e->rr_count[i]), dim3(kUThreads), sp.lds_bytes, stream, Q);
-            else if (const int rc = launch_ws2(Q, true, e->rr_count[i], accumulating)) return rc;
-            { const int rc = prof_end((double)q * e->rr_count[i] / e->nwg_live); if (rc) return rc; }
-        }
-        HIP_TRY(hipGetLastError());
-        return 0;
-    };
-    while (t < end) {
-        const bool in_acc = t >= acc_b && t < acc_e;
-        int n;
-        if (in_acc) {
-            const int rem = std::min(end, acc_e) - t;
-            n = std::min(rem, e->half_slots);
-            // the flush of a stretch's LAST segment has no step kernel to hide behind: keep that segment short
-            const int tail = e->knobs.flush_tail;
-            if (overlap && tail > 0 && rem <= e->half_slots && rem >= 2 * tail && std::min(end, acc_e) == acc_e) n = rem - tail;
-        }
-        else n = (t < acc_b ? std::min(end, acc_b) : end) - t;
-        // a launch's row-exponent words carry their generation -- the step of the launch, or step x entries + entry for a ring slot -- in 24
-        // bits (mcpc_kernels.h: rowexp_track): longer stretches are cut into several launches (a wrapped generation would never
-        // supersede the stale word)
-        n = std::min(n, ((1 << 24) - 2) / std::max(std::max(e->main.n_phases, e->u.plan.n_phases), 1));
-        int rr_q = 0;
-        if (rr_ok && in_acc) {
-            rr_q = n / e->rr_m;                               // a Hebbian segment is one cycle (fewer steps than rr_m left: plain launch)
-            if (rr_q >= 1) n = rr_q * e->rr_m;
-        } else if (rr_ok) {
-            // whole cycles, longest launches first; fewer than rr_m steps left run as one plain launch (hardware rounds)
-            while (n >= e->rr_m) {
-                const int q = std::min(std::max(1, e->knobs.rr_qmax), n / e->rr_m);
-                const int rc = run_round_cycle(P, t, q, false);
-                if (rc) return rc;
-                t += q * e->rr_m; n -= q * e->rr_m;
-            }
-            if (n == 0) continue;
-        }
-        const int slot0 = in_acc && overlap ? half * e->half_slots : 0;
-        set_window(e, r, P, t, n);
-        P.spill_t0 = t;
-        if (in_acc) {
+    // ---- the plan's items, in order: a plain launch or a cycle of the round schedule each; one inside the accumulation window
+    //      spills into its part of the ring and is followed by that part's Hebbian flush -----------------------------------
+    for (const RunItem& it : plan.items) {
+        set_window(e, r, P, it.t0, it.n);
+        P.spill_t0 = it.t0;
+        if (it.acc) {
             for (int l = 0; l < e->L; ++l) {
-                const size_t off = (size_t)slot0 * e->Bpad * e->npad[l];
+                const size_t off = (size_t)it.slot0 * e->Bpad * e->npad[l];
                 P.layer[l].spill_a = e->spill_a[l] + off;
                 if (l >= 1) P.layer[l].spill_e = e->spill_e[l] + off;
             }
-            if (e->has_head) P.head.spill_e = e->spill_eo + (size_t)slot0 * e->Bpad * e->out_pad;
+            if (e->has_head) P.head.spill_e = e->spill_eo + (size_t)it.slot0 * e->Bpad * e->out_pad;
             // this part of the ring may still be read by the flush that was started n_parts segments ago
-            if (overlap && e->flush_pending[half]) { HIP_TRY(hipStreamWaitEvent(stream, e->ev_flush[half], 0)); e->flush_pending[half] = false; }
+            if (overlap && e->flush_pending[it.part]) { HIP_TRY(hipStreamWaitEvent(stream, e->ev_flush[it.part], 0)); e->flush_pending[it.part] = false; }
             // the segment's largest |value| per spilled tensor: starts at zero, raised by the step kernel's workgroups, read by the flush
-            P.spillmax = e->spillmax + (size_t)(overlap ? half : 0) * kSpillTensors;
+            P.spillmax = e->spillmax + (size_t)it.part * kSpillTensors;
             HIP_TRY(hipMemsetAsync(P.spillmax, 0, kSpillTensors * sizeof(unsigned), stream));
         } else {
             P.spillmax = nullptr;
         }
-        if (rr_q >= 1) {
-            const int rc = run_round_cycle(P, t, rr_q, in_acc);
-            if (rc) return rc;
-        } else {
-            { const int rc = prof_begin(); if (rc) return rc; }
-            launched |= 1u;
-            if (e->lw) { const int rc = launch_lw_steps(e, r, P, t, n, stream); if (rc) return rc; }
-            else if (use_u) hipLaunchKernelGGL((mcpc_steps_u_kernel<false>), dim3(e->nwg_live), dim3(kUThreads), sp.lds_bytes, stream, P);
-            else if (e->ws == 2) { const int rc = launch_ws2(P, false, e->nwg_live, in_acc); if (rc) return rc; }
-            else hipLaunchKernelGGL((mcpc_steps_kernel<1, 4>), dim3(e->nwg), dim3(256), sp.lds_bytes, stream, P);
-            { const int rc = prof_end((double)n); if (rc) return rc; }
-        }
+        if (const int rc = it.q >= 1 ? run_round_cycle(c, P, it.t0, it.q, it.acc) : run_plain(c, P, it.t0, it.n, it.acc)) return rc;
         HIP_TRY(hipGetLastError());
 #ifdef MCPC_STAMPS
-        if (const int rc = report_stamps(e, use_u, t, n, stream)) return rc;
+        if (const int rc = report_stamps(e, c.use_u, it.t0, it.n, stream)) return rc;
 #endif
-        if (in_acc) {
-            if (overlap) {
-                // the Hebbian GEMMs of this part run on the low-priority stream while the next segment steps
-                HIP_TRY(hipEventRecord(e->ev_steps[half], stream));
-                HIP_TRY(hipStreamWaitEvent(e->aux, e->ev_steps[half], 0));
-                int rc = flush_spill(e, n, slot0, e->aux, half);
-                if (rc) return rc;
-                HIP_TRY(hipEventRecord(e->ev_flush[half], e->aux));
-                e->flush_pending[half] = true;
-                half = (half + 1) % n_parts;
-            } else {
-                int rc = flush_spill(e, n, 0, stream, 0);
-                if (rc) return rc;
-            }
+        if (it.acc && overlap) {
+            // the Hebbian GEMMs of this part run on the low-priority stream while the next segment steps
+            HIP_TRY(hipEventRecord(e->ev_steps[it.part], stream));
+            HIP_TRY(hipStreamWaitEvent(e->aux, e->ev_steps[it.part], 0));
+            if (const int rc = flush_spill(e, it.n, it.slot0, e->aux, it.part)) return rc;
+            HIP_TRY(hipEventRecord(e->ev_flush[it.part], e->aux));
+            e->flush_pending[it.part] = true;
+        } else if (it.acc) {
+            if (const int rc = flush_spill(e, it.n, 0, stream, 0)) return rc;
         }
-        t += n;
     }
-    {
-        // (a run on the generic instantiation alone reads as it always did; specialised launches are named behind the form they belong to)
-        auto spec_tag = [](unsigned specs) -> std::string {
-            if (!(specs & ~(1u << WS2_SPEC_GENERIC))) return "";
-            std::string tag;
-            for (int i = 0; i < WS2_SPEC_COUNT; ++i)
-                if (specs & (1u << i)) tag += (tag.empty() ? "" : ", ") + std::string(kWs2Specs[i].tag);
-            return " [mcpc_steps_ws2_spec_kernel: " + tag + "]";
-        };
-        std::string name;
-        if (launched & 2u) name = (use_u ? e->u_rr_name : e->rr_name) + spec_tag(specs_rr);
-        if (launched & 1u) {
-            if (!name.empty()) name += " + ";
-            name += plain_kernel_name(*e, use_u) + spec_tag(specs_plain);
-        }
-        e->last_step = name;
-    }
+    e->last_step = last_step_name(c);
     // everything that follows on the caller's stream (dw0, gradient read-out, the next run) sees finished sums
     for (int h = 0; h < kMaxRingParts; ++h)
         if (overlap && e->flush_pending[h]) { HIP_TRY(hipStreamWaitEvent(stream, e->ev_flush[h], 0)); e->flush_pending[h] = false; }
@@ -1712,6 +1612,21 @@ int mcpc_debug_plan(const mcpc_net_desc* d, int32_t n_cu, int64_t total_mem, cha
     if (const int rc = parse_tuning(d->tuning, plan.knobs)) return rc;
     if (const int rc = plan_engine(*d, n_cu, (size_t)total_mem, plan)) return rc;
     const std::string s = plan_json(plan);
+    if (needed) *needed = (int64_t)s.size() + 1;
+    if (cap > 0) { const size_t n = std::min<size_t>(s.size(), (size_t)cap - 1); std::memcpy(out, s.data(), n); out[n] = 0; }
+    return MCPC_OK;
+}
+
+int mcpc_debug_run_plan(const mcpc_net_desc* d, int32_t n_cu, int64_t total_mem, const mcpc_run_desc* r, char* out, int64_t cap, int64_t* needed) {
+    if (!d || !r || n_cu < 1 || total_mem < 0 || cap < 0 || (cap > 0 && !out)) return fail(MCPC_EINVAL, "bad argument");
+    if (const int rc = check_net_desc(d)) return rc;
+    EnginePlan plan;
+    if (const int rc = parse_tuning(d->tuning, plan.knobs)) return rc;
+    if (const int rc = plan_engine(*d, n_cu, (size_t)total_mem, plan)) return rc;
+    if (const int rc = check_step_range(*r)) return rc;
+    RunPlan run;
+    plan_run(plan, *r, MCPC_STAMPS_BUILD != 0, run);
+    const std::string s = run_plan_json(plan, run);
     if (needed) *needed = (int64_t)s.size() + 1;
     if (cap > 0) { const size_t n = std::min<size_t>(s.size(), (size_t)cap - 1); std::memcpy(out, s.data(), n); out[n] = 0; }
     return MCPC_OK;

@@ -1,7 +1,9 @@
 // Host-side planning of an engine: everything mcpc_create decides BEFORE it allocates -- padded shapes, the step-kernel form and its
-// fallbacks, the LDS plans and step tables, the layer-wise job tables, the round schedule, the spill ring's size.  Plain host code
-// that makes no HIP call, so it runs (and is tested: mcpc_debug_plan, tests/test_plan_host.py) without a device.  Included by
-// mcpc_api.hip only, after the kernel headers whose constants and table types it uses.
+// fallbacks, the LDS plans and step tables, the layer-wise job tables, the round schedule, the spill ring's size -- and what mcpc_run
+// decides before it launches: the schedule of a run (plan_run) and the shape of a Hebbian flush (plan_hebbian).  Plain host code
+// that makes no HIP call, so it runs (and is tested: mcpc_debug_plan, tests/test_plan_host.py; mcpc_debug_run_plan,
+// tests/test_run_plan_host.py) without a device.  Included by mcpc_api.hip only, after the kernel headers whose constants and table
+// types it uses.
 #pragma once
 
 #include <algorithm>
@@ -159,7 +161,7 @@ struct StepPlan {
     int take(const char* name, int layer, int& off, int floats) { regions.push_back({name, layer, off, floats}); off += floats; return off - floats; }
 };
 
-// LDS plan and step table of the unified-wave kernel (mcpc_steps_u.h), kept BESIDE the engine's main plan: use_unified (mcpc_api.hip)
+// LDS plan and step table of the unified-wave kernel (mcpc_steps_u.h), kept BESIDE the engine's main plan: use_unified
 // picks the kernel per run (lean runs: fused SGD update with or without the Philox kick, Adam without noise), everything else stays
 // on the main plan's kernel.
 struct UPlan {
@@ -648,7 +650,7 @@ inline void build_phases_u(const EnginePlan& e, StepPlan& u) {
 // A step's fixed costs per table entry are what the unified form removes; the overlap of GEMM and epilogue waves is what it gives up, and
 // at cfg-M's width that overlap is worth more.  The unit is what both scale with: (unit tile, 32-deep k-block) pairs of all GEMMs of a step.
 // A ZERO-LOSS call (unclamped generation) runs on the unified kernel whatever the width: only that kernel skips the read-out on the steps
-// nobody records (cfg-M's net: 16.6 against 25.3 us per step) -- use_unified (mcpc_api.hip) decides that per run.
+// nobody records (cfg-M's net: 16.6 against 25.3 us per step) -- use_unified decides that per run.
 inline int gemm_tile_blocks(const EnginePlan& e) {
     int n = 0;
     for (int l = 1; l < e.L; ++l) n += (e.npad[l] / 16) * kblocks(e.npad[l - 1]) + (e.npad[l - 1] / 16) * kblocks(e.npad[l]);
@@ -919,6 +921,158 @@ inline int plan_engine(const mcpc_net_desc& d, int n_cu, size_t total_mem, Engin
     return 0;
 }
 
+// How the Hebbian sums of Linear j are computed for `rows` spilled rows: the LDS-tiled kernel (mcpc_hebbian.h) for wide
+// Linears -- as one or two launches whose error-tile groups cover the output exactly (49 tiles = 17 + 16 + 16) -- the same
+// kernel with the operands swapped for a wide Linear with a narrow input (256 x 32: the narrow side takes the TE slot),
+// and the register-streaming kernel for whatever is left (few output tiles: HBM-bound whatever the tiling).
+struct HebPlan {
+    bool tiled = false, swapped = false;
+    int ra = 0;                                    // activation tiles per wave (TA = 8 ra)
+    int te[2] = {0, 0}, n_mt[2] = {0, 0};          // up to two launches: error tiles per group, number of groups
+    int n_nt = 1;
+    int wave_tiles = 0;                            // streaming kernel: 64 x 64 wave tiles
+    int ksplit = 1, rps = 0;
+    int ksplit_cap = 1;                            // upper bound of ksplit that never decreases with `rows`: sizes the slabs
+                                                   // (tests/test_run_plan_host.py: every flush of a run against a whole ring part's)
+};
+
+inline HebPlan plan_hebbian(const Knobs& kn, int ne, int na, int rows) {
+    HebPlan h;
+    const int et = ne / 16, at = na / 16;
+    const bool wide = heb_wide(et, at);
+    const bool narrow_in = heb_narrow_in(et, at);       // e.g. 256 x 32
+    h.tiled = wide || narrow_in;
+    h.swapped = narrow_in;
+    if (wide) {
+        h.ra = at >= 16 ? 2 : 1;
+        h.n_nt = at / (8 * h.ra);
+        if (et <= 8) { h.te[0] = 8; h.n_mt[0] = 1; }
+        else if (et <= 16) { h.te[0] = 16; h.n_mt[0] = 1; }
+        else {
+            // et = 17 b + 16 a exactly when b = et mod 16 groups of 17 fit; otherwise groups of 17 with a ragged last one
+            const int b17 = et % 16, a16 = (et - 17 * b17) / 16;
+            if (et - 17 * b17 >= 0) { h.te[0] = 17; h.n_mt[0] = b17; h.te[1] = 16; h.n_mt[1] = a16; }
+            else { h.te[0] = 17; h.n_mt[0] = (et + 16) / 17; }
+            if (h.n_mt[0] == 0) { h.te[0] = h.te[1]; h.n_mt[0] = h.n_mt[1]; h.te[1] = 0; h.n_mt[1] = 0; }
+        }
+    } else if (narrow_in) {
+        h.ra = 2; h.n_nt = 1; h.te[0] = at; h.n_mt[0] = 1;          // E slot = activations (at tiles), A slot = errors (16 tiles)
+    }
+    if (h.tiled) {
+        // ~48 stages of 32 rows per workgroup (0.3 ms at cfg-M): short enough that the step kernel's next segment never
+        // waits long for CUs, long enough that the slab traffic stays at a few percent of the spill's
+        int want = kn.dw_ksplit > 0 ? kn.dw_ksplit : std::max(1, rows / (48 * kHebKB));
+        // a small flush (the reference's batch of 256: 25 600 rows, 16 splits) would run 16-48 workgroups of 48 stages on an idle chip,
+        // 0.10-0.17 ms per Linear: with at least 8 stages per workgroup, split until the launch has about a workgroup per CU
+        if (kn.dw_ksplit <= 0) {
+            const int cols = std::max(1, (h.n_mt[0] + h.n_mt[1]) * h.n_nt);
+            want = std::max(want, std::min(rows / (8 * kHebKB), (256 + cols - 1) / cols));
+        }
+        want = std::min(want, std::max(1, rows / kHebKB));
+        h.ksplit_cap = want;
+        h.rps = ((rows + want - 1) / want + kHebKB - 1) / kHebKB * kHebKB;
+        h.ksplit = (rows + h.rps - 1) / h.rps;
+    } else {
+        h.wave_tiles = ((ne + 63) / 64) * ((na + 63) / 64);
+        int ksplit = std::max(1, std::min(4096 / h.wave_tiles, rows / 64));
+        h.ksplit_cap = ksplit;
+        h.rps = ((rows + ksplit - 1) / ksplit + 15) / 16 * 16;
+        h.ksplit = (rows + h.rps - 1) / h.rps;
+    }
+    return h;
+}
+
+// ---- the schedule of a run -----------------------------------------------------------------------------------------------------------------
+// energy partials per step: one slot per workgroup; the in-place kernel indexes them by 16-chain tile
+inline size_t energy_slots(const EnginePlan& e) { return e.lw ? (size_t)e.nwg_live : e.ws == 2 ? (size_t)e.Bpad / 16 : (size_t)e.nwg; }
+
+// the lean epilogues address every [Bpad][npad] image with 32-bit lane offsets (KParams::lean_ok)
+inline bool lean_ok(const EnginePlan& e) {
+    int widest = e.out_pad;
+    for (int l = 0; l < e.L; ++l) widest = std::max(widest, e.npad[l]);
+    return e.Bpad < (1 << 24) && (uint64_t)e.Bpad * (uint64_t)widest * 4u < (1ull << 32) && !e.knobs.no_lean;
+}
+
+// The unified-wave kernel (mcpc_steps_u.h) serves the lean runs of an engine that holds its plan: fused SGD update with or without
+// the Philox kick, Adam without noise.  Everything else -- gradients-only runs, injected noise -- keeps the main plan's kernel.
+inline bool use_unified(const EnginePlan& e, const mcpc_run_desc& r) {
+    return e.u.on && (e.u.prefer || (e.has_head && r.loss_kind == MCPC_LOSS_NONE)) && e.ws == 2 && r.update_x && lean_ok(e) &&
+           ((r.xopt_kind == MCPC_XOPT_SGD && r.noise_mode != MCPC_NOISE_EXTERNAL) ||
+            (r.xopt_kind == MCPC_XOPT_ADAM && r.noise_mode == MCPC_NOISE_NONE));
+}
+
+inline int check_step_range(const mcpc_run_desc& r) {
+    if (r.T < 1 || r.t_begin < 0 || r.n_steps < 1 || r.t_begin + r.n_steps > r.T)
+        return fail(MCPC_EINVAL, "bad step range: T=%d t_begin=%d n_steps=%d", r.T, r.t_begin, r.n_steps);
+    return 0;
+}
+
+// One item of a run: steps [t0, t0 + n) as ONE plain launch (q == 0: the layer-wise pair, the unified-wave, in-place or barrier kernel,
+// as the engine and the run have it) or as ONE cycle of the round schedule (q >= 1: rr_k launches of q steps, n == rr_m q).  An item
+// lies wholly on one side of the accumulation window; one inside it (`acc`) is a Hebbian segment: it spills into slots
+// [slot0, slot0 + n) of the ring -- part `part` -- and a flush of those n slots follows it.
+struct RunItem { int t0, n, q; bool acc; int part, slot0; };
+struct RunPlan {
+    bool unified = false;           // the run is served by the unified-wave kernel (use_unified), else by the engine's main plan
+    bool accumulates = false;       // some step of the run lies in the accumulation window
+    bool lean_ok = false;
+    bool overlap = false;           // flushes run on the auxiliary stream beside the next segment (a ring of n_parts parts), else serially
+    int n_parts = 1;
+    std::vector<RunItem> items;
+};
+
+// What mcpc_run launches for `r`, in order: a pure function of the engine's plan and the fields of the descriptor that shape a run
+// (T, t_begin, n_steps, acc_begin, acc_end, update_x, xopt_kind, noise_mode, loss_kind).  `stamps`: the diagnostic build with in-kernel
+// stamps, which never uses the round schedule.  Non-accumulating stretches run as one persistent launch (on the round schedule: whole
+// cycles, longest launches first, and one plain launch for fewer than rr_m steps left: hardware rounds); accumulating stretches are cut
+// at the capacity of a ring part, every segment one cycle where the round schedule applies.  `p.items` keeps its storage between runs.
+// (tests/test_run_plan_host.py, through mcpc_debug_run_plan)
+inline void plan_run(const EnginePlan& e, const mcpc_run_desc& r, bool stamps, RunPlan& p) {
+    const int acc_b = std::max(r.acc_begin, 0), acc_e = std::min(r.acc_end, r.T);
+    const int end = r.t_begin + r.n_steps;
+    p.unified = use_unified(e, r);
+    p.accumulates = acc_b < acc_e && r.t_begin < acc_e && end > acc_b;
+    p.lean_ok = lean_ok(e);
+    p.overlap = e.half_slots < e.slots;
+    p.n_parts = std::max(1, e.slots / std::max(1, e.half_slots));
+    p.items.clear();
+    const bool rr_ok = e.rr && r.update_x && !stamps;
+    // a launch's row-exponent words carry their generation -- the step of the launch, or step x entries + entry for a ring slot -- in 24
+    // bits (mcpc_kernels.h: rowexp_track): longer stretches are cut into several launches (a wrapped generation would never supersede
+    // the stale word)
+    const int gen_cap = ((1 << 24) - 2) / std::max(std::max(e.main.n_phases, e.u.plan.n_phases), 1);
+    const int tail = e.knobs.flush_tail;
+    int part = 0;                                         // part of the ring the next accumulating segment spills into
+    for (int t = r.t_begin; t < end;) {
+        const bool in_acc = t >= acc_b && t < acc_e;
+        int n;
+        if (in_acc) {
+            const int rem = std::min(end, acc_e) - t;
+            n = std::min(rem, e.half_slots);
+            // the flush of a stretch's LAST segment has no step kernel to hide behind: keep that segment short
+            if (p.overlap && tail > 0 && rem <= e.half_slots && rem >= 2 * tail && std::min(end, acc_e) == acc_e) n = rem - tail;
+        }
+        else n = (t < acc_b ? std::min(end, acc_b) : end) - t;
+        n = std::min(n, gen_cap);
+        int q = 0;
+        if (rr_ok && in_acc) {
+            q = n / e.rr_m;                                   // a Hebbian segment is one cycle (fewer steps than rr_m left: plain launch)
+            if (q >= 1) n = q * e.rr_m;
+        } else if (rr_ok) {
+            while (n >= e.rr_m) {
+                const int qc = std::min(std::max(1, e.knobs.rr_qmax), n / e.rr_m);
+                p.items.push_back({t, qc * e.rr_m, qc, false, 0, 0});
+                t += qc * e.rr_m; n -= qc * e.rr_m;
+            }
+            if (n == 0) continue;
+        }
+        const bool ring = in_acc && p.overlap;                // (a serial run keeps part 0, slot 0)
+        p.items.push_back({t, n, q, in_acc, ring ? part : 0, ring ? part * e.half_slots : 0});
+        if (ring) part = (part + 1) % p.n_parts;
+        t += n;
+    }
+}
+
 }  // namespace mcpc
 
 // ---- mcpc_debug_plan: a plan as JSON ------------------------------------------------------------------------------------------------------
@@ -971,6 +1125,34 @@ inline std::string plan_json(const EnginePlan& e) {
         s += "]";
     }
     s += "]}}";
+    return s;
+}
+
+// mcpc_debug_run_plan: the schedule of a run, and the flush plan of every Linear j >= 1 behind each of its Hebbian segments
+inline std::string run_plan_json(const EnginePlan& e, const RunPlan& p) {
+    std::string s;
+    json_add(s, "{\"unified\":%d,\"accumulates\":%d,\"lean_ok\":%d,\"overlap\":%d,\"n_parts\":%d,"
+                "\"fields\":[\"t0\",\"n\",\"q\",\"acc\",\"part\",\"slot0\",\"flush\"],\"items\":[",
+             p.unified ? 1 : 0, p.accumulates ? 1 : 0, p.lean_ok ? 1 : 0, p.overlap ? 1 : 0, p.n_parts);
+    for (size_t i = 0; i < p.items.size(); ++i) {
+        const RunItem& it = p.items[i];          // ("flush": a flush of the item's n slots follows it -- every Hebbian segment, nothing else)
+        json_add(s, "%s[%d,%d,%d,%d,%d,%d,%d]", i ? "," : "", it.t0, it.n, it.q, it.acc ? 1 : 0, it.part, it.slot0, it.acc ? 1 : 0);
+    }
+    s += "],\"flush_fields\":[\"ksplit\",\"rps\",\"ksplit_cap\"],\"flushes\":[";
+    const int nlin = e.L + (e.has_head ? 1 : 0);
+    bool first = true;
+    for (const RunItem& it : p.items) {
+        if (!it.acc) continue;
+        json_add(s, "%s{\"rows\":%d,\"lin\":[", first ? "" : ",", it.n * e.Bpad);
+        first = false;
+        for (int j = 1; j < nlin; ++j) {
+            const Lin& ln = e.lin[j];
+            const HebPlan h = plan_hebbian(e.knobs, ln.out_pad, ln.in_pad, it.n * e.Bpad);
+            json_add(s, "%s[%d,%d,%d]", j > 1 ? "," : "", h.ksplit, h.rps, plan_hebbian(e.knobs, ln.out_pad, ln.in_pad, e.half_slots * e.Bpad).ksplit_cap);
+        }
+        s += "]}";
+    }
+    s += "]}";
     return s;
 }
 
