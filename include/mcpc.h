@@ -286,6 +286,40 @@ int mcpc_cov_accumulate(int device, const float* const* rec, const int32_t* widt
                         int32_t B, int32_t first, int32_t stride, int32_t n, int32_t pool, double* outer, int accumulate,
                         void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Streaming histograms of recorded steps: integer counts of g(r) per unit, the marginal distribution a Langevin call is looked at
+ * through (the reference bins recorded trajectories with plt.hist(..., bins=np.linspace(lo, hi, k)): figure_2.py, figure_3.py,
+ * figure_4.py, figure_6.py); quantiles, credible intervals and densities follow from the counts (csrc/mcpc_hist.h).
+ * rec is a record buffer as mcpc_run writes it, [records][B][width] fp32; records first + k*stride, k = 0..n-1, are taken, exactly as
+ * in mcpc_moments_accumulate; transform is MCPC_MOM_IDENTITY or MCPC_MOM_SIGMOID.  edges is a HOST pointer to n_bins + 1 fp32 values,
+ * finite and strictly ascending, 1 <= n_bins <= MCPC_HIST_MAX_BINS; the library validates it before any device work and hands the table
+ * to the kernel by value in the launch arguments (at most 1028 B).  counts is int64 device memory with n_bins + 3 columns per row: the
+ * bins, then under, over, nan.
+ *   pool = 0:  counts [B][width][n_bins + 3], one row per chain and unit
+ *   pool = 1:  counts [width][n_bins + 3], summed over the chains
+ * A bin is decided by exact fp32 comparison against the edges; no arithmetic on the value decides it.  With v = g(r):
+ *   NaN                                  -> column n_bins + 2
+ *   v < edges[0] (-inf included)         -> column n_bins      (under)
+ *   v > edges[n_bins] (+inf included)    -> column n_bins + 1  (over)
+ *   otherwise                            -> the largest i <= n_bins - 1 with edges[i] <= v: half-open bins, the last one closed at
+ *                                           edges[n_bins]
+ * which is np.histogram(v.astype(float64), bins=edges.astype(float64)).  Denormals are compared as they are (with an edge at 0.0 the
+ * value -1e-42 is under it) and -0.0 compares equal to 0.0: the kernel compares order-preserving integer keys of the bit patterns.
+ * accumulate = 0 overwrites counts, whatever they held; accumulate != 0 adds.  Counts are integers: the result is exact, and it depends
+ * neither on the launch shape nor on how the caller chunks the records (37 records in one call, or 1 + 5 + 31 with accumulate = 1, give
+ * equal counts).  The counters of a workgroup live in LDS for the length of the call and reach counts once; workgroups that share a
+ * row of counts (pool = 1, or a record axis split over workgroups when B * width alone cannot fill the chip) add into it with 64-bit
+ * integer atomics, and an overwriting call zeroes counts first on the same stream.  Nothing outside counts is written.
+ * The library allocates nothing and copies nothing.  Stateless, asynchronous on `stream`, no engine needed, all offsets 64-bit.
+ * 16-B loads per lane when B * width % 4 == 0 and the first record taken is 16-B aligned; a scalar form otherwise.
+ * n = 0 reads nothing: it zeroes counts when accumulate = 0 and does nothing otherwise.
+ * MCPC_EINVAL, checked before any HIP call (nothing is launched then): counts or edges NULL, rec NULL with n > 0, B < 1, width < 1,
+ * stride < 1, first < 0, n < 0, n_bins outside 1..MCPC_HIST_MAX_BINS, pool not 0 or 1, an unknown transform, edges not finite or not
+ * strictly ascending. */
+#define MCPC_HIST_MAX_BINS 256
+int mcpc_hist_accumulate(int device, const float* rec, int32_t B, int32_t width, int32_t first, int32_t stride, int32_t n,
+                         int32_t transform, const float* edges, int32_t n_bins, int32_t pool, int64_t* counts, int accumulate,
+                         void* stream);
+
 /* Per-chain energies of recorded states, evaluated on the device (the reference has them per datapoint: is_return_batchelement_loss,
  * PCLayer(is_keep_energy_per_datapoint=True), get_energies(is_per_datapoint=True); pc_trainer.py:776-836, pc_layer.py:250-262).
  * A ROW is one chain at one recorded step.  x_rec[l], l < n_latent: [n_rec][batch][n_l] fp32, as mcpc_run writes rec_x[l] (n_rec = 1

@@ -15,6 +15,7 @@
 #include "mcpc_kernels.h"
 #include "mcpc_moments.h"
 #include "mcpc_cov.h"
+#include "mcpc_hist.h"
 #include "mcpc_plan.h"
 #include "mcpc_chain_energy.h"
 
@@ -1380,6 +1381,55 @@ int mcpc_cov_accumulate(int device, const float* const* rec, const int32_t* widt
         if (any_sig) hipLaunchKernelGGL((mcpc_cov_kernel<false, true>), grid, block, 0, stream, P);
         else hipLaunchKernelGGL((mcpc_cov_kernel<false, false>), grid, block, 0, stream, P);
     }
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+int mcpc_hist_accumulate(int device, const float* rec, int32_t B, int32_t width, int32_t first, int32_t stride, int32_t n, int32_t transform,
+                         const float* edges, int32_t n_bins, int32_t pool, int64_t* counts, int accumulate, void* stream_) {
+    if (!counts) return fail(MCPC_EINVAL, "hist: counts is null");
+    if (!edges) return fail(MCPC_EINVAL, "hist: edges is null");
+    if (B < 1) return fail(MCPC_EINVAL, "hist: B=%d, must be at least 1", B);
+    if (width < 1) return fail(MCPC_EINVAL, "hist: width=%d, must be at least 1", width);
+    if (stride < 1) return fail(MCPC_EINVAL, "hist: stride=%d, must be at least 1", stride);
+    if (first < 0) return fail(MCPC_EINVAL, "hist: first=%d, must not be negative", first);
+    if (n < 0) return fail(MCPC_EINVAL, "hist: n=%d, must not be negative", n);
+    if (n_bins < 1 || n_bins > MCPC_HIST_MAX_BINS) return fail(MCPC_EINVAL, "hist: n_bins=%d outside 1..%d", n_bins, MCPC_HIST_MAX_BINS);
+    if (pool != 0 && pool != 1) return fail(MCPC_EINVAL, "hist: pool=%d, must be 0 or 1", pool);
+    if (transform != MCPC_MOM_IDENTITY && transform != MCPC_MOM_SIGMOID) return fail(MCPC_EINVAL, "hist: unknown transform %d", transform);
+    for (int i = 0; i <= n_bins; ++i) {
+        if (!std::isfinite(edges[i])) return fail(MCPC_EINVAL, "hist: edges[%d] is not finite", i);
+        if (i > 0 && !(edges[i - 1] < edges[i]))
+            return fail(MCPC_EINVAL, "hist: edges are not strictly ascending at %d (%.9g, then %.9g)", i, (double)edges[i - 1], (double)edges[i]);
+    }
+    if (n > 0 && !rec) return fail(MCPC_EINVAL, "hist: rec is null with n=%d", n);
+    if (n == 0 && accumulate) return MCPC_OK;                     // nothing to add
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(device));
+    const int64_t E = (int64_t)B * width, ncol = n_bins + 3;
+    const size_t out_bytes = (size_t)(pool ? (int64_t)width : E) * ncol * sizeof(int64_t);
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(counts, 0, out_bytes, stream));
+        return MCPC_OK;
+    }
+    // all offsets in 64 bits, as in mcpc_moments_accumulate
+    const float* r0 = rec + (int64_t)first * E;
+    const int kVec = (E % 4 == 0 && (uintptr_t)r0 % 16 == 0) ? 4 : 1;
+    const HistPlan plan = hist_plan(E, width, pool, n, n_bins, kVec);
+    HistParams P{};
+    for (int i = 0; i < kHistTable; ++i) P.key[i] = i < n_bins ? hist_key(edges[i]) : 0xffffffffu;
+    P.key_hi = hist_key(edges[n_bins]);
+    P.n_bins = n_bins;
+    P.top = 1;
+    while (2 * P.top <= n_bins - 1) P.top *= 2;
+    P.TV = plan.TV; P.n = n; P.seg = plan.seg; P.width = width; P.pool = pool;
+    P.exclusive = (!pool && plan.segments == 1) ? 1 : 0;
+    P.accumulate = accumulate ? 1 : 0;
+    P.E = E; P.row_step = (int64_t)stride * E; P.tiles = plan.tiles; P.period = plan.period; P.splits = plan.splits;
+    // workgroups that share a destination add into it with integer atomics: an overwriting call starts them from zero
+    if (!P.exclusive && !accumulate) HIP_TRY(hipMemsetAsync(counts, 0, out_bytes, stream));
+    if (kVec == 4) hist_launch<4>(transform, r0, P, plan, counts, stream);
+    else hist_launch<1>(transform, r0, P, plan, counts, stream);
     HIP_TRY(hipGetLastError());
     return MCPC_OK;
 }

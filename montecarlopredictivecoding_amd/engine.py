@@ -445,3 +445,40 @@ def cov_accumulate(recs, first, stride, n, outer, transforms=None, pool=False, a
     stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     L.check(lib.mcpc_cov_accumulate(device.index or 0, ptrs, w, xf, len(recs), B, first, stride, n, 1 if pool else 0, _ptr(outer),
                                     1 if accumulate else 0, _ptr(workspace) if pool else None, ws_bytes, stream))
+
+
+def hist_accumulate(rec, first, stride, n, edges, counts, transform="identity", pool=False, accumulate=True):
+    """Count records ``rec[first + k * stride]``, k < n, into the int64 histogram ``counts`` on the device (include/mcpc.h:
+    mcpc_hist_accumulate).  ``rec``: contiguous fp32 ``[records, B, width]`` as an engine run records it.  ``edges``: 1-D fp32 CPU
+    tensor or array of ``n_bins + 1`` finite, strictly ascending values (at most ``L.HIST_MAX_BINS`` bins).  ``counts``: contiguous int64
+    ``[B, width, n_bins + 3]``, or ``[width, n_bins + 3]`` with ``pool=True`` (summed over the chains): the bins, then under, over, nan.
+    A bin is decided by fp32 comparison against the edges alone (half-open, the last one closed), as ``np.histogram`` with explicit
+    edges does.  ``transform``: "identity", or "sigmoid" for the read-out's Bernoulli mean.  ``accumulate=False`` overwrites.  Counts are
+    integers: exact, however the records are chunked over calls.  On the current torch stream."""
+    lib = L.load()
+    if transform not in _MOM_TRANSFORMS:
+        raise ValueError(f"transform: expected 'identity' or 'sigmoid', got {transform!r}")
+    if not isinstance(rec, torch.Tensor) or rec.dim() != 3:
+        raise TypeError("rec: expected a torch.Tensor [records, B, width]")
+    device = rec.device
+    if device.type != "cuda":
+        raise ValueError(f"rec: expected a tensor on a HIP device, got {device}")
+    _check_tensor(rec, rec.shape, device, "rec")
+    R, B, width = (int(d) for d in rec.shape)
+    first, stride, n = int(first), int(stride), int(n)
+    if n > 0 and first >= 0 and stride >= 1 and first + (n - 1) * stride >= R:
+        raise ValueError(f"rec holds {R} records, the last one asked for is {first + (n - 1) * stride}")
+    e = torch.as_tensor(edges)
+    if e.device.type != "cpu" or e.dtype != torch.float32 or e.dim() != 1:
+        raise TypeError("edges: expected a 1-D fp32 CPU tensor or array")
+    e = e.contiguous()
+    n_bins = e.numel() - 1
+    if not 1 <= n_bins <= L.HIST_MAX_BINS:
+        raise ValueError(f"edges: {e.numel()} values, expected 2..{L.HIST_MAX_BINS + 1} (1..{L.HIST_MAX_BINS} bins)")
+    if not isinstance(counts, torch.Tensor):
+        raise TypeError(f"counts: expected a torch.Tensor, got {type(counts)}")
+    _check_tensor(counts, (width, n_bins + 3) if pool else (B, width, n_bins + 3), device, "counts", torch.int64)
+    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    L.check(lib.mcpc_hist_accumulate(device.index or 0, _ptr(rec), B, width, first, stride, n, _MOM_TRANSFORMS[transform],
+                                     C.cast(e.data_ptr(), C.POINTER(C.c_float)), n_bins, 1 if pool else 0, _ptr(counts),
+                                     1 if accumulate else 0, stream))

@@ -247,6 +247,14 @@ class PCTrainer(object):
         self.mcpc_covariance = None
         self.mcpc_last_covariance = None
         self.mcpc_covariance_max_bytes = 2 << 30
+        # posterior histograms of a fused call, counted on the device out of the same ring (histogram.py): None = off, or
+        # dict(begin=0, stride=1, layers=(), outputs=None | "identity" | "sigmoid", bins=int | edges, range=(lo, hi), pool=None |
+        # "chains").  The result is a histogram.Histogram in mcpc_last_histogram; composes with mcpc_moments, mcpc_chain_energies and
+        # mcpc_covariance (one ring serves all four).  A request whose RESULT (the int64 counts) would take more than
+        # mcpc_histogram_max_bytes is a ValueError before anything runs.
+        self.mcpc_histogram = None
+        self.mcpc_last_histogram = None
+        self.mcpc_histogram_max_bytes = 2 << 30
 
     # ---- getters & setters (reference :268-461) -------------------------------------------------------
     def get_T(self) -> int:
@@ -481,6 +489,13 @@ class PCTrainer(object):
                                           "are accumulated by the fused HIP loop only".format(why_not_fused))
             plan["covariance"] = _covariance.validate_spec(self.mcpc_covariance, self._T, len(plan["net"].sizes), plan["net"].n_out,
                                                            plan["net"].sizes, plan["B"], self.mcpc_covariance_max_bytes)
+        if self.mcpc_histogram is not None:
+            from .. import histogram as _histogram
+            if plan is None:
+                raise NotImplementedError("mcpc_histogram is set, and this call runs on the generic torch loop ({}): posterior histograms "
+                                          "are counted by the fused HIP loop only".format(why_not_fused))
+            plan["histogram"] = _histogram.validate_spec(self.mcpc_histogram, self._T, len(plan["net"].sizes), plan["net"].n_out,
+                                                         plan["net"].sizes, plan["B"], self.mcpc_histogram_max_bytes)
         if plan is None:
             # outside what the kernels express: the package's generic torch loop (generic_loop.py), loudly, on the device the model
             # lives on ("must work, need not be fast").  It is no way around a missing GPU: without a visible HIP device
@@ -524,6 +539,9 @@ class PCTrainer(object):
         if plan["mode"] != "fused" and self.mcpc_covariance is not None:
             raise NotImplementedError("mcpc_covariance is set, and this call runs step by step ({}): posterior covariances are "
                                       "accumulated by the fused HIP loop only".format(plan["why_stepwise"]))
+        if plan["mode"] != "fused" and self.mcpc_histogram is not None:
+            raise NotImplementedError("mcpc_histogram is set, and this call runs step by step ({}): posterior histograms are "
+                                      "counted by the fused HIP loop only".format(plan["why_stepwise"]))
         if plan["mode"] == "fused":
             self.last_call_mode = "fused"
             with _few_cpu_threads(plan["staged"]):
@@ -854,14 +872,14 @@ class PCTrainer(object):
             energy_mode=L.ENERGY_ALL if is_return_results_every_t else L.ENERGY_LAST)
         host_step_bytes = 4 * plan["B"] * sum(n for n, on in zip(net.sizes, rec_layers) if on)
         self.last_record_slices = 0
-        mom, ce, cov = plan.get("moments"), plan.get("chain_energies"), plan.get("covariance")
-        if mom is not None or ce is not None or cov is not None:
-            # posterior moments / per-chain energies / covariances: the call runs as slices whatever its size, and the records they
-            # ask for are reduced on the device
+        mom, ce, cov, hist = plan.get("moments"), plan.get("chain_energies"), plan.get("covariance"), plan.get("histogram")
+        if mom is not None or ce is not None or cov is not None or hist is not None:
+            # posterior moments / per-chain energies / covariances / histograms: the call runs as slices whatever its size, and the
+            # records they ask for are reduced on the device
             ce_inputs = None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous())
             res, last_mom, last_ce = self._run_fused_sliced(
                 eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, is_return_outputs and net.n_out > 0,
-                every_t=is_return_results_every_t, mom=mom, ce=ce, ce_inputs=ce_inputs, cov=cov)
+                every_t=is_return_results_every_t, mom=mom, ce=ce, ce_inputs=ce_inputs, cov=cov, hist=hist)
             if mom is not None:
                 self.mcpc_last_moments = last_mom
             if ce is not None:
@@ -894,7 +912,7 @@ class PCTrainer(object):
                                      is_return_representations, is_return_xs, loss_fn)
 
     def _run_fused_sliced(self, eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, rec_out, every_t=True, mom=None,
-                          ce=None, ce_inputs=None, cov=None):
+                          ce=None, ce_inputs=None, cov=None, hist=None):
         """A call whose every-step trajectory would not fit the record budget on the device, or whose records feed `mcpc_moments`:
         the same T steps as slices of one `mcpc_run` each (slicing does not change a bit of the trajectories,
         tests/test_gpu_fullsize.py).  The latent records of a slice go to one half of a two-buffer device ring.  Records the caller's
@@ -906,24 +924,28 @@ class PCTrainer(object):
         ring and `Engine.chain_energies` evaluates the steps asked for out of its rows after each slice, on the call's own stream,
         under the slicing rules of `mom`.  With `cov` (a validated `mcpc_covariance`) its layers and read-out go through the ring too
         and `cov_accumulate` / `moments_accumulate` add their outer products and sums after each slice, on the call's own stream, under
-        the same rules; the result is left in `mcpc_last_covariance`.  Returns (RunResult, Moments or None, ChainEnergies or None)."""
-        from ..engine import RunResult, moments_accumulate, cov_accumulate, cov_workspace_bytes
+        the same rules; the result is left in `mcpc_last_covariance`.  With `hist` (a validated `mcpc_histogram`) its layers and
+        read-out go through the ring as well and `hist_accumulate` counts them after each slice, on the call's own stream, under the
+        same rules; the result is left in `mcpc_last_histogram`.  Returns (RunResult, Moments or None, ChainEnergies or None)."""
+        from ..engine import RunResult, moments_accumulate, cov_accumulate, cov_workspace_bytes, hist_accumulate
         dev, B = plan["device"], plan["B"]
         nl = len(net.sizes)
         mom_layers = [mom is not None and l in mom.layers for l in range(nl)]
         mom_out = mom is not None and mom.outputs is not None
         cov_layers = [cov is not None and l in cov.layers for l in range(nl)]
         cov_out = cov is not None and cov.outputs is not None
-        ring_layers = [a or b_ or c_ or ce is not None for a, b_, c_ in zip(rec_layers, mom_layers, cov_layers)]
-        reduced = mom is not None or ce is not None or cov is not None
+        hist_layers = [hist is not None and l in hist.layers for l in range(nl)]
+        hist_out = hist is not None and hist.outputs is not None
+        ring_layers = [a or b_ or c_ or d_ or ce is not None for a, b_, c_, d_ in zip(rec_layers, mom_layers, cov_layers, hist_layers)]
+        reduced = mom is not None or ce is not None or cov is not None or hist is not None
         out_direct = rec_out and every_t                     # every step's outputs are kept anyway: slices write them in place
-        ring_out = (rec_out or mom_out or cov_out) and not out_direct
+        ring_out = (rec_out or mom_out or cov_out or hist_out) and not out_direct
         S = T
         if any(rec_layers) and every_t:
             S = min(S, self.mcpc_record_chunk_bytes // max(2 * host_step_bytes, 1))
         if reduced:
             # one half of the ring is a chunk of at most mcpc_moments_chunk_bytes
-            step_bytes = 4 * B * (sum(n for n, on in zip(net.sizes, ring_layers) if on) + (net.n_out if ring_out or mom_out or cov_out else 0))
+            step_bytes = 4 * B * (sum(n for n, on in zip(net.sizes, ring_layers) if on) + (net.n_out if ring_out or mom_out or cov_out or hist_out else 0))
             S = min(S, self.mcpc_moments_chunk_bytes // max(step_bytes, 1))
         S = max(1, S)
         # A slice boundary inside the window that accumulates parameter gradients would regroup their fp32 sums (one Hebbian flush and
@@ -994,6 +1016,22 @@ class PCTrainer(object):
             cov_accumulate(blocks, first, cov.stride, cnt, cov_acc["outer"], transforms=cov_xf, pool=cov.pooled, accumulate=True,
                            workspace=cov_acc["ws"])
 
+        hist_acc = None
+        if hist is not None:
+            hist_xf = ["identity"] * len(hist.layers) + ([hist.outputs] if hist_out else [])
+            hist_acc = [torch.zeros(*((w, len(e) + 2) if hist.pooled else (B, w, len(e) + 2)), dtype=torch.int64, device=dev)
+                        for (_, w), e in zip(hist.columns, hist.edges)]
+
+        def reduce_hist(t0, n, half):
+            first, cnt = hist.chunk(t0, n)
+            if cnt == 0:
+                return
+            blocks = [ring[half][l] for l in hist.layers]
+            if hist_out:
+                blocks.append(out_full[t0:t0 + n] if out_direct else ring_o[half])
+            for blk, e, counts, xf in zip(blocks, hist.edges, hist_acc, hist_xf):
+                hist_accumulate(blk, first, hist.stride, cnt, e, counts, transform=xf, pool=hist.pooled, accumulate=True)
+
         ce_table = torch.empty(ce.n, B, L.ENERGY_COLS, dtype=torch.float64, device=dev) if ce is not None else None
         ce_kw = dict(loss_kind=run_kw["loss_kind"], loss_var=run_kw["loss_var"], mask_start=run_kw["mask_start"],
                      max_rows=self.mcpc_chain_energies_max_rows)
@@ -1027,6 +1065,8 @@ class PCTrainer(object):
                 evaluate(t0, n, half)
             if cov is not None:
                 reduce_cov(t0, n, half)
+            if hist is not None:
+                reduce_hist(t0, n, half)
             if ring_out and rec_out and last:
                 out_full[0].copy_(ring_o[half][n - 1])       # (not every_t: the last step's outputs)
             to_host = any(rec_layers) and (every_t or last)
@@ -1069,6 +1109,9 @@ class PCTrainer(object):
                 s = s.sum(dim=0)
             self.mcpc_last_covariance = Covariance(n=cov.n, B=B, pooled=cov.pooled, columns=list(cov.columns),
                                                    sum=s.to(plan["model_device"]), outer=cov_acc["outer"].to(plan["model_device"]))
+        if hist is not None:
+            from ..histogram import from_counts
+            self.mcpc_last_histogram = from_counts(hist, B, hist_acc, plan["model_device"])
         return RunResult(energies=energies, rec_x=host, rec_out=out_full), result, ce_result
 
     def mcpc_state_energies(self, inputs, loss_fn: typing.Callable = None, loss_fn_kwargs: dict = {}):

@@ -235,3 +235,49 @@ def get_posterior_covariance(gen_pc, config, trainers, loader, layers=(0,), pool
     finally:
         mcpc_trainer.mcpc_covariance = saved
     return torch.cat(means, dim=0), torch.cat(covs, dim=0), torch.cat(labels, dim=0)
+
+
+def get_posterior_histogram(gen_pc, config, trainers, loader, layers=(0,), bins=50, range=None, pool=None):
+    """Posterior histograms of the latent units, per batch of ``loader``: MAP call with ``trainers[0]``, then an MCPC call with
+    ``trainers[1]`` started from the MAP state (the protocol of ``get_posterior_covariance``), over the steps from ``config["mixing"]``
+    on, counted on the device by the call itself (``PCTrainer.mcpc_histogram``, integer counters in LDS): no trajectory is recorded.
+    ``layers``: the PC layers whose units are binned; ``bins`` / ``range``: as in ``mcpc_histogram`` (an int with ``range=(lo, hi)``, or
+    edges; the range is never taken from the data); ``pool``: None for one histogram per datum, "chains" for one per unit.  Returns
+    ``(histogram, labels)``: a ``histogram.Histogram`` whose chains are all data in the loader's order (``B`` = their number), or, pooled,
+    the merge of the batches' histograms (``n`` = the samples of all batches; the batches must be of one size, ``Histogram.merge``); and
+    the labels of all data."""
+    from ..histogram import Histogram
+    if len(trainers) != 2:
+        raise NotImplementedError
+    device = next(gen_pc.parameters()).device
+    input_size = len(gen_pc[0].bias)
+    pc_trainer, mcpc_trainer = trainers
+    parts, labels = [], []
+    saved = mcpc_trainer.mcpc_histogram
+    mcpc_trainer.mcpc_histogram = dict(begin=int(config["mixing"]), stride=1, layers=tuple(layers), outputs=None, bins=bins, range=range,
+                                       pool=pool)
+    try:
+        for data, label in loader:
+            pseudo_input = torch.zeros(data.shape[0], input_size, device=device)
+            data, label = data.to(device), label.to(device)
+            kw = dict(inputs=pseudo_input, loss_fn=config["loss_fn"],
+                      loss_fn_kwargs={"_target": data, "_var": config["input_var"]},
+                      is_log_progress=False, is_return_results_every_t=False, is_checking_after_callback_after_t=False)
+            pc_trainer.train_on_batch(**kw)
+            mcpc_trainer.train_on_batch(callback_after_t=random_step, callback_after_t_kwargs={"_pc_trainer": mcpc_trainer},
+                                        is_sample_x_at_batch_start=False, **kw)
+            parts.append(mcpc_trainer.mcpc_last_histogram)
+            labels.append(label)
+    finally:
+        mcpc_trainer.mcpc_histogram = saved
+    first = parts[0]
+    if pool is not None:
+        for h in parts[1:]:
+            first = first.merge(h)
+        return first, torch.cat(labels, dim=0)
+
+    def cat(field):
+        return {k: torch.cat([getattr(h, field)[k] for h in parts], dim=0) for k in first.names}
+    whole = Histogram(n=first.n, B=sum(h.B for h in parts), pooled=False, names=list(first.names), edges=dict(first.edges),
+                      counts=cat("counts"), under=cat("under"), over=cat("over"), nan=cat("nan"))
+    return whole, torch.cat(labels, dim=0)
