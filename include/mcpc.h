@@ -320,6 +320,38 @@ int mcpc_hist_accumulate(int device, const float* rec, int32_t B, int32_t width,
                          int32_t transform, const float* edges, int32_t n_bins, int32_t pool, int64_t* counts, int accumulate,
                          void* stream);
 
+/* Streaming lagged products of recorded steps: the raw material of the autocorrelation function, the integrated autocorrelation time
+ * and the effective sample size of a Langevin call, whose samples are strongly autocorrelated (csrc/mcpc_acov.h).  The first reducer
+ * whose result depends on the ORDER of the records and that carries state from call to call.
+ * rec is a record buffer as mcpc_run writes it, [records][B][width] fp32; records first + j*stride, j = 0..n-1, are taken, exactly as
+ * in mcpc_moments_accumulate, and are samples n_seen .. n_seen + n - 1 of a STREAM that earlier calls began; transform is
+ * MCPC_MOM_IDENTITY or MCPC_MOM_SIGMOID (g).  With E = B * width, K = max_lag (0..MCPC_ACOV_MAX_LAG) and s_j the stream's samples, the
+ * caller owns the state, all device memory:
+ *   lagged  fp64 [E][K + 1]   lagged[e][k] = sum of g(s_j[e]) * g(s_{j-k}[e]) over every sample j so far with j - k >= 0
+ *   sum     fp64 [E]          sum of g(s_j[e])
+ *   window  fp32 [K][E]       window[k][e] = g of the sample k + 1 places back from the stream's end, valid for k < min(K, samples so
+ *                             far); read when the call starts, rewritten when it ends: this is how a lag crosses a chunk boundary, and
+ *                             g is computed once per sample
+ *   head    fp32 [K][E]       g of the stream's samples 0..K-1, written by whichever call sees them
+ * n_seen = 0 starts a stream: lagged and sum are overwritten whatever they held and nothing is read from window.  Slots of window and
+ * head that are not valid yet are left as they are.  After the last call head, window (the tail), sum and lagged are what a centred
+ * estimator needs: c_k = (lagged_k - m ((sum - tail_k) + (sum - head_k)) + (N - k) m^2) / N with m = sum / N and head_k / tail_k the sums of
+ * the first / last k samples.  No second pass over the records is made.
+ * One thread owns an element and walks the samples in ascending order with its K + 1 fp64 accumulators and the last K values in
+ * registers: no atomics, no split of the record axis.  A product of two fp32 values is exact in fp64, so every accumulator is bitwise
+ * the sequential host loop acc[k] += (double)g_j * (double)g_{j-k}, whatever the launch shape and however the caller chunks the stream
+ * (37 samples in one call, or 1 + 5 + 31 with n_seen advancing, give the same bits).  A lag without a term yet (j < k) is skipped, not
+ * multiplied by a zero: an Inf in sample 0 leaves the lags above the samples seen at exactly 0.
+ * The library allocates nothing.  Asynchronous on `stream`, no engine needed, all offsets 64-bit.  With K = 0 window and head hold
+ * nothing and may be NULL.  n = 0 reads nothing: it zeroes lagged and sum when n_seen = 0 and does nothing otherwise.
+ * MCPC_EINVAL, checked before any HIP call (nothing is launched then): lagged, sum, window or head NULL (the latter two with K > 0), rec
+ * NULL with n > 0, B < 1, width < 1, stride < 1, first < 0, n < 0, n_seen < 0, max_lag outside 0..MCPC_ACOV_MAX_LAG, an unknown
+ * transform. */
+#define MCPC_ACOV_MAX_LAG 64
+int mcpc_acov_accumulate(int device, const float* rec, int32_t B, int32_t width, int32_t first, int32_t stride, int32_t n,
+                         int32_t transform, int32_t max_lag, int64_t n_seen, double* lagged, double* sum, float* window, float* head,
+                         void* stream);
+
 /* Per-chain energies of recorded states, evaluated on the device (the reference has them per datapoint: is_return_batchelement_loss,
  * PCLayer(is_keep_energy_per_datapoint=True), get_energies(is_per_datapoint=True); pc_trainer.py:776-836, pc_layer.py:250-262).
  * A ROW is one chain at one recorded step.  x_rec[l], l < n_latent: [n_rec][batch][n_l] fp32, as mcpc_run writes rec_x[l] (n_rec = 1

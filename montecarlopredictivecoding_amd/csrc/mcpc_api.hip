@@ -16,6 +16,7 @@
 #include "mcpc_moments.h"
 #include "mcpc_cov.h"
 #include "mcpc_hist.h"
+#include "mcpc_acov.h"
 #include "mcpc_plan.h"
 #include "mcpc_chain_energy.h"
 
@@ -1430,6 +1431,39 @@ int mcpc_hist_accumulate(int device, const float* rec, int32_t B, int32_t width,
     if (!P.exclusive && !accumulate) HIP_TRY(hipMemsetAsync(counts, 0, out_bytes, stream));
     if (kVec == 4) hist_launch<4>(transform, r0, P, plan, counts, stream);
     else hist_launch<1>(transform, r0, P, plan, counts, stream);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+int mcpc_acov_accumulate(int device, const float* rec, int32_t B, int32_t width, int32_t first, int32_t stride, int32_t n, int32_t transform,
+                         int32_t max_lag, int64_t n_seen, double* lagged, double* sum, float* window, float* head, void* stream_) {
+    if (max_lag < 0 || max_lag > MCPC_ACOV_MAX_LAG) return fail(MCPC_EINVAL, "acov: max_lag=%d outside 0..%d", max_lag, MCPC_ACOV_MAX_LAG);
+    if (!lagged) return fail(MCPC_EINVAL, "acov: lagged is null");
+    if (!sum) return fail(MCPC_EINVAL, "acov: sum is null");
+    if (max_lag > 0 && !window) return fail(MCPC_EINVAL, "acov: window is null with max_lag=%d", max_lag);
+    if (max_lag > 0 && !head) return fail(MCPC_EINVAL, "acov: head is null with max_lag=%d", max_lag);
+    if (B < 1) return fail(MCPC_EINVAL, "acov: B=%d, must be at least 1", B);
+    if (width < 1) return fail(MCPC_EINVAL, "acov: width=%d, must be at least 1", width);
+    if (stride < 1) return fail(MCPC_EINVAL, "acov: stride=%d, must be at least 1", stride);
+    if (first < 0) return fail(MCPC_EINVAL, "acov: first=%d, must not be negative", first);
+    if (n < 0) return fail(MCPC_EINVAL, "acov: n=%d, must not be negative", n);
+    if (n_seen < 0) return fail(MCPC_EINVAL, "acov: n_seen=%lld, must not be negative", (long long)n_seen);
+    if (transform != MCPC_MOM_IDENTITY && transform != MCPC_MOM_SIGMOID) return fail(MCPC_EINVAL, "acov: unknown transform %d", transform);
+    if (n > 0 && !rec) return fail(MCPC_EINVAL, "acov: rec is null with n=%d", n);
+    if (n == 0 && n_seen > 0) return MCPC_OK;                     // nothing to add
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(device));
+    const int64_t E = (int64_t)B * width;
+    if (n == 0) {                                                 // a stream that starts empty
+        HIP_TRY(hipMemsetAsync(lagged, 0, (size_t)E * (max_lag + 1) * sizeof(double), stream));
+        HIP_TRY(hipMemsetAsync(sum, 0, (size_t)E * sizeof(double), stream));
+        return MCPC_OK;
+    }
+    AcovParams P{};
+    P.rec = rec + (int64_t)first * E;                             // all offsets in 64 bits, as in mcpc_moments_accumulate
+    P.E = E; P.row_step = (int64_t)stride * E; P.n_seen = n_seen; P.n = n; P.K = max_lag;
+    P.lagged = lagged; P.sum = sum; P.window = window; P.head = head;
+    acov_dispatch(transform, P, stream);
     HIP_TRY(hipGetLastError());
     return MCPC_OK;
 }

@@ -482,3 +482,36 @@ def hist_accumulate(rec, first, stride, n, edges, counts, transform="identity", 
     L.check(lib.mcpc_hist_accumulate(device.index or 0, _ptr(rec), B, width, first, stride, n, _MOM_TRANSFORMS[transform],
                                      C.cast(e.data_ptr(), C.POINTER(C.c_float)), n_bins, 1 if pool else 0, _ptr(counts),
                                      1 if accumulate else 0, stream))
+
+
+def acov_accumulate(rec, first, stride, n, max_lag, n_seen, lagged, sum, window, head, transform="identity"):
+    """Add records ``rec[first + j * stride]``, j < n, as samples ``n_seen .. n_seen + n - 1`` of a stream to its lagged products on the
+    device (include/mcpc.h: mcpc_acov_accumulate).  ``rec``: contiguous fp32 ``[records, B, width]`` as an engine run records it.  The
+    caller owns the state, on the device of ``rec``: ``lagged`` fp64 ``[B, width, max_lag + 1]`` (per element and lag k the sum of
+    g(s_j) g(s_{j-k})), ``sum`` fp64 ``[B, width]``, ``window`` and ``head`` fp32 ``[max_lag, B, width]`` (the last and the first
+    ``max_lag`` samples; ``window`` carries the lags across calls).  ``max_lag``: 0..``L.ACOV_MAX_LAG``.  ``n_seen``: the samples the
+    stream held before this call; 0 starts one (``lagged`` and ``sum`` are overwritten).  ``transform``: "identity", or "sigmoid" for the
+    read-out's Bernoulli mean.  Every accumulator is bitwise a sequential fp64 loop over the stream, however it is chunked over calls.
+    On the current torch stream."""
+    lib = L.load()
+    if transform not in _MOM_TRANSFORMS:
+        raise ValueError(f"transform: expected 'identity' or 'sigmoid', got {transform!r}")
+    if not isinstance(rec, torch.Tensor) or rec.dim() != 3:
+        raise TypeError("rec: expected a torch.Tensor [records, B, width]")
+    device = rec.device
+    if device.type != "cuda":
+        raise ValueError(f"rec: expected a tensor on a HIP device, got {device}")
+    _check_tensor(rec, rec.shape, device, "rec")
+    R, B, width = (int(d) for d in rec.shape)
+    first, stride, n, max_lag, n_seen = int(first), int(stride), int(n), int(max_lag), int(n_seen)
+    if n > 0 and first >= 0 and stride >= 1 and first + (n - 1) * stride >= R:
+        raise ValueError(f"rec holds {R} records, the last one asked for is {first + (n - 1) * stride}")
+    if not 0 <= max_lag <= L.ACOV_MAX_LAG:
+        raise ValueError(f"max_lag={max_lag}, expected 0..{L.ACOV_MAX_LAG}")
+    _check_tensor(lagged, (B, width, max_lag + 1), device, "lagged", torch.float64)
+    _check_tensor(sum, (B, width), device, "sum", torch.float64)
+    _check_tensor(window, (max_lag, B, width), device, "window")
+    _check_tensor(head, (max_lag, B, width), device, "head")
+    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    L.check(lib.mcpc_acov_accumulate(device.index or 0, _ptr(rec), B, width, first, stride, n, _MOM_TRANSFORMS[transform], max_lag,
+                                     n_seen, _ptr(lagged), _ptr(sum), _ptr(window), _ptr(head), stream))

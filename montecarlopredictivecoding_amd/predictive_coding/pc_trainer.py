@@ -255,6 +255,14 @@ class PCTrainer(object):
         self.mcpc_histogram = None
         self.mcpc_last_histogram = None
         self.mcpc_histogram_max_bytes = 2 << 30
+        # lagged autocovariances of a fused call, accumulated on the device out of the same ring (autocovariance.py): None = off, or
+        # dict(begin=0, stride=1, layers=(), outputs=None | "identity" | "sigmoid", max_lag=K) with K in 0..64.  The result is an
+        # autocovariance.Autocovariance in mcpc_last_autocovariance (acf, tau, ess, mcse per chain and unit); composes with the other
+        # four (one ring serves all five).  A request whose STATE (fp64 lagged products and sums, the first and last K samples in
+        # fp32) would take more than mcpc_autocovariance_max_bytes is a ValueError before anything runs.
+        self.mcpc_autocovariance = None
+        self.mcpc_last_autocovariance = None
+        self.mcpc_autocovariance_max_bytes = 2 << 30
 
     # ---- getters & setters (reference :268-461) -------------------------------------------------------
     def get_T(self) -> int:
@@ -496,6 +504,14 @@ class PCTrainer(object):
                                           "are counted by the fused HIP loop only".format(why_not_fused))
             plan["histogram"] = _histogram.validate_spec(self.mcpc_histogram, self._T, len(plan["net"].sizes), plan["net"].n_out,
                                                          plan["net"].sizes, plan["B"], self.mcpc_histogram_max_bytes)
+        if self.mcpc_autocovariance is not None:
+            from .. import autocovariance as _autocovariance
+            if plan is None:
+                raise NotImplementedError("mcpc_autocovariance is set, and this call runs on the generic torch loop ({}): lagged "
+                                          "autocovariances are accumulated by the fused HIP loop only".format(why_not_fused))
+            plan["autocovariance"] = _autocovariance.validate_spec(self.mcpc_autocovariance, self._T, len(plan["net"].sizes),
+                                                                   plan["net"].n_out, plan["net"].sizes, plan["B"],
+                                                                   self.mcpc_autocovariance_max_bytes)
         if plan is None:
             # outside what the kernels express: the package's generic torch loop (generic_loop.py), loudly, on the device the model
             # lives on ("must work, need not be fast").  It is no way around a missing GPU: without a visible HIP device
@@ -542,6 +558,9 @@ class PCTrainer(object):
         if plan["mode"] != "fused" and self.mcpc_histogram is not None:
             raise NotImplementedError("mcpc_histogram is set, and this call runs step by step ({}): posterior histograms are "
                                       "counted by the fused HIP loop only".format(plan["why_stepwise"]))
+        if plan["mode"] != "fused" and self.mcpc_autocovariance is not None:
+            raise NotImplementedError("mcpc_autocovariance is set, and this call runs step by step ({}): lagged autocovariances are "
+                                      "accumulated by the fused HIP loop only".format(plan["why_stepwise"]))
         if plan["mode"] == "fused":
             self.last_call_mode = "fused"
             with _few_cpu_threads(plan["staged"]):
@@ -873,13 +892,14 @@ class PCTrainer(object):
         host_step_bytes = 4 * plan["B"] * sum(n for n, on in zip(net.sizes, rec_layers) if on)
         self.last_record_slices = 0
         mom, ce, cov, hist = plan.get("moments"), plan.get("chain_energies"), plan.get("covariance"), plan.get("histogram")
-        if mom is not None or ce is not None or cov is not None or hist is not None:
-            # posterior moments / per-chain energies / covariances / histograms: the call runs as slices whatever its size, and the
-            # records they ask for are reduced on the device
+        acov = plan.get("autocovariance")
+        if mom is not None or ce is not None or cov is not None or hist is not None or acov is not None:
+            # posterior moments / per-chain energies / covariances / histograms / autocovariances: the call runs as slices whatever
+            # its size, and the records they ask for are reduced on the device
             ce_inputs = None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous())
             res, last_mom, last_ce = self._run_fused_sliced(
                 eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, is_return_outputs and net.n_out > 0,
-                every_t=is_return_results_every_t, mom=mom, ce=ce, ce_inputs=ce_inputs, cov=cov, hist=hist)
+                every_t=is_return_results_every_t, mom=mom, ce=ce, ce_inputs=ce_inputs, cov=cov, hist=hist, acov=acov)
             if mom is not None:
                 self.mcpc_last_moments = last_mom
             if ce is not None:
@@ -912,7 +932,7 @@ class PCTrainer(object):
                                      is_return_representations, is_return_xs, loss_fn)
 
     def _run_fused_sliced(self, eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, rec_out, every_t=True, mom=None,
-                          ce=None, ce_inputs=None, cov=None, hist=None):
+                          ce=None, ce_inputs=None, cov=None, hist=None, acov=None):
         """A call whose every-step trajectory would not fit the record budget on the device, or whose records feed `mcpc_moments`:
         the same T steps as slices of one `mcpc_run` each (slicing does not change a bit of the trajectories,
         tests/test_gpu_fullsize.py).  The latent records of a slice go to one half of a two-buffer device ring.  Records the caller's
@@ -926,8 +946,11 @@ class PCTrainer(object):
         and `cov_accumulate` / `moments_accumulate` add their outer products and sums after each slice, on the call's own stream, under
         the same rules; the result is left in `mcpc_last_covariance`.  With `hist` (a validated `mcpc_histogram`) its layers and
         read-out go through the ring as well and `hist_accumulate` counts them after each slice, on the call's own stream, under the
-        same rules; the result is left in `mcpc_last_histogram`.  Returns (RunResult, Moments or None, ChainEnergies or None)."""
-        from ..engine import RunResult, moments_accumulate, cov_accumulate, cov_workspace_bytes, hist_accumulate
+        same rules; the result is left in `mcpc_last_histogram`.  With `acov` (a validated `mcpc_autocovariance`) its layers and
+        read-out go through the ring likewise and `acov_accumulate` adds their lagged products after each slice, in step order, on the
+        call's own stream; the samples seen so far are counted per block and the kernel's own window carries the lags across slices;
+        the result is left in `mcpc_last_autocovariance`.  Returns (RunResult, Moments or None, ChainEnergies or None)."""
+        from ..engine import RunResult, moments_accumulate, cov_accumulate, cov_workspace_bytes, hist_accumulate, acov_accumulate
         dev, B = plan["device"], plan["B"]
         nl = len(net.sizes)
         mom_layers = [mom is not None and l in mom.layers for l in range(nl)]
@@ -936,16 +959,19 @@ class PCTrainer(object):
         cov_out = cov is not None and cov.outputs is not None
         hist_layers = [hist is not None and l in hist.layers for l in range(nl)]
         hist_out = hist is not None and hist.outputs is not None
-        ring_layers = [a or b_ or c_ or d_ or ce is not None for a, b_, c_, d_ in zip(rec_layers, mom_layers, cov_layers, hist_layers)]
-        reduced = mom is not None or ce is not None or cov is not None or hist is not None
+        acov_layers = [acov is not None and l in acov.layers for l in range(nl)]
+        acov_out = acov is not None and acov.outputs is not None
+        ring_layers = [a or b_ or c_ or d_ or e_ or ce is not None
+                       for a, b_, c_, d_, e_ in zip(rec_layers, mom_layers, cov_layers, hist_layers, acov_layers)]
+        reduced = mom is not None or ce is not None or cov is not None or hist is not None or acov is not None
         out_direct = rec_out and every_t                     # every step's outputs are kept anyway: slices write them in place
-        ring_out = (rec_out or mom_out or cov_out or hist_out) and not out_direct
+        ring_out = (rec_out or mom_out or cov_out or hist_out or acov_out) and not out_direct
         S = T
         if any(rec_layers) and every_t:
             S = min(S, self.mcpc_record_chunk_bytes // max(2 * host_step_bytes, 1))
         if reduced:
             # one half of the ring is a chunk of at most mcpc_moments_chunk_bytes
-            step_bytes = 4 * B * (sum(n for n, on in zip(net.sizes, ring_layers) if on) + (net.n_out if ring_out or mom_out or cov_out or hist_out else 0))
+            step_bytes = 4 * B * (sum(n for n, on in zip(net.sizes, ring_layers) if on) + (net.n_out if ring_out or mom_out or cov_out or hist_out or acov_out else 0))
             S = min(S, self.mcpc_moments_chunk_bytes // max(step_bytes, 1))
         S = max(1, S)
         # A slice boundary inside the window that accumulates parameter gradients would regroup their fp32 sums (one Hebbian flush and
@@ -1032,6 +1058,27 @@ class PCTrainer(object):
             for blk, e, counts, xf in zip(blocks, hist.edges, hist_acc, hist_xf):
                 hist_accumulate(blk, first, hist.stride, cnt, e, counts, transform=xf, pool=hist.pooled, accumulate=True)
 
+        acov_state = None
+        if acov is not None:
+            acov_xf = ["identity"] * len(acov.layers) + ([acov.outputs] if acov_out else [])
+            K = acov.max_lag
+            acov_state = [dict(lagged=torch.zeros(B, w, K + 1, dtype=torch.float64, device=dev),
+                               sum=torch.zeros(B, w, dtype=torch.float64, device=dev),
+                               window=torch.zeros(K, B, w, dtype=torch.float32, device=dev),
+                               head=torch.zeros(K, B, w, dtype=torch.float32, device=dev), n_seen=0) for _, w in acov.columns]
+
+        def reduce_acov(t0, n, half):
+            first, cnt = acov.chunk(t0, n)
+            if cnt == 0:
+                return
+            blocks = [ring[half][l] for l in acov.layers]
+            if acov_out:
+                blocks.append(out_full[t0:t0 + n] if out_direct else ring_o[half])
+            for blk, st, xf in zip(blocks, acov_state, acov_xf):
+                acov_accumulate(blk, first, acov.stride, cnt, acov.max_lag, st["n_seen"], st["lagged"], st["sum"], st["window"],
+                                st["head"], transform=xf)
+                st["n_seen"] += cnt
+
         ce_table = torch.empty(ce.n, B, L.ENERGY_COLS, dtype=torch.float64, device=dev) if ce is not None else None
         ce_kw = dict(loss_kind=run_kw["loss_kind"], loss_var=run_kw["loss_var"], mask_start=run_kw["mask_start"],
                      max_rows=self.mcpc_chain_energies_max_rows)
@@ -1067,6 +1114,8 @@ class PCTrainer(object):
                 reduce_cov(t0, n, half)
             if hist is not None:
                 reduce_hist(t0, n, half)
+            if acov is not None:
+                reduce_acov(t0, n, half)
             if ring_out and rec_out and last:
                 out_full[0].copy_(ring_o[half][n - 1])       # (not every_t: the last step's outputs)
             to_host = any(rec_layers) and (every_t or last)
@@ -1112,6 +1161,9 @@ class PCTrainer(object):
         if hist is not None:
             from ..histogram import from_counts
             self.mcpc_last_histogram = from_counts(hist, B, hist_acc, plan["model_device"])
+        if acov is not None:
+            from ..autocovariance import from_state
+            self.mcpc_last_autocovariance = from_state(acov, B, acov_state, plan["model_device"])
         return RunResult(energies=energies, rec_x=host, rec_out=out_full), result, ce_result
 
     def mcpc_state_energies(self, inputs, loss_fn: typing.Callable = None, loss_fn_kwargs: dict = {}):

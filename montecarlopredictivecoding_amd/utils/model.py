@@ -281,3 +281,37 @@ def get_posterior_histogram(gen_pc, config, trainers, loader, layers=(0,), bins=
     whole = Histogram(n=first.n, B=sum(h.B for h in parts), pooled=False, names=list(first.names), edges=dict(first.edges),
                       counts=cat("counts"), under=cat("under"), over=cat("over"), nan=cat("nan"))
     return whole, torch.cat(labels, dim=0)
+
+
+def get_posterior_ess(gen_pc, config, trainers, loader, layers=(0,), max_lag=32):
+    """How far the posterior samples of the latent units can be trusted, per batch of ``loader``: MAP call with ``trainers[0]``, then an
+    MCPC call with ``trainers[1]`` started from the MAP state (the protocol of ``get_posterior_histogram``), over the steps from
+    ``config["mixing"]`` on; the call itself adds the lagged products of every (datum, unit) on the device
+    (``PCTrainer.mcpc_autocovariance``): no trajectory is recorded.  ``layers``: the PC layers looked at; ``max_lag``: the largest lag
+    kept (0..64).  Returns ``(autocovariance, labels)``: an ``autocovariance.Autocovariance`` whose chains are all data in the loader's
+    order (``B`` = their number; ``.acf``, ``.tau``, ``.ess``, ``.mcse``, ``.truncated`` per datum and unit), and the labels of all
+    data."""
+    from ..autocovariance import Autocovariance
+    if len(trainers) != 2:
+        raise NotImplementedError
+    device = next(gen_pc.parameters()).device
+    input_size = len(gen_pc[0].bias)
+    pc_trainer, mcpc_trainer = trainers
+    parts, labels = [], []
+    saved = mcpc_trainer.mcpc_autocovariance
+    mcpc_trainer.mcpc_autocovariance = dict(begin=int(config["mixing"]), stride=1, layers=tuple(layers), outputs=None, max_lag=max_lag)
+    try:
+        for data, label in loader:
+            pseudo_input = torch.zeros(data.shape[0], input_size, device=device)
+            data, label = data.to(device), label.to(device)
+            kw = dict(inputs=pseudo_input, loss_fn=config["loss_fn"],
+                      loss_fn_kwargs={"_target": data, "_var": config["input_var"]},
+                      is_log_progress=False, is_return_results_every_t=False, is_checking_after_callback_after_t=False)
+            pc_trainer.train_on_batch(**kw)
+            mcpc_trainer.train_on_batch(callback_after_t=random_step, callback_after_t_kwargs={"_pc_trainer": mcpc_trainer},
+                                        is_sample_x_at_batch_start=False, **kw)
+            parts.append(mcpc_trainer.mcpc_last_autocovariance)
+            labels.append(label)
+    finally:
+        mcpc_trainer.mcpc_autocovariance = saved
+    return Autocovariance.cat(parts), torch.cat(labels, dim=0)
