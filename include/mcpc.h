@@ -352,6 +352,40 @@ int mcpc_acov_accumulate(int device, const float* rec, int32_t B, int32_t width,
                          int32_t transform, int32_t max_lag, int64_t n_seen, double* lagged, double* sum, float* window, float* head,
                          void* stream);
 
+/* Streaming posterior of a linear probe on recorded steps: class probabilities of a linear read-out of a latent layer with a link, reduced
+ * per chain over the samples of a Langevin call (csrc/mcpc_probe.h; the reference adds softmax(classifier(representation)) over the recorded
+ * representations on the host: figure_2.py, comparison_ideal_observer).  The first reducer that applies a function the caller supplies.
+ * rec is a record buffer as mcpc_run writes rec_x[l], [records][B][width] fp32; records first + j*stride, j = 0..n-1, are taken in ascending
+ * order, exactly as in mcpc_moments_accumulate.  W is device fp32 [n_classes][width] row-major (nn.Linear.weight), bias device fp32
+ * [n_classes] or NULL for zeros; C = n_classes in 1..MCPC_PROBE_MAX_CLASSES, width >= 1 without an upper limit.  For chain c, record j, class i:
+ *   logit    z = (double)bias[i]; for k = 0..width-1 ascending z = z + (double)W[i][k] * (double)r_j[c][k]; v_i = (float)z.  A product of two
+ *            fp32 values is exact in fp64, so v_i is bitwise the sequential fp64 loop on the host.
+ *   link     MCPC_PROBE_IDENTITY p_i = v_i;  MCPC_PROBE_SIGMOID p_i = sigmoid_f(v_i), the library's own, as MCPC_MOM_SIGMOID;
+ *            MCPC_PROBE_SOFTMAX m = max_i v_i, e_i = expf(v_i - m), S = sum_i e_i in fp32 in one fixed order that depends on C alone (a
+ *            binary tree over C rounded up to a power of two), p_i = e_i / S (the math library's expf, IEEE division).
+ *   psum     [B][C] fp64     psum[c][i]   = (accumulate ? psum[c][i]   : 0) + sum_j (double)p_i        in ascending j
+ *   psumsq   [B][C] fp64     psumsq[c][i] = (accumulate ? psumsq[c][i] : 0) + sum_j (double)p_i * (double)p_i      (may be NULL)
+ *   votes    [B][C + 1] int64  column i < C counts the samples whose largest logit is v_i, the lowest index on a tie (np.argmax); column C
+ *            counts the samples with a NaN among their logits, which cast no vote: a row adds up to the samples taken
+ *   entsum   [B] fp64        entsum[c] += (double)H_j, H_j = logf(S) - sum_i p_i (v_i - m) in fp32, the entropy of the sample's softmax;
+ *            needed with MCPC_PROBE_SOFTMAX only, ignored (may be NULL) otherwise
+ * With MCPC_PROBE_IDENTITY psum, psumsq and votes are bitwise the host loop; with the other links the logits and votes are, and a softmax
+ * probability is within (C + 16) * 2^-24 of the fp64 softmax of the same fp32 logits.  NaN and Inf propagate by IEEE into the sums of the
+ * chain that holds them, and nowhere else.  accumulate = 0 overwrites every output, whatever it held; accumulate != 0 adds.
+ * Every (chain, class) accumulator has one owner, which walks the samples in ascending order: no atomics, no split of the record axis, no
+ * float sum ordered by scheduling, so the result depends neither on the launch shape nor on how the caller chunks the records (37 records
+ * in one call, or 1 + 5 + 31 with accumulate = 1, give the same bits).  The library allocates nothing.  Stateless, asynchronous on
+ * `stream`, no engine needed, all offsets 64-bit.  n = 0 reads nothing: it zeroes the outputs when accumulate = 0 and does nothing otherwise.
+ * MCPC_EINVAL, checked before any HIP call (nothing is launched then): W, psum or votes NULL, entsum NULL with MCPC_PROBE_SOFTMAX, rec NULL
+ * with n > 0, B < 1, width < 1, stride < 1, first < 0, n < 0, n_classes outside 1..MCPC_PROBE_MAX_CLASSES, an unknown link. */
+#define MCPC_PROBE_MAX_CLASSES 64
+#define MCPC_PROBE_IDENTITY 0
+#define MCPC_PROBE_SIGMOID  1
+#define MCPC_PROBE_SOFTMAX  2
+int mcpc_probe_accumulate(int device, const float* rec, int32_t B, int32_t width, int32_t first, int32_t stride, int32_t n,
+                          const float* W, const float* bias, int32_t n_classes, int32_t link, double* psum, double* psumsq,
+                          int64_t* votes, double* entsum, int accumulate, void* stream);
+
 /* Per-chain energies of recorded states, evaluated on the device (the reference has them per datapoint: is_return_batchelement_loss,
  * PCLayer(is_keep_energy_per_datapoint=True), get_energies(is_per_datapoint=True); pc_trainer.py:776-836, pc_layer.py:250-262).
  * A ROW is one chain at one recorded step.  x_rec[l], l < n_latent: [n_rec][batch][n_l] fp32, as mcpc_run writes rec_x[l] (n_rec = 1

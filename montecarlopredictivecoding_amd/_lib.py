@@ -20,6 +20,8 @@ ENERGY_NONE, ENERGY_LAST, ENERGY_ALL = 0, 1, 2
 MOM_IDENTITY, MOM_SIGMOID = 0, 1
 HIST_MAX_BINS = 256
 ACOV_MAX_LAG = 64
+PROBE_MAX_CLASSES = 64
+PROBE_IDENTITY, PROBE_SIGMOID, PROBE_SOFTMAX = 0, 1, 2
 
 # MCPC_LIB: developer override to load a diagnostic build (e.g. libmcpc_stamps.so) or a `make variant` A/B library; a library that
 # reports exp=1 (built with a timing-experiment switch: wrong results on purpose) is refused unless MCPC_ALLOW_EXP=1
@@ -108,6 +110,8 @@ SYMBOLS = {
                                        C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_void_p, C.c_int, C.c_void_p]),
     "mcpc_acov_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcpc_probe_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "mcpc_chain_energies": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_int32,
                                       C.c_void_p, C.c_int32, C.c_void_p]),
     "mcpc_query": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),

@@ -17,6 +17,7 @@
 #include "mcpc_cov.h"
 #include "mcpc_hist.h"
 #include "mcpc_acov.h"
+#include "mcpc_probe.h"
 #include "mcpc_plan.h"
 #include "mcpc_chain_energy.h"
 
@@ -1464,6 +1465,44 @@ int mcpc_acov_accumulate(int device, const float* rec, int32_t B, int32_t width,
     P.E = E; P.row_step = (int64_t)stride * E; P.n_seen = n_seen; P.n = n; P.K = max_lag;
     P.lagged = lagged; P.sum = sum; P.window = window; P.head = head;
     acov_dispatch(transform, P, stream);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+int mcpc_probe_accumulate(int device, const float* rec, int32_t B, int32_t width, int32_t first, int32_t stride, int32_t n, const float* W,
+                          const float* bias, int32_t n_classes, int32_t link, double* psum, double* psumsq, int64_t* votes, double* entsum,
+                          int accumulate, void* stream_) {
+    if (!W) return fail(MCPC_EINVAL, "probe: W is null");
+    if (!psum) return fail(MCPC_EINVAL, "probe: psum is null");
+    if (!votes) return fail(MCPC_EINVAL, "probe: votes is null");
+    if (link != MCPC_PROBE_IDENTITY && link != MCPC_PROBE_SIGMOID && link != MCPC_PROBE_SOFTMAX)
+        return fail(MCPC_EINVAL, "probe: unknown link %d", link);
+    if (link == MCPC_PROBE_SOFTMAX && !entsum) return fail(MCPC_EINVAL, "probe: entsum is null with the softmax link");
+    if (B < 1) return fail(MCPC_EINVAL, "probe: B=%d, must be at least 1", B);
+    if (width < 1) return fail(MCPC_EINVAL, "probe: width=%d, must be at least 1", width);
+    if (stride < 1) return fail(MCPC_EINVAL, "probe: stride=%d, must be at least 1", stride);
+    if (first < 0) return fail(MCPC_EINVAL, "probe: first=%d, must not be negative", first);
+    if (n < 0) return fail(MCPC_EINVAL, "probe: n=%d, must not be negative", n);
+    if (n_classes < 1 || n_classes > MCPC_PROBE_MAX_CLASSES)
+        return fail(MCPC_EINVAL, "probe: n_classes=%d outside 1..%d", n_classes, MCPC_PROBE_MAX_CLASSES);
+    if (n > 0 && !rec) return fail(MCPC_EINVAL, "probe: rec is null with n=%d", n);
+    if (n == 0 && accumulate) return MCPC_OK;                     // nothing to add
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(device));
+    const int64_t E = (int64_t)B * width;
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(psum, 0, (size_t)B * n_classes * sizeof(double), stream));
+        if (psumsq) HIP_TRY(hipMemsetAsync(psumsq, 0, (size_t)B * n_classes * sizeof(double), stream));
+        HIP_TRY(hipMemsetAsync(votes, 0, (size_t)B * (n_classes + 1) * sizeof(int64_t), stream));
+        if (link == MCPC_PROBE_SOFTMAX) HIP_TRY(hipMemsetAsync(entsum, 0, (size_t)B * sizeof(double), stream));
+        return MCPC_OK;
+    }
+    ProbeParams P{};
+    P.rec = rec + (int64_t)first * E;                             // all offsets in 64 bits, as in mcpc_moments_accumulate
+    P.W = W; P.bias = bias; P.row_step = (int64_t)stride * E;
+    P.B = B; P.width = width; P.n = n; P.C = n_classes; P.accumulate = accumulate ? 1 : 0;
+    P.psum = psum; P.psumsq = psumsq; P.votes = votes; P.entsum = entsum;
+    probe_dispatch(link, P, stream);
     HIP_TRY(hipGetLastError());
     return MCPC_OK;
 }

@@ -515,3 +515,50 @@ def acov_accumulate(rec, first, stride, n, max_lag, n_seen, lagged, sum, window,
     stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     L.check(lib.mcpc_acov_accumulate(device.index or 0, _ptr(rec), B, width, first, stride, n, _MOM_TRANSFORMS[transform], max_lag,
                                      n_seen, _ptr(lagged), _ptr(sum), _ptr(window), _ptr(head), stream))
+
+
+_PROBE_LINKS = {"identity": L.PROBE_IDENTITY, "sigmoid": L.PROBE_SIGMOID, "softmax": L.PROBE_SOFTMAX}
+
+
+def probe_accumulate(rec, first, stride, n, W, bias, link, psum, psumsq, votes, entsum, accumulate=True):
+    """Add the linear probe ``link(W r + bias)`` of records ``rec[first + j * stride]``, j < n, to per-chain sums on the device
+    (include/mcpc.h: mcpc_probe_accumulate).  ``rec``: contiguous fp32 ``[records, B, width]`` as an engine run records it.  ``W``:
+    contiguous fp32 ``[C, width]`` (the layout of ``nn.Linear.weight``), C in 1..``L.PROBE_MAX_CLASSES``; ``bias``: fp32 ``[C]`` or None
+    for zeros; ``link``: "identity", "sigmoid" or "softmax".  ``psum`` and ``psumsq`` (may be None): fp64 ``[B, C]``, the sums of the
+    link values and of their squares; ``votes``: int64 ``[B, C + 1]``, argmax counts of the logits (the lowest index on a tie) and, in
+    column C, the samples with a NaN logit; ``entsum``: fp64 ``[B]``, the summed entropies of the samples' softmax (softmax only, else
+    None).  Everything on the device of ``rec``.  ``accumulate=False`` overwrites.  One lane owns a (chain, class) and walks the samples
+    in order: the result does not depend on how the records are chunked over calls.  On the current torch stream."""
+    lib = L.load()
+    if link not in _PROBE_LINKS:
+        raise ValueError(f"link: expected 'identity', 'sigmoid' or 'softmax', got {link!r}")
+    if not isinstance(rec, torch.Tensor) or rec.dim() != 3:
+        raise TypeError("rec: expected a torch.Tensor [records, B, width]")
+    device = rec.device
+    if device.type != "cuda":
+        raise ValueError(f"rec: expected a tensor on a HIP device, got {device}")
+    _check_tensor(rec, rec.shape, device, "rec")
+    R, B, width = (int(d) for d in rec.shape)
+    first, stride, n = int(first), int(stride), int(n)
+    if n > 0 and first >= 0 and stride >= 1 and first + (n - 1) * stride >= R:
+        raise ValueError(f"rec holds {R} records, the last one asked for is {first + (n - 1) * stride}")
+    if not isinstance(W, torch.Tensor) or W.dim() != 2:
+        raise TypeError("W: expected a torch.Tensor [C, width]")
+    n_classes = int(W.shape[0])
+    if not 1 <= n_classes <= L.PROBE_MAX_CLASSES:
+        raise ValueError(f"W: {n_classes} classes, expected 1..{L.PROBE_MAX_CLASSES}")
+    _check_tensor(W, (n_classes, width), device, "W")
+    if bias is not None:
+        _check_tensor(bias, (n_classes,), device, "bias")
+    _check_tensor(psum, (B, n_classes), device, "psum", torch.float64)
+    if psumsq is not None:
+        _check_tensor(psumsq, (B, n_classes), device, "psumsq", torch.float64)
+    _check_tensor(votes, (B, n_classes + 1), device, "votes", torch.int64)
+    if link == "softmax":
+        _check_tensor(entsum, (B,), device, "entsum", torch.float64)
+    elif entsum is not None:
+        raise ValueError(f"entsum: the entropy is that of a softmax; expected None with link={link!r}")
+    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    L.check(lib.mcpc_probe_accumulate(device.index or 0, _ptr(rec), B, width, first, stride, n, _ptr(W), _ptr(bias), n_classes,
+                                      _PROBE_LINKS[link], _ptr(psum), _ptr(psumsq), _ptr(votes), _ptr(entsum), 1 if accumulate else 0,
+                                      stream))

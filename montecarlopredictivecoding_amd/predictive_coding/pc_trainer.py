@@ -263,6 +263,13 @@ class PCTrainer(object):
         self.mcpc_autocovariance = None
         self.mcpc_last_autocovariance = None
         self.mcpc_autocovariance_max_bytes = 2 << 30
+        # the posterior of a linear probe on a latent layer of a fused call, accumulated on the device out of the same ring (probe.py):
+        # None = off, or dict(begin=0, stride=1, layer=l, weight=W [C, n_l], bias=b | None, link="softmax" | "sigmoid" | "identity"),
+        # linear=<nn.Linear> in place of weight / bias, C in 1..64.  The result is a probe.Probe in mcpc_last_probe (mean class
+        # probabilities, their variance, argmax votes, entropy and its split, per chain); composes with the other five (one ring
+        # serves all six).
+        self.mcpc_probe = None
+        self.mcpc_last_probe = None
 
     # ---- getters & setters (reference :268-461) -------------------------------------------------------
     def get_T(self) -> int:
@@ -512,6 +519,12 @@ class PCTrainer(object):
             plan["autocovariance"] = _autocovariance.validate_spec(self.mcpc_autocovariance, self._T, len(plan["net"].sizes),
                                                                    plan["net"].n_out, plan["net"].sizes, plan["B"],
                                                                    self.mcpc_autocovariance_max_bytes)
+        if self.mcpc_probe is not None:
+            from .. import probe as _probe
+            if plan is None:
+                raise NotImplementedError("mcpc_probe is set, and this call runs on the generic torch loop ({}): the posterior of a "
+                                          "probe is accumulated by the fused HIP loop only".format(why_not_fused))
+            plan["probe"] = _probe.validate_spec(self.mcpc_probe, self._T, len(plan["net"].sizes), plan["net"].sizes, plan["B"])
         if plan is None:
             # outside what the kernels express: the package's generic torch loop (generic_loop.py), loudly, on the device the model
             # lives on ("must work, need not be fast").  It is no way around a missing GPU: without a visible HIP device
@@ -560,6 +573,9 @@ class PCTrainer(object):
                                       "counted by the fused HIP loop only".format(plan["why_stepwise"]))
         if plan["mode"] != "fused" and self.mcpc_autocovariance is not None:
             raise NotImplementedError("mcpc_autocovariance is set, and this call runs step by step ({}): lagged autocovariances are "
+                                      "accumulated by the fused HIP loop only".format(plan["why_stepwise"]))
+        if plan["mode"] != "fused" and self.mcpc_probe is not None:
+            raise NotImplementedError("mcpc_probe is set, and this call runs step by step ({}): the posterior of a probe is "
                                       "accumulated by the fused HIP loop only".format(plan["why_stepwise"]))
         if plan["mode"] == "fused":
             self.last_call_mode = "fused"
@@ -892,14 +908,14 @@ class PCTrainer(object):
         host_step_bytes = 4 * plan["B"] * sum(n for n, on in zip(net.sizes, rec_layers) if on)
         self.last_record_slices = 0
         mom, ce, cov, hist = plan.get("moments"), plan.get("chain_energies"), plan.get("covariance"), plan.get("histogram")
-        acov = plan.get("autocovariance")
-        if mom is not None or ce is not None or cov is not None or hist is not None or acov is not None:
-            # posterior moments / per-chain energies / covariances / histograms / autocovariances: the call runs as slices whatever
-            # its size, and the records they ask for are reduced on the device
+        acov, probe = plan.get("autocovariance"), plan.get("probe")
+        if mom is not None or ce is not None or cov is not None or hist is not None or acov is not None or probe is not None:
+            # posterior moments / per-chain energies / covariances / histograms / autocovariances / a probe: the call runs as slices
+            # whatever its size, and the records they ask for are reduced on the device
             ce_inputs = None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous())
             res, last_mom, last_ce = self._run_fused_sliced(
                 eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, is_return_outputs and net.n_out > 0,
-                every_t=is_return_results_every_t, mom=mom, ce=ce, ce_inputs=ce_inputs, cov=cov, hist=hist, acov=acov)
+                every_t=is_return_results_every_t, mom=mom, ce=ce, ce_inputs=ce_inputs, cov=cov, hist=hist, acov=acov, probe=probe)
             if mom is not None:
                 self.mcpc_last_moments = last_mom
             if ce is not None:
@@ -932,7 +948,7 @@ class PCTrainer(object):
                                      is_return_representations, is_return_xs, loss_fn)
 
     def _run_fused_sliced(self, eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, rec_out, every_t=True, mom=None,
-                          ce=None, ce_inputs=None, cov=None, hist=None, acov=None):
+                          ce=None, ce_inputs=None, cov=None, hist=None, acov=None, probe=None):
         """A call whose every-step trajectory would not fit the record budget on the device, or whose records feed `mcpc_moments`:
         the same T steps as slices of one `mcpc_run` each (slicing does not change a bit of the trajectories,
         tests/test_gpu_fullsize.py).  The latent records of a slice go to one half of a two-buffer device ring.  Records the caller's
@@ -949,8 +965,11 @@ class PCTrainer(object):
         same rules; the result is left in `mcpc_last_histogram`.  With `acov` (a validated `mcpc_autocovariance`) its layers and
         read-out go through the ring likewise and `acov_accumulate` adds their lagged products after each slice, in step order, on the
         call's own stream; the samples seen so far are counted per block and the kernel's own window carries the lags across slices;
-        the result is left in `mcpc_last_autocovariance`.  Returns (RunResult, Moments or None, ChainEnergies or None)."""
-        from ..engine import RunResult, moments_accumulate, cov_accumulate, cov_workspace_bytes, hist_accumulate, acov_accumulate
+        the result is left in `mcpc_last_autocovariance`.  With `probe` (a validated `mcpc_probe`) its layer goes through the ring too and
+        one `probe_accumulate` after each slice, on the call's own stream, adds the link values, votes and entropies of the slice's
+        samples (overwriting in the first slice that holds one); the result is left in `mcpc_last_probe`.  Returns (RunResult, Moments or None, ChainEnergies or None)."""
+        from ..engine import (RunResult, moments_accumulate, cov_accumulate, cov_workspace_bytes, hist_accumulate, acov_accumulate,
+                              probe_accumulate)
         dev, B = plan["device"], plan["B"]
         nl = len(net.sizes)
         mom_layers = [mom is not None and l in mom.layers for l in range(nl)]
@@ -961,9 +980,10 @@ class PCTrainer(object):
         hist_out = hist is not None and hist.outputs is not None
         acov_layers = [acov is not None and l in acov.layers for l in range(nl)]
         acov_out = acov is not None and acov.outputs is not None
-        ring_layers = [a or b_ or c_ or d_ or e_ or ce is not None
-                       for a, b_, c_, d_, e_ in zip(rec_layers, mom_layers, cov_layers, hist_layers, acov_layers)]
-        reduced = mom is not None or ce is not None or cov is not None or hist is not None or acov is not None
+        probe_layers = [probe is not None and l == probe.layer for l in range(nl)]
+        ring_layers = [a or b_ or c_ or d_ or e_ or f_ or ce is not None
+                       for a, b_, c_, d_, e_, f_ in zip(rec_layers, mom_layers, cov_layers, hist_layers, acov_layers, probe_layers)]
+        reduced = mom is not None or ce is not None or cov is not None or hist is not None or acov is not None or probe is not None
         out_direct = rec_out and every_t                     # every step's outputs are kept anyway: slices write them in place
         ring_out = (rec_out or mom_out or cov_out or hist_out or acov_out) and not out_direct
         S = T
@@ -1079,6 +1099,22 @@ class PCTrainer(object):
                                 st["head"], transform=xf)
                 st["n_seen"] += cnt
 
+        probe_state = None
+        if probe is not None:
+            from ..probe import new_state
+            probe_w, probe_b = probe.on(dev)
+            probe_state = new_state(B, probe.C, probe.link, dev)
+            probe_state["seen"] = False
+
+        def reduce_probe(t0, n, half):
+            first, cnt = probe.chunk(t0, n)
+            if cnt == 0:
+                return
+            st = probe_state
+            probe_accumulate(ring[half][probe.layer], first, probe.stride, cnt, probe_w, probe_b, probe.link, st["psum"], st["psumsq"],
+                             st["votes"], st["entsum"], accumulate=st["seen"])
+            st["seen"] = True
+
         ce_table = torch.empty(ce.n, B, L.ENERGY_COLS, dtype=torch.float64, device=dev) if ce is not None else None
         ce_kw = dict(loss_kind=run_kw["loss_kind"], loss_var=run_kw["loss_var"], mask_start=run_kw["mask_start"],
                      max_rows=self.mcpc_chain_energies_max_rows)
@@ -1116,6 +1152,8 @@ class PCTrainer(object):
                 reduce_hist(t0, n, half)
             if acov is not None:
                 reduce_acov(t0, n, half)
+            if probe is not None:
+                reduce_probe(t0, n, half)
             if ring_out and rec_out and last:
                 out_full[0].copy_(ring_o[half][n - 1])       # (not every_t: the last step's outputs)
             to_host = any(rec_layers) and (every_t or last)
@@ -1164,6 +1202,9 @@ class PCTrainer(object):
         if acov is not None:
             from ..autocovariance import from_state
             self.mcpc_last_autocovariance = from_state(acov, B, acov_state, plan["model_device"])
+        if probe is not None:
+            from ..probe import from_state as probe_from_state
+            self.mcpc_last_probe = probe_from_state(probe.n, B, probe.C, probe.link, probe_state, plan["model_device"])
         return RunResult(energies=energies, rec_x=host, rec_out=out_full), result, ce_result
 
     def mcpc_state_energies(self, inputs, loss_fn: typing.Callable = None, loss_fn_kwargs: dict = {}):
@@ -1197,6 +1238,34 @@ class PCTrainer(object):
                                        max_rows=self.mcpc_chain_energies_max_rows)
             eng.sync_check()
         return from_table(table, len(net.sizes), self._energy_coefficient, [], plan["model_device"])
+
+    def mcpc_state_probe(self, spec):
+        """The probe of ``spec`` (a dict as ``mcpc_probe`` takes; ``begin`` and ``stride`` are not consulted) on the CURRENT x of its
+        layer -- what a MAP call leaves -- through the kernel of the sampled probe (engine.probe_accumulate with one record): the
+        probabilities of the MAP state come from the same arithmetic as the sampled ones.  No step is run, nothing changes.  Returns
+        probe.Probe with n = 1 on the model's device."""
+        from .. import probe as _probe
+        from ..engine import probe_accumulate
+        layers = self.get_model_pc_layers()
+        xs = [layer.get_x() for layer in layers]
+        if any(x is None or x.dim() != 2 or x.dtype != torch.float32 for x in xs):
+            raise RuntimeError("mcpc_state_probe: a PCLayer holds no float32 x of shape [B, n]; run a call first")
+        B = int(xs[0].shape[0])
+        sp = _probe.validate_spec(dict(spec, begin=0, stride=1), 1, len(xs), [int(x.shape[1]) for x in xs], B)
+        x = xs[sp.layer].data
+        model_device = x.device
+        if model_device.type != "cuda":
+            if not torch.cuda.is_available():
+                raise L.MCPCLibraryError("no HIP device is visible (the model lives on %s): the MCPC engine runs on an MI355X only; "
+                                         "there is no CPU path" % model_device)
+            x = x.to("cuda")
+        dev = x.device
+        w, b = sp.on(dev)
+        st = _probe.new_state(B, sp.C, sp.link, dev)
+        with torch.cuda.device(dev):
+            probe_accumulate(x.contiguous().unsqueeze(0), 0, 1, 1, w, b, sp.link, st["psum"], st["psumsq"], st["votes"], st["entsum"],
+                             accumulate=False)
+        return _probe.from_state(1, B, sp.C, sp.link, st, model_device)
 
     # ---- step-wise path -------------------------------------------------------------------------------------
     def _run_stepwise(self, plan, inputs, loss_fn, is_sample_x_at_batch_start, is_reset_optimizer_x_at_batch_start,

@@ -315,3 +315,43 @@ def get_posterior_ess(gen_pc, config, trainers, loader, layers=(0,), max_lag=32)
     finally:
         mcpc_trainer.mcpc_autocovariance = saved
     return Autocovariance.cat(parts), torch.cat(labels, dim=0)
+
+
+def get_posterior_class_probabilities(gen_pc, config, trainers, loader, classifier, layer=0, link="softmax"):
+    """The posterior class probabilities a linear classifier on a latent layer assigns, per batch of ``loader``: MAP call with
+    ``trainers[0]``, then an MCPC call with ``trainers[1]`` started from the MAP state (the protocol of ``get_posterior_ess``), over
+    the steps from ``config["mixing"]`` on; the call itself applies the classifier to every sample of the layer on the device and adds
+    the class probabilities, their squares, the argmax votes and the entropies (``PCTrainer.mcpc_probe``): no trajectory is recorded
+    (the reference loops over the recorded representations on the host, figure_2.py ``comparison_ideal_observer``).  ``classifier``: an
+    ``nn.Linear`` on the layer, or a module that holds exactly one (``MNIST_LinearClassifier``).  Returns ``(probe, labels)``: a
+    ``probe.Probe`` whose chains are all data in the loader's order (``Probe.cat`` of the batches; ``.mean``, ``.var``,
+    ``.vote_share``, ``.predict``, ``.entropy``, ``.expected_entropy``, ``.mutual_information`` per datum), and the labels of all
+    data."""
+    from ..probe import Probe
+    if len(trainers) != 2:
+        raise NotImplementedError
+    linears = [m for m in classifier.modules() if isinstance(m, torch.nn.Linear)]
+    if len(linears) != 1:
+        raise ValueError("get_posterior_class_probabilities: the classifier must be an nn.Linear or hold exactly one, it holds {}".format(
+            len(linears)))
+    device = next(gen_pc.parameters()).device
+    input_size = len(gen_pc[0].bias)
+    pc_trainer, mcpc_trainer = trainers
+    parts, labels = [], []
+    saved = mcpc_trainer.mcpc_probe
+    mcpc_trainer.mcpc_probe = dict(begin=int(config["mixing"]), stride=1, layer=layer, linear=linears[0], link=link)
+    try:
+        for data, label in loader:
+            pseudo_input = torch.zeros(data.shape[0], input_size, device=device)
+            data, label = data.to(device), label.to(device)
+            kw = dict(inputs=pseudo_input, loss_fn=config["loss_fn"],
+                      loss_fn_kwargs={"_target": data, "_var": config["input_var"]},
+                      is_log_progress=False, is_return_results_every_t=False, is_checking_after_callback_after_t=False)
+            pc_trainer.train_on_batch(**kw)
+            mcpc_trainer.train_on_batch(callback_after_t=random_step, callback_after_t_kwargs={"_pc_trainer": mcpc_trainer},
+                                        is_sample_x_at_batch_start=False, **kw)
+            parts.append(mcpc_trainer.mcpc_last_probe)
+            labels.append(label)
+    finally:
+        mcpc_trainer.mcpc_probe = saved
+    return Probe.cat(parts), torch.cat(labels, dim=0)
