@@ -386,6 +386,33 @@ int mcpc_probe_accumulate(int device, const float* rec, int32_t B, int32_t width
                           const float* W, const float* bias, int32_t n_classes, int32_t link, double* psum, double* psumsq,
                           int64_t* votes, double* entsum, int accumulate, void* stream);
 
+/* The k smallest squared distances from every query row into a reference set, by brute force on the device (csrc/mcpc_knn.h): the hot
+ * path of the nearest-neighbour KL estimator between two sample clouds (the reference asks two scipy KD-trees: figure_5.py,
+ * utils/training_evaluation.py KLdivergence).  q is device fp32 [nq][d], ref device fp32 [nr][d], both contiguous; d in
+ * 1..MCPC_KNN_MAX_DIM, k in 1..MCPC_KNN_MAX_K, nq and nr in 0..MCPC_KNN_MAX_ROWS.  best is device fp32 [nq][k]:
+ *   best[i][0..k) = the k smallest, ascending, of D(i, j) = sum_c (q[i][c] - ref[j][c])^2 over all j (and, with accumulate != 0, the k
+ *                   values best[i] held before: the k best of old best and this call's distances)
+ *   D             a = 0; for c = 0..d-1 ascending: t = q[i][c] - ref[j][c] in fp32, a = fmaf(t, t, a).  Not |q|^2 + |r|^2 - 2 q.r, which
+ *                 cancels at near neighbours; within (d + 3) * 2^-24 relative of the exact distance of the same fp32 rows.
+ *   selection     by fminf / fmaxf alone.  A NaN distance (a non-finite reference row) is never selected; a query row that holds a NaN
+ *                 keeps +inf; a NaN in the old best reads as +inf.  accumulate = 0 starts every slot at +inf, whatever best held: with
+ *                 nr < k the last k - nr slots stay +inf.  No row is skipped as "self": ask for k = 2 of a set into itself.
+ * min and max are exact: best is bitwise independent of the launch shape, of the order of the reference rows and of how the caller chunks
+ * ref over calls with accumulate = 1, so a reference set larger than memory can be streamed.
+ * workspace: device memory of mcpc_knn_workspace_bytes(nq, nr, d, k) bytes (4-B aligned, contents irrelevant, free for reuse when the
+ * call has completed on `stream`); the size depends on the four arguments alone.  mcpc_knn_workspace_bytes returns -1 (and a message in
+ * mcpc_last_error) for arguments mcpc_knn_accumulate would refuse.  The library allocates nothing.  Stateless, asynchronous on `stream`
+ * (a hipStream_t), no engine needed, all offsets 64-bit.  nq = 0 does nothing; nr = 0 fills best with +inf when accumulate = 0 and does
+ * nothing otherwise.
+ * MCPC_EINVAL, checked before any HIP call (nothing is launched then): d, k, nq or nr out of range, q or best NULL with nq > 0, ref NULL
+ * with nr > 0, a workspace that is NULL or smaller than mcpc_knn_workspace_bytes when that is not 0. */
+#define MCPC_KNN_MAX_DIM 32
+#define MCPC_KNN_MAX_K 4
+#define MCPC_KNN_MAX_ROWS 2147483647LL
+int mcpc_knn_accumulate(int device, const float* q, int64_t nq, const float* ref, int64_t nr, int32_t d, int32_t k, float* best,
+                        int32_t accumulate, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t mcpc_knn_workspace_bytes(int64_t nq, int64_t nr, int32_t d, int32_t k);
+
 /* Per-chain energies of recorded states, evaluated on the device (the reference has them per datapoint: is_return_batchelement_loss,
  * PCLayer(is_keep_energy_per_datapoint=True), get_energies(is_per_datapoint=True); pc_trainer.py:776-836, pc_layer.py:250-262).
  * A ROW is one chain at one recorded step.  x_rec[l], l < n_latent: [n_rec][batch][n_l] fp32, as mcpc_run writes rec_x[l] (n_rec = 1

@@ -18,6 +18,7 @@
 #include "mcpc_hist.h"
 #include "mcpc_acov.h"
 #include "mcpc_probe.h"
+#include "mcpc_knn.h"
 #include "mcpc_plan.h"
 #include "mcpc_chain_energy.h"
 
@@ -1503,6 +1504,45 @@ int mcpc_probe_accumulate(int device, const float* rec, int32_t B, int32_t width
     P.B = B; P.width = width; P.n = n; P.C = n_classes; P.accumulate = accumulate ? 1 : 0;
     P.psum = psum; P.psumsq = psumsq; P.votes = votes; P.entsum = entsum;
     probe_dispatch(link, P, stream);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+static int knn_check_shape(int64_t nq, int64_t nr, int32_t d, int32_t k) {
+    if (d < 1 || d > MCPC_KNN_MAX_DIM) return fail(MCPC_EINVAL, "knn: d=%d outside 1..%d", d, MCPC_KNN_MAX_DIM);
+    if (k < 1 || k > MCPC_KNN_MAX_K) return fail(MCPC_EINVAL, "knn: k=%d outside 1..%d", k, MCPC_KNN_MAX_K);
+    if (nq < 0 || nq > MCPC_KNN_MAX_ROWS) return fail(MCPC_EINVAL, "knn: nq=%lld outside 0..%lld", (long long)nq, (long long)MCPC_KNN_MAX_ROWS);
+    if (nr < 0 || nr > MCPC_KNN_MAX_ROWS) return fail(MCPC_EINVAL, "knn: nr=%lld outside 0..%lld", (long long)nr, (long long)MCPC_KNN_MAX_ROWS);
+    return MCPC_OK;
+}
+
+int64_t mcpc_knn_workspace_bytes(int64_t nq, int64_t nr, int32_t d, int32_t k) {
+    if (knn_check_shape(nq, nr, d, k)) return -1;
+    const KnnGeometry g = knn_geometry(nq, nr, d, k);
+    return g.n_splits * nq * g.kt * (int64_t)sizeof(float);
+}
+
+int mcpc_knn_accumulate(int device, const float* q, int64_t nq, const float* ref, int64_t nr, int32_t d, int32_t k, float* best,
+                        int32_t accumulate, void* workspace, int64_t workspace_bytes, void* stream_) {
+    if (const int rc = knn_check_shape(nq, nr, d, k)) return rc;
+    if (nq > 0 && !q) return fail(MCPC_EINVAL, "knn: q is null with nq=%lld", (long long)nq);
+    if (nq > 0 && !best) return fail(MCPC_EINVAL, "knn: best is null with nq=%lld", (long long)nq);
+    if (nr > 0 && !ref) return fail(MCPC_EINVAL, "knn: ref is null with nr=%lld", (long long)nr);
+    const KnnGeometry g = knn_geometry(nq, nr, d, k);
+    const int64_t need = g.n_splits * nq * g.kt * (int64_t)sizeof(float);
+    if (need > 0) {
+        if (!workspace) return fail(MCPC_EINVAL, "knn: workspace is null (mcpc_knn_workspace_bytes: %lld bytes)", (long long)need);
+        if (workspace_bytes < need)
+            return fail(MCPC_EINVAL, "knn: workspace of %lld bytes is too small, %lld needed", (long long)workspace_bytes, (long long)need);
+    }
+    if (nq == 0 || (nr == 0 && accumulate)) return MCPC_OK;      // nothing to write, or nothing to add
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(device));
+    KnnParams P{};
+    P.q = q; P.ref = ref; P.nq = nq; P.nr = nr; P.d = d; P.k = k;
+    P.tiles_per_split = g.tiles_per_split; P.n_tiles = g.n_tiles; P.n_splits = g.n_splits;
+    P.part = (float*)workspace; P.best = best; P.accumulate = accumulate ? 1 : 0;
+    knn_dispatch(g, P, stream);
     HIP_TRY(hipGetLastError());
     return MCPC_OK;
 }

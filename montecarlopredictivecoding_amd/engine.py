@@ -562,3 +562,60 @@ def probe_accumulate(rec, first, stride, n, W, bias, link, psum, psumsq, votes, 
     L.check(lib.mcpc_probe_accumulate(device.index or 0, _ptr(rec), B, width, first, stride, n, _ptr(W), _ptr(bias), n_classes,
                                       _PROBE_LINKS[link], _ptr(psum), _ptr(psumsq), _ptr(votes), _ptr(entsum), 1 if accumulate else 0,
                                       stream))
+
+
+def knn_workspace_bytes(nq, nr, d, k) -> int:
+    """Bytes of device workspace ``knn_accumulate`` needs for ``nq`` queries into ``nr`` reference rows of ``d`` coordinates, ``k`` kept."""
+    lib = L.load()
+    need = lib.mcpc_knn_workspace_bytes(int(nq), int(nr), int(d), int(k))
+    if need < 0:
+        L.check(need)
+    return need
+
+
+def knn_accumulate(q, ref, k, best, accumulate=False, workspace=None):
+    """The ``k`` smallest squared distances from every row of ``q`` into the rows of ``ref``, on the device (include/mcpc.h:
+    mcpc_knn_accumulate).  ``q``: contiguous fp32 ``[nq, d]``, ``ref``: contiguous fp32 ``[nr, d]``, d in 1..``L.KNN_MAX_DIM``, k in
+    1..``L.KNN_MAX_K``; ``best``: contiguous fp32 ``[nq, k]``, ascending per row.  Differences in fp32, summed by ``fmaf`` in column
+    order; the selection is min / max alone, so a NaN distance is never selected, slots without a neighbour hold +inf, and ``best`` is
+    bitwise independent of the order of the reference rows and of how ``ref`` is chunked over calls with ``accumulate=True`` (the k best
+    of the old ``best`` and this call's distances).  ``accumulate=False`` overwrites.  ``workspace``: a contiguous device tensor of at
+    least ``knn_workspace_bytes(nq, nr, d, k)`` bytes, 4-B aligned; None allocates one for this call.  Everything on the device of
+    ``q``.  On the current torch stream."""
+    lib = L.load()
+    if not isinstance(q, torch.Tensor) or q.dim() != 2:
+        raise TypeError("q: expected a torch.Tensor [nq, d]")
+    if not isinstance(ref, torch.Tensor) or ref.dim() != 2:
+        raise TypeError("ref: expected a torch.Tensor [nr, d]")
+    device = q.device
+    if device.type != "cuda":
+        raise ValueError(f"q: expected a tensor on a HIP device, got {device}")
+    nq, d = (int(s) for s in q.shape)
+    nr = int(ref.shape[0])
+    k = int(k)
+    if not 1 <= d <= L.KNN_MAX_DIM:
+        raise ValueError(f"q: {d} coordinates, expected 1..{L.KNN_MAX_DIM}")
+    if not 1 <= k <= L.KNN_MAX_K:
+        raise ValueError(f"k: {k}, expected 1..{L.KNN_MAX_K}")
+    _check_tensor(q, (nq, d), device, "q")
+    _check_tensor(ref, (nr, d), device, "ref")
+    _check_tensor(best, (nq, k), device, "best")
+    need = lib.mcpc_knn_workspace_bytes(nq, nr, d, k)
+    if need < 0:
+        L.check(need)
+    if workspace is None:
+        workspace = torch.empty(max(need, 4), dtype=torch.uint8, device=device)
+    if not isinstance(workspace, torch.Tensor):
+        raise TypeError(f"workspace: expected a torch.Tensor, got {type(workspace)}")
+    if workspace.device != device:
+        raise ValueError(f"workspace: expected device {device}, got {workspace.device}")
+    if not workspace.is_contiguous():
+        raise ValueError("workspace: tensor must be contiguous")
+    if workspace.data_ptr() % 4:
+        raise ValueError("workspace: must be 4-byte aligned")
+    ws_bytes = workspace.numel() * workspace.element_size()
+    if ws_bytes < need:
+        raise ValueError(f"workspace: {ws_bytes} bytes, knn_workspace_bytes asks for {need}")
+    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    L.check(lib.mcpc_knn_accumulate(device.index or 0, _ptr(q), nq, _ptr(ref), nr, d, k, _ptr(best), 1 if accumulate else 0,
+                                    _ptr(workspace), ws_bytes, stream))

@@ -270,6 +270,15 @@ class PCTrainer(object):
         # serves all six).
         self.mcpc_probe = None
         self.mcpc_last_probe = None
+        # the samples themselves of a few units of one latent layer of a fused call, gathered on the device out of the same ring
+        # (cloud.py): None = off, or dict(begin=0, stride=1, layer=l, units=(u0, u1, ...) | None) with 1..32 distinct units (None =
+        # every unit of a layer at most 32 wide).  The result is a cloud.Cloud in mcpc_last_cloud, fp32 [n, B, d] ON THE ENGINE'S
+        # DEVICE (also for a model built on the CPU): the input of cloud.kl_divergence, the nearest-neighbour KL estimate between
+        # the clouds of two calls (the reference's figure_5).  Composes with the other six (one ring serves all seven).  A request
+        # whose cloud would take more than mcpc_cloud_max_bytes is a ValueError before anything runs.
+        self.mcpc_cloud = None
+        self.mcpc_last_cloud = None
+        self.mcpc_cloud_max_bytes = 1 << 30
 
     # ---- getters & setters (reference :268-461) -------------------------------------------------------
     def get_T(self) -> int:
@@ -525,6 +534,13 @@ class PCTrainer(object):
                 raise NotImplementedError("mcpc_probe is set, and this call runs on the generic torch loop ({}): the posterior of a "
                                           "probe is accumulated by the fused HIP loop only".format(why_not_fused))
             plan["probe"] = _probe.validate_spec(self.mcpc_probe, self._T, len(plan["net"].sizes), plan["net"].sizes, plan["B"])
+        if self.mcpc_cloud is not None:
+            from .. import cloud as _cloud
+            if plan is None:
+                raise NotImplementedError("mcpc_cloud is set, and this call runs on the generic torch loop ({}): the sample cloud is "
+                                          "gathered by the fused HIP loop only".format(why_not_fused))
+            plan["cloud"] = _cloud.validate_spec(self.mcpc_cloud, self._T, len(plan["net"].sizes), plan["net"].sizes, plan["B"],
+                                                 self.mcpc_cloud_max_bytes)
         if plan is None:
             # outside what the kernels express: the package's generic torch loop (generic_loop.py), loudly, on the device the model
             # lives on ("must work, need not be fast").  It is no way around a missing GPU: without a visible HIP device
@@ -577,6 +593,9 @@ class PCTrainer(object):
         if plan["mode"] != "fused" and self.mcpc_probe is not None:
             raise NotImplementedError("mcpc_probe is set, and this call runs step by step ({}): the posterior of a probe is "
                                       "accumulated by the fused HIP loop only".format(plan["why_stepwise"]))
+        if plan["mode"] != "fused" and self.mcpc_cloud is not None:
+            raise NotImplementedError("mcpc_cloud is set, and this call runs step by step ({}): the sample cloud is gathered by the "
+                                      "fused HIP loop only".format(plan["why_stepwise"]))
         if plan["mode"] == "fused":
             self.last_call_mode = "fused"
             with _few_cpu_threads(plan["staged"]):
@@ -908,14 +927,16 @@ class PCTrainer(object):
         host_step_bytes = 4 * plan["B"] * sum(n for n, on in zip(net.sizes, rec_layers) if on)
         self.last_record_slices = 0
         mom, ce, cov, hist = plan.get("moments"), plan.get("chain_energies"), plan.get("covariance"), plan.get("histogram")
-        acov, probe = plan.get("autocovariance"), plan.get("probe")
-        if mom is not None or ce is not None or cov is not None or hist is not None or acov is not None or probe is not None:
-            # posterior moments / per-chain energies / covariances / histograms / autocovariances / a probe: the call runs as slices
-            # whatever its size, and the records they ask for are reduced on the device
+        acov, probe, cloud = plan.get("autocovariance"), plan.get("probe"), plan.get("cloud")
+        if (mom is not None or ce is not None or cov is not None or hist is not None or acov is not None or probe is not None
+                or cloud is not None):
+            # posterior moments / per-chain energies / covariances / histograms / autocovariances / a probe / a cloud: the call runs
+            # as slices whatever its size, and the records they ask for are reduced on the device
             ce_inputs = None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous())
             res, last_mom, last_ce = self._run_fused_sliced(
                 eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, is_return_outputs and net.n_out > 0,
-                every_t=is_return_results_every_t, mom=mom, ce=ce, ce_inputs=ce_inputs, cov=cov, hist=hist, acov=acov, probe=probe)
+                every_t=is_return_results_every_t, mom=mom, ce=ce, ce_inputs=ce_inputs, cov=cov, hist=hist, acov=acov, probe=probe,
+                cloud=cloud)
             if mom is not None:
                 self.mcpc_last_moments = last_mom
             if ce is not None:
@@ -948,7 +969,7 @@ class PCTrainer(object):
                                      is_return_representations, is_return_xs, loss_fn)
 
     def _run_fused_sliced(self, eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, rec_out, every_t=True, mom=None,
-                          ce=None, ce_inputs=None, cov=None, hist=None, acov=None, probe=None):
+                          ce=None, ce_inputs=None, cov=None, hist=None, acov=None, probe=None, cloud=None):
         """A call whose every-step trajectory would not fit the record budget on the device, or whose records feed `mcpc_moments`:
         the same T steps as slices of one `mcpc_run` each (slicing does not change a bit of the trajectories,
         tests/test_gpu_fullsize.py).  The latent records of a slice go to one half of a two-buffer device ring.  Records the caller's
@@ -967,7 +988,10 @@ class PCTrainer(object):
         call's own stream; the samples seen so far are counted per block and the kernel's own window carries the lags across slices;
         the result is left in `mcpc_last_autocovariance`.  With `probe` (a validated `mcpc_probe`) its layer goes through the ring too and
         one `probe_accumulate` after each slice, on the call's own stream, adds the link values, votes and entropies of the slice's
-        samples (overwriting in the first slice that holds one); the result is left in `mcpc_last_probe`.  Returns (RunResult, Moments or None, ChainEnergies or None)."""
+        samples (overwriting in the first slice that holds one); the result is left in `mcpc_last_probe`.  With `cloud` (a validated
+        `mcpc_cloud`) its layer goes through the ring as well and after each slice the slice's samples of the chosen units are gathered
+        (`index_select`) into one preallocated device tensor on the call's own stream; the result is left in `mcpc_last_cloud`, on the
+        engine's device.  Returns (RunResult, Moments or None, ChainEnergies or None)."""
         from ..engine import (RunResult, moments_accumulate, cov_accumulate, cov_workspace_bytes, hist_accumulate, acov_accumulate,
                               probe_accumulate)
         dev, B = plan["device"], plan["B"]
@@ -981,9 +1005,12 @@ class PCTrainer(object):
         acov_layers = [acov is not None and l in acov.layers for l in range(nl)]
         acov_out = acov is not None and acov.outputs is not None
         probe_layers = [probe is not None and l == probe.layer for l in range(nl)]
-        ring_layers = [a or b_ or c_ or d_ or e_ or f_ or ce is not None
-                       for a, b_, c_, d_, e_, f_ in zip(rec_layers, mom_layers, cov_layers, hist_layers, acov_layers, probe_layers)]
-        reduced = mom is not None or ce is not None or cov is not None or hist is not None or acov is not None or probe is not None
+        cloud_layers = [cloud is not None and l == cloud.layer for l in range(nl)]
+        ring_layers = [a or b_ or c_ or d_ or e_ or f_ or g_ or ce is not None
+                       for a, b_, c_, d_, e_, f_, g_ in zip(rec_layers, mom_layers, cov_layers, hist_layers, acov_layers, probe_layers,
+                                                            cloud_layers)]
+        reduced = (mom is not None or ce is not None or cov is not None or hist is not None or acov is not None or probe is not None
+                   or cloud is not None)
         out_direct = rec_out and every_t                     # every step's outputs are kept anyway: slices write them in place
         ring_out = (rec_out or mom_out or cov_out or hist_out or acov_out) and not out_direct
         S = T
@@ -1115,6 +1142,19 @@ class PCTrainer(object):
                              st["votes"], st["entsum"], accumulate=st["seen"])
             st["seen"] = True
 
+        cloud_points = cloud_units = None
+        if cloud is not None:
+            cloud_points = torch.empty(cloud.n, B, cloud.d, dtype=torch.float32, device=dev)
+            cloud_units = torch.tensor(cloud.units, dtype=torch.int64, device=dev)
+
+        def gather_cloud(t0, n, half):
+            first, cnt = cloud.chunk(t0, n)
+            if cnt == 0:
+                return
+            k0 = (t0 + first - cloud.begin) // cloud.stride          # index of the slice's first sample among all of them
+            rows = ring[half][cloud.layer][first:first + (cnt - 1) * cloud.stride + 1:cloud.stride]
+            torch.index_select(rows, 2, cloud_units, out=cloud_points[k0:k0 + cnt])
+
         ce_table = torch.empty(ce.n, B, L.ENERGY_COLS, dtype=torch.float64, device=dev) if ce is not None else None
         ce_kw = dict(loss_kind=run_kw["loss_kind"], loss_var=run_kw["loss_var"], mask_start=run_kw["mask_start"],
                      max_rows=self.mcpc_chain_energies_max_rows)
@@ -1154,6 +1194,8 @@ class PCTrainer(object):
                 reduce_acov(t0, n, half)
             if probe is not None:
                 reduce_probe(t0, n, half)
+            if cloud is not None:
+                gather_cloud(t0, n, half)
             if ring_out and rec_out and last:
                 out_full[0].copy_(ring_o[half][n - 1])       # (not every_t: the last step's outputs)
             to_host = any(rec_layers) and (every_t or last)
@@ -1205,6 +1247,9 @@ class PCTrainer(object):
         if probe is not None:
             from ..probe import from_state as probe_from_state
             self.mcpc_last_probe = probe_from_state(probe.n, B, probe.C, probe.link, probe_state, plan["model_device"])
+        if cloud is not None:
+            from ..cloud import Cloud
+            self.mcpc_last_cloud = Cloud(points=cloud_points, units=cloud.units, layer=cloud.layer)
         return RunResult(energies=energies, rec_x=host, rec_out=out_full), result, ce_result
 
     def mcpc_state_energies(self, inputs, loss_fn: typing.Callable = None, loss_fn_kwargs: dict = {}):

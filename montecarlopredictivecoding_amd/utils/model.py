@@ -355,3 +355,39 @@ def get_posterior_class_probabilities(gen_pc, config, trainers, loader, classifi
     finally:
         mcpc_trainer.mcpc_probe = saved
     return Probe.cat(parts), torch.cat(labels, dim=0)
+
+
+def get_posterior_cloud(gen_pc, config, trainers, loader, layer=2, units=None, loss_fn=None):
+    """The posterior samples themselves of a few units of one latent layer, per batch of ``loader``: MAP call with ``trainers[0]``,
+    then an MCPC call with ``trainers[1]`` started from the MAP state (the protocol of ``get_posterior_ess``), over the steps from
+    ``config["mixing"]`` on; the call itself gathers the units' samples out of its record ring into a device tensor
+    (``PCTrainer.mcpc_cloud``): no trajectory goes to the host (the reference records every layer with ``is_return_xs`` and keeps 5
+    units of one, figure_5.py).  ``units``: 1..32 unit indices of the layer (None = all of a layer at most 32 wide).  ``loss_fn``: the
+    loss of both calls, ``config["loss_fn"]`` by default; ``zero_fn`` gives figure 5's spontaneous activity (the data are then not
+    looked at).  Returns a ``cloud.Cloud`` on the engine's device whose chains are all data in the loader's order (``Cloud.cat`` of
+    the batches): the input of ``cloud.kl_divergence``."""
+    from ..cloud import Cloud
+    if len(trainers) != 2:
+        raise NotImplementedError
+    device = next(gen_pc.parameters()).device
+    input_size = len(gen_pc[0].bias)
+    pc_trainer, mcpc_trainer = trainers
+    loss_fn = config["loss_fn"] if loss_fn is None else loss_fn
+    parts = []
+    saved = mcpc_trainer.mcpc_cloud
+    mcpc_trainer.mcpc_cloud = dict(begin=int(config["mixing"]), stride=1, layer=layer, units=None if units is None else tuple(units))
+    try:
+        for batch in loader:
+            data = batch[0] if isinstance(batch, (tuple, list)) else batch
+            pseudo_input = torch.zeros(data.shape[0], input_size, device=device)
+            data = data.to(device)
+            kw = dict(inputs=pseudo_input, loss_fn=loss_fn,
+                      loss_fn_kwargs={} if loss_fn is zero_fn else {"_target": data, "_var": config["input_var"]},
+                      is_log_progress=False, is_return_results_every_t=False, is_checking_after_callback_after_t=False)
+            pc_trainer.train_on_batch(**kw)
+            mcpc_trainer.train_on_batch(callback_after_t=random_step, callback_after_t_kwargs={"_pc_trainer": mcpc_trainer},
+                                        is_sample_x_at_batch_start=False, **kw)
+            parts.append(mcpc_trainer.mcpc_last_cloud)
+    finally:
+        mcpc_trainer.mcpc_cloud = saved
+    return Cloud.cat(parts)

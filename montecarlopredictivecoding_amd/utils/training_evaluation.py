@@ -193,3 +193,12 @@ def get_marginal_likelihood(gen_pc, config, dataloader, use_cuda, n_samples=5000
         raise NotImplementedError("the reference implements the Bernoulli read-out only (training_evaluation.py:196)")
     logits = sample_pc(n_samples, gen_pc, config, use_cuda=use_cuda, is_return_hidden=True)                 # [S, n0]
     return marginal_likelihood_from_logits(logits, dataloader)
+
+
+def knn_kl_divergence(x, y):
+    """The nearest-neighbour (Perez-Cruz) estimate of D(P || Q) between samples ``x`` of P and ``y`` of Q on the device: what the
+    reference's ``KLdivergence(x, y)`` (:240-284) estimates, by exact brute force instead of two KD-trees queried with ``eps=.01``, so
+    that figure 5's clouds need no thinning (``cloud.kl_divergence``; ``x``, ``y``: ``cloud.Cloud``, tensors or arrays ``[rows, d]``).
+    A 0-d fp64 tensor."""
+    from ..cloud import kl_divergence
+    return kl_divergence(x, y)
