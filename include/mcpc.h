@@ -352,6 +352,45 @@ int mcpc_acov_accumulate(int device, const float* rec, int32_t B, int32_t width,
                          int32_t transform, int32_t max_lag, int64_t n_seen, double* lagged, double* sum, float* window, float* head,
                          void* stream);
 
+/* Rolling-window variance of recorded steps: how the variability of a chain changes along a call and across the boundary of two calls
+ * (csrc/mcpc_roll.h; the reference takes a pandas rolling(window).std() of recorded trajectories on the host: figure_5.py,
+ * variability_stimulus_onset_nonlinear).  The first reducer that is resolved in time.
+ * rec is a record buffer as mcpc_run writes it, [records][B][width] fp32; records first + j*stride, j = 0..n-1, are taken, exactly as
+ * in mcpc_acov_accumulate, and are samples n_seen .. n_seen + n - 1 of a STREAM that earlier calls began; transform is
+ * MCPC_MOM_IDENTITY or MCPC_MOM_SIGMOID (g).  With E = B * width and W = window (>= 2) the caller owns the state, all device memory:
+ *   s1, s2  fp64 [E]      the sums of g and g * g over the last min(W, samples so far) samples
+ *   hist    fp32 [W][E]   a circular buffer: g of sample j lives in row j mod W; the last min(W, samples so far) samples are valid
+ * Per element, samples in ascending order:
+ *   s1 = s1 + (double)g;  s2 = s2 + (double)g * (double)g;                          the entering sample j
+ *   if (j >= W) { s1 = s1 - (double)o;  s2 = s2 - (double)o * (double)o; }          o = g of sample j - W
+ *   if (j >= W - 1 && (j - (W - 1)) % every == 0)                                   a full window: stream row (j - (W - 1)) / every
+ *       { m = s1 / W;  v = (s2 - s1 * m) / (W - 1);  v = v < 0 ? 0 : v; }           not contracted; NaN stays NaN
+ * A product of two fp32 values is exact in fp64, so v is bitwise this loop on the host, whatever the launch shape and however the
+ * caller chunks the stream (150 samples in one call, or 1 + 3 + (W - 1) + W + (W + 1) + the rest with n_seen advancing, give the same
+ * bits in the state and in both outputs).  A window that is not full emits nothing.  The rows a call emits are numbered from 0 in the
+ * call's outputs, in stream order; there are as many as samples j of the call satisfy the condition above (at most n).  Either output
+ * may be NULL, not both:
+ *   out_elem  fp64 [rows][E]   v, written by the thread that owns the element
+ *   out_pool  fp64 [rows][4]   over the elements whose v is finite: sum of sd = sqrt(v), sum of sd * sd, sum of v, and their count.  Summed
+ *             wave-first, then over the workgroups in ascending order through `workspace`; the association depends on E and on the
+ *             vector width alone, so a pooled row does not depend on the chunking either.  An element that is not finite is left out
+ *             and shows as a missing count; it never poisons a row.  Its own s1 and s2 stay non-finite for the rest of the stream.
+ * The leaving sample comes from the chunk itself when it lies in it (read again, g recomputed) and from hist otherwise; hist is written
+ * for the call's last min(n, W) samples.  n_seen = 0 starts a stream: s1 and s2 are overwritten whatever they held and nothing is read
+ * from hist.  One thread owns an element and walks the samples in ascending order: no atomics, no split of the record axis.
+ * workspace: device memory of mcpc_roll_workspace_bytes(B, width, n) bytes (8-B aligned, contents irrelevant, free for reuse when the
+ * call has completed on `stream`); needed with out_pool only.  mcpc_roll_workspace_bytes returns -1 (and a message in mcpc_last_error)
+ * for B < 1, width < 1 or n < 0.  The library allocates nothing.  Asynchronous on `stream`, no engine needed, all offsets 64-bit.  16-B
+ * loads per lane when E % 4 == 0 and the first record taken and hist are 16-B aligned; a scalar form otherwise.  n = 0 reads nothing: it
+ * zeroes s1 and s2 when n_seen = 0 and does nothing otherwise.
+ * MCPC_EINVAL, checked before any HIP call (nothing is launched then): s1, s2 or hist NULL, out_elem and out_pool both NULL, window < 2,
+ * every < 1, rec NULL with n > 0, B < 1, width < 1, stride < 1, first < 0, n < 0, n_seen < 0, an unknown transform, workspace NULL when
+ * out_pool is set and the call emits a row. */
+int mcpc_roll_accumulate(int device, const float* rec, int32_t B, int32_t width, int32_t first, int32_t stride, int32_t n,
+                         int32_t transform, int32_t window, int32_t every, int64_t n_seen, double* s1, double* s2, float* hist,
+                         double* out_elem, double* out_pool, void* workspace, void* stream);
+int64_t mcpc_roll_workspace_bytes(int32_t B, int32_t width, int32_t n);
+
 /* Streaming posterior of a linear probe on recorded steps: class probabilities of a linear read-out of a latent layer with a link, reduced
  * per chain over the samples of a Langevin call (csrc/mcpc_probe.h; the reference adds softmax(classifier(representation)) over the recorded
  * representations on the host: figure_2.py, comparison_ideal_observer).  The first reducer that applies a function the caller supplies.

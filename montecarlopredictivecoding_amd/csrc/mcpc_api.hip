@@ -17,6 +17,7 @@
 #include "mcpc_cov.h"
 #include "mcpc_hist.h"
 #include "mcpc_acov.h"
+#include "mcpc_roll.h"
 #include "mcpc_probe.h"
 #include "mcpc_knn.h"
 #include "mcpc_plan.h"
@@ -1466,6 +1467,60 @@ int mcpc_acov_accumulate(int device, const float* rec, int32_t B, int32_t width,
     P.E = E; P.row_step = (int64_t)stride * E; P.n_seen = n_seen; P.n = n; P.K = max_lag;
     P.lagged = lagged; P.sum = sum; P.window = window; P.head = head;
     acov_dispatch(transform, P, stream);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+static int roll_check_shape(int32_t B, int32_t width, int32_t n) {
+    if (B < 1) return fail(MCPC_EINVAL, "roll: B=%d, must be at least 1", B);
+    if (width < 1) return fail(MCPC_EINVAL, "roll: width=%d, must be at least 1", width);
+    if (n < 0) return fail(MCPC_EINVAL, "roll: n=%d, must not be negative", n);
+    if (roll_groups((int64_t)B * width, 1) >= kRollMaxGroups)
+        return fail(MCPC_EINVAL, "roll: B * width = %lld is more than one launch holds", (long long)B * width);
+    return MCPC_OK;
+}
+
+int64_t mcpc_roll_workspace_bytes(int32_t B, int32_t width, int32_t n) {
+    if (roll_check_shape(B, width, n)) return -1;
+    // a chunk of n samples emits at most n rows, and the scalar form has the most workgroups
+    return roll_groups((int64_t)B * width, 1) * (int64_t)n * 4 * (int64_t)sizeof(double);
+}
+
+int mcpc_roll_accumulate(int device, const float* rec, int32_t B, int32_t width, int32_t first, int32_t stride, int32_t n, int32_t transform,
+                         int32_t window, int32_t every, int64_t n_seen, double* s1, double* s2, float* hist, double* out_elem,
+                         double* out_pool, void* workspace, void* stream_) {
+    if (window < 2) return fail(MCPC_EINVAL, "roll: window=%d, must be at least 2", window);
+    if (every < 1) return fail(MCPC_EINVAL, "roll: every=%d, must be at least 1", every);
+    if (!s1) return fail(MCPC_EINVAL, "roll: s1 is null");
+    if (!s2) return fail(MCPC_EINVAL, "roll: s2 is null");
+    if (!hist) return fail(MCPC_EINVAL, "roll: hist is null");
+    if (!out_elem && !out_pool) return fail(MCPC_EINVAL, "roll: out_elem and out_pool are both null");
+    if (const int rc = roll_check_shape(B, width, n)) return rc;
+    if (stride < 1) return fail(MCPC_EINVAL, "roll: stride=%d, must be at least 1", stride);
+    if (first < 0) return fail(MCPC_EINVAL, "roll: first=%d, must not be negative", first);
+    if (n_seen < 0) return fail(MCPC_EINVAL, "roll: n_seen=%lld, must not be negative", (long long)n_seen);
+    if (transform != MCPC_MOM_IDENTITY && transform != MCPC_MOM_SIGMOID) return fail(MCPC_EINVAL, "roll: unknown transform %d", transform);
+    if (n > 0 && !rec) return fail(MCPC_EINVAL, "roll: rec is null with n=%d", n);
+    RollParams P{};
+    P.rows = roll_rows(n_seen, n, window, every, &P.emit0);
+    if (out_pool && P.rows > 0 && !workspace)
+        return fail(MCPC_EINVAL, "roll: workspace is null with out_pool set (mcpc_roll_workspace_bytes: %lld bytes)",
+                    (long long)mcpc_roll_workspace_bytes(B, width, n));
+    if (n == 0 && n_seen > 0) return MCPC_OK;                     // nothing to add
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(device));
+    const int64_t E = (int64_t)B * width;
+    if (n == 0) {                                                 // a stream that starts empty
+        HIP_TRY(hipMemsetAsync(s1, 0, (size_t)E * sizeof(double), stream));
+        HIP_TRY(hipMemsetAsync(s2, 0, (size_t)E * sizeof(double), stream));
+        return MCPC_OK;
+    }
+    P.rec = rec + (int64_t)first * E;                             // all offsets in 64 bits, as in mcpc_moments_accumulate
+    P.E = E; P.row_step = (int64_t)stride * E; P.n_seen = n_seen; P.n = n; P.W = window; P.every = every;
+    P.slot0 = (int32_t)(n_seen % window);
+    P.s1 = s1; P.s2 = s2; P.hist = hist; P.out_elem = out_elem; P.part = (double*)workspace;
+    if (roll_vec(P) == 4) roll_launch<4>(transform, P, out_pool, stream);
+    else roll_launch<1>(transform, P, out_pool, stream);
     HIP_TRY(hipGetLastError());
     return MCPC_OK;
 }

@@ -517,6 +517,95 @@ def acov_accumulate(rec, first, stride, n, max_lag, n_seen, lagged, sum, window,
                                      n_seen, _ptr(lagged), _ptr(sum), _ptr(window), _ptr(head), stream))
 
 
+def roll_workspace_bytes(B, width, n) -> int:
+    """Bytes of device workspace ``roll_accumulate`` needs for the pooled rows of a chunk of ``n`` samples of ``B`` chains x ``width``
+    units (include/mcpc.h: mcpc_roll_workspace_bytes)."""
+    lib = L.load()
+    need = lib.mcpc_roll_workspace_bytes(int(B), int(width), int(n))
+    if need < 0:
+        L.check(need)
+    return need
+
+
+def roll_rows(n_seen, n, window, every=1) -> int:
+    """Rows a chunk of ``n`` samples emits after ``n_seen`` samples of the stream: one per sample j >= window - 1 with
+    (j - (window - 1)) % every == 0."""
+    n_seen, n, window, every = int(n_seen), int(n), int(window), int(every)
+    j = max(n_seen, window - 1)
+    j += -(j - (window - 1)) % every
+    return (n_seen + n - 1 - j) // every + 1 if j < n_seen + n else 0
+
+
+def roll_accumulate(rec, first, stride, n, window, every, n_seen, s1, s2, hist, out_elem=None, out_pool=None, workspace=None,
+                    transform="identity"):
+    """Feed records ``rec[first + j * stride]``, j < n, as samples ``n_seen .. n_seen + n - 1`` of a stream to its rolling-window variance
+    on the device (include/mcpc.h: mcpc_roll_accumulate).  ``rec``: contiguous fp32 ``[records, B, width]`` as an engine run records it.
+    The caller owns the state, on the device of ``rec``: ``s1`` and ``s2`` fp64 ``[B, width]`` (the sums of g and g^2 over the current
+    window), ``hist`` fp32 ``[window, B, width]`` (a circular buffer, sample j in row j mod window).  ``n_seen``: the samples the stream
+    held before this call; 0 starts one.  Every sample j >= window - 1 with (j - (window - 1)) % every == 0 emits a row; the call's
+    ``roll_rows(n_seen, n, window, every)`` rows are numbered from 0 in its outputs: ``out_elem`` fp64 ``[rows, B, width]``, the
+    variance (ddof 1) of the window that ends at the row's sample, bitwise a sequential fp64 loop over the stream however it is
+    chunked; ``out_pool`` fp64 ``[rows, 4]``, over the elements whose variance is finite the sums of its square root, of that squared,
+    of the variance, and their count.  Either may be None, not both; both may hold more rows than the call emits.  ``workspace`` (with
+    ``out_pool``): a contiguous device tensor of at least ``roll_workspace_bytes(B, width, n)`` bytes, 8-B aligned; None allocates one
+    for this call.  ``transform``: "identity", or "sigmoid" for the read-out's Bernoulli mean.  Returns the rows emitted.  On the
+    current torch stream."""
+    lib = L.load()
+    if transform not in _MOM_TRANSFORMS:
+        raise ValueError(f"transform: expected 'identity' or 'sigmoid', got {transform!r}")
+    if not isinstance(rec, torch.Tensor) or rec.dim() != 3:
+        raise TypeError("rec: expected a torch.Tensor [records, B, width]")
+    device = rec.device
+    if device.type != "cuda":
+        raise ValueError(f"rec: expected a tensor on a HIP device, got {device}")
+    _check_tensor(rec, rec.shape, device, "rec")
+    R, B, width = (int(d) for d in rec.shape)
+    first, stride, n, window, every, n_seen = int(first), int(stride), int(n), int(window), int(every), int(n_seen)
+    if n > 0 and first >= 0 and stride >= 1 and first + (n - 1) * stride >= R:
+        raise ValueError(f"rec holds {R} records, the last one asked for is {first + (n - 1) * stride}")
+    if window < 2:
+        raise ValueError(f"window={window}, expected at least 2")
+    if every < 1:
+        raise ValueError(f"every={every}, expected at least 1")
+    _check_tensor(s1, (B, width), device, "s1", torch.float64)
+    _check_tensor(s2, (B, width), device, "s2", torch.float64)
+    _check_tensor(hist, (window, B, width), device, "hist")
+    if out_elem is None and out_pool is None:
+        raise ValueError("out_elem and out_pool are both None")
+    rows = roll_rows(n_seen, n, window, every) if n >= 0 and n_seen >= 0 else 0
+    if out_elem is not None:
+        if not isinstance(out_elem, torch.Tensor) or out_elem.dim() != 3 or out_elem.shape[0] < rows:
+            raise ValueError(f"out_elem: expected a torch.Tensor of at least {rows} rows [rows, {B}, {width}]")
+        _check_tensor(out_elem, (out_elem.shape[0], B, width), device, "out_elem", torch.float64)
+    if out_pool is not None:
+        if not isinstance(out_pool, torch.Tensor) or out_pool.dim() != 2 or out_pool.shape[0] < rows:
+            raise ValueError(f"out_pool: expected a torch.Tensor of at least {rows} rows [rows, 4]")
+        _check_tensor(out_pool, (out_pool.shape[0], 4), device, "out_pool", torch.float64)
+        need = roll_workspace_bytes(B, width, max(n, 0))
+        if workspace is None:
+            workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+        if not isinstance(workspace, torch.Tensor):
+            raise TypeError(f"workspace: expected a torch.Tensor, got {type(workspace)}")
+        if workspace.device != device:
+            raise ValueError(f"workspace: expected device {device}, got {workspace.device}")
+        if not workspace.is_contiguous():
+            raise ValueError("workspace: tensor must be contiguous")
+        if workspace.data_ptr() % 8:
+            raise ValueError("workspace: must be 8-byte aligned")
+        if workspace.numel() * workspace.element_size() < need:
+            raise ValueError(f"workspace: {workspace.numel() * workspace.element_size()} bytes, roll_workspace_bytes asks for {need}")
+
+    def out_ptr(t):
+        # a tensor without rows has no address, and the library tells the outputs asked for by their pointers: s1's stands in (a call
+        # that emits no row writes no output)
+        return None if t is None else C.c_void_p(t.data_ptr() or s1.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    L.check(lib.mcpc_roll_accumulate(device.index or 0, _ptr(rec), B, width, first, stride, n, _MOM_TRANSFORMS[transform], window, every,
+                                     n_seen, _ptr(s1), _ptr(s2), _ptr(hist), out_ptr(out_elem), out_ptr(out_pool),
+                                     _ptr(workspace) if out_pool is not None else None, stream))
+    return rows
+
+
 _PROBE_LINKS = {"identity": L.PROBE_IDENTITY, "sigmoid": L.PROBE_SIGMOID, "softmax": L.PROBE_SOFTMAX}
 
 

@@ -279,6 +279,16 @@ class PCTrainer(object):
         self.mcpc_cloud = None
         self.mcpc_last_cloud = None
         self.mcpc_cloud_max_bytes = 1 << 30
+        # the rolling-window variability of a fused call, accumulated on the device out of the same ring (rolling.py): None = off, or
+        # dict(begin=0, stride=1, layers=(), outputs=None | "identity" | "sigmoid", window=W, every=1, pool="all" | None, carry=None)
+        # with W >= 2.  The result is a rolling.Rolling in mcpc_last_rolling: per every-th full window of W samples the mean and spread
+        # across the (chain, unit) series of their rolling standard deviation, and with pool=None the variance of every series; carry=
+        # (the Rolling of an earlier call) continues that call's stream, so that a window runs across the boundary of the two calls.
+        # Composes with the other seven (one ring serves all eight).  A request whose state, workspace and result would take more than
+        # mcpc_rolling_max_bytes is a ValueError before anything runs.
+        self.mcpc_rolling = None
+        self.mcpc_last_rolling = None
+        self.mcpc_rolling_max_bytes = 2 << 30
 
     # ---- getters & setters (reference :268-461) -------------------------------------------------------
     def get_T(self) -> int:
@@ -541,6 +551,13 @@ class PCTrainer(object):
                                           "gathered by the fused HIP loop only".format(why_not_fused))
             plan["cloud"] = _cloud.validate_spec(self.mcpc_cloud, self._T, len(plan["net"].sizes), plan["net"].sizes, plan["B"],
                                                  self.mcpc_cloud_max_bytes)
+        if self.mcpc_rolling is not None:
+            from .. import rolling as _rolling
+            if plan is None:
+                raise NotImplementedError("mcpc_rolling is set, and this call runs on the generic torch loop ({}): the rolling "
+                                          "variability is accumulated by the fused HIP loop only".format(why_not_fused))
+            plan["rolling"] = _rolling.validate_spec(self.mcpc_rolling, self._T, len(plan["net"].sizes), plan["net"].n_out,
+                                                     plan["net"].sizes, plan["B"], self.mcpc_rolling_max_bytes)
         if plan is None:
             # outside what the kernels express: the package's generic torch loop (generic_loop.py), loudly, on the device the model
             # lives on ("must work, need not be fast").  It is no way around a missing GPU: without a visible HIP device
@@ -596,6 +613,9 @@ class PCTrainer(object):
         if plan["mode"] != "fused" and self.mcpc_cloud is not None:
             raise NotImplementedError("mcpc_cloud is set, and this call runs step by step ({}): the sample cloud is gathered by the "
                                       "fused HIP loop only".format(plan["why_stepwise"]))
+        if plan["mode"] != "fused" and self.mcpc_rolling is not None:
+            raise NotImplementedError("mcpc_rolling is set, and this call runs step by step ({}): the rolling variability is "
+                                      "accumulated by the fused HIP loop only".format(plan["why_stepwise"]))
         if plan["mode"] == "fused":
             self.last_call_mode = "fused"
             with _few_cpu_threads(plan["staged"]):
@@ -927,16 +947,16 @@ class PCTrainer(object):
         host_step_bytes = 4 * plan["B"] * sum(n for n, on in zip(net.sizes, rec_layers) if on)
         self.last_record_slices = 0
         mom, ce, cov, hist = plan.get("moments"), plan.get("chain_energies"), plan.get("covariance"), plan.get("histogram")
-        acov, probe, cloud = plan.get("autocovariance"), plan.get("probe"), plan.get("cloud")
+        acov, probe, cloud, roll = plan.get("autocovariance"), plan.get("probe"), plan.get("cloud"), plan.get("rolling")
         if (mom is not None or ce is not None or cov is not None or hist is not None or acov is not None or probe is not None
-                or cloud is not None):
+                or cloud is not None or roll is not None):
             # posterior moments / per-chain energies / covariances / histograms / autocovariances / a probe / a cloud: the call runs
             # as slices whatever its size, and the records they ask for are reduced on the device
             ce_inputs = None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous())
             res, last_mom, last_ce = self._run_fused_sliced(
                 eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, is_return_outputs and net.n_out > 0,
                 every_t=is_return_results_every_t, mom=mom, ce=ce, ce_inputs=ce_inputs, cov=cov, hist=hist, acov=acov, probe=probe,
-                cloud=cloud)
+                cloud=cloud, roll=roll)
             if mom is not None:
                 self.mcpc_last_moments = last_mom
             if ce is not None:
@@ -969,7 +989,7 @@ class PCTrainer(object):
                                      is_return_representations, is_return_xs, loss_fn)
 
     def _run_fused_sliced(self, eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, rec_out, every_t=True, mom=None,
-                          ce=None, ce_inputs=None, cov=None, hist=None, acov=None, probe=None, cloud=None):
+                          ce=None, ce_inputs=None, cov=None, hist=None, acov=None, probe=None, cloud=None, roll=None):
         """A call whose every-step trajectory would not fit the record budget on the device, or whose records feed `mcpc_moments`:
         the same T steps as slices of one `mcpc_run` each (slicing does not change a bit of the trajectories,
         tests/test_gpu_fullsize.py).  The latent records of a slice go to one half of a two-buffer device ring.  Records the caller's
@@ -991,9 +1011,12 @@ class PCTrainer(object):
         samples (overwriting in the first slice that holds one); the result is left in `mcpc_last_probe`.  With `cloud` (a validated
         `mcpc_cloud`) its layer goes through the ring as well and after each slice the slice's samples of the chosen units are gathered
         (`index_select`) into one preallocated device tensor on the call's own stream; the result is left in `mcpc_last_cloud`, on the
-        engine's device.  Returns (RunResult, Moments or None, ChainEnergies or None)."""
+        engine's device.  With `roll` (a validated `mcpc_rolling`) its layers and read-out go through the ring likewise and
+        `roll_accumulate` feeds each block's samples to its rolling variance after each slice, in step order, on the call's own stream;
+        the samples seen and the rows emitted so far are counted per block, and the kernel's own history carries a window across
+        slices (and, with `carry=`, across calls); the result is left in `mcpc_last_rolling`.  Returns (RunResult, Moments or None, ChainEnergies or None)."""
         from ..engine import (RunResult, moments_accumulate, cov_accumulate, cov_workspace_bytes, hist_accumulate, acov_accumulate,
-                              probe_accumulate)
+                              probe_accumulate, roll_accumulate, roll_workspace_bytes)
         dev, B = plan["device"], plan["B"]
         nl = len(net.sizes)
         mom_layers = [mom is not None and l in mom.layers for l in range(nl)]
@@ -1006,19 +1029,21 @@ class PCTrainer(object):
         acov_out = acov is not None and acov.outputs is not None
         probe_layers = [probe is not None and l == probe.layer for l in range(nl)]
         cloud_layers = [cloud is not None and l == cloud.layer for l in range(nl)]
-        ring_layers = [a or b_ or c_ or d_ or e_ or f_ or g_ or ce is not None
-                       for a, b_, c_, d_, e_, f_, g_ in zip(rec_layers, mom_layers, cov_layers, hist_layers, acov_layers, probe_layers,
-                                                            cloud_layers)]
+        roll_layers = [roll is not None and l in roll.layers for l in range(nl)]
+        roll_out = roll is not None and roll.outputs is not None
+        ring_layers = [a or b_ or c_ or d_ or e_ or f_ or g_ or h_ or ce is not None
+                       for a, b_, c_, d_, e_, f_, g_, h_ in zip(rec_layers, mom_layers, cov_layers, hist_layers, acov_layers,
+                                                                probe_layers, cloud_layers, roll_layers)]
         reduced = (mom is not None or ce is not None or cov is not None or hist is not None or acov is not None or probe is not None
-                   or cloud is not None)
+                   or cloud is not None or roll is not None)
         out_direct = rec_out and every_t                     # every step's outputs are kept anyway: slices write them in place
-        ring_out = (rec_out or mom_out or cov_out or hist_out or acov_out) and not out_direct
+        ring_out = (rec_out or mom_out or cov_out or hist_out or acov_out or roll_out) and not out_direct
         S = T
         if any(rec_layers) and every_t:
             S = min(S, self.mcpc_record_chunk_bytes // max(2 * host_step_bytes, 1))
         if reduced:
             # one half of the ring is a chunk of at most mcpc_moments_chunk_bytes
-            step_bytes = 4 * B * (sum(n for n, on in zip(net.sizes, ring_layers) if on) + (net.n_out if ring_out or mom_out or cov_out or hist_out or acov_out else 0))
+            step_bytes = 4 * B * (sum(n for n, on in zip(net.sizes, ring_layers) if on) + (net.n_out if ring_out or mom_out or cov_out or hist_out or acov_out or roll_out else 0))
             S = min(S, self.mcpc_moments_chunk_bytes // max(step_bytes, 1))
         S = max(1, S)
         # A slice boundary inside the window that accumulates parameter gradients would regroup their fp32 sums (one Hebbian flush and
@@ -1126,6 +1151,33 @@ class PCTrainer(object):
                                 st["head"], transform=xf)
                 st["n_seen"] += cnt
 
+        roll_state = roll_pooled = roll_elem = roll_ws = None
+        if roll is not None:
+            from ..rolling import new_state as roll_new_state
+            roll_xf = ["identity"] * len(roll.layers) + ([roll.outputs] if roll_out else [])
+            roll_state = roll_new_state(roll, B, dev)
+            for st in roll_state:
+                st["row"] = 0                                    # rows this call has emitted for the block
+            roll_pooled = [torch.zeros(roll.rows, 4, dtype=torch.float64, device=dev) for _ in roll.columns]
+            roll_elem = [torch.zeros(roll.rows, B, w, dtype=torch.float64, device=dev) if roll.pool is None else None
+                         for _, w in roll.columns]
+            roll_ws = torch.empty(max(max(roll_workspace_bytes(B, w, min(S, roll.n)) for _, w in roll.columns), 8), dtype=torch.uint8,
+                                  device=dev)
+
+        def reduce_roll(t0, n, half):
+            first, cnt = roll.chunk(t0, n)
+            if cnt == 0:
+                return
+            blocks = [ring[half][l] for l in roll.layers]
+            if roll_out:
+                blocks.append(out_full[t0:t0 + n] if out_direct else ring_o[half])
+            for blk, st, xf, pooled, elem in zip(blocks, roll_state, roll_xf, roll_pooled, roll_elem):
+                r0 = st["row"]
+                st["row"] += roll_accumulate(blk, first, roll.stride, cnt, roll.window, roll.every, st["n_seen"], st["s1"], st["s2"],
+                                             st["hist"], out_elem=None if elem is None else elem[r0:], out_pool=pooled[r0:],
+                                             workspace=roll_ws, transform=xf)
+                st["n_seen"] += cnt
+
         probe_state = None
         if probe is not None:
             from ..probe import new_state
@@ -1196,6 +1248,8 @@ class PCTrainer(object):
                 reduce_probe(t0, n, half)
             if cloud is not None:
                 gather_cloud(t0, n, half)
+            if roll is not None:
+                reduce_roll(t0, n, half)
             if ring_out and rec_out and last:
                 out_full[0].copy_(ring_o[half][n - 1])       # (not every_t: the last step's outputs)
             to_host = any(rec_layers) and (every_t or last)
@@ -1250,6 +1304,11 @@ class PCTrainer(object):
         if cloud is not None:
             from ..cloud import Cloud
             self.mcpc_last_cloud = Cloud(points=cloud_points, units=cloud.units, layer=cloud.layer)
+        if roll is not None:
+            from ..rolling import from_state as roll_from_state
+            for st in roll_state:
+                del st["row"]
+            self.mcpc_last_rolling = roll_from_state(roll, B, roll_state, roll_pooled, roll_elem, plan["model_device"])
         return RunResult(energies=energies, rec_x=host, rec_out=out_full), result, ce_result
 
     def mcpc_state_energies(self, inputs, loss_fn: typing.Callable = None, loss_fn_kwargs: dict = {}):

@@ -391,3 +391,45 @@ def get_posterior_cloud(gen_pc, config, trainers, loader, layer=2, units=None, l
     finally:
         mcpc_trainer.mcpc_cloud = saved
     return Cloud.cat(parts)
+
+
+def get_variability_time_course(gen_pc, config, trainers, data, window=1000, every=1, layers=None):
+    """How the variability of the latent units changes when a stimulus sets in (the reference's figure_5.py,
+    ``variability_stimulus_onset_nonlinear``), on one batch ``data``: a MAP call with ``trainers[0]`` and an MCPC call with
+    ``trainers[1]`` from its state, both without a loss; then an MCPC call under ``zero_fn`` (no input) that starts a stream of samples,
+    and an MCPC call under ``config["loss_fn"]`` on ``data`` that carries the stream on.  The two calls themselves reduce, on the
+    device, the standard deviation of the last ``window`` samples of every (datum, unit) and its mean and spread across them, per
+    ``every``-th step (``PCTrainer.mcpc_rolling`` with ``carry=``): no trajectory is recorded (the reference records every step of
+    every layer and takes pandas' ``rolling(window).std()`` of them), and the windows of the second call's first ``window - 1`` rows
+    reach back into the first.  ``layers``: the PC layers looked at (None = all).  Returns the ``rolling.Rolling`` of both calls joined
+    in time; ``.all()`` pools the layers, ``.mean_std`` / ``.sem`` of it are the figure's line and band, and the stimulus sets in at
+    step ``T`` of ``.steps``.  The plain mean and standard deviation across all series are given, not the reference's average of
+    per-chunk standard deviations; the mean is the same quantity."""
+    from ..rolling import Rolling
+    if len(trainers) != 2:
+        raise NotImplementedError
+    device = next(gen_pc.parameters()).device
+    input_size = len(gen_pc[0].bias)
+    pc_trainer, mcpc_trainer = trainers
+    if layers is None:
+        layers = range(sum(isinstance(m, PCLayer) for m in gen_pc.modules()))
+    pseudo_input = torch.zeros(data.shape[0], input_size, device=device)
+    data = data.to(device)
+    quiet = dict(is_log_progress=False, is_return_results_every_t=False, is_checking_after_callback_after_t=False)
+    mc = dict(callback_after_t=random_step, callback_after_t_kwargs={"_pc_trainer": mcpc_trainer}, is_sample_x_at_batch_start=False)
+    request = dict(begin=0, stride=1, layers=tuple(layers), outputs=None, window=int(window), every=int(every), pool="all")
+    saved = mcpc_trainer.mcpc_rolling
+    try:
+        mcpc_trainer.mcpc_rolling = None
+        pc_trainer.train_on_batch(inputs=pseudo_input, **quiet)
+        mcpc_trainer.train_on_batch(inputs=pseudo_input, **mc, **quiet)
+        mcpc_trainer.mcpc_rolling = dict(request)
+        mcpc_trainer.train_on_batch(inputs=pseudo_input, loss_fn=zero_fn, loss_fn_kwargs={}, **mc, **quiet)
+        before = mcpc_trainer.mcpc_last_rolling
+        mcpc_trainer.mcpc_rolling = dict(request, carry=before)
+        mcpc_trainer.train_on_batch(inputs=pseudo_input, loss_fn=config["loss_fn"],
+                                    loss_fn_kwargs={"_target": data, "_var": config["input_var"]}, **mc, **quiet)
+        after = mcpc_trainer.mcpc_last_rolling
+    finally:
+        mcpc_trainer.mcpc_rolling = saved
+    return Rolling.cat([before, after], dim="time")
