@@ -473,6 +473,28 @@ int64_t mcpc_knn_workspace_bytes(int64_t nq, int64_t nr, int32_t d, int32_t k);
 int mcpc_chain_energies(mcpc_engine* e, const float* inputs, const float* const* x_rec, int32_t n_rec, int32_t loss_kind,
                         double loss_var, int32_t mask_start, double* out, int32_t max_rows, void* stream);
 
+/* Prediction errors and predictions of recorded states, per unit: the other half of a predictive-coding network's population, as
+ * DERIVED RECORDS.  Rows, x_rec, `inputs`, the target, loss_kind / loss_var / mask_start, max_rows and the scratch are those of
+ * mcpc_chain_energies (the scratch is shared), and so is the forward pass: a prediction is bitwise the step kernels' and bitwise the one
+ * mcpc_chain_energies squares.  Per row r = k * batch + chain the call writes, where the destination is not NULL,
+ *   err[l][r][u]  = x_l - mu_l (NOT scaled by the layer's ecoef),        pred[l][r][u] = mu_l            l < n_latent, u < n_l
+ *   err_out[r][u] = the read-out error the step kernels back-propagate   pred_out[r][u] = the read-out's output (logits)    u < n_out
+ *                   (dloss / dout; exactly 0 for u < mask_start),
+ * each unpadded fp32 [n_rec][batch][n_l], the layout mcpc_run writes rec_x[l] / rec_out in: every stateless reducer of this header
+ * (mcpc_moments_accumulate, mcpc_cov_accumulate, mcpc_hist_accumulate, mcpc_acov_accumulate, mcpc_roll_accumulate) takes them as `rec`.
+ * err / pred: arrays of n_latent pointers; an entry that is NULL, or err / pred itself NULL, means "not wanted".  Only the Linears asked
+ * for are evaluated (a call that wants layer 2 alone launches no GEMM for layers 0 and 1), and only the records they read are consulted:
+ * x_rec[l] for a wanted layer l and for the layer below a wanted layer or read-out; the other entries of x_rec may be NULL.  loss_kind,
+ * loss_var, mask_start and the bound target matter to err_out alone.  No sums, no atomics: a value depends on its own row only, not on
+ * the other rows, n_rec, max_rows or on what else is asked for.  Nothing is written outside rows < n_rec * batch and units < n_l.
+ * Destinations need 4-byte alignment; one that is 16-byte aligned with n_l % 4 == 0 is written with 16-byte stores.
+ * MCPC_EINVAL: null engine / x_rec / a needed x_rec[l], n_rec < 0, max_rows < 0, nothing wanted at all, err_out or pred_out on an engine
+ * without a read-out, unknown loss_kind, err_out with MCPC_LOSS_NONE, loss_var <= 0 or mask_start outside 0..n_out-1 with err_out.
+ * MCPC_ESTATE: parameters of a wanted Linear not bound, err_out without a bound target.  Nothing is launched then. */
+int mcpc_prediction_errors(mcpc_engine* e, const float* inputs, const float* const* x_rec, int32_t n_rec, int32_t loss_kind,
+                           double loss_var, int32_t mask_start, float* const* err, float* const* pred, float* err_out, float* pred_out,
+                           int32_t max_rows, void* stream);
+
 /* Synchronise `stream` and report device-side faults of the runs issued so far (the wave-specialised step kernel
  * bounds every intra-workgroup wait; a wait that runs out is recorded instead of hanging the GPU).
  * Returns MCPC_ESTATE if the last results must not be used.  The only call besides create/destroy that

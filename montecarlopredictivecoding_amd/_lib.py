@@ -122,6 +122,8 @@ SYMBOLS = {
     "mcpc_knn_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "mcpc_chain_energies": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_int32,
                                       C.c_void_p, C.c_int32, C.c_void_p]),
+    "mcpc_prediction_errors": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_int32,
+                                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "mcpc_query": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                              C.POINTER(C.c_int32)]),
     "mcpc_step_kernel_name": (C.c_char_p, [C.c_void_p]),

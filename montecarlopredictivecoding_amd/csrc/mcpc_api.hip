@@ -22,6 +22,7 @@
 #include "mcpc_knn.h"
 #include "mcpc_plan.h"
 #include "mcpc_chain_energy.h"
+#include "mcpc_pred_err.h"
 
 using namespace mcpc;
 
@@ -102,6 +103,11 @@ struct mcpc_engine : EnginePlan {
     int ce_njobs = 0, ce_nhead = 0;
     CeFinish ce_finish{};
     int ce_rows = 0;                // rows the scratch holds (a multiple of kLwChains)
+    // prediction errors (mcpc_pred_err.h) share that scratch; their job table is ce_table filtered to the Linears of the last call
+    std::vector<LwJob> ce_table;    // host copy of ce_jobs
+    LwJob* pe_jobs = nullptr;       // device copy of pe_job_table(ce_table, pe_want)
+    unsigned pe_want = 0;
+    int pe_njobs = 0;
     RunPlan run_plan;               // the schedule of the last mcpc_run (plan_run); kept for its storage: no allocation per run
     // diagnostics, host strings set while launching (no device work): what the last mcpc_run and each Linear's last flush launched
     std::string last_step;                       // mcpc_last_step_kernel_name
@@ -158,7 +164,7 @@ int free_all(mcpc_engine* e) {
     for (int l = 0; l < kMaxLatent; ++l) { F(e->lw_fx[l]); F(e->lw_err[l]); }
     F(e->lw_err_o); F(e->lw_jobs);
     for (int l = 0; l < kMaxLatent; ++l) { F(e->ce_x[l]); F(e->ce_fx[l]); }
-    F(e->ce_mu1); F(e->ce_part); F(e->ce_jobs);
+    F(e->ce_mu1); F(e->ce_part); F(e->ce_jobs); F(e->pe_jobs);
     for (auto& ln : e->lin) { F(ln.Wf); F(ln.Wb); F(ln.bias_pad); F(ln.G); F(ln.Gb); }
     for (auto& ev : e->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     for (int h = 0; h < kMaxRingParts; ++h) { if (e->ev_steps[h]) (void)hipEventDestroy(e->ev_steps[h]); if (e->ev_flush[h]) (void)hipEventDestroy(e->ev_flush[h]); e->ev_steps[h] = e->ev_flush[h] = nullptr; }
@@ -1602,6 +1608,35 @@ int mcpc_knn_accumulate(int device, const float* q, int64_t nq, const float* ref
     return MCPC_OK;
 }
 
+// The evaluator's job table, mu_1 buffer and scratch for chunks of `chunk` rows (shared by mcpc_chain_energies and mcpc_prediction_errors)
+static int ce_ensure_scratch(mcpc_engine* e, int chunk, hipStream_t stream) {
+    if (!e->ce_jobs) {
+        std::vector<LwJob>& jobs = e->ce_table;
+        ce_job_table(e->L, e->npad, e->has_head ? e->out_pad : 0, jobs, e->ce_nhead, e->ce_finish);
+        if (jobs.size() > 65535) return fail(MCPC_EINVAL, "chain energies: more than 65535 unit-tile jobs");
+        if (const int rc = upload(e->ce_jobs, jobs, "the chain-energy job table")) return rc;
+        e->ce_njobs = (int)jobs.size();
+        if (const int rc = dmalloc(e->ce_mu1, (size_t)e->Bpad * e->npad[0])) return rc;
+    }
+    if (chunk > e->ce_rows) {
+        for (int l = 0; l < e->L; ++l) {
+            if (e->ce_x[l]) retire(e, e->ce_x[l], stream);
+            if (e->ce_fx[l]) retire(e, e->ce_fx[l], stream);
+            e->ce_x[l] = e->ce_fx[l] = nullptr;
+        }
+        if (e->ce_part) retire(e, e->ce_part, stream);
+        e->ce_part = nullptr;
+        e->ce_rows = 0;
+        for (int l = 0; l < e->L; ++l) {
+            int rc;
+            if ((rc = dmalloc(e->ce_x[l], (size_t)chunk * e->npad[l])) || (rc = dmalloc(e->ce_fx[l], (size_t)chunk * e->npad[l]))) return rc;
+        }
+        if (const int rc = dmalloc(e->ce_part, (size_t)e->ce_njobs * chunk)) return rc;
+        e->ce_rows = chunk;
+    }
+    return MCPC_OK;
+}
+
 int mcpc_chain_energies(mcpc_engine* e, const float* inputs, const float* const* x_rec, int32_t n_rec, int32_t loss_kind, double loss_var,
                         int32_t mask_start, double* out, int32_t max_rows, void* stream_) {
     if (!e) return fail(MCPC_EINVAL, "chain energies: null engine");
@@ -1630,30 +1665,7 @@ int mcpc_chain_energies(mcpc_engine* e, const float* inputs, const float* const*
     // the chunk: a multiple of the 64-row tile, no longer than the call
     const int64_t want = max_rows > 0 ? max_rows : kCeDefaultRows;
     const int chunk = (int)(std::min<int64_t>((want + kLwChains - 1) / kLwChains, (R + kLwChains - 1) / kLwChains) * kLwChains);
-    if (!e->ce_jobs) {
-        std::vector<LwJob> jobs;
-        ce_job_table(e->L, e->npad, e->has_head ? e->out_pad : 0, jobs, e->ce_nhead, e->ce_finish);
-        if (jobs.size() > 65535) return fail(MCPC_EINVAL, "chain energies: more than 65535 unit-tile jobs");
-        if (const int rc = upload(e->ce_jobs, jobs, "the chain-energy job table")) return rc;
-        e->ce_njobs = (int)jobs.size();
-        if (const int rc = dmalloc(e->ce_mu1, (size_t)e->Bpad * e->npad[0])) return rc;
-    }
-    if (chunk > e->ce_rows) {
-        for (int l = 0; l < e->L; ++l) {
-            if (e->ce_x[l]) retire(e, e->ce_x[l], stream);
-            if (e->ce_fx[l]) retire(e, e->ce_fx[l], stream);
-            e->ce_x[l] = e->ce_fx[l] = nullptr;
-        }
-        if (e->ce_part) retire(e, e->ce_part, stream);
-        e->ce_part = nullptr;
-        e->ce_rows = 0;
-        for (int l = 0; l < e->L; ++l) {
-            int rc;
-            if ((rc = dmalloc(e->ce_x[l], (size_t)chunk * e->npad[l])) || (rc = dmalloc(e->ce_fx[l], (size_t)chunk * e->npad[l]))) return rc;
-        }
-        if (const int rc = dmalloc(e->ce_part, (size_t)e->ce_njobs * chunk)) return rc;
-        e->ce_rows = chunk;
-    }
+    if (const int rc = ce_ensure_scratch(e, chunk, stream)) return rc;
     free_completed_retired(e);
     // mu_1 of THESE inputs (the step kernels' own kernel: the same bits)
     {
@@ -1686,6 +1698,102 @@ int mcpc_chain_energies(mcpc_engine* e, const float* inputs, const float* const*
         hipLaunchKernelGGL(mcpc_ce_kernel, dim3(padded / kLwChains, njobs), dim3(kLwThreads), 0, stream, Q);
         hipLaunchKernelGGL(mcpc_ce_finish_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, (const double*)e->ce_part, out, e->ce_finish,
                            e->L, with_loss ? 1 : 0, rows, chunk, (size_t)r0);
+    }
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+int mcpc_prediction_errors(mcpc_engine* e, const float* inputs, const float* const* x_rec, int32_t n_rec, int32_t loss_kind, double loss_var,
+                           int32_t mask_start, float* const* err, float* const* pred, float* err_out, float* pred_out, int32_t max_rows,
+                           void* stream_) {
+    if (!e) return fail(MCPC_EINVAL, "prediction errors: null engine");
+    if (!x_rec) return fail(MCPC_EINVAL, "prediction errors: x_rec is null");
+    if (n_rec < 0) return fail(MCPC_EINVAL, "prediction errors: n_rec=%d, must not be negative", n_rec);
+    if (max_rows < 0) return fail(MCPC_EINVAL, "prediction errors: max_rows=%d, must not be negative (0 = default)", max_rows);
+    const int L = e->L;
+    // the Linears asked for (bit j; bit L = the read-out) and the latent layers their predictions read
+    unsigned want = 0;
+    for (int l = 0; l < L; ++l)
+        if ((err && err[l]) || (pred && pred[l])) want |= 1u << l;
+    if (err_out || pred_out) want |= 1u << L;
+    if (!want) return fail(MCPC_EINVAL, "prediction errors: nothing is asked for (every destination is null)");
+    if ((err_out || pred_out) && !e->has_head) return fail(MCPC_EINVAL, "prediction errors: err_out / pred_out need a read-out Linear (n_out > 0)");
+    if (loss_kind < 0 || loss_kind > 2) return fail(MCPC_EINVAL, "prediction errors: loss_kind=%d", loss_kind);
+    if (err_out && loss_kind == MCPC_LOSS_NONE) return fail(MCPC_EINVAL, "prediction errors: err_out needs a loss (loss_kind is MCPC_LOSS_NONE)");
+    if (err_out) {
+        if (loss_kind == MCPC_LOSS_GAUSSIAN && !(loss_var > 0.0)) return fail(MCPC_EINVAL, "prediction errors: loss_var must be positive");
+        if (mask_start < 0 || mask_start >= e->d.n_out)
+            return fail(MCPC_EINVAL, "prediction errors: mask_start=%d outside 0..%d", mask_start, e->d.n_out - 1);
+    }
+    const unsigned need = pe_layers_read(want, L);
+    for (int l = 0; l < L; ++l)
+        if (((need >> l) & 1u) && !x_rec[l]) return fail(MCPC_EINVAL, "prediction errors: x_rec[%d] is null", l);
+    const int nlin = L + (e->has_head ? 1 : 0);
+    for (int j = 0; j < nlin; ++j)
+        if (((want >> j) & 1u) && !e->lin[j].bound)
+            return fail(MCPC_ESTATE, "prediction errors: Linear %d has no bound parameters (mcpc_bind_params + mcpc_params_changed first)", j);
+    if (err_out && !e->target_bound) return fail(MCPC_ESTATE, "prediction errors: err_out requested but no target bound");
+    const int64_t R = (int64_t)n_rec * e->d.batch;
+    if (R == 0) return MCPC_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(e->d.device));
+    const int64_t want_rows = max_rows > 0 ? max_rows : kCeDefaultRows;
+    const int chunk = (int)(std::min<int64_t>((want_rows + kLwChains - 1) / kLwChains, (R + kLwChains - 1) / kLwChains) * kLwChains);
+    if (const int rc = ce_ensure_scratch(e, chunk, stream)) return rc;
+    if (want != e->pe_want) {
+        std::vector<LwJob> jobs;
+        pe_job_table(e->ce_table, want, jobs);
+        if (e->pe_jobs) retire(e, e->pe_jobs, stream);
+        e->pe_jobs = nullptr;
+        e->pe_want = 0;
+        if (const int rc = upload(e->pe_jobs, jobs, "the prediction-error job table")) return rc;
+        e->pe_want = want;
+        e->pe_njobs = (int)jobs.size();
+    }
+    free_completed_retired(e);
+    if (want & 1u) {            // mu_1 of THESE inputs (the step kernels' own kernel: the same bits)
+        const Lin& l0 = e->lin[0];
+        const size_t total = (size_t)e->Bpad * e->npad[0];
+        hipLaunchKernelGGL(mcpc_mu1_kernel, dim3(grid_for(total)), dim3(256), 0, stream, inputs, l0.W, l0.bias, e->ce_mu1,
+                           e->d.batch, e->d.n_in, e->d.sizes[0], e->Bpad, e->npad[0]);
+    }
+    PeParams P{};
+    CeParams& Q = P.ce;
+    for (int l = 0; l < L; ++l) { Q.x[l] = e->ce_x[l]; Q.fx[l] = e->ce_fx[l]; Q.npad[l] = e->npad[l]; Q.ecoef[l] = e->d.ecoef[l]; P.n[l] = e->d.sizes[l]; }
+    for (int j = 1; j < nlin; ++j) { Q.Wf[j] = e->lin[j].Wf; Q.bias[j] = e->lin[j].bias_pad; }
+    Q.npad[L] = e->has_head ? e->out_pad : 0;
+    P.n[L] = e->d.n_out;
+    Q.mu1 = e->ce_mu1; Q.y = e->ypad; Q.wexp = e->wexp; Q.jobs = e->pe_jobs;
+    Q.L = L; Q.B = e->d.batch; Q.n_out = e->d.n_out; Q.chunk = chunk;
+    Q.loss_kind = err_out ? loss_kind : MCPC_LOSS_NONE; Q.mask_start = err_out ? mask_start : 0;
+    Q.inv_var = loss_kind == MCPC_LOSS_GAUSSIAN ? (float)(1.0 / loss_var) : 1.0f;
+    // 16-byte stores where every row of a destination starts on a 16-byte boundary
+    auto vec_ok = [](const float* p, int n) { return p && n % 4 == 0 && ((uintptr_t)p & 15u) == 0; };
+    for (int j = 0; j <= L; ++j) {
+        const float* const ep = j < L ? (err ? err[j] : nullptr) : err_out;
+        const float* const pp = j < L ? (pred ? pred[j] : nullptr) : pred_out;
+        if (vec_ok(ep, P.n[j])) P.vec_err |= 1u << j;
+        if (vec_ok(pp, P.n[j])) P.vec_pred |= 1u << j;
+    }
+    for (int64_t r0 = 0; r0 < R; r0 += chunk) {
+        const int rows = (int)std::min<int64_t>(chunk, R - r0);
+        const int padded = (rows + kLwChains - 1) / kLwChains * kLwChains;          // tiles of this chunk that hold a row
+        for (int l = 0; l < L; ++l) {
+            if (!((need >> l) & 1u)) continue;
+            const size_t total4 = (size_t)padded * e->npad[l] / 4;
+            hipLaunchKernelGGL(mcpc_ce_prep_kernel, dim3(grid_for(total4)), dim3(256), 0, stream, x_rec[l] + (size_t)r0 * e->d.sizes[l],
+                               e->ce_x[l], e->ce_fx[l], rows, padded, e->d.sizes[l], e->npad[l], e->d.acts[l]);
+        }
+        // (a chunk starts at a multiple of kLwChains rows: r0 * n_l floats keeps the 16-byte alignment where n_l % 4 == 0)
+        for (int j = 0; j <= L; ++j) {
+            float* const ep = j < L ? (err ? err[j] : nullptr) : err_out;
+            float* const pp = j < L ? (pred ? pred[j] : nullptr) : pred_out;
+            P.err[j] = ep ? ep + (size_t)r0 * P.n[j] : nullptr;
+            P.pred[j] = pp ? pp + (size_t)r0 * P.n[j] : nullptr;
+        }
+        Q.rows = rows;
+        Q.row_base = (int)(r0 % e->d.batch);
+        hipLaunchKernelGGL(mcpc_pe_kernel, dim3(padded / kLwChains, e->pe_njobs), dim3(kLwThreads), 0, stream, P);
     }
     HIP_TRY(hipGetLastError());
     return MCPC_OK;

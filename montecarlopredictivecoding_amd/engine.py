@@ -241,6 +241,64 @@ class Engine:
                                               int(max_rows), self._stream()))
         return out
 
+    def prediction_errors(self, inputs: Optional[torch.Tensor], x_rec: Sequence[Optional[torch.Tensor]], *, layers=None, quantity="error",
+                          outputs=None, loss_kind=L.LOSS_NONE, loss_var=1.0, mask_start=0, out: Optional[dict] = None,
+                          max_rows: int = 0) -> dict:
+        """Prediction errors ``x_l - mu_l`` and/or predictions ``mu_l`` of recorded states, per unit, as derived records (include/mcpc.h:
+        mcpc_prediction_errors).
+
+        ``x_rec`` / ``inputs`` / ``max_rows`` as in ``chain_energies``; an entry of ``x_rec`` may be None for a layer the evaluation
+        does not read (it reads a requested layer and the one below it; the last layer for the read-out).  ``layers``: latent layer
+        indices (None = all); ``quantity``: "error", "prediction" or "both"; ``outputs``: None, "error" (the read-out error the step
+        kernels propagate, under ``loss_kind`` / ``loss_var`` / ``mask_start`` and the bound target), "prediction" (the logits) or
+        "both".  Returns (or fills the tensors of ``out``, a dict by the same names) contiguous fp32 ``[n_rec, batch, n_l]`` tensors by
+        name: "e<l>" / "mu<l>", "eout" / "out" -- the layout of a record, so ``moments_accumulate``, ``cov_accumulate``,
+        ``hist_accumulate``, ``acov_accumulate`` and ``roll_accumulate`` take them as they take one.  On the current torch stream."""
+        if len(x_rec) != self.L:
+            raise ValueError(f"x_rec: expected one entry per latent layer ({self.L}), got {len(x_rec)}")
+        if quantity not in ("error", "prediction", "both"):
+            raise ValueError(f"quantity={quantity!r}, expected 'error', 'prediction' or 'both'")
+        if outputs not in (None, "error", "prediction", "both"):
+            raise ValueError(f"outputs={outputs!r}, expected None, 'error', 'prediction' or 'both'")
+        layers = tuple(range(self.L)) if layers is None else tuple(sorted(set(int(l) for l in layers)))
+        for l in layers:
+            if not 0 <= l < self.L:
+                raise ValueError(f"layer index {l} out of range 0..{self.L - 1}")
+        if inputs is not None:
+            _check_tensor(inputs, (self.batch, self.n_in), self.device, "inputs")
+        given = [t for t in x_rec if t is not None]
+        if not given:
+            raise ValueError("x_rec: every entry is None")
+        n_rec = 1 if given[0].dim() == 2 else int(given[0].shape[0])
+        arr = (C.c_void_p * self.L)()
+        for l, t in enumerate(x_rec):
+            if t is None:
+                continue
+            shape = (self.batch, self.sizes[l]) if t.dim() == 2 else (n_rec, self.batch, self.sizes[l])
+            _check_tensor(t, shape, self.device, f"x_rec[{l}]")
+            arr[l] = t.data_ptr()
+        res = {}
+
+        def dest(name, n):
+            if out is not None and name in out:
+                _check_tensor(out[name], (n_rec, self.batch, n), self.device, f"out[{name!r}]")
+                res[name] = out[name]
+            else:
+                res[name] = torch.empty(n_rec, self.batch, n, dtype=torch.float32, device=self.device)
+            return res[name].data_ptr()
+        err = (C.c_void_p * self.L)()
+        pred = (C.c_void_p * self.L)()
+        for l in layers:
+            if quantity in ("error", "both"):
+                err[l] = dest(f"e{l}", self.sizes[l])
+            if quantity in ("prediction", "both"):
+                pred[l] = dest(f"mu{l}", self.sizes[l])
+        err_out = dest("eout", self.n_out) if outputs in ("error", "both") else None
+        pred_out = dest("out", self.n_out) if outputs in ("prediction", "both") else None
+        L.check(self._lib.mcpc_prediction_errors(self._h, _ptr(inputs), arr, n_rec, loss_kind, loss_var, mask_start, err, pred, err_out,
+                                                 pred_out, int(max_rows), self._stream()))
+        return res
+
     # ---- parameter gradients ---------------------------------------------------------------------
     def read_param_grads(self, j: int, dW: torch.Tensor, db: Optional[torch.Tensor], scale=1.0, accumulate=False):
         n_out, n_in = self.lin_shape(j)

@@ -289,6 +289,16 @@ class PCTrainer(object):
         self.mcpc_rolling = None
         self.mcpc_last_rolling = None
         self.mcpc_rolling_max_bytes = 2 << 30
+        # posterior moments (and covariances) of the ERROR UNITS eps_l = x_l - mu_l or the PREDICTIONS mu_l of a fused call (errors.py):
+        # None = off, or dict(begin=0, stride=1, layers=(), quantity="error" | "prediction", outputs=None | "error" | "prediction",
+        # variance=True, covariance=None | "chain" | "chains").  The requested layers and the layers their predictions read go through
+        # the same ring; after each slice Engine.prediction_errors evaluates the slice's samples into derived records on the device and
+        # moments_accumulate / cov_accumulate reduce those.  The result is an errors.Errors in mcpc_last_errors; composes with the other
+        # eight.  A request whose derived buffers, sums and covariance result would take more than mcpc_errors_max_bytes is a
+        # ValueError before anything runs.
+        self.mcpc_errors = None
+        self.mcpc_last_errors = None
+        self.mcpc_errors_max_bytes = 2 << 30
 
     # ---- getters & setters (reference :268-461) -------------------------------------------------------
     def get_T(self) -> int:
@@ -558,6 +568,14 @@ class PCTrainer(object):
                                           "variability is accumulated by the fused HIP loop only".format(why_not_fused))
             plan["rolling"] = _rolling.validate_spec(self.mcpc_rolling, self._T, len(plan["net"].sizes), plan["net"].n_out,
                                                      plan["net"].sizes, plan["B"], self.mcpc_rolling_max_bytes)
+        if self.mcpc_errors is not None:
+            from .. import errors as _errors
+            if plan is None:
+                raise NotImplementedError("mcpc_errors is set, and this call runs on the generic torch loop ({}): prediction errors "
+                                          "are evaluated out of the fused HIP loop's record ring only".format(why_not_fused))
+            plan["errors"] = _errors.validate_spec(self.mcpc_errors, self._T, len(plan["net"].sizes), plan["net"].n_out,
+                                                   plan["net"].sizes, plan["B"], plan["loss"].kind != L.LOSS_NONE,
+                                                   self.mcpc_errors_max_bytes)
         if plan is None:
             # outside what the kernels express: the package's generic torch loop (generic_loop.py), loudly, on the device the model
             # lives on ("must work, need not be fast").  It is no way around a missing GPU: without a visible HIP device
@@ -616,6 +634,9 @@ class PCTrainer(object):
         if plan["mode"] != "fused" and self.mcpc_rolling is not None:
             raise NotImplementedError("mcpc_rolling is set, and this call runs step by step ({}): the rolling variability is "
                                       "accumulated by the fused HIP loop only".format(plan["why_stepwise"]))
+        if plan["mode"] != "fused" and self.mcpc_errors is not None:
+            raise NotImplementedError("mcpc_errors is set, and this call runs step by step ({}): prediction errors are evaluated "
+                                      "out of the fused HIP loop's record ring only".format(plan["why_stepwise"]))
         if plan["mode"] == "fused":
             self.last_call_mode = "fused"
             with _few_cpu_threads(plan["staged"]):
@@ -948,15 +969,16 @@ class PCTrainer(object):
         self.last_record_slices = 0
         mom, ce, cov, hist = plan.get("moments"), plan.get("chain_energies"), plan.get("covariance"), plan.get("histogram")
         acov, probe, cloud, roll = plan.get("autocovariance"), plan.get("probe"), plan.get("cloud"), plan.get("rolling")
+        perr = plan.get("errors")
         if (mom is not None or ce is not None or cov is not None or hist is not None or acov is not None or probe is not None
-                or cloud is not None or roll is not None):
-            # posterior moments / per-chain energies / covariances / histograms / autocovariances / a probe / a cloud: the call runs
-            # as slices whatever its size, and the records they ask for are reduced on the device
+                or cloud is not None or roll is not None or perr is not None):
+            # posterior moments / per-chain energies / covariances / histograms / autocovariances / a probe / a cloud / prediction
+            # errors: the call runs as slices whatever its size, and the records they ask for are reduced on the device
             ce_inputs = None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous())
             res, last_mom, last_ce = self._run_fused_sliced(
                 eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, is_return_outputs and net.n_out > 0,
                 every_t=is_return_results_every_t, mom=mom, ce=ce, ce_inputs=ce_inputs, cov=cov, hist=hist, acov=acov, probe=probe,
-                cloud=cloud, roll=roll)
+                cloud=cloud, roll=roll, perr=perr)
             if mom is not None:
                 self.mcpc_last_moments = last_mom
             if ce is not None:
@@ -989,7 +1011,7 @@ class PCTrainer(object):
                                      is_return_representations, is_return_xs, loss_fn)
 
     def _run_fused_sliced(self, eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, rec_out, every_t=True, mom=None,
-                          ce=None, ce_inputs=None, cov=None, hist=None, acov=None, probe=None, cloud=None, roll=None):
+                          ce=None, ce_inputs=None, cov=None, hist=None, acov=None, probe=None, cloud=None, roll=None, perr=None):
         """A call whose every-step trajectory would not fit the record budget on the device, or whose records feed `mcpc_moments`:
         the same T steps as slices of one `mcpc_run` each (slicing does not change a bit of the trajectories,
         tests/test_gpu_fullsize.py).  The latent records of a slice go to one half of a two-buffer device ring.  Records the caller's
@@ -1014,7 +1036,11 @@ class PCTrainer(object):
         engine's device.  With `roll` (a validated `mcpc_rolling`) its layers and read-out go through the ring likewise and
         `roll_accumulate` feeds each block's samples to its rolling variance after each slice, in step order, on the call's own stream;
         the samples seen and the rows emitted so far are counted per block, and the kernel's own history carries a window across
-        slices (and, with `carry=`, across calls); the result is left in `mcpc_last_rolling`.  Returns (RunResult, Moments or None, ChainEnergies or None)."""
+        slices (and, with `carry=`, across calls); the result is left in `mcpc_last_rolling`.  With `perr` (a validated `mcpc_errors`)
+        its layers and the layers their predictions read go through the ring too; after each slice the slice's samples (gathered first
+        when the stride is above 1) are evaluated by `Engine.prediction_errors` into one set of derived buffers on the call's own
+        stream, and `moments_accumulate` / `cov_accumulate` reduce those under the slicing rules of `mom`; the result is left in
+        `mcpc_last_errors`.  Returns (RunResult, Moments or None, ChainEnergies or None)."""
         from ..engine import (RunResult, moments_accumulate, cov_accumulate, cov_workspace_bytes, hist_accumulate, acov_accumulate,
                               probe_accumulate, roll_accumulate, roll_workspace_bytes)
         dev, B = plan["device"], plan["B"]
@@ -1031,11 +1057,12 @@ class PCTrainer(object):
         cloud_layers = [cloud is not None and l == cloud.layer for l in range(nl)]
         roll_layers = [roll is not None and l in roll.layers for l in range(nl)]
         roll_out = roll is not None and roll.outputs is not None
-        ring_layers = [a or b_ or c_ or d_ or e_ or f_ or g_ or h_ or ce is not None
-                       for a, b_, c_, d_, e_, f_, g_, h_ in zip(rec_layers, mom_layers, cov_layers, hist_layers, acov_layers,
-                                                                probe_layers, cloud_layers, roll_layers)]
+        perr_layers = [perr is not None and l in perr.reads for l in range(nl)]
+        ring_layers = [a or b_ or c_ or d_ or e_ or f_ or g_ or h_ or i_ or ce is not None
+                       for a, b_, c_, d_, e_, f_, g_, h_, i_ in zip(rec_layers, mom_layers, cov_layers, hist_layers, acov_layers,
+                                                                    probe_layers, cloud_layers, roll_layers, perr_layers)]
         reduced = (mom is not None or ce is not None or cov is not None or hist is not None or acov is not None or probe is not None
-                   or cloud is not None or roll is not None)
+                   or cloud is not None or roll is not None or perr is not None)
         out_direct = rec_out and every_t                     # every step's outputs are kept anyway: slices write them in place
         ring_out = (rec_out or mom_out or cov_out or hist_out or acov_out or roll_out) and not out_direct
         S = T
@@ -1044,6 +1071,8 @@ class PCTrainer(object):
         if reduced:
             # one half of the ring is a chunk of at most mcpc_moments_chunk_bytes
             step_bytes = 4 * B * (sum(n for n, on in zip(net.sizes, ring_layers) if on) + (net.n_out if ring_out or mom_out or cov_out or hist_out or acov_out or roll_out else 0))
+            if perr is not None:
+                step_bytes += -(-4 * B * perr.D // perr.stride)          # the derived records of a step's share of the samples
             S = min(S, self.mcpc_moments_chunk_bytes // max(step_bytes, 1))
         S = max(1, S)
         # A slice boundary inside the window that accumulates parameter gradients would regroup their fp32 sums (one Hebbian flush and
@@ -1058,6 +1087,9 @@ class PCTrainer(object):
             bounds.append((t0, n))
             t0 += n
         S = max(n for _, n in bounds)
+        if perr is not None:
+            from ..errors import check_bytes as perr_check_bytes
+            perr_check_bytes(perr, B, perr.max_samples(S), self.mcpc_errors_max_bytes)
         rows = T if every_t else 1
         host = [torch.empty(rows, B, n, dtype=torch.float32, pin_memory=True) if on else None for n, on in zip(net.sizes, rec_layers)]
         ring = [[torch.empty(S, B, n, dtype=torch.float32, device=dev) if on else None for n, on in zip(net.sizes, ring_layers)]
@@ -1223,6 +1255,34 @@ class PCTrainer(object):
                     row = first + k * ce.stride
                     eng.chain_energies(ce_inputs, [r_[row:row + 1] for r_ in ring[half]], out=ce_table[k0 + k:k0 + k + 1], **ce_kw)
 
+        perr_bufs = perr_sum = perr_sumsq = perr_outer = perr_ws = None
+        if perr is not None:
+            perr_rows = perr.max_samples(S)
+            perr_bufs = {name: torch.empty(perr_rows, B, w, dtype=torch.float32, device=dev) for name, _, w in perr.columns}
+            perr_sum = {name: torch.zeros(B, w, dtype=torch.float64, device=dev) for name, _, w in perr.columns}
+            perr_sumsq = {name: torch.zeros(B, w, dtype=torch.float64, device=dev) if perr.variance else None
+                          for name, _, w in perr.columns}
+            if perr.covariance is not None:
+                D = perr.D
+                perr_outer = torch.zeros(*((D, D) if perr.pooled else (B, D, D)), dtype=torch.float64, device=dev)
+                if perr.pooled:
+                    perr_ws = torch.empty(max(cov_workspace_bytes(B, [w for _, _, w in perr.columns]), 8), dtype=torch.uint8, device=dev)
+            perr_kw = dict(layers=perr.layers, quantity=perr.quantity, outputs=perr.outputs, loss_kind=run_kw["loss_kind"],
+                           loss_var=run_kw["loss_var"], mask_start=run_kw["mask_start"], max_rows=self.mcpc_chain_energies_max_rows)
+
+        def reduce_perr(t0, n, half):
+            first, cnt = perr.chunk(t0, n)
+            if cnt == 0:
+                return
+            # the slice's samples alone (a copy when the stride skips steps): the derived buffers hold samples only
+            stop = first + (cnt - 1) * perr.stride + 1
+            recs = [ring[half][l][first:stop:perr.stride].contiguous() if on else None for l, on in enumerate(perr_layers)]
+            eng.prediction_errors(ce_inputs, recs, out={name: buf[:cnt] for name, buf in perr_bufs.items()}, **perr_kw)
+            for name, buf in perr_bufs.items():
+                moments_accumulate(buf, 0, 1, cnt, perr_sum[name], perr_sumsq[name], accumulate=True)
+            if perr_outer is not None:
+                cov_accumulate(list(perr_bufs.values()), 0, 1, cnt, perr_outer, pool=perr.pooled, accumulate=True, workspace=perr_ws)
+
         n_slices = 0
         for t0, n in bounds:
             half = n_slices & 1
@@ -1250,6 +1310,8 @@ class PCTrainer(object):
                 gather_cloud(t0, n, half)
             if roll is not None:
                 reduce_roll(t0, n, half)
+            if perr is not None:
+                reduce_perr(t0, n, half)
             if ring_out and rec_out and last:
                 out_full[0].copy_(ring_o[half][n - 1])       # (not every_t: the last step's outputs)
             to_host = any(rec_layers) and (every_t or last)
@@ -1309,6 +1371,18 @@ class PCTrainer(object):
             for st in roll_state:
                 del st["row"]
             self.mcpc_last_rolling = roll_from_state(roll, B, roll_state, roll_pooled, roll_elem, plan["model_device"])
+        if perr is not None:
+            from ..covariance import Covariance as _Covariance
+            from ..errors import Errors
+            md = plan["model_device"]
+            pcov = None
+            if perr_outer is not None:
+                s = torch.cat([perr_sum[name] for name, _, _ in perr.columns], dim=1)
+                if perr.pooled:
+                    s = s.sum(dim=0)
+                pcov = _Covariance(n=perr.n, B=B, pooled=perr.pooled, columns=list(perr.columns), sum=s.to(md), outer=perr_outer.to(md))
+            self.mcpc_last_errors = Errors(n=perr.n, sum={k: v.to(md) for k, v in perr_sum.items()},
+                                           sumsq={k: None if v is None else v.to(md) for k, v in perr_sumsq.items()}, covariance=pcov)
         return RunResult(energies=energies, rec_x=host, rec_out=out_full), result, ce_result
 
     def mcpc_state_energies(self, inputs, loss_fn: typing.Callable = None, loss_fn_kwargs: dict = {}):
@@ -1342,6 +1416,39 @@ class PCTrainer(object):
                                        max_rows=self.mcpc_chain_energies_max_rows)
             eng.sync_check()
         return from_table(table, len(net.sizes), self._energy_coefficient, [], plan["model_device"])
+
+    def mcpc_state_errors(self, inputs, loss_fn: typing.Callable = None, loss_fn_kwargs: dict = {}, layers=None, quantity="error",
+                          outputs=None):
+        """Prediction errors ``x_l - mu_l`` and/or predictions ``mu_l`` of every chain for the CURRENT x of the PCLayers, per unit,
+        evaluated on the device (Engine.prediction_errors with one record; no step is run, no state or gradient changes).  ``layers``
+        (None = all), ``quantity`` and ``outputs`` as in Engine.prediction_errors.  Returns a dict of fp32 ``[B, n_l]`` tensors on the
+        model's device by name: "e<l>" / "mu<l>", "eout" / "out".  ``inputs``, ``loss_fn`` and ``loss_fn_kwargs`` as in
+        train_on_batch; a model or loss the fused loop does not express raises NotImplementedError."""
+        plan, why = self._plan(inputs, loss_fn, loss_fn_kwargs, False, False, None, None, {}, {}, False, False)
+        if plan is None:
+            raise NotImplementedError("mcpc_state_errors: outside what the HIP engine expresses ({})".format(why))
+        net, loss = plan["net"], plan["loss"]
+        xs = []
+        for l, layer in enumerate(net.pc_layers):
+            x = layer.get_x()
+            if x is None or tuple(x.shape) != (plan["B"], net.sizes[l]) or x.dtype != torch.float32:
+                raise RuntimeError("mcpc_state_errors: PCLayer {} holds no float32 x of shape {}; run a call first".format(
+                    l, (plan["B"], net.sizes[l])))
+            xs.append(x)
+        eng = self._engine_for(plan)
+        with _few_cpu_threads(plan["staged"]):
+            self._sync_params(eng, net, plan=plan)
+            if loss.target is not None:
+                tgt = loss.target
+                if tgt.dtype != torch.float32 or not tgt.is_contiguous() or tgt.device != plan["device"]:
+                    tgt = tgt.to(device=plan["device"], dtype=torch.float32).contiguous()
+                eng.bind_target(tgt)
+            res = eng.prediction_errors(None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous()),
+                                        [self._on_engine(plan, x.data.contiguous()) for x in xs], layers=layers, quantity=quantity,
+                                        outputs=outputs, loss_kind=loss.kind, loss_var=loss.var, mask_start=loss.mask_start,
+                                        max_rows=self.mcpc_chain_energies_max_rows)
+            eng.sync_check()
+        return {k: v[0].to(plan["model_device"]) for k, v in res.items()}
 
     def mcpc_state_probe(self, spec):
         """The probe of ``spec`` (a dict as ``mcpc_probe`` takes; ``begin`` and ``stride`` are not consulted) on the CURRENT x of its

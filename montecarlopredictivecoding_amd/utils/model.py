@@ -237,6 +237,46 @@ def get_posterior_covariance(gen_pc, config, trainers, loader, layers=(0,), pool
     return torch.cat(means, dim=0), torch.cat(covs, dim=0), torch.cat(labels, dim=0)
 
 
+def get_posterior_error_statistics(gen_pc, config, trainers, loader, layers=(0,), quantity="error", outputs=None):
+    """Posterior means, variances and rms of the error units ``eps_l = x_l - mu_l`` (``quantity="error"``) or of the predictions
+    ``mu_l`` (``"prediction"``), per batch of ``loader``: MAP call with ``trainers[0]``, then an MCPC call with ``trainers[1]`` started
+    from the MAP state (the protocol of ``get_posterior_covariance``), over the steps from ``config["mixing"]`` on, evaluated and
+    accumulated on the device by the call itself (``PCTrainer.mcpc_errors``): no trajectory is recorded and no forward pass is
+    replayed.  ``layers``: the PC layers asked for; ``outputs``: None, "error" or "prediction" for the read-out.  Returns ``(means,
+    variances, rms, labels)``: three dicts by block name ("e0".. / "mu0".., "eout" / "out") of fp64 ``[N, n_l]`` over all data in the
+    loader's order, and the labels ``[N]``."""
+    if len(trainers) != 2:
+        raise NotImplementedError
+    device = next(gen_pc.parameters()).device
+    input_size = len(gen_pc[0].bias)
+    pc_trainer, mcpc_trainer = trainers
+    means, variances, rms, labels = {}, {}, {}, []
+    saved = mcpc_trainer.mcpc_errors
+    mcpc_trainer.mcpc_errors = dict(begin=int(config["mixing"]), stride=1, layers=tuple(layers), quantity=quantity, outputs=outputs)
+    try:
+        for data, label in loader:
+            pseudo_input = torch.zeros(data.shape[0], input_size, device=device)
+            data, label = data.to(device), label.to(device)
+            kw = dict(inputs=pseudo_input, loss_fn=config["loss_fn"],
+                      loss_fn_kwargs={"_target": data, "_var": config["input_var"]},
+                      is_log_progress=False, is_return_results_every_t=False, is_checking_after_callback_after_t=False)
+            pc_trainer.train_on_batch(**kw)
+            mcpc_trainer.train_on_batch(callback_after_t=random_step, callback_after_t_kwargs={"_pc_trainer": mcpc_trainer},
+                                        is_sample_x_at_batch_start=False, **kw)
+            e = mcpc_trainer.mcpc_last_errors
+            for name in e.names:
+                means.setdefault(name, []).append(e.mean(name))
+                variances.setdefault(name, []).append(e.var(name, ddof=1))
+                rms.setdefault(name, []).append(e.rms(name))
+            labels.append(label)
+    finally:
+        mcpc_trainer.mcpc_errors = saved
+
+    def cat(d):
+        return {k: torch.cat(v, dim=0) for k, v in d.items()}
+    return cat(means), cat(variances), cat(rms), torch.cat(labels, dim=0)
+
+
 def get_posterior_histogram(gen_pc, config, trainers, loader, layers=(0,), bins=50, range=None, pool=None):
     """Posterior histograms of the latent units, per batch of ``loader``: MAP call with ``trainers[0]``, then an MCPC call with
     ``trainers[1]`` started from the MAP state (the protocol of ``get_posterior_covariance``), over the steps from ``config["mixing"]``
