@@ -21,7 +21,8 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from .covariance import human_bytes, sample_steps
+from .sampling import (SampleWindow, column_list, human_bytes, parse_keys, parse_layers, parse_outputs, parse_window,  # noqa: F401
+                       require_columns, sample_steps)
 
 _KEYS = ("begin", "stride", "layers", "outputs", "max_lag")
 _OUTPUTS = (None, "identity", "sigmoid")
@@ -29,25 +30,12 @@ MAX_LAG = 64                                     # include/mcpc.h: MCPC_ACOV_MAX
 
 
 @dataclass(frozen=True, eq=False)
-class AutocovarianceSpec:
+class AutocovarianceSpec(SampleWindow):
     """A validated ``mcpc_autocovariance`` request for a call of ``T`` steps."""
-    begin: int
-    stride: int
     layers: Tuple[int, ...]
     outputs: Optional[str]
     max_lag: int
-    T: int
     columns: Tuple[Tuple[str, int], ...]            # (name, width) of every block, in order: "x0", "x1", ..., "out"
-
-    @property
-    def n(self) -> int:
-        return len(sample_steps(self.begin, self.T, self.stride))
-
-    def chunk(self, t0: int, n_steps: int):
-        """(first, count): the samples among steps t0 .. t0 + n_steps - 1 are rows first, first + stride, ... of a chunk that holds
-        one record per step from t0 on."""
-        f = self.begin if t0 <= self.begin else self.begin + -(-(t0 - self.begin) // self.stride) * self.stride
-        return f - t0, len(range(f, min(t0 + n_steps, self.T), self.stride))
 
 
 def state_bytes(columns, B: int, max_lag: int) -> int:
@@ -59,40 +47,11 @@ def validate_spec(spec, T: int, n_layers: int, n_out: int, sizes, B: int, max_by
     """``PCTrainer.mcpc_autocovariance`` -> AutocovarianceSpec, or ValueError: not a dict, unknown keys, ``begin`` outside [0, T),
     ``stride`` < 1, a layer index out of range, no column at all, ``outputs`` on a model without a read-out, no ``max_lag`` or one
     outside 0..64, a state larger than ``max_bytes``.  Defaults: begin=0, stride=1, layers=(), outputs=None."""
-    if not isinstance(spec, dict):
-        raise ValueError(f"mcpc_autocovariance: expected a dict or None, got {type(spec).__name__}")
-    unknown = sorted(k for k in spec if k not in _KEYS)
-    if unknown:
-        raise ValueError(f"mcpc_autocovariance: unknown keys {unknown}; known: {list(_KEYS)}")
-    begin, stride = spec.get("begin", 0), spec.get("stride", 1)
-    for name, v in (("begin", begin), ("stride", stride)):
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise ValueError(f"mcpc_autocovariance: {name} must be an int, got {v!r}")
-    if not 0 <= begin < T:
-        raise ValueError(f"mcpc_autocovariance: begin={begin} outside [0, T={T})")
-    if stride < 1:
-        raise ValueError(f"mcpc_autocovariance: stride={stride}, must be at least 1")
-    layers = spec.get("layers", ())
-    if layers is None:
-        layers = ()
-    if isinstance(layers, int) and not isinstance(layers, bool):
-        layers = (layers,)
-    try:
-        layers = tuple(layers)
-    except TypeError:
-        raise ValueError(f"mcpc_autocovariance: layers must be a sequence of layer indices, got {layers!r}") from None
-    for l in layers:
-        if isinstance(l, bool) or not isinstance(l, int) or not 0 <= l < n_layers:
-            raise ValueError(f"mcpc_autocovariance: layer index {l!r} out of range, the model has {n_layers} PC layers "
-                             f"(0..{n_layers - 1})")
-    layers = tuple(sorted(set(layers)))
-    outputs = spec.get("outputs", None)
-    if outputs not in _OUTPUTS:
-        raise ValueError(f"mcpc_autocovariance: outputs={outputs!r}, expected None, 'identity' or 'sigmoid'")
-    if outputs is not None and n_out < 1:
-        raise ValueError("mcpc_autocovariance: outputs asked of a model without a read-out (it ends with a PCLayer)")
-    if not layers and outputs is None:
-        raise ValueError("mcpc_autocovariance: no columns: layers is empty and outputs is None")
+    parse_keys("mcpc_autocovariance", spec, _KEYS)
+    begin, stride = parse_window("mcpc_autocovariance", spec, T)
+    layers = parse_layers("mcpc_autocovariance", spec, n_layers, none_means="empty")
+    outputs = parse_outputs("mcpc_autocovariance", spec, n_out, _OUTPUTS)
+    require_columns("mcpc_autocovariance", layers, outputs)
     if "max_lag" not in spec or spec["max_lag"] is None:
         raise ValueError(f"mcpc_autocovariance: max_lag is required: the largest lag kept, an int in 0..{MAX_LAG}")
     max_lag = spec["max_lag"]
@@ -100,13 +59,13 @@ def validate_spec(spec, T: int, n_layers: int, n_out: int, sizes, B: int, max_by
         raise ValueError(f"mcpc_autocovariance: max_lag must be an int, got {max_lag!r}")
     if not 0 <= max_lag <= MAX_LAG:
         raise ValueError(f"mcpc_autocovariance: max_lag={max_lag} outside 0..{MAX_LAG}")
-    columns = [(f"x{l}", int(sizes[l])) for l in layers] + ([("out", int(n_out))] if outputs is not None else [])
+    columns = column_list(layers, sizes, None if outputs is None else "out", n_out)
     need = state_bytes(columns, B, max_lag)
     if need > max_bytes:
         raise ValueError(f"mcpc_autocovariance: the state ({B} chains x {sum(w for _, w in columns)} units x {max_lag + 1} lags in fp64, "
                          f"and the first and last {max_lag} samples) takes {human_bytes(need)}, more than "
                          f"mcpc_autocovariance_max_bytes = {human_bytes(max_bytes)}: ask for fewer layers or fewer lags")
-    return AutocovarianceSpec(begin=begin, stride=stride, layers=layers, outputs=outputs, max_lag=max_lag, T=T, columns=tuple(columns))
+    return AutocovarianceSpec(begin=begin, stride=stride, layers=layers, outputs=outputs, max_lag=max_lag, T=T, columns=columns)
 
 
 def geyer(rho: torch.Tensor, n: int):

@@ -11,52 +11,21 @@ from typing import List
 
 import torch
 
+from .sampling import SampleWindow, parse_keys, parse_window, sample_steps  # noqa: F401
+
 _KEYS = ("begin", "stride")
 
 
-def sample_steps(begin: int, T: int, stride: int) -> range:
-    """The steps of a call of T steps whose states are evaluated."""
-    return range(begin, T, stride)
-
-
 @dataclass(frozen=True)
-class ChainEnergySpec:
-    """A validated ``mcpc_chain_energies`` request for a call of ``T`` steps."""
-    begin: int
-    stride: int
-    T: int
-
-    @property
-    def steps(self) -> List[int]:
-        return list(sample_steps(self.begin, self.T, self.stride))
-
-    @property
-    def n(self) -> int:
-        return len(sample_steps(self.begin, self.T, self.stride))
-
-    def chunk(self, t0: int, n_steps: int):
-        """(first, count): the evaluated steps among t0 .. t0 + n_steps - 1 are rows first, first + stride, ... of a chunk that holds
-        one record per step from t0 on."""
-        f = self.begin if t0 <= self.begin else self.begin + -(-(t0 - self.begin) // self.stride) * self.stride
-        return f - t0, len(range(f, min(t0 + n_steps, self.T), self.stride))
+class ChainEnergySpec(SampleWindow):
+    """A validated ``mcpc_chain_energies`` request for a call of ``T`` steps: the samples are the steps whose states are evaluated."""
 
 
 def validate_spec(spec, T: int) -> ChainEnergySpec:
     """``PCTrainer.mcpc_chain_energies`` -> ChainEnergySpec, or ValueError: not a dict, unknown keys, ``begin`` outside [0, T),
     ``stride`` < 1.  Defaults: begin=0, stride=1."""
-    if not isinstance(spec, dict):
-        raise ValueError(f"mcpc_chain_energies: expected a dict or None, got {type(spec).__name__}")
-    unknown = sorted(k for k in spec if k not in _KEYS)
-    if unknown:
-        raise ValueError(f"mcpc_chain_energies: unknown keys {unknown}; known: {list(_KEYS)}")
-    begin, stride = spec.get("begin", 0), spec.get("stride", 1)
-    for name, v in (("begin", begin), ("stride", stride)):
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise ValueError(f"mcpc_chain_energies: {name} must be an int, got {v!r}")
-    if not 0 <= begin < T:
-        raise ValueError(f"mcpc_chain_energies: begin={begin} outside [0, T={T})")
-    if stride < 1:
-        raise ValueError(f"mcpc_chain_energies: stride={stride}, must be at least 1")
+    parse_keys("mcpc_chain_energies", spec, _KEYS)
+    begin, stride = parse_window("mcpc_chain_energies", spec, T)
     return ChainEnergySpec(begin=begin, stride=stride, T=T)
 
 

@@ -18,7 +18,7 @@ import math
 import torch
 
 from . import _lib as L
-from .covariance import human_bytes, sample_steps
+from .sampling import SampleWindow, human_bytes, parse_keys, parse_layer, parse_window, sample_steps  # noqa: F401
 
 _KEYS = ("begin", "stride", "layer", "units")
 MAX_UNITS = 32                                   # include/mcpc.h: MCPC_KNN_MAX_DIM
@@ -26,53 +26,23 @@ KNN_CHUNK_BYTES = 256 << 20                      # reference rows handed to one 
 
 
 @dataclass(frozen=True)
-class CloudSpec:
+class CloudSpec(SampleWindow):
     """A validated ``mcpc_cloud`` request for a call of ``T`` steps."""
-    begin: int
-    stride: int
     layer: int
     units: Tuple[int, ...]
-    T: int
-
-    @property
-    def n(self) -> int:
-        return len(sample_steps(self.begin, self.T, self.stride))
 
     @property
     def d(self) -> int:
         return len(self.units)
-
-    def chunk(self, t0: int, n_steps: int):
-        """(first, count): the samples among steps t0 .. t0 + n_steps - 1 are rows first, first + stride, ... of a chunk that holds
-        one record per step from t0 on."""
-        f = self.begin if t0 <= self.begin else self.begin + -(-(t0 - self.begin) // self.stride) * self.stride
-        return f - t0, len(range(f, min(t0 + n_steps, self.T), self.stride))
 
 
 def validate_spec(spec, T: int, n_layers: int, sizes, B: int, max_bytes: int) -> CloudSpec:
     """``PCTrainer.mcpc_cloud`` -> CloudSpec, or ValueError: not a dict, unknown keys, ``begin`` outside [0, T), ``stride`` < 1, no
     ``layer`` or one out of range, ``units`` that are not 1..32 distinct ints inside the layer (None = every unit, an error on a layer
     wider than 32), a cloud of more than ``max_bytes``.  Defaults: begin=0, stride=1, units=None."""
-    if not isinstance(spec, dict):
-        raise ValueError(f"mcpc_cloud: expected a dict or None, got {type(spec).__name__}")
-    unknown = sorted(k for k in spec if k not in _KEYS)
-    if unknown:
-        raise ValueError(f"mcpc_cloud: unknown keys {unknown}; known: {list(_KEYS)}")
-    begin, stride = spec.get("begin", 0), spec.get("stride", 1)
-    for name, v in (("begin", begin), ("stride", stride)):
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise ValueError(f"mcpc_cloud: {name} must be an int, got {v!r}")
-    if not 0 <= begin < T:
-        raise ValueError(f"mcpc_cloud: begin={begin} outside [0, T={T})")
-    if stride < 1:
-        raise ValueError(f"mcpc_cloud: stride={stride}, must be at least 1")
-    if "layer" not in spec or spec["layer"] is None:
-        raise ValueError(f"mcpc_cloud: layer is required: the PC layer the cloud is taken from, an int in 0..{n_layers - 1}")
-    layer = spec["layer"]
-    if isinstance(layer, bool) or not isinstance(layer, int):
-        raise ValueError(f"mcpc_cloud: layer must be an int, got {layer!r}")
-    if not 0 <= layer < n_layers:
-        raise ValueError(f"mcpc_cloud: layer index {layer!r} out of range, the model has {n_layers} PC layers (0..{n_layers - 1})")
+    parse_keys("mcpc_cloud", spec, _KEYS)
+    begin, stride = parse_window("mcpc_cloud", spec, T)
+    layer = parse_layer("mcpc_cloud", spec, n_layers, "the cloud is taken from")
     width = int(sizes[layer])
     units = spec.get("units", None)
     if units is None:

@@ -12,47 +12,25 @@ from typing import List, Optional, Tuple
 
 import torch
 
+from .sampling import (SampleWindow, column_list, human_bytes, parse_keys, parse_layers, parse_outputs, parse_window,  # noqa: F401
+                       require_columns, sample_steps)
+
 _KEYS = ("begin", "stride", "layers", "outputs", "pool")
 _OUTPUTS = (None, "identity", "sigmoid")
 _POOLS = (None, "chains")
 
 
-def sample_steps(begin: int, T: int, stride: int) -> range:
-    """The steps of a call of T steps whose records are samples."""
-    return range(begin, T, stride)
-
-
-def human_bytes(n: int) -> str:
-    for unit, size in (("GiB", 1 << 30), ("MiB", 1 << 20), ("KiB", 1 << 10)):
-        if n >= size:
-            return f"{n / size:.1f} {unit}"
-    return f"{n} B"
-
-
 @dataclass(frozen=True)
-class CovarianceSpec:
+class CovarianceSpec(SampleWindow):
     """A validated ``mcpc_covariance`` request for a call of ``T`` steps."""
-    begin: int
-    stride: int
     layers: Tuple[int, ...]
     outputs: Optional[str]
     pooled: bool
-    T: int
     columns: Tuple[Tuple[str, int, int], ...]       # (name, start, width) of every column group, in order
-
-    @property
-    def n(self) -> int:
-        return len(sample_steps(self.begin, self.T, self.stride))
 
     @property
     def D(self) -> int:
         return sum(w for _, _, w in self.columns)
-
-    def chunk(self, t0: int, n_steps: int):
-        """(first, count): the samples among steps t0 .. t0 + n_steps - 1 are rows first, first + stride, ... of a chunk that holds
-        one record per step from t0 on."""
-        f = self.begin if t0 <= self.begin else self.begin + -(-(t0 - self.begin) // self.stride) * self.stride
-        return f - t0, len(range(f, min(t0 + n_steps, self.T), self.stride))
 
 
 def result_bytes(D: int, B: int, pooled: bool) -> int:
@@ -66,56 +44,23 @@ def validate_spec(spec, T: int, n_layers: int, n_out: int, sizes, B: int, max_by
     """``PCTrainer.mcpc_covariance`` -> CovarianceSpec, or ValueError: not a dict, unknown keys, ``begin`` outside [0, T), ``stride``
     < 1, a layer index out of range, no column at all, ``outputs`` on a model without a read-out, an unknown ``pool``, a result larger
     than ``max_bytes``.  Defaults: begin=0, stride=1, layers=all latent layers, outputs=None, pool=None (one matrix per chain)."""
-    if not isinstance(spec, dict):
-        raise ValueError(f"mcpc_covariance: expected a dict or None, got {type(spec).__name__}")
-    unknown = sorted(k for k in spec if k not in _KEYS)
-    if unknown:
-        raise ValueError(f"mcpc_covariance: unknown keys {unknown}; known: {list(_KEYS)}")
-    begin, stride = spec.get("begin", 0), spec.get("stride", 1)
-    for name, v in (("begin", begin), ("stride", stride)):
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise ValueError(f"mcpc_covariance: {name} must be an int, got {v!r}")
-    if not 0 <= begin < T:
-        raise ValueError(f"mcpc_covariance: begin={begin} outside [0, T={T})")
-    if stride < 1:
-        raise ValueError(f"mcpc_covariance: stride={stride}, must be at least 1")
-    layers = spec.get("layers", None)
-    if layers is None:
-        layers = tuple(range(n_layers))
-    if isinstance(layers, int) and not isinstance(layers, bool):
-        layers = (layers,)
-    try:
-        layers = tuple(layers)
-    except TypeError:
-        raise ValueError(f"mcpc_covariance: layers must be a sequence of layer indices, got {layers!r}") from None
-    for l in layers:
-        if isinstance(l, bool) or not isinstance(l, int) or not 0 <= l < n_layers:
-            raise ValueError(f"mcpc_covariance: layer index {l!r} out of range, the model has {n_layers} PC layers (0..{n_layers - 1})")
-    layers = tuple(sorted(set(layers)))
-    outputs = spec.get("outputs", None)
-    if outputs not in _OUTPUTS:
-        raise ValueError(f"mcpc_covariance: outputs={outputs!r}, expected None, 'identity' or 'sigmoid'")
-    if outputs is not None and n_out < 1:
-        raise ValueError("mcpc_covariance: outputs asked of a model without a read-out (it ends with a PCLayer)")
+    parse_keys("mcpc_covariance", spec, _KEYS)
+    begin, stride = parse_window("mcpc_covariance", spec, T)
+    layers = parse_layers("mcpc_covariance", spec, n_layers, none_means="all")
+    outputs = parse_outputs("mcpc_covariance", spec, n_out, _OUTPUTS)
     pool = spec.get("pool", None)
     if pool not in _POOLS:
         raise ValueError(f"mcpc_covariance: pool={pool!r}, expected None (one matrix per chain) or 'chains'")
-    if not layers and outputs is None:
-        raise ValueError("mcpc_covariance: no columns: layers is empty and outputs is None")
-    columns, start = [], 0
-    for l in layers:
-        columns.append((f"x{l}", start, int(sizes[l])))
-        start += int(sizes[l])
-    if outputs is not None:
-        columns.append(("out", start, int(n_out)))
-        start += int(n_out)
+    require_columns("mcpc_covariance", layers, outputs)
+    columns = column_list(layers, sizes, None if outputs is None else "out", n_out, starts=True)
+    start = sum(w for _, _, w in columns)
     pooled = pool == "chains"
     need = result_bytes(start, B, pooled)
     if need > max_bytes:
         what = f"one {start} x {start} fp64 matrix" if pooled else f"{B} chains x {start} x {start} fp64"
         raise ValueError(f"mcpc_covariance: the result ({what}) takes {human_bytes(need)}, more than mcpc_covariance_max_bytes = "
                          f"{human_bytes(max_bytes)}: ask for fewer layers" + ("" if pooled else " or pool='chains'"))
-    return CovarianceSpec(begin=begin, stride=stride, layers=layers, outputs=outputs, pooled=pooled, T=T, columns=tuple(columns))
+    return CovarianceSpec(begin=begin, stride=stride, layers=layers, outputs=outputs, pooled=pooled, T=T, columns=columns)
 
 
 @dataclass

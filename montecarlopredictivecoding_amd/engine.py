@@ -31,6 +31,47 @@ def _check_tensor(t: torch.Tensor, shape, device, name, dtype=torch.float32):
         raise ValueError(f"{name}: tensor must be contiguous")
 
 
+def _check_records(rec, rank=3, what="[records, B, width]"):
+    """A record buffer as an engine run fills it: a contiguous fp32 tensor of ``rank`` dimensions (None: one at least) on a HIP
+    device.  Returns (device, shape)."""
+    if not isinstance(rec, torch.Tensor) or (rec.dim() < 1 if rank is None else rec.dim() != rank):
+        raise TypeError(f"rec: expected a torch.Tensor {what}")
+    device = rec.device
+    if device.type != "cuda":
+        raise ValueError(f"rec: expected a tensor on a HIP device, got {device}")
+    _check_tensor(rec, rec.shape, device, "rec")
+    return device, tuple(int(d) for d in rec.shape)
+
+
+def _check_last_record(records, first, stride, n, what="rec holds"):
+    """Records ``first + k * stride``, k < n, lie inside a buffer of ``records`` (the library refuses negative ones itself)."""
+    if n > 0 and first >= 0 and stride >= 1 and first + (n - 1) * stride >= records:
+        raise ValueError(f"{what} {records} records, the last one asked for is {first + (n - 1) * stride}")
+
+
+def _check_workspace(workspace, device, need, align, asks):
+    """A caller's workspace (None: one is allocated): a contiguous tensor on ``device``, ``align``-byte aligned, of at least ``need``
+    bytes, the figure the function named ``asks`` gave.  Returns (workspace, its bytes)."""
+    if workspace is None:
+        workspace = torch.empty(max(need, align), dtype=torch.uint8, device=device)
+    if not isinstance(workspace, torch.Tensor):
+        raise TypeError(f"workspace: expected a torch.Tensor, got {type(workspace)}")
+    if workspace.device != device:
+        raise ValueError(f"workspace: expected device {device}, got {workspace.device}")
+    if not workspace.is_contiguous():
+        raise ValueError("workspace: tensor must be contiguous")
+    if workspace.data_ptr() % align:
+        raise ValueError(f"workspace: must be {align}-byte aligned")
+    ws_bytes = workspace.numel() * workspace.element_size()
+    if ws_bytes < need:
+        raise ValueError(f"workspace: {ws_bytes} bytes, {asks} asks for {need}")
+    return workspace, ws_bytes
+
+
+def _current_stream(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
 @dataclass
 class RunResult:
     energies: Optional[torch.Tensor] = None      # float64 [rows, ENERGY_COLS]: loss, E_1..E_L, overall
@@ -88,7 +129,7 @@ class Engine:
             pass
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _current_stream(self.device)
 
     def lin_shape(self, j):
         n_in = self.n_in if j == 0 else self.sizes[j - 1]
@@ -378,7 +419,7 @@ def debug_poison_lds(device, word=0x7FA00000):
     """Diagnostic (tests only): fill the LDS of every compute unit of `device` with a 32-bit pattern (default: a signalling NaN)."""
     lib = L.load()
     device = torch.device(device)
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    stream = _current_stream(device)
     L.check(lib.mcpc_debug_poison_lds(device.index or 0, word, stream))
 
 
@@ -387,7 +428,7 @@ def philox_normals(seed, step, layer, chain_base, batch, n_units, device, raw=Fa
     lib = L.load()
     device = torch.device(device)
     out = torch.empty(batch, n_units, dtype=torch.float32, device=device)
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    stream = _current_stream(device)
     L.check(lib.mcpc_philox_normals(device.index or 0, seed, step, layer, chain_base, batch, n_units,
                                     _ptr(out), 1 if raw else 0, stream))
     return out.view(torch.int32) if raw else out
@@ -406,18 +447,12 @@ def moments_accumulate(rec, first, stride, n, sum, sumsq=None, transform="identi
     lib = L.load()
     if transform not in _MOM_TRANSFORMS:
         raise ValueError(f"transform: expected 'identity' or 'sigmoid', got {transform!r}")
-    if not isinstance(rec, torch.Tensor) or rec.dim() < 1:
-        raise TypeError("rec: expected a torch.Tensor [records, ...]")
-    device = rec.device
-    if device.type != "cuda":
-        raise ValueError(f"rec: expected a tensor on a HIP device, got {device}")
-    _check_tensor(rec, rec.shape, device, "rec")
+    device, shape = _check_records(rec, rank=None, what="[records, ...]")
     row = 1
-    for d in rec.shape[1:]:
-        row *= int(d)
+    for d in shape[1:]:
+        row *= d
     first, stride, n = int(first), int(stride), int(n)
-    if n > 0 and first >= 0 and stride >= 1 and first + (n - 1) * stride >= rec.shape[0]:
-        raise ValueError(f"rec holds {rec.shape[0]} records, the last one asked for is {first + (n - 1) * stride}")
+    _check_last_record(shape[0], first, stride, n)
     for t, name in ((sum, "sum"), (sumsq, "sumsq")):
         if t is None and name == "sumsq":
             continue
@@ -426,7 +461,7 @@ def moments_accumulate(rec, first, stride, n, sum, sumsq=None, transform="identi
         if t.numel() != row:
             raise ValueError(f"{name}: expected {row} elements (one per element of a record), got {t.numel()}")
         _check_tensor(t, t.shape, device, name, torch.float64)
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    stream = _current_stream(device)
     L.check(lib.mcpc_moments_accumulate(device.index or 0, _ptr(rec), row, first, stride, n, _MOM_TRANSFORMS[transform],
                                         _ptr(sum), _ptr(sumsq), 1 if accumulate else 0, stream))
 
@@ -474,8 +509,7 @@ def cov_accumulate(recs, first, stride, n, outer, transforms=None, pool=False, a
     widths = [int(r.shape[2]) for r in recs]
     D = sum(widths)
     first, stride, n = int(first), int(stride), int(n)
-    if n > 0 and first >= 0 and stride >= 1 and first + (n - 1) * stride >= R:
-        raise ValueError(f"recs hold {R} records, the last one asked for is {first + (n - 1) * stride}")
+    _check_last_record(R, first, stride, n, what="recs hold")
     if not isinstance(outer, torch.Tensor):
         raise TypeError(f"outer: expected a torch.Tensor, got {type(outer)}")
     _check_tensor(outer, (D, D) if pool else (B, D, D), device, "outer", torch.float64)
@@ -485,22 +519,10 @@ def cov_accumulate(recs, first, stride, n, outer, transforms=None, pool=False, a
         L.check(need)
     ws_bytes = 0
     if pool:
-        if workspace is None:
-            workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
-        if not isinstance(workspace, torch.Tensor):
-            raise TypeError(f"workspace: expected a torch.Tensor, got {type(workspace)}")
-        if workspace.device != device:
-            raise ValueError(f"workspace: expected device {device}, got {workspace.device}")
-        if not workspace.is_contiguous():
-            raise ValueError("workspace: tensor must be contiguous")
-        if workspace.data_ptr() % 8:
-            raise ValueError("workspace: must be 8-byte aligned")
-        ws_bytes = workspace.numel() * workspace.element_size()
-        if ws_bytes < need:
-            raise ValueError(f"workspace: {ws_bytes} bytes, cov_workspace_bytes asks for {need}")
+        workspace, ws_bytes = _check_workspace(workspace, device, need, 8, "cov_workspace_bytes")
     ptrs = (C.c_void_p * len(recs))(*[r.data_ptr() for r in recs])
     xf = (C.c_int32 * len(recs))(*[_MOM_TRANSFORMS[t] for t in transforms])
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    stream = _current_stream(device)
     L.check(lib.mcpc_cov_accumulate(device.index or 0, ptrs, w, xf, len(recs), B, first, stride, n, 1 if pool else 0, _ptr(outer),
                                     1 if accumulate else 0, _ptr(workspace) if pool else None, ws_bytes, stream))
 
@@ -516,16 +538,9 @@ def hist_accumulate(rec, first, stride, n, edges, counts, transform="identity", 
     lib = L.load()
     if transform not in _MOM_TRANSFORMS:
         raise ValueError(f"transform: expected 'identity' or 'sigmoid', got {transform!r}")
-    if not isinstance(rec, torch.Tensor) or rec.dim() != 3:
-        raise TypeError("rec: expected a torch.Tensor [records, B, width]")
-    device = rec.device
-    if device.type != "cuda":
-        raise ValueError(f"rec: expected a tensor on a HIP device, got {device}")
-    _check_tensor(rec, rec.shape, device, "rec")
-    R, B, width = (int(d) for d in rec.shape)
+    device, (R, B, width) = _check_records(rec)
     first, stride, n = int(first), int(stride), int(n)
-    if n > 0 and first >= 0 and stride >= 1 and first + (n - 1) * stride >= R:
-        raise ValueError(f"rec holds {R} records, the last one asked for is {first + (n - 1) * stride}")
+    _check_last_record(R, first, stride, n)
     e = torch.as_tensor(edges)
     if e.device.type != "cpu" or e.dtype != torch.float32 or e.dim() != 1:
         raise TypeError("edges: expected a 1-D fp32 CPU tensor or array")
@@ -536,7 +551,7 @@ def hist_accumulate(rec, first, stride, n, edges, counts, transform="identity", 
     if not isinstance(counts, torch.Tensor):
         raise TypeError(f"counts: expected a torch.Tensor, got {type(counts)}")
     _check_tensor(counts, (width, n_bins + 3) if pool else (B, width, n_bins + 3), device, "counts", torch.int64)
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    stream = _current_stream(device)
     L.check(lib.mcpc_hist_accumulate(device.index or 0, _ptr(rec), B, width, first, stride, n, _MOM_TRANSFORMS[transform],
                                      C.cast(e.data_ptr(), C.POINTER(C.c_float)), n_bins, 1 if pool else 0, _ptr(counts),
                                      1 if accumulate else 0, stream))
@@ -554,23 +569,16 @@ def acov_accumulate(rec, first, stride, n, max_lag, n_seen, lagged, sum, window,
     lib = L.load()
     if transform not in _MOM_TRANSFORMS:
         raise ValueError(f"transform: expected 'identity' or 'sigmoid', got {transform!r}")
-    if not isinstance(rec, torch.Tensor) or rec.dim() != 3:
-        raise TypeError("rec: expected a torch.Tensor [records, B, width]")
-    device = rec.device
-    if device.type != "cuda":
-        raise ValueError(f"rec: expected a tensor on a HIP device, got {device}")
-    _check_tensor(rec, rec.shape, device, "rec")
-    R, B, width = (int(d) for d in rec.shape)
+    device, (R, B, width) = _check_records(rec)
     first, stride, n, max_lag, n_seen = int(first), int(stride), int(n), int(max_lag), int(n_seen)
-    if n > 0 and first >= 0 and stride >= 1 and first + (n - 1) * stride >= R:
-        raise ValueError(f"rec holds {R} records, the last one asked for is {first + (n - 1) * stride}")
+    _check_last_record(R, first, stride, n)
     if not 0 <= max_lag <= L.ACOV_MAX_LAG:
         raise ValueError(f"max_lag={max_lag}, expected 0..{L.ACOV_MAX_LAG}")
     _check_tensor(lagged, (B, width, max_lag + 1), device, "lagged", torch.float64)
     _check_tensor(sum, (B, width), device, "sum", torch.float64)
     _check_tensor(window, (max_lag, B, width), device, "window")
     _check_tensor(head, (max_lag, B, width), device, "head")
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    stream = _current_stream(device)
     L.check(lib.mcpc_acov_accumulate(device.index or 0, _ptr(rec), B, width, first, stride, n, _MOM_TRANSFORMS[transform], max_lag,
                                      n_seen, _ptr(lagged), _ptr(sum), _ptr(window), _ptr(head), stream))
 
@@ -611,16 +619,9 @@ def roll_accumulate(rec, first, stride, n, window, every, n_seen, s1, s2, hist, 
     lib = L.load()
     if transform not in _MOM_TRANSFORMS:
         raise ValueError(f"transform: expected 'identity' or 'sigmoid', got {transform!r}")
-    if not isinstance(rec, torch.Tensor) or rec.dim() != 3:
-        raise TypeError("rec: expected a torch.Tensor [records, B, width]")
-    device = rec.device
-    if device.type != "cuda":
-        raise ValueError(f"rec: expected a tensor on a HIP device, got {device}")
-    _check_tensor(rec, rec.shape, device, "rec")
-    R, B, width = (int(d) for d in rec.shape)
+    device, (R, B, width) = _check_records(rec)
     first, stride, n, window, every, n_seen = int(first), int(stride), int(n), int(window), int(every), int(n_seen)
-    if n > 0 and first >= 0 and stride >= 1 and first + (n - 1) * stride >= R:
-        raise ValueError(f"rec holds {R} records, the last one asked for is {first + (n - 1) * stride}")
+    _check_last_record(R, first, stride, n)
     if window < 2:
         raise ValueError(f"window={window}, expected at least 2")
     if every < 1:
@@ -640,24 +641,13 @@ def roll_accumulate(rec, first, stride, n, window, every, n_seen, s1, s2, hist, 
             raise ValueError(f"out_pool: expected a torch.Tensor of at least {rows} rows [rows, 4]")
         _check_tensor(out_pool, (out_pool.shape[0], 4), device, "out_pool", torch.float64)
         need = roll_workspace_bytes(B, width, max(n, 0))
-        if workspace is None:
-            workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
-        if not isinstance(workspace, torch.Tensor):
-            raise TypeError(f"workspace: expected a torch.Tensor, got {type(workspace)}")
-        if workspace.device != device:
-            raise ValueError(f"workspace: expected device {device}, got {workspace.device}")
-        if not workspace.is_contiguous():
-            raise ValueError("workspace: tensor must be contiguous")
-        if workspace.data_ptr() % 8:
-            raise ValueError("workspace: must be 8-byte aligned")
-        if workspace.numel() * workspace.element_size() < need:
-            raise ValueError(f"workspace: {workspace.numel() * workspace.element_size()} bytes, roll_workspace_bytes asks for {need}")
+        workspace, _ = _check_workspace(workspace, device, need, 8, "roll_workspace_bytes")
 
     def out_ptr(t):
         # a tensor without rows has no address, and the library tells the outputs asked for by their pointers: s1's stands in (a call
         # that emits no row writes no output)
         return None if t is None else C.c_void_p(t.data_ptr() or s1.data_ptr())
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    stream = _current_stream(device)
     L.check(lib.mcpc_roll_accumulate(device.index or 0, _ptr(rec), B, width, first, stride, n, _MOM_TRANSFORMS[transform], window, every,
                                      n_seen, _ptr(s1), _ptr(s2), _ptr(hist), out_ptr(out_elem), out_ptr(out_pool),
                                      _ptr(workspace) if out_pool is not None else None, stream))
@@ -679,16 +669,9 @@ def probe_accumulate(rec, first, stride, n, W, bias, link, psum, psumsq, votes, 
     lib = L.load()
     if link not in _PROBE_LINKS:
         raise ValueError(f"link: expected 'identity', 'sigmoid' or 'softmax', got {link!r}")
-    if not isinstance(rec, torch.Tensor) or rec.dim() != 3:
-        raise TypeError("rec: expected a torch.Tensor [records, B, width]")
-    device = rec.device
-    if device.type != "cuda":
-        raise ValueError(f"rec: expected a tensor on a HIP device, got {device}")
-    _check_tensor(rec, rec.shape, device, "rec")
-    R, B, width = (int(d) for d in rec.shape)
+    device, (R, B, width) = _check_records(rec)
     first, stride, n = int(first), int(stride), int(n)
-    if n > 0 and first >= 0 and stride >= 1 and first + (n - 1) * stride >= R:
-        raise ValueError(f"rec holds {R} records, the last one asked for is {first + (n - 1) * stride}")
+    _check_last_record(R, first, stride, n)
     if not isinstance(W, torch.Tensor) or W.dim() != 2:
         raise TypeError("W: expected a torch.Tensor [C, width]")
     n_classes = int(W.shape[0])
@@ -705,7 +688,7 @@ def probe_accumulate(rec, first, stride, n, W, bias, link, psum, psumsq, votes, 
         _check_tensor(entsum, (B,), device, "entsum", torch.float64)
     elif entsum is not None:
         raise ValueError(f"entsum: the entropy is that of a softmax; expected None with link={link!r}")
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    stream = _current_stream(device)
     L.check(lib.mcpc_probe_accumulate(device.index or 0, _ptr(rec), B, width, first, stride, n, _ptr(W), _ptr(bias), n_classes,
                                       _PROBE_LINKS[link], _ptr(psum), _ptr(psumsq), _ptr(votes), _ptr(entsum), 1 if accumulate else 0,
                                       stream))
@@ -750,19 +733,7 @@ def knn_accumulate(q, ref, k, best, accumulate=False, workspace=None):
     need = lib.mcpc_knn_workspace_bytes(nq, nr, d, k)
     if need < 0:
         L.check(need)
-    if workspace is None:
-        workspace = torch.empty(max(need, 4), dtype=torch.uint8, device=device)
-    if not isinstance(workspace, torch.Tensor):
-        raise TypeError(f"workspace: expected a torch.Tensor, got {type(workspace)}")
-    if workspace.device != device:
-        raise ValueError(f"workspace: expected device {device}, got {workspace.device}")
-    if not workspace.is_contiguous():
-        raise ValueError("workspace: tensor must be contiguous")
-    if workspace.data_ptr() % 4:
-        raise ValueError("workspace: must be 4-byte aligned")
-    ws_bytes = workspace.numel() * workspace.element_size()
-    if ws_bytes < need:
-        raise ValueError(f"workspace: {ws_bytes} bytes, knn_workspace_bytes asks for {need}")
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    workspace, ws_bytes = _check_workspace(workspace, device, need, 4, "knn_workspace_bytes")
+    stream = _current_stream(device)
     L.check(lib.mcpc_knn_accumulate(device.index or 0, _ptr(q), nq, _ptr(ref), nr, d, k, _ptr(best), 1 if accumulate else 0,
                                     _ptr(workspace), ws_bytes, stream))

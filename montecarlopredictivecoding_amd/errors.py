@@ -13,17 +13,14 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from .covariance import Covariance, human_bytes, result_bytes as cov_result_bytes
+from .covariance import Covariance, result_bytes as cov_result_bytes
+from .sampling import (SampleWindow, column_list, human_bytes, parse_keys, parse_layers, parse_outputs, parse_window,  # noqa: F401
+                       require_columns, sample_steps)
 
 _KEYS = ("begin", "stride", "layers", "quantity", "outputs", "variance", "covariance")
 _QUANTITIES = ("error", "prediction")
 _OUTPUTS = (None, "error", "prediction")
 _COVARIANCES = (None, "chain", "chains")
-
-
-def sample_steps(begin: int, T: int, stride: int) -> range:
-    """The steps of a call of T steps whose records are samples."""
-    return range(begin, T, stride)
 
 
 def block_name(quantity: str, layer: Optional[int]) -> str:
@@ -47,22 +44,15 @@ def layers_read(layers, with_output: bool, n_layers: int) -> Tuple[int, ...]:
 
 
 @dataclass(frozen=True)
-class ErrorsSpec:
+class ErrorsSpec(SampleWindow):
     """A validated ``mcpc_errors`` request for a call of ``T`` steps."""
-    begin: int
-    stride: int
     layers: Tuple[int, ...]
     quantity: str
     outputs: Optional[str]
     variance: bool
     covariance: Optional[str]                       # None, "chain" (one matrix per chain) or "chains" (pooled over the chains)
-    T: int
     columns: Tuple[Tuple[str, int, int], ...]       # (name, start, width) of every block, in order
     reads: Tuple[int, ...]                          # latent layers that go through the record ring
-
-    @property
-    def n(self) -> int:
-        return len(sample_steps(self.begin, self.T, self.stride))
 
     @property
     def D(self) -> int:
@@ -71,12 +61,6 @@ class ErrorsSpec:
     @property
     def pooled(self) -> bool:
         return self.covariance == "chains"
-
-    def chunk(self, t0: int, n_steps: int):
-        """(first, count): the samples among steps t0 .. t0 + n_steps - 1 are rows first, first + stride, ... of a chunk that holds
-        one record per step from t0 on."""
-        f = self.begin if t0 <= self.begin else self.begin + -(-(t0 - self.begin) // self.stride) * self.stride
-        return f - t0, len(range(f, min(t0 + n_steps, self.T), self.stride))
 
     def max_samples(self, n_steps: int) -> int:
         """The most samples a slice of n_steps steps can hold (a derived buffer has that many records)."""
@@ -111,54 +95,23 @@ def validate_spec(spec, T: int, n_layers: int, n_out: int, sizes, B: int, has_lo
     a read-out, ``outputs="error"`` on a call without a loss, a request that takes more than ``max_bytes`` even with derived buffers
     of one sample (the trainer checks again with the samples one slice holds, before anything runs).  Defaults: begin=0, stride=1,
     layers=(), quantity="error", outputs=None, variance=True, covariance=None."""
-    if not isinstance(spec, dict):
-        raise ValueError(f"mcpc_errors: expected a dict or None, got {type(spec).__name__}")
-    unknown = sorted(k for k in spec if k not in _KEYS)
-    if unknown:
-        raise ValueError(f"mcpc_errors: unknown keys {unknown}; known: {list(_KEYS)}")
-    begin, stride = spec.get("begin", 0), spec.get("stride", 1)
-    for name, v in (("begin", begin), ("stride", stride)):
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise ValueError(f"mcpc_errors: {name} must be an int, got {v!r}")
-    if not 0 <= begin < T:
-        raise ValueError(f"mcpc_errors: begin={begin} outside [0, T={T})")
-    if stride < 1:
-        raise ValueError(f"mcpc_errors: stride={stride}, must be at least 1")
-    layers = spec.get("layers", ())
-    if isinstance(layers, int) and not isinstance(layers, bool):
-        layers = (layers,)
-    try:
-        layers = tuple(layers)
-    except TypeError:
-        raise ValueError(f"mcpc_errors: layers must be a sequence of layer indices, got {layers!r}") from None
-    for l in layers:
-        if isinstance(l, bool) or not isinstance(l, int) or not 0 <= l < n_layers:
-            raise ValueError(f"mcpc_errors: layer index {l!r} out of range, the model has {n_layers} PC layers (0..{n_layers - 1})")
-    layers = tuple(sorted(set(layers)))
+    parse_keys("mcpc_errors", spec, _KEYS)
+    begin, stride = parse_window("mcpc_errors", spec, T)
+    layers = parse_layers("mcpc_errors", spec, n_layers)            # layers=None is not a sequence here
     quantity = spec.get("quantity", "error")
     if quantity not in _QUANTITIES:
         raise ValueError(f"mcpc_errors: quantity={quantity!r}, expected 'error' or 'prediction'")
-    outputs = spec.get("outputs", None)
-    if outputs not in _OUTPUTS:
-        raise ValueError(f"mcpc_errors: outputs={outputs!r}, expected None, 'error' or 'prediction'")
-    if outputs is not None and n_out < 1:
-        raise ValueError("mcpc_errors: outputs asked of a model without a read-out (it ends with a PCLayer)")
+    outputs = parse_outputs("mcpc_errors", spec, n_out, _OUTPUTS)
     if outputs == "error" and not has_loss:
         raise ValueError("mcpc_errors: outputs='error' asked of a call without a loss (the read-out has no error then)")
     covariance = spec.get("covariance", None)
     if covariance not in _COVARIANCES:
         raise ValueError(f"mcpc_errors: covariance={covariance!r}, expected None, 'chain' (one matrix per chain) or 'chains' (pooled)")
-    if not layers and outputs is None:
-        raise ValueError("mcpc_errors: no columns: layers is empty and outputs is None")
-    columns, start = [], 0
-    for l in layers:
-        columns.append((block_name(quantity, l), start, int(sizes[l])))
-        start += int(sizes[l])
-    if outputs is not None:
-        columns.append((block_name(outputs, None), start, int(n_out)))
-        start += int(n_out)
+    require_columns("mcpc_errors", layers, outputs)
+    columns = column_list(layers, sizes, None if outputs is None else block_name(outputs, None), n_out,
+                          layer_name=lambda l: block_name(quantity, l), starts=True)
     out = ErrorsSpec(begin=begin, stride=stride, layers=layers, quantity=quantity, outputs=outputs, variance=bool(spec.get("variance", True)),
-                     covariance=covariance, T=T, columns=tuple(columns), reads=layers_read(layers, outputs is not None, n_layers))
+                     covariance=covariance, T=T, columns=columns, reads=layers_read(layers, outputs is not None, n_layers))
     check_bytes(out, B, 1, max_bytes)
     return out
 

@@ -17,7 +17,8 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from .covariance import human_bytes, sample_steps
+from .sampling import (SampleWindow, column_list, human_bytes, parse_keys, parse_layers, parse_outputs, parse_window,  # noqa: F401
+                       require_columns, sample_steps)
 
 _KEYS = ("begin", "stride", "layers", "outputs", "bins", "range", "pool")
 _OUTPUTS = (None, "identity", "sigmoid")
@@ -26,26 +27,13 @@ MAX_BINS = 256                                   # include/mcpc.h: MCPC_HIST_MAX
 
 
 @dataclass(frozen=True, eq=False)
-class HistogramSpec:
+class HistogramSpec(SampleWindow):
     """A validated ``mcpc_histogram`` request for a call of ``T`` steps."""
-    begin: int
-    stride: int
     layers: Tuple[int, ...]
     outputs: Optional[str]
     pooled: bool
-    T: int
     columns: Tuple[Tuple[str, int], ...]            # (name, width) of every block, in order: "x0", "x1", ..., "out"
     edges: Tuple[np.ndarray, ...]                   # per block: the fp32 edges, [n_bins + 1]
-
-    @property
-    def n(self) -> int:
-        return len(sample_steps(self.begin, self.T, self.stride))
-
-    def chunk(self, t0: int, n_steps: int):
-        """(first, count): the samples among steps t0 .. t0 + n_steps - 1 are rows first, first + stride, ... of a chunk that holds
-        one record per step from t0 on."""
-        f = self.begin if t0 <= self.begin else self.begin + -(-(t0 - self.begin) // self.stride) * self.stride
-        return f - t0, len(range(f, min(t0 + n_steps, self.T), self.stride))
 
 
 def result_bytes(columns, edges, B: int, pooled: bool) -> int:
@@ -94,43 +82,15 @@ def validate_spec(spec, T: int, n_layers: int, n_out: int, sizes, B: int, max_by
     ``bins`` without ``range``, edges that are not finite and strictly ascending in fp32, a result larger than ``max_bytes``.
     Defaults: begin=0, stride=1, layers=(), outputs=None, pool=None (one histogram per chain and unit).  ``bins`` and ``range`` may be
     dicts keyed by block name ("x0", ..., "out")."""
-    if not isinstance(spec, dict):
-        raise ValueError(f"mcpc_histogram: expected a dict or None, got {type(spec).__name__}")
-    unknown = sorted(k for k in spec if k not in _KEYS)
-    if unknown:
-        raise ValueError(f"mcpc_histogram: unknown keys {unknown}; known: {list(_KEYS)}")
-    begin, stride = spec.get("begin", 0), spec.get("stride", 1)
-    for name, v in (("begin", begin), ("stride", stride)):
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise ValueError(f"mcpc_histogram: {name} must be an int, got {v!r}")
-    if not 0 <= begin < T:
-        raise ValueError(f"mcpc_histogram: begin={begin} outside [0, T={T})")
-    if stride < 1:
-        raise ValueError(f"mcpc_histogram: stride={stride}, must be at least 1")
-    layers = spec.get("layers", ())
-    if layers is None:
-        layers = ()
-    if isinstance(layers, int) and not isinstance(layers, bool):
-        layers = (layers,)
-    try:
-        layers = tuple(layers)
-    except TypeError:
-        raise ValueError(f"mcpc_histogram: layers must be a sequence of layer indices, got {layers!r}") from None
-    for l in layers:
-        if isinstance(l, bool) or not isinstance(l, int) or not 0 <= l < n_layers:
-            raise ValueError(f"mcpc_histogram: layer index {l!r} out of range, the model has {n_layers} PC layers (0..{n_layers - 1})")
-    layers = tuple(sorted(set(layers)))
-    outputs = spec.get("outputs", None)
-    if outputs not in _OUTPUTS:
-        raise ValueError(f"mcpc_histogram: outputs={outputs!r}, expected None, 'identity' or 'sigmoid'")
-    if outputs is not None and n_out < 1:
-        raise ValueError("mcpc_histogram: outputs asked of a model without a read-out (it ends with a PCLayer)")
+    parse_keys("mcpc_histogram", spec, _KEYS)
+    begin, stride = parse_window("mcpc_histogram", spec, T)
+    layers = parse_layers("mcpc_histogram", spec, n_layers, none_means="empty")
+    outputs = parse_outputs("mcpc_histogram", spec, n_out, _OUTPUTS)
     pool = spec.get("pool", None)
     if pool not in _POOLS:
         raise ValueError(f"mcpc_histogram: pool={pool!r}, expected None (one histogram per chain) or 'chains'")
-    if not layers and outputs is None:
-        raise ValueError("mcpc_histogram: no columns: layers is empty and outputs is None")
-    columns = [(f"x{l}", int(sizes[l])) for l in layers] + ([("out", int(n_out))] if outputs is not None else [])
+    require_columns("mcpc_histogram", layers, outputs)
+    columns = column_list(layers, sizes, None if outputs is None else "out", n_out)
     if "bins" not in spec or spec["bins"] is None:
         raise ValueError("mcpc_histogram: bins is required: an int with range=(lo, hi), or a sequence of edges (either may be a dict "
                          "keyed by block name)")
@@ -158,7 +118,7 @@ def validate_spec(spec, T: int, n_layers: int, n_out: int, sizes, B: int, max_by
         raise ValueError(f"mcpc_histogram: the result ({what} x up to {max(len(e) for e in edges) + 2} int64 counters) takes "
                          f"{human_bytes(need)}, more than mcpc_histogram_max_bytes = {human_bytes(max_bytes)}: ask for fewer layers"
                          " or fewer bins" + ("" if pooled else " or pool='chains'"))
-    return HistogramSpec(begin=begin, stride=stride, layers=layers, outputs=outputs, pooled=pooled, T=T, columns=tuple(columns),
+    return HistogramSpec(begin=begin, stride=stride, layers=layers, outputs=outputs, pooled=pooled, T=T, columns=columns,
                          edges=tuple(edges))
 
 

@@ -10,69 +10,29 @@ from typing import List, Optional, Tuple
 
 import torch
 
+from .sampling import SampleWindow, parse_keys, parse_layers, parse_outputs, parse_window, sample_steps  # noqa: F401
+
 _KEYS = ("begin", "stride", "layers", "outputs", "variance")
 _OUTPUTS = (None, "identity", "sigmoid")
 
 
-def sample_steps(begin: int, T: int, stride: int) -> range:
-    """The steps of a call of T steps whose records are samples."""
-    return range(begin, T, stride)
-
-
 @dataclass(frozen=True)
-class MomentsSpec:
+class MomentsSpec(SampleWindow):
     """A validated ``mcpc_moments`` request for a call of ``T`` steps."""
-    begin: int
-    stride: int
     layers: Tuple[int, ...]
     outputs: Optional[str]
     variance: bool
-    T: int
-
-    @property
-    def n(self) -> int:
-        return len(sample_steps(self.begin, self.T, self.stride))
-
-    def chunk(self, t0: int, n_steps: int):
-        """(first, count): the samples among steps t0 .. t0 + n_steps - 1 are rows first, first + stride, ... of a chunk that holds
-        one record per step from t0 on."""
-        f = self.begin if t0 <= self.begin else self.begin + -(-(t0 - self.begin) // self.stride) * self.stride
-        return f - t0, len(range(f, min(t0 + n_steps, self.T), self.stride))
 
 
 def validate_spec(spec, T: int, n_layers: int, n_out: int) -> MomentsSpec:
     """``PCTrainer.mcpc_moments`` -> MomentsSpec, or ValueError: unknown keys, ``begin`` outside [0, T), ``stride`` < 1, a layer
     index out of range, ``outputs`` on a model without a read-out.  Defaults: begin=0, stride=1, layers=(), outputs=None,
     variance=True."""
-    if not isinstance(spec, dict):
-        raise ValueError(f"mcpc_moments: expected a dict or None, got {type(spec).__name__}")
-    unknown = sorted(k for k in spec if k not in _KEYS)
-    if unknown:
-        raise ValueError(f"mcpc_moments: unknown keys {unknown}; known: {list(_KEYS)}")
-    begin, stride = spec.get("begin", 0), spec.get("stride", 1)
-    for name, v in (("begin", begin), ("stride", stride)):
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise ValueError(f"mcpc_moments: {name} must be an int, got {v!r}")
-    if not 0 <= begin < T:
-        raise ValueError(f"mcpc_moments: begin={begin} outside [0, T={T})")
-    if stride < 1:
-        raise ValueError(f"mcpc_moments: stride={stride}, must be at least 1")
-    layers = spec.get("layers", ())
-    if isinstance(layers, int) and not isinstance(layers, bool):
-        layers = (layers,)
-    try:
-        layers = tuple(layers)
-    except TypeError:
-        raise ValueError(f"mcpc_moments: layers must be a sequence of layer indices, got {layers!r}") from None
-    for l in layers:
-        if isinstance(l, bool) or not isinstance(l, int) or not 0 <= l < n_layers:
-            raise ValueError(f"mcpc_moments: layer index {l!r} out of range, the model has {n_layers} PC layers (0..{n_layers - 1})")
-    outputs = spec.get("outputs", None)
-    if outputs not in _OUTPUTS:
-        raise ValueError(f"mcpc_moments: outputs={outputs!r}, expected None, 'identity' or 'sigmoid'")
-    if outputs is not None and n_out < 1:
-        raise ValueError("mcpc_moments: outputs asked of a model without a read-out (it ends with a PCLayer)")
-    return MomentsSpec(begin=begin, stride=stride, layers=tuple(sorted(set(layers))), outputs=outputs,
+    parse_keys("mcpc_moments", spec, _KEYS)
+    begin, stride = parse_window("mcpc_moments", spec, T)
+    layers = parse_layers("mcpc_moments", spec, n_layers)          # layers=None is not a sequence here
+    outputs = parse_outputs("mcpc_moments", spec, n_out, _OUTPUTS)
+    return MomentsSpec(begin=begin, stride=stride, layers=layers, outputs=outputs,
                        variance=bool(spec.get("variance", True)), T=T)
 
 

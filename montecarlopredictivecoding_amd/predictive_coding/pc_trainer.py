@@ -45,7 +45,7 @@ import torch.optim as optim
 from .. import _lib as L
 from .. import dist
 from ..engine import Engine
-from . import recognise
+from . import recognise, ring
 from .generic_loop import run_generic
 from .pc_layer import PCLayer
 from .utils import slow_down_warning
@@ -223,79 +223,49 @@ class PCTrainer(object):
         # 10 000 steps x all latents to the host, pc_trainer.py:440-445,772-774)
         self.mcpc_record_chunk_bytes = 1 << 30
         self.last_record_slices = 0
-        # posterior moments of a fused call, accumulated on the device (moments.py): None = off, or
-        # dict(begin=0, stride=1, layers=(), outputs=None | "identity" | "sigmoid", variance=True); the call then leaves a
-        # moments.Moments in mcpc_last_moments.  The records are reduced out of a two-buffer device ring whose halves hold at most
-        # mcpc_moments_chunk_bytes each, on the call's own stream (mcpc_moments_side_stream = True reduces one
-        # half on a side stream while the next slice fills the other).
-        self.mcpc_moments = None
-        self.mcpc_last_moments = None
+        # ---- statistics of a fused call, reduced on the device out of its record ring (ring.py) ----------------
+        # Each mcpc_<x> below is None (off) or a dict; a fused call then leaves its result in mcpc_last_<x>.  Every request takes
+        # begin=0 and stride=1 (which steps are samples, sampling.py).  Any of them compose: one ring serves all that are set, its halves
+        # hold at most mcpc_moments_chunk_bytes each, and the reducers run after each slice on the call's own stream
+        # (mcpc_moments_side_stream = True reduces the moments on a side stream while the next slice fills the other half).  A request
+        # whose result or state would take more than its mcpc_<x>_max_bytes is a ValueError before anything runs; a call that does not
+        # run on the fused loop raises NotImplementedError.  The request modules document their keys.
         self.mcpc_moments_chunk_bytes = 1 << 30
         self.mcpc_moments_side_stream = False
-        # per-chain energies of a fused call, evaluated on the device out of the same ring (chain_energies.py): None = off, or
-        # dict(begin=0, stride=1).  A fused call then leaves chain_energies.ChainEnergies in mcpc_last_chain_energies; composes with
-        # mcpc_moments (one ring serves both).  mcpc_chain_energies_max_rows: rows per scratch chunk of the evaluator (0 = its default).
+        # layers=(), outputs=None | "identity" | "sigmoid", variance=True -> moments.Moments
+        self.mcpc_moments = None
+        self.mcpc_last_moments = None
+        # (no further keys) -> chain_energies.ChainEnergies; mcpc_chain_energies_max_rows: rows per scratch chunk of the evaluator (0 = default)
         self.mcpc_chain_energies = None
         self.mcpc_last_chain_energies = None
         self.mcpc_chain_energies_max_rows = 0
-        # posterior covariances of a fused call, accumulated on the device out of the same ring (covariance.py): None = off, or
-        # dict(begin=0, stride=1, layers=all, outputs=None | "identity" | "sigmoid", pool=None | "chains").  A fused call then leaves
-        # covariance.Covariance in mcpc_last_covariance; composes with mcpc_moments and mcpc_chain_energies (one ring serves all
-        # three).  A request whose RESULT (the fp64 outer products and first-order sums) would take more than mcpc_covariance_max_bytes
-        # is refused; the pooled form holds beside it the per-chain first-order sums (8 B per chain and column) and the kernel's
-        # workspace (engine.cov_workspace_bytes) while the call runs.
+        # layers=all, outputs=None | "identity" | "sigmoid", pool=None | "chains" -> covariance.Covariance
         self.mcpc_covariance = None
         self.mcpc_last_covariance = None
         self.mcpc_covariance_max_bytes = 2 << 30
-        # posterior histograms of a fused call, counted on the device out of the same ring (histogram.py): None = off, or
-        # dict(begin=0, stride=1, layers=(), outputs=None | "identity" | "sigmoid", bins=int | edges, range=(lo, hi), pool=None |
-        # "chains").  The result is a histogram.Histogram in mcpc_last_histogram; composes with mcpc_moments, mcpc_chain_energies and
-        # mcpc_covariance (one ring serves all four).  A request whose RESULT (the int64 counts) would take more than
-        # mcpc_histogram_max_bytes is a ValueError before anything runs.
+        # layers=(), outputs=None | "identity" | "sigmoid", bins=int | edges, range=(lo, hi), pool=None | "chains" -> histogram.Histogram
         self.mcpc_histogram = None
         self.mcpc_last_histogram = None
         self.mcpc_histogram_max_bytes = 2 << 30
-        # lagged autocovariances of a fused call, accumulated on the device out of the same ring (autocovariance.py): None = off, or
-        # dict(begin=0, stride=1, layers=(), outputs=None | "identity" | "sigmoid", max_lag=K) with K in 0..64.  The result is an
-        # autocovariance.Autocovariance in mcpc_last_autocovariance (acf, tau, ess, mcse per chain and unit); composes with the other
-        # four (one ring serves all five).  A request whose STATE (fp64 lagged products and sums, the first and last K samples in
-        # fp32) would take more than mcpc_autocovariance_max_bytes is a ValueError before anything runs.
+        # layers=(), outputs=None | "identity" | "sigmoid", max_lag=K in 0..64 -> autocovariance.Autocovariance (acf, tau, ess, mcse)
         self.mcpc_autocovariance = None
         self.mcpc_last_autocovariance = None
         self.mcpc_autocovariance_max_bytes = 2 << 30
-        # the posterior of a linear probe on a latent layer of a fused call, accumulated on the device out of the same ring (probe.py):
-        # None = off, or dict(begin=0, stride=1, layer=l, weight=W [C, n_l], bias=b | None, link="softmax" | "sigmoid" | "identity"),
-        # linear=<nn.Linear> in place of weight / bias, C in 1..64.  The result is a probe.Probe in mcpc_last_probe (mean class
-        # probabilities, their variance, argmax votes, entropy and its split, per chain); composes with the other five (one ring
-        # serves all six).
+        # layer=l, weight=W [C, n_l], bias=b | None (or linear=<nn.Linear>), link="softmax" | "sigmoid" | "identity", C in 1..64 -> probe.Probe
         self.mcpc_probe = None
         self.mcpc_last_probe = None
-        # the samples themselves of a few units of one latent layer of a fused call, gathered on the device out of the same ring
-        # (cloud.py): None = off, or dict(begin=0, stride=1, layer=l, units=(u0, u1, ...) | None) with 1..32 distinct units (None =
-        # every unit of a layer at most 32 wide).  The result is a cloud.Cloud in mcpc_last_cloud, fp32 [n, B, d] ON THE ENGINE'S
-        # DEVICE (also for a model built on the CPU): the input of cloud.kl_divergence, the nearest-neighbour KL estimate between
-        # the clouds of two calls (the reference's figure_5).  Composes with the other six (one ring serves all seven).  A request
-        # whose cloud would take more than mcpc_cloud_max_bytes is a ValueError before anything runs.
+        # layer=l, units=(u0, ...) | None, 1..32 distinct units -> cloud.Cloud, fp32 [n, B, d] ON THE ENGINE'S DEVICE (also for a model
+        # built on the CPU): the input of cloud.kl_divergence
         self.mcpc_cloud = None
         self.mcpc_last_cloud = None
         self.mcpc_cloud_max_bytes = 1 << 30
-        # the rolling-window variability of a fused call, accumulated on the device out of the same ring (rolling.py): None = off, or
-        # dict(begin=0, stride=1, layers=(), outputs=None | "identity" | "sigmoid", window=W, every=1, pool="all" | None, carry=None)
-        # with W >= 2.  The result is a rolling.Rolling in mcpc_last_rolling: per every-th full window of W samples the mean and spread
-        # across the (chain, unit) series of their rolling standard deviation, and with pool=None the variance of every series; carry=
-        # (the Rolling of an earlier call) continues that call's stream, so that a window runs across the boundary of the two calls.
-        # Composes with the other seven (one ring serves all eight).  A request whose state, workspace and result would take more than
-        # mcpc_rolling_max_bytes is a ValueError before anything runs.
+        # layers=(), outputs=None | "identity" | "sigmoid", window=W >= 2, every=1, pool="all" | None, carry=None | the Rolling of an
+        # earlier call, whose stream this call continues -> rolling.Rolling
         self.mcpc_rolling = None
         self.mcpc_last_rolling = None
         self.mcpc_rolling_max_bytes = 2 << 30
-        # posterior moments (and covariances) of the ERROR UNITS eps_l = x_l - mu_l or the PREDICTIONS mu_l of a fused call (errors.py):
-        # None = off, or dict(begin=0, stride=1, layers=(), quantity="error" | "prediction", outputs=None | "error" | "prediction",
-        # variance=True, covariance=None | "chain" | "chains").  The requested layers and the layers their predictions read go through
-        # the same ring; after each slice Engine.prediction_errors evaluates the slice's samples into derived records on the device and
-        # moments_accumulate / cov_accumulate reduce those.  The result is an errors.Errors in mcpc_last_errors; composes with the other
-        # eight.  A request whose derived buffers, sums and covariance result would take more than mcpc_errors_max_bytes is a
-        # ValueError before anything runs.
+        # layers=(), quantity="error" | "prediction", outputs=None | "error" | "prediction", variance=True, covariance=None | "chain" |
+        # "chains" -> errors.Errors, of the error units eps_l = x_l - mu_l or the predictions mu_l
         self.mcpc_errors = None
         self.mcpc_last_errors = None
         self.mcpc_errors_max_bytes = 2 << 30
@@ -514,68 +484,8 @@ class PCTrainer(object):
         plan, why_not_fused = self._plan(inputs, loss_fn, loss_fn_kwargs, is_unwrap_inputs, is_optimize_inputs,
                                          callback_after_backward, callback_after_t, callback_after_t_kwargs,
                                          backward_kwargs, is_clear_energy_after_use, is_return_batchelement_loss)
-        if self.mcpc_moments is not None:
-            from .. import moments as _moments
-            if plan is None:
-                raise NotImplementedError("mcpc_moments is set, and this call runs on the generic torch loop ({}): posterior moments are "
-                                          "accumulated by the fused HIP loop only".format(why_not_fused))
-            plan["moments"] = _moments.validate_spec(self.mcpc_moments, self._T, len(plan["net"].sizes), plan["net"].n_out)
-        if self.mcpc_chain_energies is not None:
-            from .. import chain_energies as _chain_energies
-            if plan is None:
-                raise NotImplementedError("mcpc_chain_energies is set, and this call runs on the generic torch loop ({}): per-chain energies "
-                                          "are evaluated out of the fused HIP loop's record ring only".format(why_not_fused))
-            plan["chain_energies"] = _chain_energies.validate_spec(self.mcpc_chain_energies, self._T)
-        if self.mcpc_covariance is not None:
-            from .. import covariance as _covariance
-            if plan is None:
-                raise NotImplementedError("mcpc_covariance is set, and this call runs on the generic torch loop ({}): posterior covariances "
-                                          "are accumulated by the fused HIP loop only".format(why_not_fused))
-            plan["covariance"] = _covariance.validate_spec(self.mcpc_covariance, self._T, len(plan["net"].sizes), plan["net"].n_out,
-                                                           plan["net"].sizes, plan["B"], self.mcpc_covariance_max_bytes)
-        if self.mcpc_histogram is not None:
-            from .. import histogram as _histogram
-            if plan is None:
-                raise NotImplementedError("mcpc_histogram is set, and this call runs on the generic torch loop ({}): posterior histograms "
-                                          "are counted by the fused HIP loop only".format(why_not_fused))
-            plan["histogram"] = _histogram.validate_spec(self.mcpc_histogram, self._T, len(plan["net"].sizes), plan["net"].n_out,
-                                                         plan["net"].sizes, plan["B"], self.mcpc_histogram_max_bytes)
-        if self.mcpc_autocovariance is not None:
-            from .. import autocovariance as _autocovariance
-            if plan is None:
-                raise NotImplementedError("mcpc_autocovariance is set, and this call runs on the generic torch loop ({}): lagged "
-                                          "autocovariances are accumulated by the fused HIP loop only".format(why_not_fused))
-            plan["autocovariance"] = _autocovariance.validate_spec(self.mcpc_autocovariance, self._T, len(plan["net"].sizes),
-                                                                   plan["net"].n_out, plan["net"].sizes, plan["B"],
-                                                                   self.mcpc_autocovariance_max_bytes)
-        if self.mcpc_probe is not None:
-            from .. import probe as _probe
-            if plan is None:
-                raise NotImplementedError("mcpc_probe is set, and this call runs on the generic torch loop ({}): the posterior of a "
-                                          "probe is accumulated by the fused HIP loop only".format(why_not_fused))
-            plan["probe"] = _probe.validate_spec(self.mcpc_probe, self._T, len(plan["net"].sizes), plan["net"].sizes, plan["B"])
-        if self.mcpc_cloud is not None:
-            from .. import cloud as _cloud
-            if plan is None:
-                raise NotImplementedError("mcpc_cloud is set, and this call runs on the generic torch loop ({}): the sample cloud is "
-                                          "gathered by the fused HIP loop only".format(why_not_fused))
-            plan["cloud"] = _cloud.validate_spec(self.mcpc_cloud, self._T, len(plan["net"].sizes), plan["net"].sizes, plan["B"],
-                                                 self.mcpc_cloud_max_bytes)
-        if self.mcpc_rolling is not None:
-            from .. import rolling as _rolling
-            if plan is None:
-                raise NotImplementedError("mcpc_rolling is set, and this call runs on the generic torch loop ({}): the rolling "
-                                          "variability is accumulated by the fused HIP loop only".format(why_not_fused))
-            plan["rolling"] = _rolling.validate_spec(self.mcpc_rolling, self._T, len(plan["net"].sizes), plan["net"].n_out,
-                                                     plan["net"].sizes, plan["B"], self.mcpc_rolling_max_bytes)
-        if self.mcpc_errors is not None:
-            from .. import errors as _errors
-            if plan is None:
-                raise NotImplementedError("mcpc_errors is set, and this call runs on the generic torch loop ({}): prediction errors "
-                                          "are evaluated out of the fused HIP loop's record ring only".format(why_not_fused))
-            plan["errors"] = _errors.validate_spec(self.mcpc_errors, self._T, len(plan["net"].sizes), plan["net"].n_out,
-                                                   plan["net"].sizes, plan["B"], plan["loss"].kind != L.LOSS_NONE,
-                                                   self.mcpc_errors_max_bytes)
+        # the statistics asked of this call (ring.REQUESTS): validated into the plan, or refused where the fused loop does not run
+        ring.validate(self, plan, self._T, runs_on=None if plan is not None else "on the generic torch loop ({})".format(why_not_fused))
         if plan is None:
             # outside what the kernels express: the package's generic torch loop (generic_loop.py), loudly, on the device the model
             # lives on ("must work, need not be fast").  It is no way around a missing GPU: without a visible HIP device
@@ -610,33 +520,8 @@ class PCTrainer(object):
             # call is replayed step-wise with the trainer's own persistent torch optimizer
             plan["mode"] = "stepwise"
             plan["why_stepwise"] = "Adam state of optimizer_x carried over from the previous call"
-        if plan["mode"] != "fused" and self.mcpc_moments is not None:
-            raise NotImplementedError("mcpc_moments is set, and this call runs step by step ({}): posterior moments are accumulated by "
-                                      "the fused HIP loop only".format(plan["why_stepwise"]))
-        if plan["mode"] != "fused" and self.mcpc_chain_energies is not None:
-            raise NotImplementedError("mcpc_chain_energies is set, and this call runs step by step ({}): per-chain energies are "
-                                      "evaluated out of the fused HIP loop's record ring only".format(plan["why_stepwise"]))
-        if plan["mode"] != "fused" and self.mcpc_covariance is not None:
-            raise NotImplementedError("mcpc_covariance is set, and this call runs step by step ({}): posterior covariances are "
-                                      "accumulated by the fused HIP loop only".format(plan["why_stepwise"]))
-        if plan["mode"] != "fused" and self.mcpc_histogram is not None:
-            raise NotImplementedError("mcpc_histogram is set, and this call runs step by step ({}): posterior histograms are "
-                                      "counted by the fused HIP loop only".format(plan["why_stepwise"]))
-        if plan["mode"] != "fused" and self.mcpc_autocovariance is not None:
-            raise NotImplementedError("mcpc_autocovariance is set, and this call runs step by step ({}): lagged autocovariances are "
-                                      "accumulated by the fused HIP loop only".format(plan["why_stepwise"]))
-        if plan["mode"] != "fused" and self.mcpc_probe is not None:
-            raise NotImplementedError("mcpc_probe is set, and this call runs step by step ({}): the posterior of a probe is "
-                                      "accumulated by the fused HIP loop only".format(plan["why_stepwise"]))
-        if plan["mode"] != "fused" and self.mcpc_cloud is not None:
-            raise NotImplementedError("mcpc_cloud is set, and this call runs step by step ({}): the sample cloud is gathered by the "
-                                      "fused HIP loop only".format(plan["why_stepwise"]))
-        if plan["mode"] != "fused" and self.mcpc_rolling is not None:
-            raise NotImplementedError("mcpc_rolling is set, and this call runs step by step ({}): the rolling variability is "
-                                      "accumulated by the fused HIP loop only".format(plan["why_stepwise"]))
-        if plan["mode"] != "fused" and self.mcpc_errors is not None:
-            raise NotImplementedError("mcpc_errors is set, and this call runs step by step ({}): prediction errors are evaluated "
-                                      "out of the fused HIP loop's record ring only".format(plan["why_stepwise"]))
+        if plan["mode"] != "fused":
+            ring.validate(self, plan, self._T, runs_on="step by step ({})".format(plan["why_stepwise"]))
         if plan["mode"] == "fused":
             self.last_call_mode = "fused"
             with _few_cpu_threads(plan["staged"]):
@@ -967,25 +852,17 @@ class PCTrainer(object):
             energy_mode=L.ENERGY_ALL if is_return_results_every_t else L.ENERGY_LAST)
         host_step_bytes = 4 * plan["B"] * sum(n for n, on in zip(net.sizes, rec_layers) if on)
         self.last_record_slices = 0
-        mom, ce, cov, hist = plan.get("moments"), plan.get("chain_energies"), plan.get("covariance"), plan.get("histogram")
-        acov, probe, cloud, roll = plan.get("autocovariance"), plan.get("probe"), plan.get("cloud"), plan.get("rolling")
-        perr = plan.get("errors")
-        if (mom is not None or ce is not None or cov is not None or hist is not None or acov is not None or probe is not None
-                or cloud is not None or roll is not None or perr is not None):
-            # posterior moments / per-chain energies / covariances / histograms / autocovariances / a probe / a cloud / prediction
-            # errors: the call runs as slices whatever its size, and the records they ask for are reduced on the device
-            ce_inputs = None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous())
-            res, last_mom, last_ce = self._run_fused_sliced(
-                eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, is_return_outputs and net.n_out > 0,
-                every_t=is_return_results_every_t, mom=mom, ce=ce, ce_inputs=ce_inputs, cov=cov, hist=hist, acov=acov, probe=probe,
-                cloud=cloud, roll=roll, perr=perr)
-            if mom is not None:
-                self.mcpc_last_moments = last_mom
-            if ce is not None:
-                self.mcpc_last_chain_energies = last_ce
+        if any(row.key in plan for row in ring.REQUESTS):
+            # statistics of the call: it runs as slices whatever its size, and the records they ask for are reduced on the device
+            call = ring.Call(trainer=self, eng=eng, net=net, model_device=plan["model_device"],
+                             inputs=None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous()),
+                             loss_kw=dict(loss_kind=loss.kind, loss_var=loss.var, mask_start=loss.mask_start))
+            res = self._run_fused_sliced(eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes,
+                                         is_return_outputs and net.n_out > 0, every_t=is_return_results_every_t,
+                                         reducers=ring.reducers(plan, call))
         elif any(rec_layers) and n_rec == T and T * host_step_bytes > self.mcpc_record_chunk_bytes:
-            res, _, _ = self._run_fused_sliced(eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes,
-                                               is_return_outputs and net.n_out > 0)
+            res = self._run_fused_sliced(eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes,
+                                         is_return_outputs and net.n_out > 0)
         else:
             res = eng.run(T, acc_reset=acc_reset, rec_begin=rec_begin, rec_stride=1, rec_count=n_rec if any_rec else 0,
                           rec_x=rec_layers, rec_out=is_return_outputs and net.n_out > 0, **run_kw)
@@ -1010,320 +887,78 @@ class PCTrainer(object):
         return self._collect_results(plan, res, T, is_return_results_every_t, is_return_outputs,
                                      is_return_representations, is_return_xs, loss_fn)
 
-    def _run_fused_sliced(self, eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, rec_out, every_t=True, mom=None,
-                          ce=None, ce_inputs=None, cov=None, hist=None, acov=None, probe=None, cloud=None, roll=None, perr=None):
-        """A call whose every-step trajectory would not fit the record budget on the device, or whose records feed `mcpc_moments`:
-        the same T steps as slices of one `mcpc_run` each (slicing does not change a bit of the trajectories,
-        tests/test_gpu_fullsize.py).  The latent records of a slice go to one half of a two-buffer device ring.  Records the caller's
+    def _run_fused_sliced(self, eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes, rec_out, every_t=True, reducers=()):
+        """A call whose every-step trajectory would not fit the record budget on the device, or whose records feed `reducers`
+        (ring.py): the same T steps as slices of one `mcpc_run` each (slicing does not change a bit of the trajectories,
+        tests/test_gpu_fullsize.py).  The records of a slice go to one half of a two-buffer device ring.  Records the caller's
         keywords ask for (`rec_layers`, `rec_out`) are copied to pinned host memory on a side stream while the next slice computes;
-        outputs stay on the device, as in the reference (live tensors, pc_trainer.py:733,770).  Records `mom` (a validated
-        `mcpc_moments`) asks for are reduced on the device by `moments_accumulate` after each slice, out of the same ring rows, and
-        are neither copied nor kept unless the caller asked too.  With `every_t` false the caller gets the last step's records and
-        energies only, as from an unsliced call.  With `ce` (a validated `mcpc_chain_energies`) every latent layer goes through the
-        ring and `Engine.chain_energies` evaluates the steps asked for out of its rows after each slice, on the call's own stream,
-        under the slicing rules of `mom`.  With `cov` (a validated `mcpc_covariance`) its layers and read-out go through the ring too
-        and `cov_accumulate` / `moments_accumulate` add their outer products and sums after each slice, on the call's own stream, under
-        the same rules; the result is left in `mcpc_last_covariance`.  With `hist` (a validated `mcpc_histogram`) its layers and
-        read-out go through the ring as well and `hist_accumulate` counts them after each slice, on the call's own stream, under the
-        same rules; the result is left in `mcpc_last_histogram`.  With `acov` (a validated `mcpc_autocovariance`) its layers and
-        read-out go through the ring likewise and `acov_accumulate` adds their lagged products after each slice, in step order, on the
-        call's own stream; the samples seen so far are counted per block and the kernel's own window carries the lags across slices;
-        the result is left in `mcpc_last_autocovariance`.  With `probe` (a validated `mcpc_probe`) its layer goes through the ring too and
-        one `probe_accumulate` after each slice, on the call's own stream, adds the link values, votes and entropies of the slice's
-        samples (overwriting in the first slice that holds one); the result is left in `mcpc_last_probe`.  With `cloud` (a validated
-        `mcpc_cloud`) its layer goes through the ring as well and after each slice the slice's samples of the chosen units are gathered
-        (`index_select`) into one preallocated device tensor on the call's own stream; the result is left in `mcpc_last_cloud`, on the
-        engine's device.  With `roll` (a validated `mcpc_rolling`) its layers and read-out go through the ring likewise and
-        `roll_accumulate` feeds each block's samples to its rolling variance after each slice, in step order, on the call's own stream;
-        the samples seen and the rows emitted so far are counted per block, and the kernel's own history carries a window across
-        slices (and, with `carry=`, across calls); the result is left in `mcpc_last_rolling`.  With `perr` (a validated `mcpc_errors`)
-        its layers and the layers their predictions read go through the ring too; after each slice the slice's samples (gathered first
-        when the stride is above 1) are evaluated by `Engine.prediction_errors` into one set of derived buffers on the call's own
-        stream, and `moments_accumulate` / `cov_accumulate` reduce those under the slicing rules of `mom`; the result is left in
-        `mcpc_last_errors`.  Returns (RunResult, Moments or None, ChainEnergies or None)."""
-        from ..engine import (RunResult, moments_accumulate, cov_accumulate, cov_workspace_bytes, hist_accumulate, acov_accumulate,
-                              probe_accumulate, roll_accumulate, roll_workspace_bytes)
+        outputs stay on the device, as in the reference (live tensors, pc_trainer.py:733,770).  Records the reducers ask for are
+        reduced on the device after each slice, out of the same ring rows, in the order of the list, and are neither copied nor kept
+        unless the caller asked too; each result is left in its reducer's trainer attribute.  With `every_t` false the caller gets
+        the last step's records and energies only, as from an unsliced call.  Returns the RunResult."""
+        from ..engine import RunResult
+        from ..sampling import slice_bounds
         dev, B = plan["device"], plan["B"]
-        nl = len(net.sizes)
-        mom_layers = [mom is not None and l in mom.layers for l in range(nl)]
-        mom_out = mom is not None and mom.outputs is not None
-        cov_layers = [cov is not None and l in cov.layers for l in range(nl)]
-        cov_out = cov is not None and cov.outputs is not None
-        hist_layers = [hist is not None and l in hist.layers for l in range(nl)]
-        hist_out = hist is not None and hist.outputs is not None
-        acov_layers = [acov is not None and l in acov.layers for l in range(nl)]
-        acov_out = acov is not None and acov.outputs is not None
-        probe_layers = [probe is not None and l == probe.layer for l in range(nl)]
-        cloud_layers = [cloud is not None and l == cloud.layer for l in range(nl)]
-        roll_layers = [roll is not None and l in roll.layers for l in range(nl)]
-        roll_out = roll is not None and roll.outputs is not None
-        perr_layers = [perr is not None and l in perr.reads for l in range(nl)]
-        ring_layers = [a or b_ or c_ or d_ or e_ or f_ or g_ or h_ or i_ or ce is not None
-                       for a, b_, c_, d_, e_, f_, g_, h_, i_ in zip(rec_layers, mom_layers, cov_layers, hist_layers, acov_layers,
-                                                                    probe_layers, cloud_layers, roll_layers, perr_layers)]
-        reduced = (mom is not None or ce is not None or cov is not None or hist is not None or acov is not None or probe is not None
-                   or cloud is not None or roll is not None or perr is not None)
+        read = set().union(*(r.layers for r in reducers))
+        ring_layers = [on or l in read for l, on in enumerate(rec_layers)]
+        reads_out = any(r.reads_out for r in reducers)
         out_direct = rec_out and every_t                     # every step's outputs are kept anyway: slices write them in place
-        ring_out = (rec_out or mom_out or cov_out or hist_out or acov_out or roll_out) and not out_direct
+        ring_out = (rec_out or reads_out) and not out_direct
         S = T
         if any(rec_layers) and every_t:
             S = min(S, self.mcpc_record_chunk_bytes // max(2 * host_step_bytes, 1))
-        if reduced:
-            # one half of the ring is a chunk of at most mcpc_moments_chunk_bytes
-            step_bytes = 4 * B * (sum(n for n, on in zip(net.sizes, ring_layers) if on) + (net.n_out if ring_out or mom_out or cov_out or hist_out or acov_out or roll_out else 0))
-            if perr is not None:
-                step_bytes += -(-4 * B * perr.D // perr.stride)          # the derived records of a step's share of the samples
+        if reducers:
+            # one half of the ring is a chunk of at most mcpc_moments_chunk_bytes; the read-out counts whenever a reducer reads it
+            step_bytes = 4 * B * (sum(n for n, on in zip(net.sizes, ring_layers) if on) + (net.n_out if ring_out or reads_out else 0))
+            step_bytes += sum(r.step_bytes(B) for r in reducers)
             S = min(S, self.mcpc_moments_chunk_bytes // max(step_bytes, 1))
         S = max(1, S)
         # A slice boundary inside the window that accumulates parameter gradients would regroup their fp32 sums (one Hebbian flush and
-        # one fold of Linear 0's sum per run; tests/test_gpu_widening.py).  A call with moments must leave param.grad bitwise as
+        # one fold of Linear 0's sum per run; tests/test_gpu_widening.py).  A call with reducers must leave param.grad bitwise as
         # without them, so it keeps that window in ONE slice: the ring is then as long as the window, whatever the chunk budget says.
-        keep = (run_kw["acc_begin"], run_kw["acc_end"]) if reduced and run_kw["acc_end"] > run_kw["acc_begin"] else None
-        bounds, t0 = [], 0
-        while t0 < T:
-            n = min(S, T - t0)
-            if keep is not None and keep[0] < t0 + n < keep[1]:              # it would end inside the window
-                n = keep[0] - t0 if t0 < keep[0] else keep[1] - t0
-            bounds.append((t0, n))
-            t0 += n
+        keep = (run_kw["acc_begin"], run_kw["acc_end"]) if reducers and run_kw["acc_end"] > run_kw["acc_begin"] else None
+        bounds = slice_bounds(T, S, keep)
         S = max(n for _, n in bounds)
-        if perr is not None:
-            from ..errors import check_bytes as perr_check_bytes
-            perr_check_bytes(perr, B, perr.max_samples(S), self.mcpc_errors_max_bytes)
+        for r in reducers:
+            r.start(B, dev, S)
         rows = T if every_t else 1
         host = [torch.empty(rows, B, n, dtype=torch.float32, pin_memory=True) if on else None for n, on in zip(net.sizes, rec_layers)]
-        ring = [[torch.empty(S, B, n, dtype=torch.float32, device=dev) if on else None for n, on in zip(net.sizes, ring_layers)]
-                for _ in range(2)]
+        ring_x = [[torch.empty(S, B, n, dtype=torch.float32, device=dev) if on else None for n, on in zip(net.sizes, ring_layers)]
+                  for _ in range(2)]
         ring_o = [torch.empty(S, B, net.n_out, dtype=torch.float32, device=dev) if ring_out else None for _ in range(2)]
         out_full = torch.empty(rows, B, net.n_out, dtype=torch.float32, device=dev) if rec_out else None
         energies = torch.zeros(rows, L.ENERGY_COLS, dtype=torch.float64, device=dev)
-        acc = None
-        if mom is not None:
-            def zeros(n):
-                return torch.zeros(B, n, dtype=torch.float64, device=dev)
-            acc = dict(x_sum=[zeros(n) if on else None for n, on in zip(net.sizes, mom_layers)],
-                       x_sumsq=[zeros(n) if on and mom.variance else None for n, on in zip(net.sizes, mom_layers)],
-                       out_sum=zeros(net.n_out) if mom_out else None,
-                       out_sumsq=zeros(net.n_out) if mom_out and mom.variance else None)
         main, side = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
         drained = [None, None]                              # event: the side stream has finished with this half of the ring
         acc_b = run_kw["acc_begin"]
         run_kw = dict(run_kw, energy_mode=L.ENERGY_ALL if every_t else L.ENERGY_LAST)
-        reduce_on_side = mom is not None and self.mcpc_moments_side_stream
-
-        def reduce(t0, n, half):
-            first, cnt = mom.chunk(t0, n)
-            if cnt == 0:
-                return
-            for l in range(nl):
-                if mom_layers[l]:
-                    moments_accumulate(ring[half][l], first, mom.stride, cnt, acc["x_sum"][l], acc["x_sumsq"][l], accumulate=True)
-            if mom_out:
-                src = out_full[t0:t0 + n] if out_direct else ring_o[half]
-                moments_accumulate(src, first, mom.stride, cnt, acc["out_sum"], acc["out_sumsq"], transform=mom.outputs,
-                                   accumulate=True)
-
-        cov_acc = None
-        if cov is not None:
-            D = cov.D
-            cov_widths = [w for _, _, w in cov.columns]
-            cov_xf = ["identity"] * len(cov.layers) + ([cov.outputs] if cov_out else [])
-            cov_acc = dict(outer=torch.zeros(*((D, D) if cov.pooled else (B, D, D)), dtype=torch.float64, device=dev),
-                           # the first-order sums of a block, contiguous for moments_accumulate; gathered into `sum` at the end
-                           part=[torch.zeros(B, w, dtype=torch.float64, device=dev) for w in cov_widths],
-                           ws=torch.empty(max(cov_workspace_bytes(B, cov_widths), 8), dtype=torch.uint8, device=dev)
-                           if cov.pooled else None)
-
-        def reduce_cov(t0, n, half):
-            first, cnt = cov.chunk(t0, n)
-            if cnt == 0:
-                return
-            blocks = [ring[half][l] for l in cov.layers]
-            if cov_out:
-                blocks.append(out_full[t0:t0 + n] if out_direct else ring_o[half])
-            for blk, part, xf in zip(blocks, cov_acc["part"], cov_xf):
-                moments_accumulate(blk, first, cov.stride, cnt, part, None, transform=xf, accumulate=True)
-            cov_accumulate(blocks, first, cov.stride, cnt, cov_acc["outer"], transforms=cov_xf, pool=cov.pooled, accumulate=True,
-                           workspace=cov_acc["ws"])
-
-        hist_acc = None
-        if hist is not None:
-            hist_xf = ["identity"] * len(hist.layers) + ([hist.outputs] if hist_out else [])
-            hist_acc = [torch.zeros(*((w, len(e) + 2) if hist.pooled else (B, w, len(e) + 2)), dtype=torch.int64, device=dev)
-                        for (_, w), e in zip(hist.columns, hist.edges)]
-
-        def reduce_hist(t0, n, half):
-            first, cnt = hist.chunk(t0, n)
-            if cnt == 0:
-                return
-            blocks = [ring[half][l] for l in hist.layers]
-            if hist_out:
-                blocks.append(out_full[t0:t0 + n] if out_direct else ring_o[half])
-            for blk, e, counts, xf in zip(blocks, hist.edges, hist_acc, hist_xf):
-                hist_accumulate(blk, first, hist.stride, cnt, e, counts, transform=xf, pool=hist.pooled, accumulate=True)
-
-        acov_state = None
-        if acov is not None:
-            acov_xf = ["identity"] * len(acov.layers) + ([acov.outputs] if acov_out else [])
-            K = acov.max_lag
-            acov_state = [dict(lagged=torch.zeros(B, w, K + 1, dtype=torch.float64, device=dev),
-                               sum=torch.zeros(B, w, dtype=torch.float64, device=dev),
-                               window=torch.zeros(K, B, w, dtype=torch.float32, device=dev),
-                               head=torch.zeros(K, B, w, dtype=torch.float32, device=dev), n_seen=0) for _, w in acov.columns]
-
-        def reduce_acov(t0, n, half):
-            first, cnt = acov.chunk(t0, n)
-            if cnt == 0:
-                return
-            blocks = [ring[half][l] for l in acov.layers]
-            if acov_out:
-                blocks.append(out_full[t0:t0 + n] if out_direct else ring_o[half])
-            for blk, st, xf in zip(blocks, acov_state, acov_xf):
-                acov_accumulate(blk, first, acov.stride, cnt, acov.max_lag, st["n_seen"], st["lagged"], st["sum"], st["window"],
-                                st["head"], transform=xf)
-                st["n_seen"] += cnt
-
-        roll_state = roll_pooled = roll_elem = roll_ws = None
-        if roll is not None:
-            from ..rolling import new_state as roll_new_state
-            roll_xf = ["identity"] * len(roll.layers) + ([roll.outputs] if roll_out else [])
-            roll_state = roll_new_state(roll, B, dev)
-            for st in roll_state:
-                st["row"] = 0                                    # rows this call has emitted for the block
-            roll_pooled = [torch.zeros(roll.rows, 4, dtype=torch.float64, device=dev) for _ in roll.columns]
-            roll_elem = [torch.zeros(roll.rows, B, w, dtype=torch.float64, device=dev) if roll.pool is None else None
-                         for _, w in roll.columns]
-            roll_ws = torch.empty(max(max(roll_workspace_bytes(B, w, min(S, roll.n)) for _, w in roll.columns), 8), dtype=torch.uint8,
-                                  device=dev)
-
-        def reduce_roll(t0, n, half):
-            first, cnt = roll.chunk(t0, n)
-            if cnt == 0:
-                return
-            blocks = [ring[half][l] for l in roll.layers]
-            if roll_out:
-                blocks.append(out_full[t0:t0 + n] if out_direct else ring_o[half])
-            for blk, st, xf, pooled, elem in zip(blocks, roll_state, roll_xf, roll_pooled, roll_elem):
-                r0 = st["row"]
-                st["row"] += roll_accumulate(blk, first, roll.stride, cnt, roll.window, roll.every, st["n_seen"], st["s1"], st["s2"],
-                                             st["hist"], out_elem=None if elem is None else elem[r0:], out_pool=pooled[r0:],
-                                             workspace=roll_ws, transform=xf)
-                st["n_seen"] += cnt
-
-        probe_state = None
-        if probe is not None:
-            from ..probe import new_state
-            probe_w, probe_b = probe.on(dev)
-            probe_state = new_state(B, probe.C, probe.link, dev)
-            probe_state["seen"] = False
-
-        def reduce_probe(t0, n, half):
-            first, cnt = probe.chunk(t0, n)
-            if cnt == 0:
-                return
-            st = probe_state
-            probe_accumulate(ring[half][probe.layer], first, probe.stride, cnt, probe_w, probe_b, probe.link, st["psum"], st["psumsq"],
-                             st["votes"], st["entsum"], accumulate=st["seen"])
-            st["seen"] = True
-
-        cloud_points = cloud_units = None
-        if cloud is not None:
-            cloud_points = torch.empty(cloud.n, B, cloud.d, dtype=torch.float32, device=dev)
-            cloud_units = torch.tensor(cloud.units, dtype=torch.int64, device=dev)
-
-        def gather_cloud(t0, n, half):
-            first, cnt = cloud.chunk(t0, n)
-            if cnt == 0:
-                return
-            k0 = (t0 + first - cloud.begin) // cloud.stride          # index of the slice's first sample among all of them
-            rows = ring[half][cloud.layer][first:first + (cnt - 1) * cloud.stride + 1:cloud.stride]
-            torch.index_select(rows, 2, cloud_units, out=cloud_points[k0:k0 + cnt])
-
-        ce_table = torch.empty(ce.n, B, L.ENERGY_COLS, dtype=torch.float64, device=dev) if ce is not None else None
-        ce_kw = dict(loss_kind=run_kw["loss_kind"], loss_var=run_kw["loss_var"], mask_start=run_kw["mask_start"],
-                     max_rows=self.mcpc_chain_energies_max_rows)
-
-        def evaluate(t0, n, half):
-            first, cnt = ce.chunk(t0, n)
-            if cnt == 0:
-                return
-            k0 = (t0 + first - ce.begin) // ce.stride                # index of the slice's first evaluated step among all of them
-            if ce.stride == 1:
-                eng.chain_energies(ce_inputs, [r_[first:first + cnt] for r_ in ring[half]], out=ce_table[k0:k0 + cnt], **ce_kw)
-            else:
-                for k in range(cnt):
-                    row = first + k * ce.stride
-                    eng.chain_energies(ce_inputs, [r_[row:row + 1] for r_ in ring[half]], out=ce_table[k0 + k:k0 + k + 1], **ce_kw)
-
-        perr_bufs = perr_sum = perr_sumsq = perr_outer = perr_ws = None
-        if perr is not None:
-            perr_rows = perr.max_samples(S)
-            perr_bufs = {name: torch.empty(perr_rows, B, w, dtype=torch.float32, device=dev) for name, _, w in perr.columns}
-            perr_sum = {name: torch.zeros(B, w, dtype=torch.float64, device=dev) for name, _, w in perr.columns}
-            perr_sumsq = {name: torch.zeros(B, w, dtype=torch.float64, device=dev) if perr.variance else None
-                          for name, _, w in perr.columns}
-            if perr.covariance is not None:
-                D = perr.D
-                perr_outer = torch.zeros(*((D, D) if perr.pooled else (B, D, D)), dtype=torch.float64, device=dev)
-                if perr.pooled:
-                    perr_ws = torch.empty(max(cov_workspace_bytes(B, [w for _, _, w in perr.columns]), 8), dtype=torch.uint8, device=dev)
-            perr_kw = dict(layers=perr.layers, quantity=perr.quantity, outputs=perr.outputs, loss_kind=run_kw["loss_kind"],
-                           loss_var=run_kw["loss_var"], mask_start=run_kw["mask_start"], max_rows=self.mcpc_chain_energies_max_rows)
-
-        def reduce_perr(t0, n, half):
-            first, cnt = perr.chunk(t0, n)
-            if cnt == 0:
-                return
-            # the slice's samples alone (a copy when the stride skips steps): the derived buffers hold samples only
-            stop = first + (cnt - 1) * perr.stride + 1
-            recs = [ring[half][l][first:stop:perr.stride].contiguous() if on else None for l, on in enumerate(perr_layers)]
-            eng.prediction_errors(ce_inputs, recs, out={name: buf[:cnt] for name, buf in perr_bufs.items()}, **perr_kw)
-            for name, buf in perr_bufs.items():
-                moments_accumulate(buf, 0, 1, cnt, perr_sum[name], perr_sumsq[name], accumulate=True)
-            if perr_outer is not None:
-                cov_accumulate(list(perr_bufs.values()), 0, 1, cnt, perr_outer, pool=perr.pooled, accumulate=True, workspace=perr_ws)
-
+        on_side = [r for r in reducers if r.side_stream]
+        on_main = [r for r in reducers if not r.side_stream]
         n_slices = 0
         for t0, n in bounds:
             half = n_slices & 1
             last = t0 + n == T
+            view = ring.RingView(x=ring_x[half], out=out_full[t0:t0 + n] if out_direct else ring_o[half])
             if drained[half] is not None:
                 main.wait_event(drained[half])
             eng.run(T, t_begin=t0, n_steps=n, adam_step0=t0, energies_out=energies,
                     acc_reset=acc_reset and (t0 <= acc_b < t0 + n),
-                    rec_begin=t0, rec_stride=1, rec_count=n, rec_x=ring_layers, rec_x_bufs=ring[half],
-                    rec_out=out_direct or ring_out,
-                    rec_out_buf=out_full[t0:t0 + n] if out_direct else ring_o[half], **run_kw)
-            if mom is not None and not reduce_on_side:
-                reduce(t0, n, half)
-            if ce is not None:
-                evaluate(t0, n, half)
-            if cov is not None:
-                reduce_cov(t0, n, half)
-            if hist is not None:
-                reduce_hist(t0, n, half)
-            if acov is not None:
-                reduce_acov(t0, n, half)
-            if probe is not None:
-                reduce_probe(t0, n, half)
-            if cloud is not None:
-                gather_cloud(t0, n, half)
-            if roll is not None:
-                reduce_roll(t0, n, half)
-            if perr is not None:
-                reduce_perr(t0, n, half)
+                    rec_begin=t0, rec_stride=1, rec_count=n, rec_x=ring_layers, rec_x_bufs=view.x,
+                    rec_out=out_direct or ring_out, rec_out_buf=view.out, **run_kw)
+            for r in on_main:
+                r.reduce(t0, n, view)
             if ring_out and rec_out and last:
                 out_full[0].copy_(ring_o[half][n - 1])       # (not every_t: the last step's outputs)
             to_host = any(rec_layers) and (every_t or last)
-            if to_host or reduce_on_side:
+            if to_host or on_side:
                 filled = torch.cuda.Event()
                 filled.record(main)
                 side.wait_event(filled)
                 with torch.cuda.stream(side):
-                    if reduce_on_side:
-                        reduce(t0, n, half)
+                    for r in on_side:
+                        r.reduce(t0, n, view)
                     if to_host:
-                        for h, d in zip(host, ring[half]):
+                        for h, d in zip(host, view.x):
                             if h is not None:
                                 if every_t:
                                     h[t0:t0 + n].copy_(d[:n], non_blocking=True)
@@ -1334,56 +969,9 @@ class PCTrainer(object):
             n_slices += 1
         side.synchronize()
         self.last_record_slices = n_slices
-        result = None
-        if mom is not None:
-            from ..moments import Moments
-            md = plan["model_device"]
-
-            def back(t):
-                return None if t is None else t.to(md)
-            result = Moments(n=mom.n, x_sum=[back(t) for t in acc["x_sum"]], x_sumsq=[back(t) for t in acc["x_sumsq"]],
-                             out_sum=back(acc["out_sum"]), out_sumsq=back(acc["out_sumsq"]))
-        ce_result = None
-        if ce is not None:
-            from ..chain_energies import from_table
-            ce_result = from_table(ce_table, nl, self._energy_coefficient, ce.steps, plan["model_device"])
-        if cov is not None:
-            from ..covariance import Covariance
-            s = torch.cat(cov_acc["part"], dim=1)
-            if cov.pooled:
-                s = s.sum(dim=0)
-            self.mcpc_last_covariance = Covariance(n=cov.n, B=B, pooled=cov.pooled, columns=list(cov.columns),
-                                                   sum=s.to(plan["model_device"]), outer=cov_acc["outer"].to(plan["model_device"]))
-        if hist is not None:
-            from ..histogram import from_counts
-            self.mcpc_last_histogram = from_counts(hist, B, hist_acc, plan["model_device"])
-        if acov is not None:
-            from ..autocovariance import from_state
-            self.mcpc_last_autocovariance = from_state(acov, B, acov_state, plan["model_device"])
-        if probe is not None:
-            from ..probe import from_state as probe_from_state
-            self.mcpc_last_probe = probe_from_state(probe.n, B, probe.C, probe.link, probe_state, plan["model_device"])
-        if cloud is not None:
-            from ..cloud import Cloud
-            self.mcpc_last_cloud = Cloud(points=cloud_points, units=cloud.units, layer=cloud.layer)
-        if roll is not None:
-            from ..rolling import from_state as roll_from_state
-            for st in roll_state:
-                del st["row"]
-            self.mcpc_last_rolling = roll_from_state(roll, B, roll_state, roll_pooled, roll_elem, plan["model_device"])
-        if perr is not None:
-            from ..covariance import Covariance as _Covariance
-            from ..errors import Errors
-            md = plan["model_device"]
-            pcov = None
-            if perr_outer is not None:
-                s = torch.cat([perr_sum[name] for name, _, _ in perr.columns], dim=1)
-                if perr.pooled:
-                    s = s.sum(dim=0)
-                pcov = _Covariance(n=perr.n, B=B, pooled=perr.pooled, columns=list(perr.columns), sum=s.to(md), outer=perr_outer.to(md))
-            self.mcpc_last_errors = Errors(n=perr.n, sum={k: v.to(md) for k, v in perr_sum.items()},
-                                           sumsq={k: None if v is None else v.to(md) for k, v in perr_sumsq.items()}, covariance=pcov)
-        return RunResult(energies=energies, rec_x=host, rec_out=out_full), result, ce_result
+        for r in reducers:
+            setattr(self, r.attr, r.result())
+        return RunResult(energies=energies, rec_x=host, rec_out=out_full)
 
     def mcpc_state_energies(self, inputs, loss_fn: typing.Callable = None, loss_fn_kwargs: dict = {}):
         """Loss, layer energies and overall of every chain for the CURRENT x of the PCLayers -- what a MAP call leaves -- evaluated on

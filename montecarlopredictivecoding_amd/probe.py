@@ -14,7 +14,7 @@ from typing import Optional
 
 import torch
 
-from .covariance import sample_steps
+from .sampling import SampleWindow, parse_keys, parse_layer, parse_window, sample_steps  # noqa: F401
 
 _KEYS = ("begin", "stride", "layer", "weight", "bias", "linear", "link")
 LINKS = ("identity", "sigmoid", "softmax")
@@ -22,26 +22,13 @@ MAX_CLASSES = 64                                 # include/mcpc.h: MCPC_PROBE_MA
 
 
 @dataclass(frozen=True, eq=False)
-class ProbeSpec:
+class ProbeSpec(SampleWindow):
     """A validated ``mcpc_probe`` request for a call of ``T`` steps.  ``weight`` / ``bias`` are the caller's tensors, detached."""
-    begin: int
-    stride: int
     layer: int
     weight: torch.Tensor
     bias: Optional[torch.Tensor]
     link: str
-    T: int
     C: int
-
-    @property
-    def n(self) -> int:
-        return len(sample_steps(self.begin, self.T, self.stride))
-
-    def chunk(self, t0: int, n_steps: int):
-        """(first, count): the samples among steps t0 .. t0 + n_steps - 1 are rows first, first + stride, ... of a chunk that holds
-        one record per step from t0 on."""
-        f = self.begin if t0 <= self.begin else self.begin + -(-(t0 - self.begin) // self.stride) * self.stride
-        return f - t0, len(range(f, min(t0 + n_steps, self.T), self.stride))
 
     def on(self, device):
         """(W, bias or None) as contiguous fp32 on ``device``: what the kernel reads."""
@@ -54,26 +41,9 @@ def validate_spec(spec, T: int, n_layers: int, sizes, B: int) -> ProbeSpec:
     """``PCTrainer.mcpc_probe`` -> ProbeSpec, or ValueError: not a dict, unknown keys, ``begin`` outside [0, T), ``stride`` < 1, no
     ``layer`` or one out of range, both or neither of ``linear`` and ``weight``, a weight that is not ``[C, sizes[layer]]`` with C in
     1..64, a bias that is not ``[C]``, an unknown link.  Defaults: begin=0, stride=1, bias=None, link="softmax"."""
-    if not isinstance(spec, dict):
-        raise ValueError(f"mcpc_probe: expected a dict or None, got {type(spec).__name__}")
-    unknown = sorted(k for k in spec if k not in _KEYS)
-    if unknown:
-        raise ValueError(f"mcpc_probe: unknown keys {unknown}; known: {list(_KEYS)}")
-    begin, stride = spec.get("begin", 0), spec.get("stride", 1)
-    for name, v in (("begin", begin), ("stride", stride)):
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise ValueError(f"mcpc_probe: {name} must be an int, got {v!r}")
-    if not 0 <= begin < T:
-        raise ValueError(f"mcpc_probe: begin={begin} outside [0, T={T})")
-    if stride < 1:
-        raise ValueError(f"mcpc_probe: stride={stride}, must be at least 1")
-    if "layer" not in spec or spec["layer"] is None:
-        raise ValueError(f"mcpc_probe: layer is required: the PC layer the probe reads, an int in 0..{n_layers - 1}")
-    layer = spec["layer"]
-    if isinstance(layer, bool) or not isinstance(layer, int):
-        raise ValueError(f"mcpc_probe: layer must be an int, got {layer!r}")
-    if not 0 <= layer < n_layers:
-        raise ValueError(f"mcpc_probe: layer index {layer!r} out of range, the model has {n_layers} PC layers (0..{n_layers - 1})")
+    parse_keys("mcpc_probe", spec, _KEYS)
+    begin, stride = parse_window("mcpc_probe", spec, T)
+    layer = parse_layer("mcpc_probe", spec, n_layers, "the probe reads")
     linear, weight, bias = spec.get("linear"), spec.get("weight"), spec.get("bias")
     if linear is not None and (weight is not None or bias is not None):
         raise ValueError("mcpc_probe: both linear and weight / bias are given; pass one of them")

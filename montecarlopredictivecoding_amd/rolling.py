@@ -21,7 +21,8 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from .covariance import human_bytes, sample_steps
+from .sampling import (SampleWindow, column_list, human_bytes, parse_keys, parse_layers, parse_outputs, parse_window,  # noqa: F401
+                       require_columns, sample_steps)
 
 _KEYS = ("begin", "stride", "layers", "outputs", "window", "every", "pool", "carry")
 _OUTPUTS = (None, "identity", "sigmoid")
@@ -38,22 +39,15 @@ def emitted_rows(n_seen: int, n: int, window: int, every: int = 1) -> int:
 
 
 @dataclass(frozen=True, eq=False)
-class RollingSpec:
+class RollingSpec(SampleWindow):
     """A validated ``mcpc_rolling`` request for a call of ``T`` steps."""
-    begin: int
-    stride: int
     layers: Tuple[int, ...]
     outputs: Optional[str]
     window: int
     every: int
     pool: Optional[str]
     carry: Optional["Rolling"]
-    T: int
     columns: Tuple[Tuple[str, int], ...]            # (name, width) of every block, in order: "x0", "x1", ..., "out"
-
-    @property
-    def n(self) -> int:
-        return len(sample_steps(self.begin, self.T, self.stride))
 
     @property
     def n_seen(self) -> int:
@@ -63,12 +57,6 @@ class RollingSpec:
     @property
     def rows(self) -> int:
         return emitted_rows(self.n_seen, self.n, self.window, self.every)
-
-    def chunk(self, t0: int, n_steps: int):
-        """(first, count): the samples among steps t0 .. t0 + n_steps - 1 are rows first, first + stride, ... of a chunk that holds
-        one record per step from t0 on."""
-        f = self.begin if t0 <= self.begin else self.begin + -(-(t0 - self.begin) // self.stride) * self.stride
-        return f - t0, len(range(f, min(t0 + n_steps, self.T), self.stride))
 
     def chunk_rows(self, n_seen: int, count: int) -> int:
         """Rows a chunk of ``count`` samples emits when the stream held ``n_seen`` samples before it."""
@@ -98,41 +86,13 @@ def validate_spec(spec, T: int, n_layers: int, n_out: int, sizes, B: int, max_by
     layer index out of range, no column at all, ``outputs`` on a model without a read-out, no ``window`` or one below 2, ``every`` < 1,
     ``pool`` not None or "all", a ``carry`` that is no Rolling of the same request, state + workspace + result larger than
     ``max_bytes``.  Defaults: begin=0, stride=1, layers=(), outputs=None, every=1, pool="all", carry=None."""
-    if not isinstance(spec, dict):
-        raise ValueError(f"mcpc_rolling: expected a dict or None, got {type(spec).__name__}")
-    unknown = sorted(k for k in spec if k not in _KEYS)
-    if unknown:
-        raise ValueError(f"mcpc_rolling: unknown keys {unknown}; known: {list(_KEYS)}")
-    begin, stride, every = spec.get("begin", 0), spec.get("stride", 1), spec.get("every", 1)
-    for name, v in (("begin", begin), ("stride", stride), ("every", every)):
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise ValueError(f"mcpc_rolling: {name} must be an int, got {v!r}")
-    if not 0 <= begin < T:
-        raise ValueError(f"mcpc_rolling: begin={begin} outside [0, T={T})")
-    if stride < 1:
-        raise ValueError(f"mcpc_rolling: stride={stride}, must be at least 1")
+    parse_keys("mcpc_rolling", spec, _KEYS)
+    begin, stride, every = parse_window("mcpc_rolling", spec, T, more_ints=(("every", 1),))
     if every < 1:
         raise ValueError(f"mcpc_rolling: every={every}, must be at least 1")
-    layers = spec.get("layers", ())
-    if layers is None:
-        layers = ()
-    if isinstance(layers, int) and not isinstance(layers, bool):
-        layers = (layers,)
-    try:
-        layers = tuple(layers)
-    except TypeError:
-        raise ValueError(f"mcpc_rolling: layers must be a sequence of layer indices, got {layers!r}") from None
-    for l in layers:
-        if isinstance(l, bool) or not isinstance(l, int) or not 0 <= l < n_layers:
-            raise ValueError(f"mcpc_rolling: layer index {l!r} out of range, the model has {n_layers} PC layers (0..{n_layers - 1})")
-    layers = tuple(sorted(set(layers)))
-    outputs = spec.get("outputs", None)
-    if outputs not in _OUTPUTS:
-        raise ValueError(f"mcpc_rolling: outputs={outputs!r}, expected None, 'identity' or 'sigmoid'")
-    if outputs is not None and n_out < 1:
-        raise ValueError("mcpc_rolling: outputs asked of a model without a read-out (it ends with a PCLayer)")
-    if not layers and outputs is None:
-        raise ValueError("mcpc_rolling: no columns: layers is empty and outputs is None")
+    layers = parse_layers("mcpc_rolling", spec, n_layers, none_means="empty")
+    outputs = parse_outputs("mcpc_rolling", spec, n_out, _OUTPUTS)
+    require_columns("mcpc_rolling", layers, outputs)
     if "window" not in spec or spec["window"] is None:
         raise ValueError("mcpc_rolling: window is required: the samples a rolling variance covers, an int of at least 2")
     window = spec["window"]
@@ -143,7 +103,7 @@ def validate_spec(spec, T: int, n_layers: int, n_out: int, sizes, B: int, max_by
     pool = spec.get("pool", "all")
     if pool not in _POOLS:
         raise ValueError(f"mcpc_rolling: pool={pool!r}, expected None or 'all'")
-    columns = tuple([(f"x{l}", int(sizes[l])) for l in layers] + ([("out", int(n_out))] if outputs is not None else []))
+    columns = column_list(layers, sizes, None if outputs is None else "out", n_out)
     carry = spec.get("carry", None)
     if carry is not None:
         if not isinstance(carry, Rolling) or carry.state is None:

@@ -22,7 +22,8 @@ OTHERS = dict(mcpc_moments=dict(begin=20, stride=1, layers=(0, 2), outputs="iden
               mcpc_histogram=dict(begin=20, stride=3, layers=(0, 2), outputs="identity", bins=19, range=(-3.0, 3.0)),
               mcpc_autocovariance=dict(begin=20, stride=1, layers=(0, 2), outputs="identity", max_lag=8),
               mcpc_probe=dict(begin=10, stride=2, layer=1, weight=torch.linspace(-1, 1, 36).reshape(3, 12), bias=None, link="softmax"),
-              mcpc_cloud=dict(begin=5, stride=4, layer=2, units=(0, 3, 8)))
+              mcpc_cloud=dict(begin=5, stride=4, layer=2, units=(0, 3, 8)),
+              mcpc_errors=dict(begin=11, stride=3, layers=(1, 2), quantity="error", outputs="error", covariance="chain"))
 
 
 def _net(device):
@@ -179,7 +180,7 @@ def test_two_calls_with_carry_are_one_stream():
         _run(tr, um, data, inputs, sample=False)
 
 
-def test_all_eight_features_compose_in_a_learning_call():
+def test_all_nine_features_compose_in_a_learning_call():
     um, model, data, inputs = _net(DEV)
     w0 = {k: v.clone() for k, v in model.state_dict().items() if "_x" not in k}
     runs = []
@@ -216,6 +217,49 @@ def test_all_eight_features_compose_in_a_learning_call():
     a, b = t0.mcpc_last_probe, t1.mcpc_last_probe
     assert torch.equal(a.psum, b.psum) and torch.equal(a.psumsq, b.psumsq) and torch.equal(a.votes, b.votes) and torch.equal(a.entsum, b.entsum)
     assert torch.equal(t0.mcpc_last_cloud.points, t1.mcpc_last_cloud.points)
+    a, b = t0.mcpc_last_errors, t1.mcpc_last_errors
+    assert a.names == b.names == ["e1", "e2", "eout"] and a.n == b.n == len(range(11, T, 3))
+    for nm in a.names:
+        assert torch.equal(a.sum[nm], b.sum[nm]) and torch.equal(a.sumsq[nm], b.sumsq[nm]), nm
+    assert a.covariance.columns == b.covariance.columns and torch.equal(a.covariance.sum, b.covariance.sum)
+    assert torch.equal(a.covariance.outer, b.covariance.outer)
+
+
+def test_the_side_stream_reduces_the_same_bits_beside_other_reducers():
+    """The driver's side-stream branch with more than one reducer: moments on the side stream while the histogram and the
+    autocovariance stay on the call's own, in slices of 7 steps, against the same call with everything on the call's own stream."""
+    import montecarlopredictivecoding_amd.predictive_coding.pc_trainer as pt
+    um, model, data, inputs = _net(DEV)
+    asked = {k: OTHERS[k] for k in ("mcpc_moments", "mcpc_histogram", "mcpc_autocovariance")}
+    runs = []
+    for side in (True, False):
+        tr = _trainer(model)
+        for k, v in asked.items():
+            setattr(tr, k, dict(v))
+        tr.mcpc_moments_side_stream = side
+        tr.mcpc_moments_chunk_bytes = 7 * 4 * B * (SIZES[0] + SIZES[2] + N_OUT)
+        base = pt._PHILOX_STEPS[0]
+        _run(tr, um, data, inputs, xs=False, outputs=False)
+        pt._PHILOX_STEPS[0] = base
+        assert tr.last_call_mode == "fused" and tr.last_record_slices == -(-T // 7)
+        runs.append(tr)
+    t0, t1 = runs
+    m, k = t0.mcpc_last_moments, t1.mcpc_last_moments
+    assert m.n == k.n == T - 20
+    for p, q in zip([m.out_sum, m.out_sumsq, m.x_sum[0], m.x_sumsq[0], m.x_sum[2], m.x_sumsq[2]],
+                    [k.out_sum, k.out_sumsq, k.x_sum[0], k.x_sumsq[0], k.x_sum[2], k.x_sumsq[2]]):
+        assert torch.equal(p, q)
+    h, i = t0.mcpc_last_histogram, t1.mcpc_last_histogram
+    assert h.names == i.names == NAMES
+    for nm in h.names:
+        for fld in ("counts", "under", "over", "nan"):
+            assert torch.equal(getattr(h, fld)[nm], getattr(i, fld)[nm])
+        assert bool((h.total(nm) == h.n).all())
+    a, b = t0.mcpc_last_autocovariance, t1.mcpc_last_autocovariance
+    assert a.names == b.names == NAMES
+    for nm in a.names:
+        for fld in ("lagged", "sum", "head", "tail"):
+            assert torch.equal(getattr(a, fld)[nm], getattr(b, fld)[nm])
 
 
 def test_calls_that_are_not_fused_are_rejected():
