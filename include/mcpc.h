@@ -237,6 +237,12 @@ int mcpc_comm_destroy(mcpc_engine* e);
 int mcpc_philox_normals(int device, uint64_t seed, uint64_t step, int layer, uint64_t chain_base,
                         int batch, int n_units, float* out, int raw, void* stream);
 
+/* (z0[i], z1[i]) = the step kernels' Box-Muller transform (csrc/mcpc_device.h: box_muller) of the bit pair (a[i], b[i]), i < n: the
+ * transform exposed on bits the caller chooses, so that its whole domain (2^24 radii from a >> 8, 2^24 angles from b >> 8) can be compared
+ * with fp64 (tests/test_gpu_box_muller.py).  Diagnostic, no engine needed; stateless, asynchronous on `stream`.  a, b, z0, z1: device
+ * memory of n elements each.  n = 0 launches nothing.  MCPC_EINVAL: a pointer NULL, n < 0. */
+int mcpc_box_muller(int device, const uint32_t* a, const uint32_t* b, int64_t n, float* z0, float* z1, void* stream);
+
 /* Streaming first and second moments of recorded steps: what a Langevin call is consumed as (the reference reduces the recorded steps in
  * torch: get_representations(rep_type="expectation"), utils/model.py:150-156; the histograms and means of figure_2.py / figure_3.py).
  * A host reduces the record ring of a sliced call on the device, between the slices of mcpc_run, instead of keeping the trajectory.

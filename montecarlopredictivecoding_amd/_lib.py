@@ -101,6 +101,7 @@ SYMBOLS = {
     "mcpc_comm_destroy": (C.c_int, [C.c_void_p]),
     "mcpc_philox_normals": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_int,
                                       C.c_void_p, C.c_int, C.c_void_p]),
+    "mcpc_box_muller": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcpc_moments_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "mcpc_cov_workspace_bytes": (C.c_int64, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32]),

@@ -1287,6 +1287,17 @@ int mcpc_philox_normals(int device, uint64_t seed, uint64_t step, int layer, uin
     return MCPC_OK;
 }
 
+int mcpc_box_muller(int device, const uint32_t* a, const uint32_t* b, int64_t n, float* z0, float* z1, void* stream_) {
+    if (n < 0) return fail(MCPC_EINVAL, "box_muller: n=%lld, must not be negative", (long long)n);
+    if (!a || !b) return fail(MCPC_EINVAL, "box_muller: a or b is null");
+    if (!z0 || !z1) return fail(MCPC_EINVAL, "box_muller: z0 or z1 is null");
+    if (n == 0) return MCPC_OK;
+    HIP_TRY(hipSetDevice(device));
+    hipLaunchKernelGGL(mcpc_box_muller_kernel, dim3(grid_for((size_t)n)), dim3(256), 0, (hipStream_t)stream_, a, b, (size_t)n, z0, z1);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
 int mcpc_moments_accumulate(int device, const float* rec, int64_t row_elems, int32_t first, int32_t stride, int32_t n, int32_t transform,
                             double* sum, double* sumsq, int accumulate, void* stream_) {
     if (!sum) return fail(MCPC_EINVAL, "moments: sum is null");

@@ -986,6 +986,13 @@ __global__ void mcpc_philox_kernel(uint64_t seed, uint64_t step, int layer, uint
     }
 }
 
+// box_muller on bits the caller chooses (diagnostic: the transform's whole domain is 2^24 radii x 2^24 angles)
+__global__ void mcpc_box_muller_kernel(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, size_t n,
+                                       float* __restrict__ z0, float* __restrict__ z1) {
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (size_t)gridDim.x * blockDim.x)
+        box_muller(a[idx], b[idx], z0[idx], z1[idx]);
+}
+
 }  // namespace mcpc
 
 #include "mcpc_steps_ws.h"

@@ -434,6 +434,32 @@ def philox_normals(seed, step, layer, chain_base, batch, n_units, device, raw=Fa
     return out.view(torch.int32) if raw else out
 
 
+def box_muller(a, b):
+    """``(z0, z1)``: the step kernels' Box-Muller transform of the bit pairs ``(a[i], b[i])`` (include/mcpc.h: mcpc_box_muller), the
+    transform on bits the caller chooses instead of Philox outputs.  ``a``, ``b``: contiguous int32 or uint32 device tensors of one
+    dimension and equal length (int32 is read as the same 32 bits: what ``philox_normals(raw=True)`` returns).  The radius comes from
+    ``a >> 8``, the angle from ``b >> 8``.  On the current torch stream."""
+    lib = L.load()
+    for t, name in ((a, "a"), (b, "b")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise TypeError(f"{name}: expected a torch.Tensor [n]")
+        if t.dtype not in (torch.int32, torch.uint32):
+            raise TypeError(f"{name}: expected torch.int32 or torch.uint32, got {t.dtype}")
+    device = a.device
+    if device.type != "cuda":
+        raise ValueError(f"a: expected a tensor on a HIP device, got {device}")
+    n = int(a.shape[0])
+    _check_tensor(a, (n,), device, "a", dtype=a.dtype)
+    _check_tensor(b, (n,), device, "b", dtype=b.dtype)
+    z0 = torch.empty(n, dtype=torch.float32, device=device)
+    z1 = torch.empty(n, dtype=torch.float32, device=device)
+    if n == 0:                                     # an empty tensor has no address to hand over
+        return z0, z1
+    stream = _current_stream(device)
+    L.check(lib.mcpc_box_muller(device.index or 0, _ptr(a), _ptr(b), n, _ptr(z0), _ptr(z1), stream))
+    return z0, z1
+
+
 _MOM_TRANSFORMS = {None: L.MOM_IDENTITY, "identity": L.MOM_IDENTITY, "sigmoid": L.MOM_SIGMOID,
                    L.MOM_IDENTITY: L.MOM_IDENTITY, L.MOM_SIGMOID: L.MOM_SIGMOID}
 
