@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -208,7 +209,12 @@ void retire(mcpc_engine* e, void* p, hipStream_t stream) {
     }
     e->retired.push_back({p, ev});
 }
-// ... and freed by a later run once that event has completed (never under a kernel that uses it)
+// The engine gives a buffer up (retired if there is one, the pointer cleared), and replaces it by one of `count` elements: nothing waits
+template <typename T>
+void give_up(mcpc_engine* e, T*& p, hipStream_t stream) { if (p) retire(e, (void*)p, stream); p = nullptr; }
+template <typename T>
+int regrow(mcpc_engine* e, T*& p, size_t count, hipStream_t stream) { give_up(e, p, stream); return dmalloc(p, count); }
+// A retired buffer is freed by a later run once its event has completed (never under a kernel that uses it)
 void free_completed_retired(mcpc_engine* e) {
     size_t keep = 0;
     for (size_t i = 0; i < e->retired.size(); ++i) {
@@ -265,6 +271,14 @@ void set_window(const mcpc_engine* e, const mcpc_run_desc* r, KParams& P, int t0
     P.adam_coef = r->xopt_kind == MCPC_XOPT_ADAM ? e->adam_coef + 2 * s0 : nullptr;
     if (r->noise_mode == MCPC_NOISE_EXTERNAL)
         for (int l = 0; l < e->L; ++l) P.layer[l].ext_noise = r->ext_noise[l] + s0 * e->d.batch * e->d.sizes[l];
+}
+
+// mu_1 = inputs W0^T + b0 into `dst` [Bpad][npad_0]: one kernel for the runs and the evaluators, so that all of them see the same bits
+void launch_mu1(const mcpc_engine* e, const float* inputs, float* dst, hipStream_t stream) {
+    const Lin& l0 = e->lin[0];
+    const size_t total = (size_t)e->Bpad * e->npad[0];
+    hipLaunchKernelGGL(mcpc_mu1_kernel, dim3(grid_for(total)), dim3(256), 0, stream, inputs, l0.W, l0.bias, dst,
+                       e->d.batch, e->d.n_in, e->d.sizes[0], e->Bpad, e->npad[0]);
 }
 
 // steps [t0, t0 + n) of a run on the layer-wise kernels: two launches per step on the caller's stream.  `P` carries the segment's spill
@@ -728,18 +742,27 @@ int flush_spill(mcpc_engine* e, int n_slots, int slot0, hipStream_t stream, int 
 
 namespace {
 
+// The loss arguments of a run or of an evaluator call.  `pre` opens every message: "" for mcpc_run, "<entry>: " for an evaluator.
+int check_loss_kind(const char* pre, int32_t kind) { return kind < 0 || kind > 2 ? fail(MCPC_EINVAL, "%sloss_kind=%d", pre, kind) : 0; }
+int check_loss_values(const char* pre, const mcpc_engine* e, int32_t loss_kind, double loss_var, int32_t mask_start) {
+    if (loss_kind == MCPC_LOSS_GAUSSIAN && !(loss_var > 0.0)) return fail(MCPC_EINVAL, "%sloss_var must be positive", pre);
+    if (mask_start < 0 || mask_start >= e->d.n_out) return fail(MCPC_EINVAL, "%smask_start=%d outside 0..%d", pre, mask_start, e->d.n_out - 1);
+    return 0;
+}
+int check_loss(const char* pre, const mcpc_engine* e, int32_t loss_kind, double loss_var, int32_t mask_start) {
+    if (const int rc = check_loss_kind(pre, loss_kind)) return rc;
+    if (loss_kind == MCPC_LOSS_NONE) return 0;
+    if (!e->has_head) return fail(MCPC_EINVAL, "%sa loss needs a read-out Linear (n_out > 0)", pre);
+    if (!e->target_bound) return fail(MCPC_ESTATE, "%sloss requested but no target bound", pre);
+    return check_loss_values(pre, e, loss_kind, loss_var, mask_start);
+}
+
 int check_run(const mcpc_engine* e, const mcpc_run_desc* r) {
     const int nlin = e->L + (e->has_head ? 1 : 0);
     for (int j = 0; j < nlin; ++j)
         if (!e->lin[j].bound) return fail(MCPC_ESTATE, "Linear %d has no bound parameters (mcpc_bind_params + mcpc_params_changed first)", j);
     if (const int rc = check_step_range(*r)) return rc;
-    if (r->loss_kind < 0 || r->loss_kind > 2) return fail(MCPC_EINVAL, "loss_kind=%d", r->loss_kind);
-    if (r->loss_kind != MCPC_LOSS_NONE) {
-        if (!e->has_head) return fail(MCPC_EINVAL, "a loss needs a read-out Linear (n_out > 0)");
-        if (!e->target_bound) return fail(MCPC_ESTATE, "loss requested but no target bound");
-        if (r->loss_kind == MCPC_LOSS_GAUSSIAN && !(r->loss_var > 0.0)) return fail(MCPC_EINVAL, "loss_var must be positive");
-        if (r->mask_start < 0 || r->mask_start >= e->d.n_out) return fail(MCPC_EINVAL, "mask_start=%d outside 0..%d", r->mask_start, e->d.n_out - 1);
-    }
+    if (const int rc = check_loss("", e, r->loss_kind, r->loss_var, r->mask_start)) return rc;
     if (r->xopt_kind != MCPC_XOPT_SGD && r->xopt_kind != MCPC_XOPT_ADAM) return fail(MCPC_EINVAL, "xopt_kind=%d", r->xopt_kind);
     if (!(r->lr > 0.0)) return fail(MCPC_EINVAL, "lr must be positive");
     if (r->noise_mode < 0 || r->noise_mode > 2) return fail(MCPC_EINVAL, "noise_mode=%d", r->noise_mode);
@@ -764,13 +787,9 @@ int prepare_run(mcpc_engine* e, const mcpc_run_desc* r, bool run_accumulates, hi
     if (r->xopt_kind == MCPC_XOPT_ADAM) {
         const size_t need = (size_t)r->n_steps * 2;
         if (need > e->adam_cap) {
-            // earlier launches may still read the old table: retire it instead of synchronising
-            if (e->adam_coef) retire(e, e->adam_coef, stream);
-            e->adam_coef = nullptr;
             size_t cap = 1024;
             while (cap < need) cap *= 2;
-            int rc = dmalloc(e->adam_coef, cap);
-            if (rc) return rc;
+            if (const int rc = regrow(e, e->adam_coef, cap, stream)) return rc;
             e->adam_cap = cap;
         }
         // pinned staging table, double-buffered; the event wait below is a no-op unless the upload issued two Adam runs ago
@@ -803,23 +822,14 @@ int prepare_run(mcpc_engine* e, const mcpc_run_desc* r, bool run_accumulates, hi
     }
     const size_t erows = r->energy_mode == MCPC_ENERGY_ALL ? (size_t)r->T : 1, eslots = energy_slots(*e);
     if (r->energy_mode != MCPC_ENERGY_NONE && erows > e->epart_rows) {
-        if (e->epart) retire(e, e->epart, stream);        // earlier launches may still write it
-        e->epart = nullptr;
         // geometric growth: a caller whose T creeps up call by call re-allocates O(log T) times, not every call
         const size_t cap = std::max(erows, e->epart_rows + e->epart_rows / 2);
-        int rc = dmalloc(e->epart, cap * eslots * (kMaxLatent + 1));
-        if (rc) return rc;
+        if (const int rc = regrow(e, e->epart, cap * eslots * (kMaxLatent + 1), stream)) return rc;
         // (the slots of a 16-chain unit that is all padding are never written: they must read as zero)
         HIP_TRY(hipMemsetAsync(e->epart, 0, cap * eslots * (kMaxLatent + 1) * sizeof(double), stream));
         e->epart_rows = cap;
     }
-    // mu_1 = inputs W0^T + b0 (constant during the run: weights only change between runs)
-    {
-        const Lin& l0 = e->lin[0];
-        const size_t total = (size_t)e->Bpad * e->npad[0];
-        hipLaunchKernelGGL(mcpc_mu1_kernel, dim3(grid_for(total)), dim3(256), 0, stream, e->inputs, l0.W, l0.bias, e->mu1,
-                           e->d.batch, e->d.n_in, e->d.sizes[0], e->Bpad, e->npad[0]);
-    }
+    launch_mu1(e, e->inputs, e->mu1, stream);             // constant during the run: weights only change between runs
     // layer-wise kernels: f(x_l) of the state the run starts from (the backward launches keep it current from there)
     if (e->lw)
         for (int l = 0; l < e->L; ++l) {
@@ -1298,25 +1308,46 @@ int mcpc_box_muller(int device, const uint32_t* a, const uint32_t* b, int64_t n,
     return MCPC_OK;
 }
 
+namespace {
+// The record window of the accumulate entries: records first, first + stride, ... (n of them) of a ring `rec` whose rows hold B x width
+// floats.  The checks they share; `who`, the entry's name, opens every message.
+int check_shape(const char* who, int32_t B, int32_t width) {
+    if (B < 1) return fail(MCPC_EINVAL, "%s: B=%d, must be at least 1", who, B);
+    if (width < 1) return fail(MCPC_EINVAL, "%s: width=%d, must be at least 1", who, width);
+    return 0;
+}
+int check_window(const char* who, const void* rec, int32_t first, int32_t stride, int32_t n) {
+    if (stride < 1) return fail(MCPC_EINVAL, "%s: stride=%d, must be at least 1", who, stride);
+    if (first < 0) return fail(MCPC_EINVAL, "%s: first=%d, must not be negative", who, first);
+    if (n < 0) return fail(MCPC_EINVAL, "%s: n=%d, must not be negative", who, n);
+    if (n > 0 && !rec) return fail(MCPC_EINVAL, "%s: rec is null with n=%d", who, n);
+    return 0;
+}
+int check_transform(const char* who, int32_t xf) {
+    return xf != MCPC_MOM_IDENTITY && xf != MCPC_MOM_SIGMOID ? fail(MCPC_EINVAL, "%s: unknown transform %d", who, xf) : 0;
+}
+// The window itself: the row length E, the first record, the distance between two records.
+// All offsets in 64 bits: (first + k * stride) * E passes 2^31 elements at the shapes the step kernels are built for.
+struct RecWindow { int64_t E; const float* r0; int64_t row_step; };
+RecWindow rec_window(const float* rec, int64_t E, int32_t first, int32_t stride, int32_t n) {
+    return {E, n > 0 ? rec + (int64_t)first * E : rec, (int64_t)stride * E};
+}
+}  // namespace
+
 int mcpc_moments_accumulate(int device, const float* rec, int64_t row_elems, int32_t first, int32_t stride, int32_t n, int32_t transform,
                             double* sum, double* sumsq, int accumulate, void* stream_) {
     if (!sum) return fail(MCPC_EINVAL, "moments: sum is null");
     if (row_elems < 1) return fail(MCPC_EINVAL, "moments: row_elems=%lld, must be at least 1", (long long)row_elems);
-    if (stride < 1) return fail(MCPC_EINVAL, "moments: stride=%d, must be at least 1", stride);
-    if (first < 0) return fail(MCPC_EINVAL, "moments: first=%d, must not be negative", first);
-    if (n < 0) return fail(MCPC_EINVAL, "moments: n=%d, must not be negative", n);
-    if (transform != MCPC_MOM_IDENTITY && transform != MCPC_MOM_SIGMOID) return fail(MCPC_EINVAL, "moments: unknown transform %d", transform);
-    if (n > 0 && !rec) return fail(MCPC_EINVAL, "moments: rec is null with n=%d", n);
+    if (const int rc = check_window("moments", rec, first, stride, n)) return rc;
+    if (const int rc = check_transform("moments", transform)) return rc;
     if (n == 0 && accumulate) return MCPC_OK;                     // nothing to add
     HIP_TRY(hipSetDevice(device));
-    // all offsets in 64 bits: (first + k * stride) * row_elems passes 2^31 elements at the shapes the step kernels are built for
-    const float* r0 = n > 0 ? rec + (int64_t)first * row_elems : rec;
-    const int64_t row_step = (int64_t)stride * row_elems;
-    const uintptr_t align = (uintptr_t)r0 | (uintptr_t)sum | (uintptr_t)sumsq;
+    const RecWindow w = rec_window(rec, row_elems, first, stride, n);
+    const uintptr_t align = (uintptr_t)w.r0 | (uintptr_t)sum | (uintptr_t)sumsq;
     if (row_elems % 4 == 0 && align % 16 == 0)
-        mom_dispatch<4>(transform, r0, row_elems, row_step, n, sum, sumsq, accumulate, (hipStream_t)stream_);
+        mom_dispatch<4>(transform, w.r0, w.E, w.row_step, n, sum, sumsq, accumulate, (hipStream_t)stream_);
     else
-        mom_dispatch<1>(transform, r0, row_elems, row_step, n, sum, sumsq, accumulate, (hipStream_t)stream_);
+        mom_dispatch<1>(transform, w.r0, w.E, w.row_step, n, sum, sumsq, accumulate, (hipStream_t)stream_);
     HIP_TRY(hipGetLastError());
     return MCPC_OK;
 }
@@ -1352,20 +1383,15 @@ int mcpc_cov_accumulate(int device, const float* const* rec, const int32_t* widt
     CovPlan plan;
     if (const int rc = cov_check_shape(B, widths, n_blocks, pool, plan)) return rc;
     if (!outer) return fail(MCPC_EINVAL, "cov: outer is null");
-    if (stride < 1) return fail(MCPC_EINVAL, "cov: stride=%d, must be at least 1", stride);
-    if (first < 0) return fail(MCPC_EINVAL, "cov: first=%d, must not be negative", first);
-    if (n < 0) return fail(MCPC_EINVAL, "cov: n=%d, must not be negative", n);
+    if (const int rc = check_window("cov", rec, first, stride, n)) return rc;
     bool any_sig = false;
     for (int b = 0; b < n_blocks; ++b) {
         const int32_t xf = transforms ? transforms[b] : MCPC_MOM_IDENTITY;
         if (xf != MCPC_MOM_IDENTITY && xf != MCPC_MOM_SIGMOID) return fail(MCPC_EINVAL, "cov: unknown transform %d of block %d", xf, b);
         any_sig = any_sig || xf == MCPC_MOM_SIGMOID;
     }
-    if (n > 0) {
-        if (!rec) return fail(MCPC_EINVAL, "cov: rec is null with n=%d", n);
-        for (int b = 0; b < n_blocks; ++b)
-            if (!rec[b]) return fail(MCPC_EINVAL, "cov: rec[%d] is null with n=%d", b, n);
-    }
+    for (int b = 0; n > 0 && b < n_blocks; ++b)
+        if (!rec[b]) return fail(MCPC_EINVAL, "cov: rec[%d] is null with n=%d", b, n);
     const int64_t need = pool ? (int64_t)plan.groups * plan.Dpad * plan.Dpad * (int64_t)sizeof(double) : 0;
     if (n > 0 && pool) {
         if (!workspace) return fail(MCPC_EINVAL, "cov: workspace is null with pool=1 (mcpc_cov_workspace_bytes: %lld bytes)", (long long)need);
@@ -1410,32 +1436,27 @@ int mcpc_hist_accumulate(int device, const float* rec, int32_t B, int32_t width,
                          const float* edges, int32_t n_bins, int32_t pool, int64_t* counts, int accumulate, void* stream_) {
     if (!counts) return fail(MCPC_EINVAL, "hist: counts is null");
     if (!edges) return fail(MCPC_EINVAL, "hist: edges is null");
-    if (B < 1) return fail(MCPC_EINVAL, "hist: B=%d, must be at least 1", B);
-    if (width < 1) return fail(MCPC_EINVAL, "hist: width=%d, must be at least 1", width);
-    if (stride < 1) return fail(MCPC_EINVAL, "hist: stride=%d, must be at least 1", stride);
-    if (first < 0) return fail(MCPC_EINVAL, "hist: first=%d, must not be negative", first);
-    if (n < 0) return fail(MCPC_EINVAL, "hist: n=%d, must not be negative", n);
+    if (const int rc = check_shape("hist", B, width)) return rc;
+    if (const int rc = check_window("hist", rec, first, stride, n)) return rc;
     if (n_bins < 1 || n_bins > MCPC_HIST_MAX_BINS) return fail(MCPC_EINVAL, "hist: n_bins=%d outside 1..%d", n_bins, MCPC_HIST_MAX_BINS);
     if (pool != 0 && pool != 1) return fail(MCPC_EINVAL, "hist: pool=%d, must be 0 or 1", pool);
-    if (transform != MCPC_MOM_IDENTITY && transform != MCPC_MOM_SIGMOID) return fail(MCPC_EINVAL, "hist: unknown transform %d", transform);
+    if (const int rc = check_transform("hist", transform)) return rc;
     for (int i = 0; i <= n_bins; ++i) {
         if (!std::isfinite(edges[i])) return fail(MCPC_EINVAL, "hist: edges[%d] is not finite", i);
         if (i > 0 && !(edges[i - 1] < edges[i]))
             return fail(MCPC_EINVAL, "hist: edges are not strictly ascending at %d (%.9g, then %.9g)", i, (double)edges[i - 1], (double)edges[i]);
     }
-    if (n > 0 && !rec) return fail(MCPC_EINVAL, "hist: rec is null with n=%d", n);
     if (n == 0 && accumulate) return MCPC_OK;                     // nothing to add
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(device));
-    const int64_t E = (int64_t)B * width, ncol = n_bins + 3;
+    const RecWindow w = rec_window(rec, (int64_t)B * width, first, stride, n);
+    const int64_t E = w.E, ncol = n_bins + 3;
     const size_t out_bytes = (size_t)(pool ? (int64_t)width : E) * ncol * sizeof(int64_t);
     if (n == 0) {
         HIP_TRY(hipMemsetAsync(counts, 0, out_bytes, stream));
         return MCPC_OK;
     }
-    // all offsets in 64 bits, as in mcpc_moments_accumulate
-    const float* r0 = rec + (int64_t)first * E;
-    const int kVec = (E % 4 == 0 && (uintptr_t)r0 % 16 == 0) ? 4 : 1;
+    const int kVec = (E % 4 == 0 && (uintptr_t)w.r0 % 16 == 0) ? 4 : 1;
     const HistPlan plan = hist_plan(E, width, pool, n, n_bins, kVec);
     HistParams P{};
     for (int i = 0; i < kHistTable; ++i) P.key[i] = i < n_bins ? hist_key(edges[i]) : 0xffffffffu;
@@ -1446,11 +1467,11 @@ int mcpc_hist_accumulate(int device, const float* rec, int32_t B, int32_t width,
     P.TV = plan.TV; P.n = n; P.seg = plan.seg; P.width = width; P.pool = pool;
     P.exclusive = (!pool && plan.segments == 1) ? 1 : 0;
     P.accumulate = accumulate ? 1 : 0;
-    P.E = E; P.row_step = (int64_t)stride * E; P.tiles = plan.tiles; P.period = plan.period; P.splits = plan.splits;
+    P.E = E; P.row_step = w.row_step; P.tiles = plan.tiles; P.period = plan.period; P.splits = plan.splits;
     // workgroups that share a destination add into it with integer atomics: an overwriting call starts them from zero
     if (!P.exclusive && !accumulate) HIP_TRY(hipMemsetAsync(counts, 0, out_bytes, stream));
-    if (kVec == 4) hist_launch<4>(transform, r0, P, plan, counts, stream);
-    else hist_launch<1>(transform, r0, P, plan, counts, stream);
+    if (kVec == 4) hist_launch<4>(transform, w.r0, P, plan, counts, stream);
+    else hist_launch<1>(transform, w.r0, P, plan, counts, stream);
     HIP_TRY(hipGetLastError());
     return MCPC_OK;
 }
@@ -1462,26 +1483,21 @@ int mcpc_acov_accumulate(int device, const float* rec, int32_t B, int32_t width,
     if (!sum) return fail(MCPC_EINVAL, "acov: sum is null");
     if (max_lag > 0 && !window) return fail(MCPC_EINVAL, "acov: window is null with max_lag=%d", max_lag);
     if (max_lag > 0 && !head) return fail(MCPC_EINVAL, "acov: head is null with max_lag=%d", max_lag);
-    if (B < 1) return fail(MCPC_EINVAL, "acov: B=%d, must be at least 1", B);
-    if (width < 1) return fail(MCPC_EINVAL, "acov: width=%d, must be at least 1", width);
-    if (stride < 1) return fail(MCPC_EINVAL, "acov: stride=%d, must be at least 1", stride);
-    if (first < 0) return fail(MCPC_EINVAL, "acov: first=%d, must not be negative", first);
-    if (n < 0) return fail(MCPC_EINVAL, "acov: n=%d, must not be negative", n);
+    if (const int rc = check_shape("acov", B, width)) return rc;
+    if (const int rc = check_window("acov", rec, first, stride, n)) return rc;
     if (n_seen < 0) return fail(MCPC_EINVAL, "acov: n_seen=%lld, must not be negative", (long long)n_seen);
-    if (transform != MCPC_MOM_IDENTITY && transform != MCPC_MOM_SIGMOID) return fail(MCPC_EINVAL, "acov: unknown transform %d", transform);
-    if (n > 0 && !rec) return fail(MCPC_EINVAL, "acov: rec is null with n=%d", n);
+    if (const int rc = check_transform("acov", transform)) return rc;
     if (n == 0 && n_seen > 0) return MCPC_OK;                     // nothing to add
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(device));
-    const int64_t E = (int64_t)B * width;
+    const RecWindow w = rec_window(rec, (int64_t)B * width, first, stride, n);
     if (n == 0) {                                                 // a stream that starts empty
-        HIP_TRY(hipMemsetAsync(lagged, 0, (size_t)E * (max_lag + 1) * sizeof(double), stream));
-        HIP_TRY(hipMemsetAsync(sum, 0, (size_t)E * sizeof(double), stream));
+        HIP_TRY(hipMemsetAsync(lagged, 0, (size_t)w.E * (max_lag + 1) * sizeof(double), stream));
+        HIP_TRY(hipMemsetAsync(sum, 0, (size_t)w.E * sizeof(double), stream));
         return MCPC_OK;
     }
     AcovParams P{};
-    P.rec = rec + (int64_t)first * E;                             // all offsets in 64 bits, as in mcpc_moments_accumulate
-    P.E = E; P.row_step = (int64_t)stride * E; P.n_seen = n_seen; P.n = n; P.K = max_lag;
+    P.rec = w.r0; P.E = w.E; P.row_step = w.row_step; P.n_seen = n_seen; P.n = n; P.K = max_lag;
     P.lagged = lagged; P.sum = sum; P.window = window; P.head = head;
     acov_dispatch(transform, P, stream);
     HIP_TRY(hipGetLastError());
@@ -1489,8 +1505,7 @@ int mcpc_acov_accumulate(int device, const float* rec, int32_t B, int32_t width,
 }
 
 static int roll_check_shape(int32_t B, int32_t width, int32_t n) {
-    if (B < 1) return fail(MCPC_EINVAL, "roll: B=%d, must be at least 1", B);
-    if (width < 1) return fail(MCPC_EINVAL, "roll: width=%d, must be at least 1", width);
+    if (const int rc = check_shape("roll", B, width)) return rc;
     if (n < 0) return fail(MCPC_EINVAL, "roll: n=%d, must not be negative", n);
     if (roll_groups((int64_t)B * width, 1) >= kRollMaxGroups)
         return fail(MCPC_EINVAL, "roll: B * width = %lld is more than one launch holds", (long long)B * width);
@@ -1513,11 +1528,9 @@ int mcpc_roll_accumulate(int device, const float* rec, int32_t B, int32_t width,
     if (!hist) return fail(MCPC_EINVAL, "roll: hist is null");
     if (!out_elem && !out_pool) return fail(MCPC_EINVAL, "roll: out_elem and out_pool are both null");
     if (const int rc = roll_check_shape(B, width, n)) return rc;
-    if (stride < 1) return fail(MCPC_EINVAL, "roll: stride=%d, must be at least 1", stride);
-    if (first < 0) return fail(MCPC_EINVAL, "roll: first=%d, must not be negative", first);
+    if (const int rc = check_window("roll", rec, first, stride, n)) return rc;      // (n: checked with the shape already)
     if (n_seen < 0) return fail(MCPC_EINVAL, "roll: n_seen=%lld, must not be negative", (long long)n_seen);
-    if (transform != MCPC_MOM_IDENTITY && transform != MCPC_MOM_SIGMOID) return fail(MCPC_EINVAL, "roll: unknown transform %d", transform);
-    if (n > 0 && !rec) return fail(MCPC_EINVAL, "roll: rec is null with n=%d", n);
+    if (const int rc = check_transform("roll", transform)) return rc;
     RollParams P{};
     P.rows = roll_rows(n_seen, n, window, every, &P.emit0);
     if (out_pool && P.rows > 0 && !workspace)
@@ -1526,14 +1539,13 @@ int mcpc_roll_accumulate(int device, const float* rec, int32_t B, int32_t width,
     if (n == 0 && n_seen > 0) return MCPC_OK;                     // nothing to add
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(device));
-    const int64_t E = (int64_t)B * width;
+    const RecWindow w = rec_window(rec, (int64_t)B * width, first, stride, n);
     if (n == 0) {                                                 // a stream that starts empty
-        HIP_TRY(hipMemsetAsync(s1, 0, (size_t)E * sizeof(double), stream));
-        HIP_TRY(hipMemsetAsync(s2, 0, (size_t)E * sizeof(double), stream));
+        HIP_TRY(hipMemsetAsync(s1, 0, (size_t)w.E * sizeof(double), stream));
+        HIP_TRY(hipMemsetAsync(s2, 0, (size_t)w.E * sizeof(double), stream));
         return MCPC_OK;
     }
-    P.rec = rec + (int64_t)first * E;                             // all offsets in 64 bits, as in mcpc_moments_accumulate
-    P.E = E; P.row_step = (int64_t)stride * E; P.n_seen = n_seen; P.n = n; P.W = window; P.every = every;
+    P.rec = w.r0; P.E = w.E; P.row_step = w.row_step; P.n_seen = n_seen; P.n = n; P.W = window; P.every = every;
     P.slot0 = (int32_t)(n_seen % window);
     P.s1 = s1; P.s2 = s2; P.hist = hist; P.out_elem = out_elem; P.part = (double*)workspace;
     if (roll_vec(P) == 4) roll_launch<4>(transform, P, out_pool, stream);
@@ -1551,18 +1563,13 @@ int mcpc_probe_accumulate(int device, const float* rec, int32_t B, int32_t width
     if (link != MCPC_PROBE_IDENTITY && link != MCPC_PROBE_SIGMOID && link != MCPC_PROBE_SOFTMAX)
         return fail(MCPC_EINVAL, "probe: unknown link %d", link);
     if (link == MCPC_PROBE_SOFTMAX && !entsum) return fail(MCPC_EINVAL, "probe: entsum is null with the softmax link");
-    if (B < 1) return fail(MCPC_EINVAL, "probe: B=%d, must be at least 1", B);
-    if (width < 1) return fail(MCPC_EINVAL, "probe: width=%d, must be at least 1", width);
-    if (stride < 1) return fail(MCPC_EINVAL, "probe: stride=%d, must be at least 1", stride);
-    if (first < 0) return fail(MCPC_EINVAL, "probe: first=%d, must not be negative", first);
-    if (n < 0) return fail(MCPC_EINVAL, "probe: n=%d, must not be negative", n);
+    if (const int rc = check_shape("probe", B, width)) return rc;
+    if (const int rc = check_window("probe", rec, first, stride, n)) return rc;
     if (n_classes < 1 || n_classes > MCPC_PROBE_MAX_CLASSES)
         return fail(MCPC_EINVAL, "probe: n_classes=%d outside 1..%d", n_classes, MCPC_PROBE_MAX_CLASSES);
-    if (n > 0 && !rec) return fail(MCPC_EINVAL, "probe: rec is null with n=%d", n);
     if (n == 0 && accumulate) return MCPC_OK;                     // nothing to add
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(device));
-    const int64_t E = (int64_t)B * width;
     if (n == 0) {
         HIP_TRY(hipMemsetAsync(psum, 0, (size_t)B * n_classes * sizeof(double), stream));
         if (psumsq) HIP_TRY(hipMemsetAsync(psumsq, 0, (size_t)B * n_classes * sizeof(double), stream));
@@ -1571,8 +1578,8 @@ int mcpc_probe_accumulate(int device, const float* rec, int32_t B, int32_t width
         return MCPC_OK;
     }
     ProbeParams P{};
-    P.rec = rec + (int64_t)first * E;                             // all offsets in 64 bits, as in mcpc_moments_accumulate
-    P.W = W; P.bias = bias; P.row_step = (int64_t)stride * E;
+    const RecWindow w = rec_window(rec, (int64_t)B * width, first, stride, n);
+    P.rec = w.r0; P.W = W; P.bias = bias; P.row_step = w.row_step;
     P.B = B; P.width = width; P.n = n; P.C = n_classes; P.accumulate = accumulate ? 1 : 0;
     P.psum = psum; P.psumsq = psumsq; P.votes = votes; P.entsum = entsum;
     probe_dispatch(link, P, stream);
@@ -1619,8 +1626,17 @@ int mcpc_knn_accumulate(int device, const float* q, int64_t nq, const float* ref
     return MCPC_OK;
 }
 
-// The evaluator's job table, mu_1 buffer and scratch for chunks of `chunk` rows (shared by mcpc_chain_energies and mcpc_prediction_errors)
-static int ce_ensure_scratch(mcpc_engine* e, int chunk, hipStream_t stream) {
+namespace {
+// The front the two evaluators share (mcpc_chain_energies, mcpc_prediction_errors).  What a call reads and launches over:
+struct EvalCall {
+    unsigned layers;        // bit l: latent layer l is read -- x_rec[l] is required, and prepared chunk by chunk
+    unsigned lins;          // bit j (bit L: the read-out): Linear j is evaluated -- it must be bound; Linear 0 needs mu_1 of the call's inputs
+    unsigned pe_table;      // the Linears of the prediction-error job table the call launches over; 0: it launches over the chain-energy table
+    bool with_loss;         // the read-out's error is the loss's (its kind and mask reach the kernels)
+};
+
+// The evaluators' job tables, mu_1 buffer and scratch for chunks of `chunk` rows
+int ce_ensure_scratch(mcpc_engine* e, int chunk, unsigned pe_table, hipStream_t stream) {
     if (!e->ce_jobs) {
         std::vector<LwJob>& jobs = e->ce_table;
         ce_job_table(e->L, e->npad, e->has_head ? e->out_pad : 0, jobs, e->ce_nhead, e->ce_finish);
@@ -1630,13 +1646,9 @@ static int ce_ensure_scratch(mcpc_engine* e, int chunk, hipStream_t stream) {
         if (const int rc = dmalloc(e->ce_mu1, (size_t)e->Bpad * e->npad[0])) return rc;
     }
     if (chunk > e->ce_rows) {
-        for (int l = 0; l < e->L; ++l) {
-            if (e->ce_x[l]) retire(e, e->ce_x[l], stream);
-            if (e->ce_fx[l]) retire(e, e->ce_fx[l], stream);
-            e->ce_x[l] = e->ce_fx[l] = nullptr;
-        }
-        if (e->ce_part) retire(e, e->ce_part, stream);
-        e->ce_part = nullptr;
+        // everything is given up before the first new allocation: one that fails leaves a consistent, empty scratch
+        for (int l = 0; l < e->L; ++l) { give_up(e, e->ce_x[l], stream); give_up(e, e->ce_fx[l], stream); }
+        give_up(e, e->ce_part, stream);
         e->ce_rows = 0;
         for (int l = 0; l < e->L; ++l) {
             int rc;
@@ -1645,82 +1657,109 @@ static int ce_ensure_scratch(mcpc_engine* e, int chunk, hipStream_t stream) {
         if (const int rc = dmalloc(e->ce_part, (size_t)e->ce_njobs * chunk)) return rc;
         e->ce_rows = chunk;
     }
+    if (pe_table && pe_table != e->pe_want) {
+        std::vector<LwJob> jobs;
+        pe_job_table(e->ce_table, pe_table, jobs);
+        give_up(e, e->pe_jobs, stream);
+        e->pe_want = 0;                  // (an upload that fails leaves no table, and no set of Linears it would be the table of)
+        if (const int rc = upload(e->pe_jobs, jobs, "the prediction-error job table")) return rc;
+        e->pe_want = pe_table;
+        e->pe_njobs = (int)jobs.size();
+    }
     return MCPC_OK;
 }
 
-int mcpc_chain_energies(mcpc_engine* e, const float* inputs, const float* const* x_rec, int32_t n_rec, int32_t loss_kind, double loss_var,
-                        int32_t mask_start, double* out, int32_t max_rows, void* stream_) {
-    if (!e) return fail(MCPC_EINVAL, "chain energies: null engine");
-    if (!x_rec) return fail(MCPC_EINVAL, "chain energies: x_rec is null");
-    if (!out) return fail(MCPC_EINVAL, "chain energies: out is null");
-    if (n_rec < 0) return fail(MCPC_EINVAL, "chain energies: n_rec=%d, must not be negative", n_rec);
-    if (max_rows < 0) return fail(MCPC_EINVAL, "chain energies: max_rows=%d, must not be negative (0 = default)", max_rows);
+// The checks of a call, before anything of the device is touched; `pre` ("<entry>: ") opens every message
+int eval_check_call(const char* pre, const mcpc_engine* e, const float* const* x_rec, int32_t n_rec, int32_t max_rows) {
+    if (!e) return fail(MCPC_EINVAL, "%snull engine", pre);
+    if (!x_rec) return fail(MCPC_EINVAL, "%sx_rec is null", pre);
+    if (n_rec < 0) return fail(MCPC_EINVAL, "%sn_rec=%d, must not be negative", pre, n_rec);
+    if (max_rows < 0) return fail(MCPC_EINVAL, "%smax_rows=%d, must not be negative (0 = default)", pre, max_rows);
+    return 0;
+}
+int eval_check_reads(const char* pre, const mcpc_engine* e, const float* const* x_rec, const EvalCall& c) {
     for (int l = 0; l < e->L; ++l)
-        if (!x_rec[l]) return fail(MCPC_EINVAL, "chain energies: x_rec[%d] is null", l);
-    const bool with_loss = loss_kind != MCPC_LOSS_NONE;
-    const int nlin = e->L + (e->has_head ? 1 : 0);
-    for (int j = 0; j < nlin; ++j)
-        if (!e->lin[j].bound) return fail(MCPC_ESTATE, "chain energies: Linear %d has no bound parameters (mcpc_bind_params + mcpc_params_changed first)", j);
-    if (loss_kind < 0 || loss_kind > 2) return fail(MCPC_EINVAL, "chain energies: loss_kind=%d", loss_kind);
-    if (loss_kind != MCPC_LOSS_NONE) {
-        if (!e->has_head) return fail(MCPC_EINVAL, "chain energies: a loss needs a read-out Linear (n_out > 0)");
-        if (!e->target_bound) return fail(MCPC_ESTATE, "chain energies: loss requested but no target bound");
-        if (loss_kind == MCPC_LOSS_GAUSSIAN && !(loss_var > 0.0)) return fail(MCPC_EINVAL, "chain energies: loss_var must be positive");
-        if (mask_start < 0 || mask_start >= e->d.n_out)
-            return fail(MCPC_EINVAL, "chain energies: mask_start=%d outside 0..%d", mask_start, e->d.n_out - 1);
-    }
-    const int64_t R = (int64_t)n_rec * e->d.batch;
-    if (R == 0) return MCPC_OK;
-    hipStream_t stream = (hipStream_t)stream_;
+        if (((c.layers >> l) & 1u) && !x_rec[l]) return fail(MCPC_EINVAL, "%sx_rec[%d] is null", pre, l);
+    for (int j = 0; j < e->L + (e->has_head ? 1 : 0); ++j)
+        if (((c.lins >> j) & 1u) && !e->lin[j].bound)
+            return fail(MCPC_ESTATE, "%sLinear %d has no bound parameters (mcpc_bind_params + mcpc_params_changed first)", pre, j);
+    return 0;
+}
+
+// An accepted call of R rows: the chunk, the scratch and the tables for it, mu_1 where it is read, and what the two kernels' parameters share
+int eval_setup(mcpc_engine* e, const EvalCall& c, const float* inputs, int64_t R, int32_t max_rows, int32_t loss_kind, double loss_var,
+               int32_t mask_start, hipStream_t stream, CeParams& Q) {
     HIP_TRY(hipSetDevice(e->d.device));
     // the chunk: a multiple of the 64-row tile, no longer than the call
     const int64_t want = max_rows > 0 ? max_rows : kCeDefaultRows;
     const int chunk = (int)(std::min<int64_t>((want + kLwChains - 1) / kLwChains, (R + kLwChains - 1) / kLwChains) * kLwChains);
-    if (const int rc = ce_ensure_scratch(e, chunk, stream)) return rc;
+    if (const int rc = ce_ensure_scratch(e, chunk, c.pe_table, stream)) return rc;
     free_completed_retired(e);
-    // mu_1 of THESE inputs (the step kernels' own kernel: the same bits)
-    {
-        const Lin& l0 = e->lin[0];
-        const size_t total = (size_t)e->Bpad * e->npad[0];
-        hipLaunchKernelGGL(mcpc_mu1_kernel, dim3(grid_for(total)), dim3(256), 0, stream, inputs, l0.W, l0.bias, e->ce_mu1,
-                           e->d.batch, e->d.n_in, e->d.sizes[0], e->Bpad, e->npad[0]);
-    }
-    CeParams Q{};
+    if (c.lins & 1u) launch_mu1(e, inputs, e->ce_mu1, stream);      // mu_1 of THESE inputs (the step kernels' own kernel: the same bits)
+    const int nlin = e->L + (e->has_head ? 1 : 0);
     for (int l = 0; l < e->L; ++l) { Q.x[l] = e->ce_x[l]; Q.fx[l] = e->ce_fx[l]; Q.npad[l] = e->npad[l]; Q.ecoef[l] = e->d.ecoef[l]; }
     for (int j = 1; j < nlin; ++j) { Q.Wf[j] = e->lin[j].Wf; Q.bias[j] = e->lin[j].bias_pad; }
     Q.npad[e->L] = e->has_head ? e->out_pad : 0;
-    Q.mu1 = e->ce_mu1; Q.y = e->ypad; Q.wexp = e->wexp; Q.part = e->ce_part;
-    Q.job0 = with_loss ? 0 : e->ce_nhead;
-    Q.jobs = e->ce_jobs + Q.job0;
+    Q.mu1 = e->ce_mu1; Q.y = e->ypad; Q.wexp = e->wexp;
     Q.L = e->L; Q.B = e->d.batch; Q.n_out = e->d.n_out; Q.chunk = chunk;
-    Q.loss_kind = loss_kind; Q.mask_start = with_loss ? mask_start : 0;
+    Q.loss_kind = c.with_loss ? loss_kind : MCPC_LOSS_NONE; Q.mask_start = c.with_loss ? mask_start : 0;
     Q.inv_var = loss_kind == MCPC_LOSS_GAUSSIAN ? (float)(1.0 / loss_var) : 1.0f;
-    const int njobs = e->ce_njobs - Q.job0;
-    for (int64_t r0 = 0; r0 < R; r0 += chunk) {
-        const int rows = (int)std::min<int64_t>(chunk, R - r0);
-        const int padded = (rows + kLwChains - 1) / kLwChains * kLwChains;          // tiles of this chunk that hold a row
+    return MCPC_OK;
+}
+
+// The chunk loop: x_l and f(x_l) of the layers the call reads go to the scratch, then `launch(r0, rows, padded)` launches the entry's own
+// kernels for rows [r0, r0 + rows) of the call, with Q.rows and Q.row_base set (padded: the rows of the tiles that hold one)
+int eval_chunks(const mcpc_engine* e, const EvalCall& c, const float* const* x_rec, int64_t R, CeParams& Q, hipStream_t stream,
+                const std::function<void(int64_t, int, int)>& launch) {
+    for (int64_t r0 = 0; r0 < R; r0 += Q.chunk) {
+        const int rows = (int)std::min<int64_t>(Q.chunk, R - r0);
+        const int padded = (rows + kLwChains - 1) / kLwChains * kLwChains;
         for (int l = 0; l < e->L; ++l) {
+            if (!((c.layers >> l) & 1u)) continue;
             const size_t total4 = (size_t)padded * e->npad[l] / 4;
             hipLaunchKernelGGL(mcpc_ce_prep_kernel, dim3(grid_for(total4)), dim3(256), 0, stream, x_rec[l] + (size_t)r0 * e->d.sizes[l],
                                e->ce_x[l], e->ce_fx[l], rows, padded, e->d.sizes[l], e->npad[l], e->d.acts[l]);
         }
         Q.rows = rows;
         Q.row_base = (int)(r0 % e->d.batch);
-        hipLaunchKernelGGL(mcpc_ce_kernel, dim3(padded / kLwChains, njobs), dim3(kLwThreads), 0, stream, Q);
-        hipLaunchKernelGGL(mcpc_ce_finish_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, (const double*)e->ce_part, out, e->ce_finish,
-                           e->L, with_loss ? 1 : 0, rows, chunk, (size_t)r0);
+        launch(r0, rows, padded);
     }
     HIP_TRY(hipGetLastError());
     return MCPC_OK;
+}
+}  // namespace
+
+int mcpc_chain_energies(mcpc_engine* e, const float* inputs, const float* const* x_rec, int32_t n_rec, int32_t loss_kind, double loss_var,
+                        int32_t mask_start, double* out, int32_t max_rows, void* stream_) {
+    static const char pre[] = "chain energies: ";
+    if (const int rc = eval_check_call(pre, e, x_rec, n_rec, max_rows)) return rc;
+    if (!out) return fail(MCPC_EINVAL, "chain energies: out is null");
+    // every layer is read and every Linear evaluated
+    const bool with_loss = loss_kind != MCPC_LOSS_NONE;
+    const EvalCall c{(1u << e->L) - 1u, (1u << (e->L + (e->has_head ? 1 : 0))) - 1u, 0u, with_loss};
+    if (const int rc = eval_check_reads(pre, e, x_rec, c)) return rc;
+    if (const int rc = check_loss(pre, e, loss_kind, loss_var, mask_start)) return rc;
+    const int64_t R = (int64_t)n_rec * e->d.batch;
+    if (R == 0) return MCPC_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    CeParams Q{};
+    if (const int rc = eval_setup(e, c, inputs, R, max_rows, loss_kind, loss_var, mask_start, stream, Q)) return rc;
+    Q.part = e->ce_part;
+    Q.job0 = with_loss ? 0 : e->ce_nhead;
+    Q.jobs = e->ce_jobs + Q.job0;
+    const int njobs = e->ce_njobs - Q.job0;
+    return eval_chunks(e, c, x_rec, R, Q, stream, [&](int64_t r0, int rows, int padded) {
+        hipLaunchKernelGGL(mcpc_ce_kernel, dim3(padded / kLwChains, njobs), dim3(kLwThreads), 0, stream, Q);
+        hipLaunchKernelGGL(mcpc_ce_finish_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, (const double*)e->ce_part, out, e->ce_finish,
+                           e->L, with_loss ? 1 : 0, rows, Q.chunk, (size_t)r0);
+    });
 }
 
 int mcpc_prediction_errors(mcpc_engine* e, const float* inputs, const float* const* x_rec, int32_t n_rec, int32_t loss_kind, double loss_var,
                            int32_t mask_start, float* const* err, float* const* pred, float* err_out, float* pred_out, int32_t max_rows,
                            void* stream_) {
-    if (!e) return fail(MCPC_EINVAL, "prediction errors: null engine");
-    if (!x_rec) return fail(MCPC_EINVAL, "prediction errors: x_rec is null");
-    if (n_rec < 0) return fail(MCPC_EINVAL, "prediction errors: n_rec=%d, must not be negative", n_rec);
-    if (max_rows < 0) return fail(MCPC_EINVAL, "prediction errors: max_rows=%d, must not be negative (0 = default)", max_rows);
+    static const char pre[] = "prediction errors: ";
+    if (const int rc = eval_check_call(pre, e, x_rec, n_rec, max_rows)) return rc;
     const int L = e->L;
     // the Linears asked for (bit j; bit L = the read-out) and the latent layers their predictions read
     unsigned want = 0;
@@ -1729,55 +1768,22 @@ int mcpc_prediction_errors(mcpc_engine* e, const float* inputs, const float* con
     if (err_out || pred_out) want |= 1u << L;
     if (!want) return fail(MCPC_EINVAL, "prediction errors: nothing is asked for (every destination is null)");
     if ((err_out || pred_out) && !e->has_head) return fail(MCPC_EINVAL, "prediction errors: err_out / pred_out need a read-out Linear (n_out > 0)");
-    if (loss_kind < 0 || loss_kind > 2) return fail(MCPC_EINVAL, "prediction errors: loss_kind=%d", loss_kind);
+    if (const int rc = check_loss_kind(pre, loss_kind)) return rc;
     if (err_out && loss_kind == MCPC_LOSS_NONE) return fail(MCPC_EINVAL, "prediction errors: err_out needs a loss (loss_kind is MCPC_LOSS_NONE)");
-    if (err_out) {
-        if (loss_kind == MCPC_LOSS_GAUSSIAN && !(loss_var > 0.0)) return fail(MCPC_EINVAL, "prediction errors: loss_var must be positive");
-        if (mask_start < 0 || mask_start >= e->d.n_out)
-            return fail(MCPC_EINVAL, "prediction errors: mask_start=%d outside 0..%d", mask_start, e->d.n_out - 1);
-    }
-    const unsigned need = pe_layers_read(want, L);
-    for (int l = 0; l < L; ++l)
-        if (((need >> l) & 1u) && !x_rec[l]) return fail(MCPC_EINVAL, "prediction errors: x_rec[%d] is null", l);
-    const int nlin = L + (e->has_head ? 1 : 0);
-    for (int j = 0; j < nlin; ++j)
-        if (((want >> j) & 1u) && !e->lin[j].bound)
-            return fail(MCPC_ESTATE, "prediction errors: Linear %d has no bound parameters (mcpc_bind_params + mcpc_params_changed first)", j);
+    if (err_out)
+        if (const int rc = check_loss_values(pre, e, loss_kind, loss_var, mask_start)) return rc;
+    const EvalCall c{pe_layers_read(want, L), want, want, err_out != nullptr};
+    if (const int rc = eval_check_reads(pre, e, x_rec, c)) return rc;
     if (err_out && !e->target_bound) return fail(MCPC_ESTATE, "prediction errors: err_out requested but no target bound");
     const int64_t R = (int64_t)n_rec * e->d.batch;
     if (R == 0) return MCPC_OK;
     hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipSetDevice(e->d.device));
-    const int64_t want_rows = max_rows > 0 ? max_rows : kCeDefaultRows;
-    const int chunk = (int)(std::min<int64_t>((want_rows + kLwChains - 1) / kLwChains, (R + kLwChains - 1) / kLwChains) * kLwChains);
-    if (const int rc = ce_ensure_scratch(e, chunk, stream)) return rc;
-    if (want != e->pe_want) {
-        std::vector<LwJob> jobs;
-        pe_job_table(e->ce_table, want, jobs);
-        if (e->pe_jobs) retire(e, e->pe_jobs, stream);
-        e->pe_jobs = nullptr;
-        e->pe_want = 0;
-        if (const int rc = upload(e->pe_jobs, jobs, "the prediction-error job table")) return rc;
-        e->pe_want = want;
-        e->pe_njobs = (int)jobs.size();
-    }
-    free_completed_retired(e);
-    if (want & 1u) {            // mu_1 of THESE inputs (the step kernels' own kernel: the same bits)
-        const Lin& l0 = e->lin[0];
-        const size_t total = (size_t)e->Bpad * e->npad[0];
-        hipLaunchKernelGGL(mcpc_mu1_kernel, dim3(grid_for(total)), dim3(256), 0, stream, inputs, l0.W, l0.bias, e->ce_mu1,
-                           e->d.batch, e->d.n_in, e->d.sizes[0], e->Bpad, e->npad[0]);
-    }
     PeParams P{};
     CeParams& Q = P.ce;
-    for (int l = 0; l < L; ++l) { Q.x[l] = e->ce_x[l]; Q.fx[l] = e->ce_fx[l]; Q.npad[l] = e->npad[l]; Q.ecoef[l] = e->d.ecoef[l]; P.n[l] = e->d.sizes[l]; }
-    for (int j = 1; j < nlin; ++j) { Q.Wf[j] = e->lin[j].Wf; Q.bias[j] = e->lin[j].bias_pad; }
-    Q.npad[L] = e->has_head ? e->out_pad : 0;
+    if (const int rc = eval_setup(e, c, inputs, R, max_rows, loss_kind, loss_var, mask_start, stream, Q)) return rc;
+    Q.jobs = e->pe_jobs;
+    for (int l = 0; l < L; ++l) P.n[l] = e->d.sizes[l];
     P.n[L] = e->d.n_out;
-    Q.mu1 = e->ce_mu1; Q.y = e->ypad; Q.wexp = e->wexp; Q.jobs = e->pe_jobs;
-    Q.L = L; Q.B = e->d.batch; Q.n_out = e->d.n_out; Q.chunk = chunk;
-    Q.loss_kind = err_out ? loss_kind : MCPC_LOSS_NONE; Q.mask_start = err_out ? mask_start : 0;
-    Q.inv_var = loss_kind == MCPC_LOSS_GAUSSIAN ? (float)(1.0 / loss_var) : 1.0f;
     // 16-byte stores where every row of a destination starts on a 16-byte boundary
     auto vec_ok = [](const float* p, int n) { return p && n % 4 == 0 && ((uintptr_t)p & 15u) == 0; };
     for (int j = 0; j <= L; ++j) {
@@ -1786,15 +1792,7 @@ int mcpc_prediction_errors(mcpc_engine* e, const float* inputs, const float* con
         if (vec_ok(ep, P.n[j])) P.vec_err |= 1u << j;
         if (vec_ok(pp, P.n[j])) P.vec_pred |= 1u << j;
     }
-    for (int64_t r0 = 0; r0 < R; r0 += chunk) {
-        const int rows = (int)std::min<int64_t>(chunk, R - r0);
-        const int padded = (rows + kLwChains - 1) / kLwChains * kLwChains;          // tiles of this chunk that hold a row
-        for (int l = 0; l < L; ++l) {
-            if (!((need >> l) & 1u)) continue;
-            const size_t total4 = (size_t)padded * e->npad[l] / 4;
-            hipLaunchKernelGGL(mcpc_ce_prep_kernel, dim3(grid_for(total4)), dim3(256), 0, stream, x_rec[l] + (size_t)r0 * e->d.sizes[l],
-                               e->ce_x[l], e->ce_fx[l], rows, padded, e->d.sizes[l], e->npad[l], e->d.acts[l]);
-        }
+    return eval_chunks(e, c, x_rec, R, Q, stream, [&](int64_t r0, int /*rows*/, int padded) {
         // (a chunk starts at a multiple of kLwChains rows: r0 * n_l floats keeps the 16-byte alignment where n_l % 4 == 0)
         for (int j = 0; j <= L; ++j) {
             float* const ep = j < L ? (err ? err[j] : nullptr) : err_out;
@@ -1802,12 +1800,8 @@ int mcpc_prediction_errors(mcpc_engine* e, const float* inputs, const float* con
             P.err[j] = ep ? ep + (size_t)r0 * P.n[j] : nullptr;
             P.pred[j] = pp ? pp + (size_t)r0 * P.n[j] : nullptr;
         }
-        Q.rows = rows;
-        Q.row_base = (int)(r0 % e->d.batch);
         hipLaunchKernelGGL(mcpc_pe_kernel, dim3(padded / kLwChains, e->pe_njobs), dim3(kLwThreads), 0, stream, P);
-    }
-    HIP_TRY(hipGetLastError());
-    return MCPC_OK;
+    });
 }
 
 int mcpc_query(const mcpc_engine* e, int32_t* lds_bytes, int32_t* chains_per_wg, int32_t* n_workgroups, int32_t* spill_slots) {
