@@ -458,6 +458,46 @@ int mcpc_knn_accumulate(int device, const float* q, int64_t nq, const float* ref
                         int32_t accumulate, void* workspace, int64_t workspace_bytes, void* stream);
 int64_t mcpc_knn_workspace_bytes(int64_t nq, int64_t nr, int32_t d, int32_t k);
 
+/* The importance-sampled log marginal likelihood of every datum from read-outs of prior samples, on the device (csrc/mcpc_loglik.h):
+ * the hot path of the reference's get_marginal_likelihood (utils/training_evaluation.py), which forms one fp32 [batch][samples] matrix
+ * per batch and keeps one scalar.  y is device fp32 [n_data][width], the data; out device fp32 [n_samp][width], the read-outs of the
+ * samples (logits for MCPC_LOSS_BERNOULLI, means for MCPC_LOSS_GAUSSIAN); both contiguous; n_data and n_samp in
+ * 0..MCPC_LOGLIK_MAX_ROWS, width >= 1.  With c = out clamped to [-clamp, +clamp] (clamp = +inf: none; the reference clamps to 20; a
+ * NaN stays a NaN),
+ *   Bernoulli  nll(i, s) = b_s - sum_j y_ij c_sj                                  b_s = sum_j softplus(c_sj)
+ *   Gaussian   nll(i, s) = (0.5 / loss_var) (a_i + b_s - 2 sum_j y_ij c_sj) + 0.5 width log(2 pi loss_var)
+ *                                                                                 a_i = sum_j y_ij^2, b_s = sum_j c_sj^2
+ * state is device fp64 [n_data][4]:
+ *   state[i] = { m, s1, s2, cnt }   m = min_s nll(i, s), s1 = sum_s e^-(nll - m), s2 = sum_s e^-2(nll - m), cnt = samples taken,
+ * so that log p(y_i) ~ log(s1 / cnt) - m, and s1^2 / s2 is the effective sample size of the importance weights.  A state without
+ * samples is the EMPTY state { +inf, 0, 0, 0 }.
+ *   arithmetic    fp64 throughout; the dot products on the fp64 MFMA with the operands converted from fp32 on load, a_i and b_s summed
+ *                 in one fixed order, softplus(c) = max(c, 0) + log1p(exp(-|c|)).
+ *   merge rule    of two states A, B of the same datum over disjoint samples (also LogLikelihood.merge in Python): m = min(mA, mB); if
+ *                 m = +inf the result is the empty state; else fA = exp(m - mA), fB = exp(m - mB), the factor of an empty state taken
+ *                 as 0 (inf - inf is never formed), and s1 = s1A fA + s1B fB, s2 = s2A fA^2 + s2B fB^2, cnt = cntA + cntB.
+ *                 accumulate != 0 merges the old state[i] with this call's; accumulate = 0 overwrites whatever state held.
+ *   non-finite    a sample whose nll for a datum is not finite is neither taken nor counted for that datum and affects no other
+ *                 (datum, sample) pair; a datum row that holds a NaN ends with cnt = 0.
+ * What is bitwise: two runs of the same call (the launch shape depends on n_data and n_samp alone, every sum and merge has one fixed
+ * order, no atomics).  What holds only within a bound: the same samples chunked differently over calls with accumulate = 1, and
+ * another order of the samples -- the running minimum rescales the sums at other points.  With gamma = (width + 16) 2^-53 and
+ * delta(i, s) = gamma (sum_j |y_ij c_sj| + b_s) (Gaussian: gamma (0.5 / loss_var) (a_i + b_s + 2 sum_j |y_ij c_sj|)), log(s1 / cnt) - m
+ * stays within 4 max_s delta(i, s) + (n_samp + 64) 2^-52 of the exact value, and s1^2 / s2 within that, relative (tests/loglik_cases.py).
+ * workspace: device memory of mcpc_loglik_workspace_bytes(n_data, n_samp, width) bytes (8-B aligned, contents irrelevant, free for reuse
+ * when the call has completed on `stream`); the size depends on the three arguments alone.  mcpc_loglik_workspace_bytes returns -1 (and
+ * a message in mcpc_last_error) for arguments mcpc_loglik_accumulate would refuse.  The library allocates nothing.  Stateless,
+ * asynchronous on `stream` (a hipStream_t), no engine needed, all offsets 64-bit.  n_data = 0 does nothing; n_samp = 0 writes empty
+ * states when accumulate = 0 and does nothing otherwise.
+ * MCPC_EINVAL, checked before any HIP call (nothing is launched then): width < 1, n_data or n_samp out of range, MCPC_LOSS_NONE or an
+ * unknown loss_kind, MCPC_LOSS_GAUSSIAN with loss_var <= 0, clamp <= 0 or NaN, y or state NULL with n_data > 0, out NULL with
+ * n_samp > 0, a workspace that is NULL or smaller than mcpc_loglik_workspace_bytes when that is not 0. */
+#define MCPC_LOGLIK_MAX_ROWS 2147483647LL
+int mcpc_loglik_accumulate(int device, const float* y, int64_t n_data, const float* out, int64_t n_samp, int32_t width,
+                           int32_t loss_kind, double loss_var, double clamp, double* state, int32_t accumulate, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+int64_t mcpc_loglik_workspace_bytes(int64_t n_data, int64_t n_samp, int32_t width);
+
 /* Per-chain energies of recorded states, evaluated on the device (the reference has them per datapoint: is_return_batchelement_loss,
  * PCLayer(is_keep_energy_per_datapoint=True), get_energies(is_per_datapoint=True); pc_trainer.py:776-836, pc_layer.py:250-262).
  * A ROW is one chain at one recorded step.  x_rec[l], l < n_latent: [n_rec][batch][n_l] fp32, as mcpc_run writes rec_x[l] (n_rec = 1

@@ -21,6 +21,7 @@
 #include "mcpc_roll.h"
 #include "mcpc_probe.h"
 #include "mcpc_knn.h"
+#include "mcpc_loglik.h"
 #include "mcpc_plan.h"
 #include "mcpc_chain_energy.h"
 #include "mcpc_pred_err.h"
@@ -1622,6 +1623,62 @@ int mcpc_knn_accumulate(int device, const float* q, int64_t nq, const float* ref
     P.tiles_per_split = g.tiles_per_split; P.n_tiles = g.n_tiles; P.n_splits = g.n_splits;
     P.part = (float*)workspace; P.best = best; P.accumulate = accumulate ? 1 : 0;
     knn_dispatch(g, P, stream);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+static int loglik_check_shape(int64_t n_data, int64_t n_samp, int32_t width) {
+    if (width < 1) return fail(MCPC_EINVAL, "loglik: width=%d, must be at least 1", width);
+    if (n_data < 0 || n_data > MCPC_LOGLIK_MAX_ROWS)
+        return fail(MCPC_EINVAL, "loglik: n_data=%lld outside 0..%lld", (long long)n_data, (long long)MCPC_LOGLIK_MAX_ROWS);
+    if (n_samp < 0 || n_samp > MCPC_LOGLIK_MAX_ROWS)
+        return fail(MCPC_EINVAL, "loglik: n_samp=%lld outside 0..%lld", (long long)n_samp, (long long)MCPC_LOGLIK_MAX_ROWS);
+    return MCPC_OK;
+}
+
+int64_t mcpc_loglik_workspace_bytes(int64_t n_data, int64_t n_samp, int32_t width) {
+    if (loglik_check_shape(n_data, n_samp, width)) return -1;
+    return loglik_workspace_doubles(loglik_plan(n_data, n_samp, width), n_data, n_samp) * (int64_t)sizeof(double);
+}
+
+int mcpc_loglik_accumulate(int device, const float* y, int64_t n_data, const float* out, int64_t n_samp, int32_t width,
+                           int32_t loss_kind, double loss_var, double clamp, double* state, int32_t accumulate, void* workspace,
+                           int64_t workspace_bytes, void* stream_) {
+    if (const int rc = loglik_check_shape(n_data, n_samp, width)) return rc;
+    if (loss_kind != MCPC_LOSS_BERNOULLI && loss_kind != MCPC_LOSS_GAUSSIAN)
+        return fail(MCPC_EINVAL, "loglik: loss_kind=%d, expected MCPC_LOSS_GAUSSIAN (%d) or MCPC_LOSS_BERNOULLI (%d)", loss_kind,
+                    MCPC_LOSS_GAUSSIAN, MCPC_LOSS_BERNOULLI);
+    if (loss_kind == MCPC_LOSS_GAUSSIAN && !(loss_var > 0.0)) return fail(MCPC_EINVAL, "loglik: loss_var=%g, must be positive", loss_var);
+    if (!(clamp > 0.0)) return fail(MCPC_EINVAL, "loglik: clamp=%g, must be positive (+inf: none)", clamp);
+    if (n_data > 0 && !y) return fail(MCPC_EINVAL, "loglik: y is null with n_data=%lld", (long long)n_data);
+    if (n_data > 0 && !state) return fail(MCPC_EINVAL, "loglik: state is null with n_data=%lld", (long long)n_data);
+    if (n_samp > 0 && !out) return fail(MCPC_EINVAL, "loglik: out is null with n_samp=%lld", (long long)n_samp);
+    const LoglikPlan g = loglik_plan(n_data, n_samp, width);
+    const int64_t need = loglik_workspace_doubles(g, n_data, n_samp) * (int64_t)sizeof(double);
+    if (need > 0) {
+        if (!workspace) return fail(MCPC_EINVAL, "loglik: workspace is null (mcpc_loglik_workspace_bytes: %lld bytes)", (long long)need);
+        if (workspace_bytes < need)
+            return fail(MCPC_EINVAL, "loglik: workspace of %lld bytes is too small, %lld needed", (long long)workspace_bytes, (long long)need);
+    }
+    if (n_data == 0 || (n_samp == 0 && accumulate)) return MCPC_OK;      // nothing to write, or nothing to add
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(device));
+    LoglikParams P{};
+    P.y = y; P.o = out; P.n_data = n_data; P.n_samp = n_samp; P.width = width;
+    P.gauss = loss_kind == MCPC_LOSS_GAUSSIAN ? 1 : 0;
+    P.accumulate = accumulate ? 1 : 0;
+    P.vec = (width % 4 == 0 && (uintptr_t)y % 16 == 0 && (uintptr_t)out % 16 == 0) ? 1 : 0;
+    P.clamp = clamp;
+    if (P.gauss) {
+        P.half_inv_var = 0.5 / loss_var;
+        P.cst = 0.5 * (double)width * log(2.0 * M_PI * loss_var);
+    }
+    P.tiles_per_group = g.tiles_per_group; P.n_stiles = g.n_stiles; P.groups = g.groups; P.ndpad = g.n_dtiles * 16;
+    P.part = (double*)workspace;
+    P.a = P.part + g.groups * P.ndpad * 4;
+    P.b = P.a + n_data;
+    P.state = state;
+    loglik_dispatch(g, P, stream);
     HIP_TRY(hipGetLastError());
     return MCPC_OK;
 }

@@ -763,3 +763,61 @@ def knn_accumulate(q, ref, k, best, accumulate=False, workspace=None):
     stream = _current_stream(device)
     L.check(lib.mcpc_knn_accumulate(device.index or 0, _ptr(q), nq, _ptr(ref), nr, d, k, _ptr(best), 1 if accumulate else 0,
                                     _ptr(workspace), ws_bytes, stream))
+
+
+_LOGLIK_LOSSES = {"bernoulli": L.LOSS_BERNOULLI, "gaussian": L.LOSS_GAUSSIAN}
+
+
+def loglik_workspace_bytes(n_data, n_samp, width) -> int:
+    """Bytes of device workspace ``loglik_accumulate`` needs for ``n_data`` data against ``n_samp`` samples of ``width`` columns."""
+    lib = L.load()
+    need = lib.mcpc_loglik_workspace_bytes(int(n_data), int(n_samp), int(width))
+    if need < 0:
+        L.check(need)
+    return need
+
+
+def loglik_accumulate(y, out, loss, var, clamp, state, accumulate=False, workspace=None):
+    """The importance-sampling state of every datum's log marginal likelihood over the read-outs of prior samples, on the device
+    (include/mcpc.h: mcpc_loglik_accumulate).  ``y``: contiguous fp32 ``[n_data, width]``, the data; ``out``: contiguous fp32
+    ``[n_samp, width]``, logits (``loss="bernoulli"``) or means (``loss="gaussian"``, with the variance ``var``; None otherwise),
+    clamped to ``+-clamp`` (``math.inf``: not at all); ``state``: contiguous fp64 ``[n_data, 4]``, per datum ``(m, s1, s2, cnt)`` --
+    the smallest nll, the sums of ``exp(-(nll - m))`` and of its square, the samples taken.  fp64 throughout, the dot products on the
+    fp64 MFMA.  ``accumulate=False`` overwrites; ``accumulate=True`` merges the old state with this call's, so the samples can be
+    streamed -- equal to the one-shot call within a rounding bound, not bitwise; two runs of the same call are bitwise equal.  A
+    (datum, sample) pair with a non-finite nll is neither taken nor counted.  ``workspace``: a contiguous device tensor of at least
+    ``loglik_workspace_bytes(n_data, n_samp, width)`` bytes, 8-B aligned; None allocates one for this call.  Everything on the device
+    of ``y``.  On the current torch stream."""
+    lib = L.load()
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise TypeError("y: expected a torch.Tensor [n_data, width]")
+    if not isinstance(out, torch.Tensor) or out.dim() != 2:
+        raise TypeError("out: expected a torch.Tensor [n_samp, width]")
+    device = y.device
+    if device.type != "cuda":
+        raise ValueError(f"y: expected a tensor on a HIP device, got {device}")
+    if loss not in _LOGLIK_LOSSES:
+        raise ValueError(f"loss: expected 'bernoulli' or 'gaussian', got {loss!r}")
+    if loss == "gaussian":
+        if var is None or not float(var) > 0.0:
+            raise ValueError(f"var: the Gaussian read-out needs a positive variance, got {var!r}")
+    elif var is not None:
+        raise ValueError(f"var: expected None with loss={loss!r}")
+    clamp = float(clamp)
+    if not clamp > 0.0:
+        raise ValueError(f"clamp: expected a positive bound (math.inf: none), got {clamp!r}")
+    n_data, width = (int(s) for s in y.shape)
+    n_samp = int(out.shape[0])
+    if width < 1:
+        raise ValueError("y: expected at least one column")
+    _check_tensor(y, (n_data, width), device, "y")
+    _check_tensor(out, (n_samp, width), device, "out")
+    _check_tensor(state, (n_data, 4), device, "state", torch.float64)
+    need = lib.mcpc_loglik_workspace_bytes(n_data, n_samp, width)
+    if need < 0:
+        L.check(need)
+    workspace, ws_bytes = _check_workspace(workspace, device, need, 8, "loglik_workspace_bytes")
+    stream = _current_stream(device)
+    L.check(lib.mcpc_loglik_accumulate(device.index or 0, _ptr(y), n_data, _ptr(out), n_samp, width, _LOGLIK_LOSSES[loss],
+                                       float(var) if loss == "gaussian" else 1.0, clamp, _ptr(state), 1 if accumulate else 0,
+                                       _ptr(workspace), ws_bytes, stream))

@@ -195,6 +195,39 @@ def get_marginal_likelihood(gen_pc, config, dataloader, use_cuda, n_samples=5000
     return marginal_likelihood_from_logits(logits, dataloader)
 
 
+def get_marginal_likelihood_per_datum(gen_pc, config, dataloader, use_cuda, n_samples=5000, sample_chunk=None, clamp=20.0):
+    """``get_marginal_likelihood`` per datum, in fp64 on the device, for both read-outs: a ``likelihood.LogLikelihood`` over the loader's
+    data, in the loader's order -- ``.log_p`` per datum, ``.ess`` (the effective sample size of its importance weights),
+    ``.n_samples``; ``.mean()`` is the reference's scalar.  The data are gathered onto the model's device once.  The prior samples are
+    drawn with ``sample_pc(..., is_return_hidden=True)``: ``sample_chunk=None`` draws all ``n_samples`` at once and consumes the torch
+    generator exactly as ``get_marginal_likelihood`` does (the same seed gives the same samples); otherwise they are drawn
+    ``sample_chunk`` at a time and the state is accumulated over the chunks, so ``n_samples`` is not bounded by memory.
+    ``bernoulli_fn`` reads the samples' read-outs as logits, ``fe_fn`` as means of a Gaussian of variance ``config["input_var"]``;
+    both are clamped to ``+-clamp`` as the reference clamps (``math.inf``: not at all)."""
+    import torch
+    from ..likelihood import log_likelihood
+    from ..utils.model import bernoulli_fn, fe_fn
+    if config["loss_fn"] is bernoulli_fn:
+        loss, var = "bernoulli", None
+    elif config["loss_fn"] is fe_fn:
+        loss, var = "gaussian", float(config["input_var"])
+    else:
+        raise NotImplementedError("get_marginal_likelihood_per_datum: the read-out is bernoulli_fn or fe_fn")
+    n_samples = int(n_samples)
+    chunk = n_samples if sample_chunk is None else int(sample_chunk)
+    if n_samples < 1 or chunk < 1:
+        raise ValueError(f"n_samples={n_samples} and sample_chunk={sample_chunk!r} must be at least 1")
+    device = next(gen_pc.parameters()).device
+    data, state = None, None
+    for s0 in range(0, n_samples, chunk):
+        outputs = sample_pc(min(chunk, n_samples - s0), gen_pc, config, use_cuda=use_cuda, is_return_hidden=True)
+        if data is None:
+            # after the first draw, as get_marginal_likelihood walks its loader: a DataLoader's iterator takes a seed from the torch generator
+            data = torch.cat([d.to(device).to(torch.float32).reshape(d.shape[0], -1) for d, _ in dataloader])
+        state = log_likelihood(data, outputs, loss=loss, var=var, clamp=clamp, state=state)
+    return state
+
+
 def knn_kl_divergence(x, y):
     """The nearest-neighbour (Perez-Cruz) estimate of D(P || Q) between samples ``x`` of P and ``y`` of Q on the device: what the
     reference's ``KLdivergence(x, y)`` (:240-284) estimates, by exact brute force instead of two KD-trees queried with ``eps=.01``, so
