@@ -608,7 +608,8 @@ int mcpc_debug_chain_energy_jobs(int32_t n_latent, const int32_t* sizes, int32_t
 /* Diagnostic (tests only; no device work, no device needed): everything mcpc_create would decide for `desc` on a device of `n_cu` compute
  * units and `total_mem` bytes of memory (read only when desc->spill_budget_bytes <= 0; 0 = unknown), as one JSON object: "form"
  * (in-place | barrier | layer-wise), "kernel" (mcpc_step_kernel_name), "Bpad", "workgroups" and "chains_per_wg" (mcpc_query), "npad",
- * "out_pad", "slots" / "half_slots" of the spill ring, "spill_tm" per Linear; "main" and "unified"."plan", the LDS plan and step table
+ * "out_pad", "slots" / "half_slots" of the spill ring, "spill_tm" per Linear, "slabs" per Linear as [float offset, floats, K-splits held]
+ * of its split-K slabs and their total "slab_floats"; "main" and "unified"."plan", the LDS plan and step table
  * of the main form and of the unified-wave kernel ("unified" also says whether the plan fits, is held and is preferred): "lds_bytes",
  * "regions" as [name, layer | -1, float offset, floats], "xl", "chunk" / "ring" / "overlay" of the in-place plan, and "table", one row
  * of numbers per entry in the order "fields" names (every KPhase field but the weight pointer; the unified table holds "rows" rows of
@@ -624,9 +625,16 @@ int mcpc_debug_plan(const mcpc_net_desc* desc, int32_t n_cu, int64_t total_mem, 
  * flushes run beside the next segment, through a spill ring of "n_parts" parts, else serially; "items", one row of numbers per item in
  * the order "fields" names: steps [t0, t0 + n) as one plain launch (q = 0) or as one cycle of the round schedule (rr_k launches of q
  * steps, n = rr_m q), "acc" when they lie in the window -- then the item spills into slots [slot0, slot0 + n) of the ring, part "part",
- * and "flush" says that a flush of those n slots follows it; "flushes", one entry per flushing item: "rows" = n x Bpad and per Linear
- * j >= 1, in the order "flush_fields" names, the K-splits and rows per split of that flush and the bound of the splits that sizes the
- * Linear's slabs (that of a flush of a whole ring part).  out / cap / needed and the failures as for mcpc_debug_plan. */
+ * and "flush" says that a flush of those n slots follows it; "flushes", one entry per flushing item, the flush as mcpc_run has planned
+ * it before it launches anything: "rows" = n x Bpad; "lin", per Linear j >= 1 in the order "flush_fields" names, the K-splits and rows
+ * per split of that flush and the bound of the splits that sizes the Linear's slabs (that of a flush of a whole ring part);
+ * "launches", per Linear j >= 1 its launches in launch order, each a row in the order "launch_fields" names: "family" ("heb7", "heb" or
+ * "dw": mcpc_heb7_kernel, mcpc_heb_kernel, mcpc_dw_kernel), "form" (the index of the tiled kernels' instantiation <te, ra, swapped> in
+ * the list csrc/mcpc_hebbian.h holds, MCPC_HEB_FORMS; -1 for "dw"), the grid "n_mt" x "n_nt" x K-splits, "col0" (the first output
+ * column), "stream" (0 or 1: which of the flush's streams; all 0 unless "two_streams") and "wave_tiles" ("dw" only); "reduce", per
+ * Linear j >= 1 in the order "reduce_fields" names, the sign its sums enter the gradient with and the transposed dimensions of its
+ * weight slab (0, 0: not transposed); "max_blocks", gridDim.x of the one reduction launch; "text", per Linear j >= 1 what
+ * mcpc_last_flush_plan returns after that flush.  out / cap / needed and the failures as for mcpc_debug_plan. */
 int mcpc_debug_run_plan(const mcpc_net_desc* desc, int32_t n_cu, int64_t total_mem, const mcpc_run_desc* run, char* out, int64_t cap,
                         int64_t* needed);
 

@@ -68,8 +68,7 @@ struct mcpc_engine : EnginePlan {
     float* spill_a[kMaxLatent]{};
     float* spill_e[kMaxLatent]{};
     float* spill_eo = nullptr;
-    float* slab = nullptr;
-    size_t slab_floats = 0;
+    float* slab = nullptr;          // EnginePlan::slab_floats floats
     // energies
     double* epart = nullptr;
     size_t epart_rows = 0;
@@ -538,40 +537,32 @@ int mcpc_store_adam_state(mcpc_engine* e, float* const* m, float* const* v, void
 
 namespace {
 
-template <int TE, int RA, bool SW = false>
-int launch_heb(const HebArgs& a, hipStream_t stream) {
-    constexpr int lds_bytes = 2 * kHebKB * (heb_lds_stride(16 * TE) + heb_lds_stride(16 * 8 * RA)) * (int)sizeof(float);
-    static bool attr_set[16] = {false};      // per device
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-        if (hipFuncSetAttribute((const void*)mcpc_heb_kernel<TE, RA, SW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
-            return fail(MCPC_EHIP, "hipFuncSetAttribute failed for the Hebbian kernel");
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL((mcpc_heb_kernel<TE, RA, SW>), dim3(a.n_mt * a.n_nt * a.ksplit), dim3(kHebThreads), lds_bytes, stream, a);
-    return 0;
-}
+// The tiled Hebbian kernels, family (HEB_F16, HEB_FP32: mcpc_plan.h) x form (kHebForms: mcpc_hebbian.h): every instantiation the
+// library holds, with its dynamic LDS.  A planned launch names its entry; nothing else chooses a kernel.
+struct HebKernel { void (*fn)(HebArgs); int lds_bytes; bool attr_set[16]; };      // (attr_set: per device)
+#define MCPC_HEB7_ROW(te, ra, sw) {mcpc_heb7_kernel<te, ra, sw>, heb7_lds_bytes(te), {false}},
+#define MCPC_HEB_ROW(te, ra, sw) {mcpc_heb_kernel<te, ra, sw>, heb_lds_bytes(te, ra), {false}},
+HebKernel g_heb_kernels[2][kNumHebForms] = {{MCPC_HEB_FORMS(MCPC_HEB7_ROW)}, {MCPC_HEB_FORMS(MCPC_HEB_ROW)}};
+#undef MCPC_HEB7_ROW
+#undef MCPC_HEB_ROW
 
-template <int TE, int RA, bool SW = false>
-int launch_heb7(const HebArgs& a, hipStream_t stream) {
-    // two plane buffers + the bias sums + every wave's transpose scratch for one activation tile (2 row tiles x 4 x 17 float4)
-    constexpr int lds_bytes = 2 * 2 * 16 * TE * kHeb7LD * 2 + 16 * TE * (int)sizeof(float) + 8 * 2 * 272 * (int)sizeof(float);
-    static bool attr_set[16] = {false};      // per device
+int launch_heb(const FlushLaunch& l, const HebArgs& a, hipStream_t stream) {
+    if ((l.family != HEB_F16 && l.family != HEB_FP32) || l.form < 0 || l.form >= kNumHebForms)
+        return fail(MCPC_ESTATE, "internal: no Hebbian kernel %s<%d,%d%s> (form %d)", heb_family_name(l.family), l.te, l.ra, l.swapped ? ",T" : "", l.form);
+    HebKernel& k = g_heb_kernels[l.family][l.form];
     int dev = 0;
     (void)hipGetDevice(&dev);
-    if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-        if (hipFuncSetAttribute((const void*)mcpc_heb7_kernel<TE, RA, SW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
+    if (dev >= 0 && dev < 16 && !k.attr_set[dev]) {
+        if (hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds_bytes) != hipSuccess)
             return fail(MCPC_EHIP, "hipFuncSetAttribute failed for the Hebbian kernel");
-        attr_set[dev] = true;
+        k.attr_set[dev] = true;
     }
-    hipLaunchKernelGGL((mcpc_heb7_kernel<TE, RA, SW>), dim3(a.n_mt * a.n_nt * a.ksplit), dim3(kHebThreads), lds_bytes, stream, a);
+    hipLaunchKernelGGL(k.fn, dim3(a.n_mt * a.n_nt * a.ksplit), dim3(kHebThreads), k.lds_bytes, stream, a);
     return 0;
 }
 
 // Allocated by the first run that accumulates Hebbian sums (inference-only engines never pay for it): the spill ring, the
-// slabs of the split-K partial sums (sized for a flush of one part of the ring), the low-priority stream and events of the
-// overlapped flush.
+// slabs of the split-K partial sums (sized by plan_engine), the low-priority stream and events of the overlapped flush.
 int ensure_spill(mcpc_engine* e, hipStream_t stream) {
     if (e->spill_ready) return 0;
     int rc;
@@ -614,127 +605,49 @@ int ensure_spill(mcpc_engine* e, hipStream_t stream) {
         if (e->has_head) ok = ok && zero_tail(e->spill_eo, e->out_pad);
         if (!ok) return fail(MCPC_EHIP, "hipMemset2D of the spill ring's padding rows failed");
     }
-    const int nlin = e->L + (e->has_head ? 1 : 0);
-    const int max_rows = e->half_slots * e->Bpad;
-    size_t total = 0;
-    for (int j = 1; j < nlin; ++j) {
-        Lin& ln = e->lin[j];
-        const HebPlan h = plan_hebbian(e->knobs, ln.out_pad, ln.in_pad, max_rows);
-        ln.slab_off = total;
-        ln.slab_floats = (size_t)h.ksplit_cap * ((size_t)ln.out_pad * ln.in_pad + ln.out_pad);
-        total += ln.slab_floats;
-    }
-    if (!e->slab && (rc = dmalloc(e->slab, total))) return rc;
-    e->slab_floats = total;
+    if (!e->slab && (rc = dmalloc(e->slab, e->slab_floats))) return rc;
     e->spill_ready = true;
     return 0;
 }
 
-// One Hebbian flush: fold `n_slots` spilled steps into the gradient sums of every Linear j >= 1.  Every Linear has its own
-// slab region, so the GEMMs of a flush are independent launches and ONE reduction launch follows them.
-static inline int spill_id_a_host(int l) { return l; }                  // (mcpc_kernels.h: spill_id_a)
-int flush_spill(mcpc_engine* e, int n_slots, int slot0, hipStream_t stream, int part) {
+// One Hebbian flush, as planned (mcpc_plan.h: plan_flush): fold the spilled steps from slot `slot0` on into the gradient sums of every
+// Linear j >= 1.  Every Linear has its own slab region, so the GEMMs of a flush are independent launches and ONE reduction launch
+// follows them.  An overlapped flush spreads them over two low-priority streams (`stream` and aux3); the reduction joins them.
+int flush_spill(mcpc_engine* e, const FlushPlan& f, int slot0, hipStream_t stream, int part) {
     const unsigned* const smax = e->spillmax + (size_t)part * kSpillTensors;      // largest |value| per spilled tensor of this segment
-    const int rows = n_slots * e->Bpad;
-    const int nlin = e->L + (e->has_head ? 1 : 0);
+    if (f.two_streams && !e->aux3) return fail(MCPC_ESTATE, "internal: a flush planned for two streams on an engine that has one");
+    hipStream_t const streams[2] = {stream, f.two_streams ? e->aux3 : stream};
+    if (f.two_streams) { HIP_TRY(hipEventRecord(e->ev_fork, stream)); HIP_TRY(hipStreamWaitEvent(e->aux3, e->ev_fork, 0)); }
     ReduceJobs jobs{};
-    unsigned max_blocks = 1;
-    // Overlapped flush: the launches alternate between two low-priority streams (kernels of one stream run one after the
-    // other, each leaving the idle CUs half empty while its last workgroups finish); the reduction joins them.
-    hipStream_t const main_stream = stream;
-    const bool two = e->aux3 != nullptr && stream == e->aux;
-    double load[2] = {0.0, 0.0};                            // work queued on each stream so far (output columns x rows)
-    if (two) { HIP_TRY(hipEventRecord(e->ev_fork, main_stream)); HIP_TRY(hipStreamWaitEvent(e->aux3, e->ev_fork, 0)); }
-    auto next_stream = [&](double cost) {                   // greedy: the launch goes to the stream with less work queued
-        const int k = (two && load[1] < load[0]) ? 1 : 0;
-        load[k] += cost;
-        return k ? e->aux3 : main_stream;
-    };
-    for (int j = 1; j < nlin; ++j) {
-        Lin& ln = e->lin[j];
+    for (int j = 1; j < e->L + e->has_head; ++j) {
+        const Lin& ln = e->lin[j];
+        const LinFlush& lf = f.lin[j];
         const int ne = ln.out_pad, na = ln.in_pad;
         const float* E = (j < e->L ? e->spill_e[j] : e->spill_eo) + (size_t)slot0 * e->Bpad * ne;
         const float* A = e->spill_a[j - 1] + (size_t)slot0 * e->Bpad * na;
-        const HebPlan h = plan_hebbian(e->knobs, ne, na, rows);
-        std::string plan;                                       // mcpc_last_flush_plan: one "kernel<args>x<groups>[*<act groups>]" per launch
-        auto name_launch = [&](const char* kern, int te, int ra, bool sw, int n_mt, int n_nt) {
-            char buf[64];
-            snprintf(buf, sizeof buf, "%s%s<%d,%d%s>x%d", plan.empty() ? "" : "+", kern, te, ra, sw ? ",T" : "", n_mt);
-            plan += buf;
-            if (n_nt > 1) plan += "*" + std::to_string(n_nt);
-        };
-        const char* const heb_name = e->knobs.heb_fp32 ? "heb" : "heb7";
-        const int e_id = j < e->L ? kMaxLatent + j : kSpillIdEo;          // (mcpc_kernels.h: spill_id_e / kSpillIdEo)
+        const unsigned* const e_max = smax + (j < e->L ? spill_id_e(j) : kSpillIdEo), * const a_max = smax + spill_id_a(j - 1);
         float* slab = e->slab + ln.slab_off;
-        float* slab_b = slab + (size_t)h.ksplit * ne * na;
-        if ((size_t)h.ksplit * ((size_t)ne * na + ne) > ln.slab_floats)
-            return fail(MCPC_ESTATE, "internal: Hebbian slabs of Linear %d (%d splits) exceed their allocation", j, h.ksplit);
-        if (h.swapped) {
-            stream = next_stream((double)ne * na);
-            // transposed product: the activations take the E slot, the errors the A slot; slab = [split][na][ne]
-            HebArgs a{A, E, slab, slab_b, rows, na, ne, h.rps, 1, 1, h.ksplit, 0, smax + spill_id_a_host(j - 1), smax + e_id};
-            name_launch(heb_name, h.te[0], 2, true, 1, 1);
-            int rc = 0;
-            if (!e->knobs.heb_fp32) {
-                if (h.te[0] == 1) rc = launch_heb7<1, 2, true>(a, stream);
-                else if (h.te[0] == 2) rc = launch_heb7<2, 2, true>(a, stream);
-                else rc = launch_heb7<4, 2, true>(a, stream);
-            } else
-            if (h.te[0] == 1) rc = launch_heb<1, 2, true>(a, stream);
-            else if (h.te[0] == 2) rc = launch_heb<2, 2, true>(a, stream);
-            else rc = launch_heb<4, 2, true>(a, stream);
-            if (rc) return rc;
-        } else if (h.tiled) {
-            int col = 0;
-            for (int part = 0; part < 2; ++part) {
-                if (h.n_mt[part] == 0) continue;
-                HebArgs a{E, A, slab, slab_b, rows, ne, na, h.rps, h.n_mt[part], h.n_nt, h.ksplit, col, smax + e_id, smax + spill_id_a_host(j - 1)};
-                stream = next_stream((double)h.n_mt[part] * h.te[part] * 16 * na);
-                int rc = 0;
-                const int te = h.te[part];
-                const bool resplit = te == 17 && h.ra == 2 && !e->knobs.heb_fp32 && e->knobs.heb171;        // (named where it launches)
-                if (!resplit) name_launch(heb_name, te, h.ra, false, h.n_mt[part], h.n_nt);
-                if (!e->knobs.heb_fp32) {
-                    if (te == 17 && h.ra == 2 && !e->knobs.heb171) rc = launch_heb7<17, 2>(a, stream);
-                    else if (te == 17 && h.ra == 2) {
-                        // 136 accumulators + the rest do not fit 256 registers (19 spilled): 8 activation tiles per workgroup instead,
-                        // i.e. twice the activation groups -- this group's 272 error columns are read twice (+6.5 MB per step at cfg-M)
-                        HebArgs a1 = a;
-                        a1.n_nt = 2 * a.n_nt;
-                        name_launch(heb_name, 17, 1, false, a1.n_mt, a1.n_nt);
-                        rc = launch_heb7<17, 1>(a1, stream);
-                    }
-                    else if (te == 16 && h.ra == 2) rc = launch_heb7<16, 2>(a, stream);
-                    else if (te == 8 && h.ra == 2) rc = launch_heb7<8, 2>(a, stream);
-                    else if (te == 17) rc = launch_heb7<17, 1>(a, stream);
-                    else if (te == 16) rc = launch_heb7<16, 1>(a, stream);
-                    else rc = launch_heb7<8, 1>(a, stream);
-                } else
-                if (te == 17 && h.ra == 2) rc = launch_heb<17, 2>(a, stream);
-                else if (te == 16 && h.ra == 2) rc = launch_heb<16, 2>(a, stream);
-                else if (te == 8 && h.ra == 2) rc = launch_heb<8, 2>(a, stream);
-                else if (te == 17) rc = launch_heb<17, 1>(a, stream);
-                else if (te == 16) rc = launch_heb<16, 1>(a, stream);
-                else rc = launch_heb<8, 1>(a, stream);
-                if (rc) return rc;
-                col += h.n_mt[part] * te * 16;
+        float* slab_b = slab + (size_t)lf.ksplit * ne * na;
+        for (int i = 0; i < lf.n_launch; ++i) {
+            const FlushLaunch& l = lf.launch[i];
+            if (l.family == HEB_DW) {
+                hipLaunchKernelGGL(mcpc_dw_kernel, dim3((l.wave_tiles + 3) / 4, lf.ksplit), dim3(256), 0, streams[l.stream], E, A, slab, slab_b,
+                                   f.rows, ne, na, lf.rps);
+                continue;
             }
-        } else {
-            stream = next_stream((double)ne * na);
-            hipLaunchKernelGGL(mcpc_dw_kernel, dim3((h.wave_tiles + 3) / 4, h.ksplit), dim3(256), 0, stream, E, A, slab, slab_b,
-                               rows, ne, na, h.rps);
-            plan = "dw tiles=" + std::to_string(h.wave_tiles);
+            // (swapped: the transposed product -- the activations take the E slot, the errors the A slot; slab = [split][na][ne])
+            const bool sw = l.swapped;
+            const HebArgs a{sw ? A : E, sw ? E : A, slab, slab_b, f.rows, sw ? na : ne, sw ? ne : na, lf.rps, l.n_mt, l.n_nt, lf.ksplit, l.col0,
+                            sw ? a_max : e_max, sw ? e_max : a_max};
+            if (const int rc = launch_heb(l, a, streams[l.stream])) return rc;
         }
-        e->last_flush[j] = plan + " ksplit=" + std::to_string(h.ksplit) + " rps=" + std::to_string(h.rps) + (ln.spill_tm ? " tm" : " rm");
-        const float sign = j < e->L ? -1.0f : 1.0f;
-        jobs.job[jobs.n_jobs++] = ReduceJob{slab, ln.G, ne * na, h.ksplit, sign, h.swapped ? ne : 0, h.swapped ? na : 0};
-        jobs.job[jobs.n_jobs++] = ReduceJob{slab_b, ln.Gb, ne, h.ksplit, sign, 0, 0};
-        max_blocks = std::max(max_blocks, (unsigned)std::min<size_t>(((size_t)ne * na + 255) / 256, 2048));
+        e->last_flush[j] = lf.text;
+        jobs.job[jobs.n_jobs++] = ReduceJob{slab, ln.G, ne * na, lf.ksplit, lf.sign, lf.tr_cols, lf.tr_ld};
+        jobs.job[jobs.n_jobs++] = ReduceJob{slab_b, ln.Gb, ne, lf.ksplit, lf.sign, 0, 0};
     }
-    stream = main_stream;
-    if (two) { HIP_TRY(hipEventRecord(e->ev_join, e->aux3)); HIP_TRY(hipStreamWaitEvent(main_stream, e->ev_join, 0)); }
+    if (f.two_streams) { HIP_TRY(hipEventRecord(e->ev_join, e->aux3)); HIP_TRY(hipStreamWaitEvent(stream, e->ev_join, 0)); }
     if (jobs.n_jobs > 0)
-        hipLaunchKernelGGL(mcpc_reduce_jobs_kernel, dim3(max_blocks, jobs.n_jobs), dim3(256), 0, stream, jobs);
+        hipLaunchKernelGGL(mcpc_reduce_jobs_kernel, dim3(f.max_blocks, jobs.n_jobs), dim3(256), 0, stream, jobs);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1169,11 +1082,11 @@ int mcpc_run(mcpc_engine* e, const mcpc_run_desc* r, void* stream_) {
             // the Hebbian GEMMs of this part run on the low-priority stream while the next segment steps
             HIP_TRY(hipEventRecord(e->ev_steps[it.part], stream));
             HIP_TRY(hipStreamWaitEvent(e->aux, e->ev_steps[it.part], 0));
-            if (const int rc = flush_spill(e, it.n, it.slot0, e->aux, it.part)) return rc;
+            if (const int rc = flush_spill(e, plan.flushes[it.flush], it.slot0, e->aux, it.part)) return rc;
             HIP_TRY(hipEventRecord(e->ev_flush[it.part], e->aux));
             e->flush_pending[it.part] = true;
         } else if (it.acc) {
-            if (const int rc = flush_spill(e, it.n, 0, stream, 0)) return rc;
+            if (const int rc = flush_spill(e, plan.flushes[it.flush], 0, stream, 0)) return rc;
         }
     }
     e->last_step = last_step_name(c);

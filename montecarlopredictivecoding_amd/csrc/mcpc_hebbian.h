@@ -47,6 +47,23 @@ struct HebArgs {
 #define MCPC_HEB_LDS_PAD 16        // floats added to a 256-float panel row in LDS (0: the linear image of round 2, for A/B runs)
 #endif
 constexpr int heb_lds_stride(int row_floats) { return row_floats == 256 ? row_floats + MCPC_HEB_LDS_PAD : row_floats; }
+// dynamic LDS of mcpc_heb_kernel<TE, RA, *>: two stages of both panels (host side: the launch, mcpc_api.hip)
+constexpr int heb_lds_bytes(int te, int ra) { return 2 * kHebKB * (heb_lds_stride(16 * te) + heb_lds_stride(16 * 8 * ra)) * (int)sizeof(float); }
+
+// The <TE, RA, SWAPPED> forms BOTH tiled kernels are instantiated for, listed once: the planner resolves every launch of a flush to an
+// index into this list (mcpc_plan.h: plan_flush), the executor's kernel table is built from it (mcpc_api.hip).
+#define MCPC_HEB_FORMS(X) X(17, 2, false) X(17, 1, false) X(16, 2, false) X(16, 1, false) X(8, 2, false) X(8, 1, false) \
+                          X(1, 2, true) X(2, 2, true) X(4, 2, true)
+struct HebForm { int te, ra; bool swapped; };
+#define MCPC_HEB_FORM_ROW(te, ra, sw) {te, ra, sw},
+constexpr HebForm kHebForms[] = {MCPC_HEB_FORMS(MCPC_HEB_FORM_ROW)};
+#undef MCPC_HEB_FORM_ROW
+constexpr int kNumHebForms = (int)(sizeof(kHebForms) / sizeof(kHebForms[0]));
+constexpr int heb_form_index(int te, int ra, bool swapped) {            // -1: no such instantiation
+    for (int i = 0; i < kNumHebForms; ++i)
+        if (kHebForms[i].te == te && kHebForms[i].ra == ra && kHebForms[i].swapped == swapped) return i;
+    return -1;
+}
 
 __device__ __forceinline__ void heb_glds16(const float* gsrc, float* lds_dst) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
@@ -226,6 +243,9 @@ __global__ __launch_bounds__(kHebThreads, 2) void mcpc_heb_kernel(const HebArgs 
 //     banks (no conflicts), as do the 16 lanes of the operand's ds_read_b128.
 constexpr int kHeb7KB = 32;            // spilled rows per stage = K of one bf16 MFMA = two row tiles
 constexpr int kHeb7LD = 40;            // bf16 elements between the rows of two units in an LDS plane: 32 of data + 8 of padding (80 B)
+// dynamic LDS of mcpc_heb7_kernel<TE, *, *>: two plane buffers + the bias sums + every wave's transpose scratch for one activation tile
+// (2 row tiles x 4 x 17 float4) (host side: the launch, mcpc_api.hip)
+constexpr int heb7_lds_bytes(int te) { return 2 * 2 * 16 * te * kHeb7LD * 2 + 16 * te * (int)sizeof(float) + 8 * 2 * 272 * (int)sizeof(float); }
 
 // SWAPPED: the launch computes the TRANSPOSED product for a Linear with a narrow input (the E slot holds its activations, the A slot
 // its errors); the bias sums (column sums of the errors) then come from the A operand, and the reduction writes the slab back transposed.

@@ -185,8 +185,8 @@ __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4
 // ---- largest |value| per spilled tensor (for the Hebbian GEMM's operand scaling) ---------------------------------------------------------
 // tensor ids: activations A_l = l, errors E_l = kMaxLatent + l, read-out errors E_o = 2 kMaxLatent
 constexpr int kSpillTensors = 16;
-__device__ __forceinline__ int spill_id_a(int l) { return l; }
-__device__ __forceinline__ int spill_id_e(int l) { return kMaxLatent + l; }
+__host__ __device__ __forceinline__ int spill_id_a(int l) { return l; }
+__host__ __device__ __forceinline__ int spill_id_e(int l) { return kMaxLatent + l; }
 constexpr int kSpillIdEo = 2 * kMaxLatent;
 __device__ __forceinline__ float absmax4(float m, f32x4 v) {
     return fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));

@@ -1,6 +1,6 @@
 // Host-side planning of an engine: everything mcpc_create decides BEFORE it allocates -- padded shapes, the step-kernel form and its
 // fallbacks, the LDS plans and step tables, the layer-wise job tables, the round schedule, the spill ring's size -- and what mcpc_run
-// decides before it launches: the schedule of a run (plan_run) and the shape of a Hebbian flush (plan_hebbian).  Plain host code
+// decides before it launches: the schedule of a run (plan_run) and every launch of its Hebbian flushes (plan_flush).  Plain host code
 // that makes no HIP call, so it runs (and is tested: mcpc_debug_plan, tests/test_plan_host.py; mcpc_debug_run_plan,
 // tests/test_run_plan_host.py) without a device.  Included by mcpc_api.hip only, after the kernel headers whose constants and table
 // types it uses.
@@ -49,8 +49,9 @@ struct Lin {
     float* Gb = nullptr;           // [out_pad]
     int g_ld = 0;
     bool spill_tm = false;         // its Hebbian operands are spilled tile-major (the fp16 kernel mcpc_heb7_kernel reads them)
-    size_t slab_off = 0;           // float offset of this Linear's split-K slabs inside mcpc_engine::slab
-    size_t slab_floats = 0;        // ... and their size
+    size_t slab_off = 0;           // float offset of this Linear's split-K slabs inside mcpc_engine::slab (plan_engine)
+    size_t slab_floats = 0;        // ... and their size: `slab_splits` weight and bias slabs, the most K-splits a flush of a whole
+    int slab_splits = 0;           //     ring part asks for (HebPlan::ksplit_cap)
 };
 
 // Developer overrides of the schedule heuristics, parsed ONCE from mcpc_net_desc::tuning at mcpc_create
@@ -199,6 +200,7 @@ struct EnginePlan {
     // Hebbian spill ring: `slots` steps in parts of `half_slots`; the flush of one part runs on `aux` while the step kernel fills another
     int slots = 0, half_slots = 0;
     size_t slot_bytes = 0;          // ... and the bytes one step spills
+    size_t slab_floats = 0;         // the split-K slabs of all Linears j >= 1 (Lin::slab_off, slab_floats)
 };
 
 // the pair of launches a step on the layer-wise kernels is (mcpc_step_kernel_name, mcpc_last_step_kernel_name: as a trace shows them)
@@ -823,6 +825,7 @@ inline int check_net_desc(const mcpc_net_desc* d) {
 // more units than CUs on the round schedule, plan_rounds).  The barrier kernel (16 chains, 4 waves, generic epilogues) is the
 // fallback when the in-place LDS plan does not fit, and the independent form the parity checks replay the default against
 // (bench.py self_check, tests): tuning ws=0 forces it, ws=2 insists on the in-place kernel.
+inline void plan_slabs(EnginePlan& e);       // (behind plan_hebbian, below)
 inline int plan_engine(const mcpc_net_desc& d, int n_cu, size_t total_mem, EnginePlan& e) {
     const Knobs& kn = e.knobs;
     e.L = d.n_latent;
@@ -906,6 +909,7 @@ inline int plan_engine(const mcpc_net_desc& d, int n_cu, size_t total_mem, Engin
     if (kn.no_overlap || e.slots < 2) e.half_slots = e.slots;          // serial flushes on the caller's stream: one part
     else if (e.slots >= kn.ring_parts) { e.half_slots = e.slots / kn.ring_parts; e.slots = e.half_slots * kn.ring_parts; }
     else { e.slots &= ~1; e.half_slots = e.slots / 2; }                   // fewer slots than parts: two halves
+    plan_slabs(e);
     // the tables
     if (e.lw) {
         std::vector<LwJob> bwd;
@@ -982,6 +986,92 @@ inline HebPlan plan_hebbian(const Knobs& kn, int ne, int na, int rows) {
     return h;
 }
 
+// The split-K slabs: every Linear j >= 1 has a region of its own, sized for the most splits a flush of a whole ring part asks for --
+// no shorter flush asks for more (tests/test_run_plan_host.py holds every planned flush to it)
+inline void plan_slabs(EnginePlan& e) {
+    e.slab_floats = 0;
+    for (int j = 1; j < e.L + e.has_head; ++j) {
+        Lin& ln = e.lin[j];
+        ln.slab_splits = plan_hebbian(e.knobs, ln.out_pad, ln.in_pad, e.half_slots * e.Bpad).ksplit_cap;
+        ln.slab_off = e.slab_floats;
+        ln.slab_floats = (size_t)ln.slab_splits * ((size_t)ln.out_pad * ln.in_pad + ln.out_pad);
+        e.slab_floats += ln.slab_floats;
+    }
+}
+
+// ---- a Hebbian flush as data ----------------------------------------------------------------------------------------------------------------
+// One launch of a flush.  The tiled kernels (HEB_F16: mcpc_heb7_kernel, HEB_FP32: mcpc_heb_kernel) run the instantiation `form` of
+// kHebForms (mcpc_hebbian.h) on a grid of n_mt x n_nt x ksplit workgroups from output column col0 on; the streaming kernel (HEB_DW:
+// mcpc_dw_kernel) covers the Linear with `wave_tiles` 64 x 64 wave tiles.  `stream`: which of the flush's two streams it goes to.
+enum { HEB_F16 = 0, HEB_FP32 = 1, HEB_DW = 2 };
+inline const char* heb_family_name(int family) { return family == HEB_F16 ? "heb7" : family == HEB_FP32 ? "heb" : "dw"; }
+struct FlushLaunch { int family, form, te, ra; bool swapped; int n_mt, n_nt, col0, stream, wave_tiles; };
+struct LinFlush {
+    int n_launch;
+    FlushLaunch launch[2];
+    int ksplit, rps;
+    float sign;                 // of the sums in the gradient: -1 for a latent Linear, +1 for the read-out
+    int tr_cols, tr_ld;         // its weight slab is reduced transposed (ReduceJob; 0, 0: as it lies)
+    char text[96];              // mcpc_last_flush_plan
+};
+struct FlushPlan {
+    int n_slots, rows;
+    bool two_streams;           // the launches are spread over two streams; else every `stream` is 0
+    LinFlush lin[kMaxLatent + 1];       // per Linear j >= 1 (entry 0 is unused)
+    unsigned max_blocks;        // gridDim.x of the one mcpc_reduce_jobs_kernel launch behind the GEMMs
+};
+
+// The flush of `n_slots` spilled steps: what is launched for every Linear j >= 1, in launch order.  With two streams a launch goes to
+// the one with less work queued so far (output columns x input columns of the launch; kernels of one stream run one after the other,
+// each leaving the idle CUs half empty while its last workgroups finish).
+inline void plan_flush(const EnginePlan& e, int n_slots, bool two_streams, FlushPlan& f) {
+    const Knobs& kn = e.knobs;
+    f.n_slots = n_slots; f.rows = n_slots * e.Bpad; f.two_streams = two_streams; f.max_blocks = 1;
+    const int tiled_family = kn.heb_fp32 ? HEB_FP32 : HEB_F16;
+    double load[2] = {0.0, 0.0};
+    for (int j = 1; j < e.L + e.has_head; ++j) {
+        const Lin& ln = e.lin[j];
+        const int ne = ln.out_pad, na = ln.in_pad;
+        const HebPlan h = plan_hebbian(kn, ne, na, f.rows);
+        LinFlush& lf = f.lin[j];
+        lf.n_launch = 0; lf.ksplit = h.ksplit; lf.rps = h.rps;
+        lf.sign = j < e.L ? -1.0f : 1.0f;
+        lf.tr_cols = h.swapped ? ne : 0; lf.tr_ld = h.swapped ? na : 0;
+        int len = 0;
+        auto put = [&](const char* fmt, auto... v) { if (len < (int)sizeof lf.text) len += snprintf(lf.text + len, sizeof lf.text - len, fmt, v...); };
+        auto add = [&](FlushLaunch l, double cost) {
+            l.form = l.family == HEB_DW ? -1 : heb_form_index(l.te, l.ra, l.swapped);
+            l.stream = (two_streams && load[1] < load[0]) ? 1 : 0;
+            load[l.stream] += cost;
+            if (l.family == HEB_DW) put("dw tiles=%d", l.wave_tiles);
+            else {
+                put("%s%s<%d,%d%s>x%d", lf.n_launch ? "+" : "", heb_family_name(l.family), l.te, l.ra, l.swapped ? ",T" : "", l.n_mt);
+                if (l.n_nt > 1) put("*%d", l.n_nt);
+            }
+            lf.launch[lf.n_launch++] = l;
+        };
+        if (h.swapped) {
+            // transposed product: the activations take the E slot (te = their tiles), the errors the A slot
+            add({tiled_family, 0, h.te[0], 2, true, 1, 1, 0, 0, 0}, (double)ne * na);
+        } else if (h.tiled) {
+            int col = 0;
+            for (int g = 0; g < 2; ++g) {
+                if (h.n_mt[g] == 0) continue;
+                int ra = h.ra, n_nt = h.n_nt;
+                // tuning heb171=1: <17, 2>'s 136 accumulators + the rest do not fit 256 registers (19 spilled) -- 8 activation tiles per
+                // workgroup instead, i.e. twice the activation groups: this group's 272 error columns are read twice (+6.5 MB per step at cfg-M)
+                if (h.te[g] == 17 && ra == 2 && tiled_family == HEB_F16 && kn.heb171) { ra = 1; n_nt *= 2; }
+                add({tiled_family, 0, h.te[g], ra, false, h.n_mt[g], n_nt, col, 0, 0}, (double)h.n_mt[g] * h.te[g] * 16 * na);
+                col += h.n_mt[g] * h.te[g] * 16;
+            }
+        } else {
+            add({HEB_DW, 0, 0, 0, false, 0, 0, 0, 0, h.wave_tiles}, (double)ne * na);
+        }
+        put(" ksplit=%d rps=%d %s", h.ksplit, h.rps, ln.spill_tm ? "tm" : "rm");
+        f.max_blocks = std::max(f.max_blocks, (unsigned)std::min<size_t>(((size_t)ne * na + 255) / 256, 2048));
+    }
+}
+
 // ---- the schedule of a run -----------------------------------------------------------------------------------------------------------------
 // energy partials per step: one slot per workgroup; the in-place kernel indexes them by 16-chain tile
 inline size_t energy_slots(const EnginePlan& e) { return e.lw ? (size_t)e.nwg_live : e.ws == 2 ? (size_t)e.Bpad / 16 : (size_t)e.nwg; }
@@ -1010,8 +1100,8 @@ inline int check_step_range(const mcpc_run_desc& r) {
 // One item of a run: steps [t0, t0 + n) as ONE plain launch (q == 0: the layer-wise pair, the unified-wave, in-place or barrier kernel,
 // as the engine and the run have it) or as ONE cycle of the round schedule (q >= 1: rr_k launches of q steps, n == rr_m q).  An item
 // lies wholly on one side of the accumulation window; one inside it (`acc`) is a Hebbian segment: it spills into slots
-// [slot0, slot0 + n) of the ring -- part `part` -- and a flush of those n slots follows it.
-struct RunItem { int t0, n, q; bool acc; int part, slot0; };
+// [slot0, slot0 + n) of the ring -- part `part` -- and a flush of those n slots follows it: `flush` is its index in RunPlan::flushes (-1: none).
+struct RunItem { int t0, n, q; bool acc; int part, slot0, flush; };
 struct RunPlan {
     bool unified = false;           // the run is served by the unified-wave kernel (use_unified), else by the engine's main plan
     bool accumulates = false;       // some step of the run lies in the accumulation window
@@ -1019,13 +1109,16 @@ struct RunPlan {
     bool overlap = false;           // flushes run on the auxiliary stream beside the next segment (a ring of n_parts parts), else serially
     int n_parts = 1;
     std::vector<RunItem> items;
+    std::vector<FlushPlan> flushes; // one per distinct length of the run's Hebbian segments (plan_flush)
 };
 
 // What mcpc_run launches for `r`, in order: a pure function of the engine's plan and the fields of the descriptor that shape a run
 // (T, t_begin, n_steps, acc_begin, acc_end, update_x, xopt_kind, noise_mode, loss_kind).  `stamps`: the diagnostic build with in-kernel
 // stamps, which never uses the round schedule.  Non-accumulating stretches run as one persistent launch (on the round schedule: whole
 // cycles, longest launches first, and one plain launch for fewer than rr_m steps left: hardware rounds); accumulating stretches are cut
-// at the capacity of a ring part, every segment one cycle where the round schedule applies.  `p.items` keeps its storage between runs.
+// at the capacity of a ring part, every segment one cycle where the round schedule applies, and the flush behind a segment is planned
+// once per distinct segment length (two flush streams: overlapped flushes and tuning flush_streams >= 2).  `p.items` and `p.flushes`
+// keep their storage between runs.
 // (tests/test_run_plan_host.py, through mcpc_debug_run_plan)
 inline void plan_run(const EnginePlan& e, const mcpc_run_desc& r, bool stamps, RunPlan& p) {
     const int acc_b = std::max(r.acc_begin, 0), acc_e = std::min(r.acc_end, r.T);
@@ -1036,6 +1129,7 @@ inline void plan_run(const EnginePlan& e, const mcpc_run_desc& r, bool stamps, R
     p.overlap = e.half_slots < e.slots;
     p.n_parts = std::max(1, e.slots / std::max(1, e.half_slots));
     p.items.clear();
+    p.flushes.clear();
     const bool rr_ok = e.rr && r.update_x && !stamps;
     // a launch's row-exponent words carry their generation -- the step of the launch, or step x entries + entry for a ring slot -- in 24
     // bits (mcpc_kernels.h: rowexp_track): longer stretches are cut into several launches (a wrapped generation would never supersede
@@ -1061,13 +1155,21 @@ inline void plan_run(const EnginePlan& e, const mcpc_run_desc& r, bool stamps, R
         } else if (rr_ok) {
             while (n >= e.rr_m) {
                 const int qc = std::min(std::max(1, e.knobs.rr_qmax), n / e.rr_m);
-                p.items.push_back({t, qc * e.rr_m, qc, false, 0, 0});
+                p.items.push_back({t, qc * e.rr_m, qc, false, 0, 0, -1});
                 t += qc * e.rr_m; n -= qc * e.rr_m;
             }
             if (n == 0) continue;
         }
+        int flush = -1;
+        for (size_t i = 0; in_acc && i < p.flushes.size(); ++i)
+            if (p.flushes[i].n_slots == n) flush = (int)i;
+        if (in_acc && flush < 0) {
+            flush = (int)p.flushes.size();
+            p.flushes.emplace_back();
+            plan_flush(e, n, p.overlap && e.knobs.flush_streams >= 2, p.flushes.back());
+        }
         const bool ring = in_acc && p.overlap;                // (a serial run keeps part 0, slot 0)
-        p.items.push_back({t, n, q, in_acc, ring ? part : 0, ring ? part * e.half_slots : 0});
+        p.items.push_back({t, n, q, in_acc, ring ? part : 0, ring ? part * e.half_slots : 0, flush});
         if (ring) part = (part + 1) % p.n_parts;
         t += n;
     }
@@ -1111,6 +1213,8 @@ inline std::string plan_json(const EnginePlan& e) {
     for (int l = 0; l < e.L; ++l) json_add(s, "%s%d", l ? "," : "", e.npad[l]);
     s += "],\"spill_tm\":[";
     for (int j = 0; j < nlin; ++j) json_add(s, "%s%d", j ? "," : "", e.lin[j].spill_tm ? 1 : 0);
+    json_add(s, "],\"slab_floats\":%zu,\"slabs\":[", e.slab_floats);
+    for (int j = 0; j < nlin; ++j) json_add(s, "%s[%zu,%zu,%d]", j ? "," : "", e.lin[j].slab_off, e.lin[j].slab_floats, e.lin[j].slab_splits);
     s += "],\"main\":";
     json_step_plan(s, e.main);
     json_add(s, ",\"unified\":{\"ok\":%d,\"on\":%d,\"prefer\":%d,\"plan\":", e.u.ok ? 1 : 0, e.u.on ? 1 : 0, e.u.prefer ? 1 : 0);
@@ -1128,7 +1232,7 @@ inline std::string plan_json(const EnginePlan& e) {
     return s;
 }
 
-// mcpc_debug_run_plan: the schedule of a run, and the flush plan of every Linear j >= 1 behind each of its Hebbian segments
+// mcpc_debug_run_plan: the schedule of a run, and the planned flush (RunPlan::flushes) behind each of its Hebbian segments
 inline std::string run_plan_json(const EnginePlan& e, const RunPlan& p) {
     std::string s;
     json_add(s, "{\"unified\":%d,\"accumulates\":%d,\"lean_ok\":%d,\"overlap\":%d,\"n_parts\":%d,"
@@ -1138,18 +1242,31 @@ inline std::string run_plan_json(const EnginePlan& e, const RunPlan& p) {
         const RunItem& it = p.items[i];          // ("flush": a flush of the item's n slots follows it -- every Hebbian segment, nothing else)
         json_add(s, "%s[%d,%d,%d,%d,%d,%d,%d]", i ? "," : "", it.t0, it.n, it.q, it.acc ? 1 : 0, it.part, it.slot0, it.acc ? 1 : 0);
     }
-    s += "],\"flush_fields\":[\"ksplit\",\"rps\",\"ksplit_cap\"],\"flushes\":[";
+    s += "],\"flush_fields\":[\"ksplit\",\"rps\",\"ksplit_cap\"],"
+         "\"launch_fields\":[\"family\",\"form\",\"te\",\"ra\",\"swapped\",\"n_mt\",\"n_nt\",\"col0\",\"stream\",\"wave_tiles\"],"
+         "\"reduce_fields\":[\"sign\",\"tr_cols\",\"tr_ld\"],\"flushes\":[";
     const int nlin = e.L + (e.has_head ? 1 : 0);
     bool first = true;
     for (const RunItem& it : p.items) {
-        if (!it.acc) continue;
-        json_add(s, "%s{\"rows\":%d,\"lin\":[", first ? "" : ",", it.n * e.Bpad);
+        if (it.flush < 0) continue;
+        const FlushPlan& f = p.flushes[it.flush];
+        json_add(s, "%s{\"rows\":%d,\"two_streams\":%d,\"max_blocks\":%u,\"lin\":[", first ? "" : ",", f.rows, f.two_streams ? 1 : 0, f.max_blocks);
         first = false;
+        for (int j = 1; j < nlin; ++j) json_add(s, "%s[%d,%d,%d]", j > 1 ? "," : "", f.lin[j].ksplit, f.lin[j].rps, e.lin[j].slab_splits);
+        s += "],\"launches\":[";
         for (int j = 1; j < nlin; ++j) {
-            const Lin& ln = e.lin[j];
-            const HebPlan h = plan_hebbian(e.knobs, ln.out_pad, ln.in_pad, it.n * e.Bpad);
-            json_add(s, "%s[%d,%d,%d]", j > 1 ? "," : "", h.ksplit, h.rps, plan_hebbian(e.knobs, ln.out_pad, ln.in_pad, e.half_slots * e.Bpad).ksplit_cap);
+            s += j > 1 ? ",[" : "[";
+            for (int i = 0; i < f.lin[j].n_launch; ++i) {
+                const FlushLaunch& l = f.lin[j].launch[i];
+                json_add(s, "%s[\"%s\",%d,%d,%d,%d,%d,%d,%d,%d,%d]", i ? "," : "", heb_family_name(l.family), l.form, l.te, l.ra, l.swapped ? 1 : 0,
+                         l.n_mt, l.n_nt, l.col0, l.stream, l.wave_tiles);
+            }
+            s += "]";
         }
+        s += "],\"reduce\":[";
+        for (int j = 1; j < nlin; ++j) json_add(s, "%s[%g,%d,%d]", j > 1 ? "," : "", (double)f.lin[j].sign, f.lin[j].tr_cols, f.lin[j].tr_ld);
+        s += "],\"text\":[";
+        for (int j = 1; j < nlin; ++j) json_add(s, "%s\"%s\"", j > 1 ? "," : "", f.lin[j].text);
         s += "]}";
     }
     s += "]}";

@@ -1,9 +1,12 @@
-"""The Hebbian flush against fp64 sums of the recorded states, on every plan `flush_spill` (csrc/mcpc_api.hip) can choose.
+"""The Hebbian flush against fp64 sums of the recorded states, on every plan `plan_flush` (csrc/mcpc_plan.h) can choose; `flush_spill`
+(csrc/mcpc_api.hip) executes the planned launches.
 
 A learning call records x_t on every step of its accumulation window; the fp64 sums of the same window are then built from the records
 (as tests/test_gpu_headline.py does):  dF/dW_j = -sum e_j^T f(x_{j-1}) for the latent Linears, +sum e_o^T f(x_L) for the
 read-out, the bias sums alike (Linear 0's -sum e_1 through e0sum / mcpc_dw0_kernel).  Every entry is compared with a bound relative to
-ITS OWN sum of |terms|, and `mcpc_last_flush_plan` proves which kernels, K-splits and layouts computed it.
+ITS OWN sum of |terms|, and `mcpc_last_flush_plan` proves which kernels, K-splits and layouts computed it: the text the planner
+formatted for the flush that ran -- every runner holds it to the "text" mcpc_debug_run_plan gives, for the device's own CU count, for
+the run's last flushing item.
 
 EXACT-IMAGE PROBLEMS isolate the flush (the `_flush_problem` of test_gpu_accuracy.py): all-zero weights and biases, identity
 activations, a Gaussian read-out with var = 1.  Every prediction is an exact 0, so e_l = x_l, f(x_l) = x_l and e_o = -y: the spilled images
@@ -85,7 +88,7 @@ def parse_plan(s):
 
 
 def instantiations(p, heb171=False):
-    """Kernel instantiations a parsed plan launched, as flush_spill names them: 'heb7<17,2>', 'heb<4,2,T>', 'heb7<17,1>/heb171', 'dw'."""
+    """Kernel instantiations a parsed plan launched, as plan_flush names them: 'heb7<17,2>', 'heb<4,2,T>', 'heb7<17,1>/heb171', 'dw'."""
     if p["kernel"] == "dw":
         return {"dw"}
     out = set()
@@ -110,6 +113,16 @@ def b_coeff(p, n_flush):
 
 def _bpad(B):
     return (B + 31) // 32 * 32
+
+
+def _planned_text(sizes, n_out, B, tuning, run):
+    """The flush texts, Linear 1 first, that mcpc_debug_run_plan plans on this device for the last flushing item of `run`."""
+    from tests.plan_util import run_plan
+    props = torch.cuda.get_device_properties(0)
+    rp = run_plan(sizes=sizes, n_out=n_out, batch=B, tuning=tuning, n_cu=props.multi_processor_count, total_mem=props.total_memory,
+                  n_in=N_IN, run=run)
+    assert rp["flushes"], "the run accumulates: it flushes"
+    return rp["flushes"][-1]["text"]
 
 
 def _pad_rows(x, B):
@@ -206,6 +219,9 @@ def _run_exact(sizes, n_out, B, T, tuning, seed=1, seg_len=None, seg_exps=None):
         eng.sync_check()
         plans = {j: eng.last_flush_plan(j) for j in range(1, len(dims) - 1)}
         assert eng.last_flush_plan(0) == "" and eng.last_flush_plan(len(dims) - 1) == ""
+        assert [plans[j] for j in sorted(plans)] == _planned_text(sizes, n_out, B, tuning, dict(
+            T=T, t_begin=0, n_steps=T, acc_begin=0, acc_end=T, update_x=1, xopt_kind=L.XOPT_SGD, noise_mode=L.NOISE_EXTERNAL,
+            loss_kind=L.LOSS_GAUSSIAN if n_out else L.LOSS_NONE))
         q = eng.query()
         step = eng.last_step_kernel()
     finally:
@@ -449,6 +465,9 @@ def _step_case(net, tuning):
         eng.sync_check()
         step = eng.last_step_kernel()
         plans = [eng.last_flush_plan(j) for j in range(1, len(dims) - 1)]
+        assert plans == _planned_text(sizes, n_out, B, tuning, dict(
+            T=STEP_T, t_begin=0, n_steps=STEP_T, acc_begin=STEP_T - STEP_ACC, acc_end=STEP_T, update_x=1, xopt_kind=L.XOPT_SGD,
+            noise_mode=L.NOISE_PHILOX, loss_kind=L.LOSS_BERNOULLI))
         pref = eng.query()["step_kernel"]
     finally:
         eng.close()

@@ -2,7 +2,7 @@
 
 With profiling on, mcpc_run brackets every launch of the step kernel with HIP events and counts the steps the launches cover
 (mcpc_last_step_kernel_ms); mcpc_last_step_kernel_name names the forms it launched.  Both must be what mcpc_debug_run_plan plans for
-the device's own CU count:
+the device's own CU count, and mcpc_last_flush_plan must be the text planned for the run's last flushing item:
   * one bracket per plain item -- also on the layer-wise kernels, where the bracket is around the whole pair-per-step sequence of
     the item (launch_lw_steps), not around each of its 2 n launches -- and rr_k per cycle of the round schedule;
   * the steps of all items, which tile the run: n_steps;
@@ -63,6 +63,7 @@ def _ran(name):
                   acc_end=WINDOW[1], energy_mode=L.ENERGY_ALL, rec_begin=0, rec_stride=9, rec_count=5, rec_x=True)
     _, launches, steps = eng.last_step_kernel_ms()
     name_ran = eng.last_step_kernel()
+    flush_text = [eng.last_flush_plan(j) for j in (1, 2)]
     eng.set_profiling(False)
     out = [torch.empty_like(x) for x in xs]
     eng.store_state(out)
@@ -75,7 +76,7 @@ def _ran(name):
                noise_mode=L.NOISE_PHILOX, loss_kind=L.LOSS_BERNOULLI)
     rp = run_plan(run=run, **net)
     return dict(plan=plan(**net), items=[dict(zip(rp["fields"], it)) for it in rp["items"]], unified=rp["unified"], launches=launches,
-                steps=steps, name=name_ran, states=[t.cpu().numpy() for t in out + list(res.rec_x)], energies=res.energies.cpu().numpy(),
+                steps=steps, name=name_ran, flush_text=flush_text, planned_text=rp["flushes"][-1]["text"], states=[t.cpu().numpy() for t in out + list(res.rec_x)], energies=res.energies.cpu().numpy(),
                 grads=grads.cpu().numpy())
 
 
@@ -86,6 +87,7 @@ def test_a_run_launches_what_its_plan_holds(name):
     rr_k = p["rounds"]["k"]
     assert c["launches"] == sum(rr_k if k["q"] else 1 for k in items), (c["launches"], items)
     assert c["steps"] == T == sum(k["n"] for k in items)
+    assert c["flush_text"] == c["planned_text"]          # the last flush ran the launches planned for the last flushing item
     has_plain, has_cycle = any(not k["q"] for k in items), any(k["q"] for k in items)
     plain = PLAIN.get(p["form"], "mcpc::mcpc_steps_u_kernel<false>" if c["unified"] else "mcpc::mcpc_steps_ws2_kernel<1, false>")
     cycle = "mcpc::mcpc_steps_u_kernel<true>" if c["unified"] else "mcpc::mcpc_steps_ws2_kernel<1, true>"

@@ -5,7 +5,10 @@
 schedule and with which q, and which part of the spill ring a segment fills.  The library's plan is compared with it item for item
 over a seeded sweep of (net, tuning, run shape), and held to the properties the executor and the ring rely on without the model.
 `_heb_model` mirrors plan_hebbian of the same commit (lines 528-572): the split count of a flush never exceeds the one the slabs
-are sized for."""
+are sized for.  `_flush_model` is a transcription of what flush_spill decided while it launched, before the flush became data too
+(commit e752590, csrc/mcpc_api.hip lines 636-740): the kernel instantiation of every launch, its grid, first column and stream, the
+reduction jobs and the text of mcpc_last_flush_plan.  The library's planned flushes (plan_flush) equal it launch for launch and
+character for character over the same sweep and over directed shapes that reach every instantiation and every branch."""
 import random
 
 import pytest
@@ -21,7 +24,7 @@ LOSS_NONE, LOSS_BERNOULLI = 0, 2
 
 
 def _knobs(tuning):
-    kn = dict(flush_tail=0, rr_qmax=100, dw_ksplit=0)
+    kn = dict(flush_tail=0, rr_qmax=100, dw_ksplit=0, heb_fp32=0, heb171=0, flush_streams=2)
     for item in (tuning or "").split(","):
         if "=" in item and item.split("=")[0] in kn:
             kn[item.split("=")[0]] = int(item.split("=")[1])
@@ -82,28 +85,36 @@ def _use_unified(p, tuning, run):
                     and run["update_x"] and lean and serves))
 
 
-def _heb_model(ne, na, rows, dw_ksplit=0):
-    """(ksplit, rps, ksplit_cap) of plan_hebbian for a Linear of ne x na padded units and `rows` spilled rows."""
-    KB = 32
+def _heb_tiles(ne, na):
+    """The tiling plan_hebbian gives a Linear of ne x na padded units: (wide, narrow_in, ra, te[2], n_mt[2], n_nt)."""
     et, at = ne // 16, na // 16
     wide = et >= 8 and at % 8 == 0 and (at <= 16 or at % 16 == 0)
     narrow_in = not wide and et == 16 and at in (1, 2, 4)
-    n_mt, n_nt = [0, 0], 1
+    ra, te, n_mt, n_nt = 0, [0, 0], [0, 0], 1
     if wide:
         ra = 2 if at >= 16 else 1
         n_nt = at // (8 * ra)
-        if et <= 16:
-            n_mt = [1, 0]
+        if et <= 8:
+            te, n_mt = [8, 0], [1, 0]
+        elif et <= 16:
+            te, n_mt = [16, 0], [1, 0]
         else:
             b17 = et % 16
             if et - 17 * b17 >= 0:
-                n_mt = [b17, (et - 17 * b17) // 16]
+                te, n_mt = [17, 16], [b17, (et - 17 * b17) // 16]
             else:
-                n_mt = [(et + 16) // 17, 0]
+                te, n_mt = [17, 0], [(et + 16) // 17, 0]
             if n_mt[0] == 0:
-                n_mt = [n_mt[1], 0]
+                te, n_mt = [te[1], 0], [n_mt[1], 0]
     elif narrow_in:
-        n_mt = [1, 0]
+        ra, te, n_mt = 2, [at, 0], [1, 0]
+    return wide, narrow_in, ra, te, n_mt, n_nt
+
+
+def _heb_model(ne, na, rows, dw_ksplit=0):
+    """(ksplit, rps, ksplit_cap) of plan_hebbian for a Linear of ne x na padded units and `rows` spilled rows."""
+    KB = 32
+    wide, narrow_in, _, _, n_mt, n_nt = _heb_tiles(ne, na)
     if wide or narrow_in:
         want = dw_ksplit if dw_ksplit > 0 else max(1, rows // (48 * KB))
         if dw_ksplit <= 0:
@@ -116,6 +127,123 @@ def _heb_model(ne, na, rows, dw_ksplit=0):
         want = max(1, min(4096 // wave_tiles, rows // 64))
         rps = ((rows + want - 1) // want + 15) // 16 * 16
     return (rows + rps - 1) // rps, rps, want
+
+
+# the <TE, RA, SWAPPED> instantiations of the tiled Hebbian kernels, in the order of csrc/mcpc_hebbian.h: MCPC_HEB_FORMS
+HEB_FORMS = [(17, 2, 0), (17, 1, 0), (16, 2, 0), (16, 1, 0), (8, 2, 0), (8, 1, 0), (1, 2, 1), (2, 2, 1), (4, 2, 1)]
+LAUNCH_FIELDS = ["family", "form", "te", "ra", "swapped", "n_mt", "n_nt", "col0", "stream", "wave_tiles"]
+
+
+def _lins(p):
+    """(out_pad, in_pad) of every Linear j >= 1 of an engine plan."""
+    return list(zip(p["npad"][1:] + ([p["out_pad"]] if p["out_pad"] else []), p["npad"]))
+
+
+def _flush_model(p, tuning, rows, two):
+    """What flush_spill of commit e752590 (csrc/mcpc_api.hip lines 636-740, with plan_hebbian of csrc/mcpc_plan.h lines 939-983) launched
+    for a flush of `rows` spilled rows on the engine plan `p`, decided as it decided them while launching.  `two`: its
+    `aux3 != nullptr && stream == aux` -- ensure_spill (lines 578-592) created aux when the flushes overlap and aux3 when also
+    flush_streams >= 2, and only an overlapped flush ran on aux.  Per Linear j >= 1: the launches as rows of LAUNCH_FIELDS without
+    "form" (te, ra, swapped: the template arguments the if / else chains of lines 678-718 picked, their last `else` included), the
+    text of mcpc_last_flush_plan, (sign, tr_cols, tr_ld) of its weight slab's reduction job; and the reduction launch's max_blocks."""
+    kn = _knobs(tuning)
+    fp32, heb171 = bool(kn["heb_fp32"]), bool(kn["heb171"])
+    heb_name = "heb" if fp32 else "heb7"
+    load = [0.0, 0.0]
+
+    def next_stream(cost):                                   # greedy: the launch goes to the stream with less work queued
+        k = 1 if two and load[1] < load[0] else 0
+        load[k] += cost
+        return k
+
+    def name_launch(plan, kern, te, ra, sw, n_mt, n_nt):
+        return plan + "%s%s<%d,%d%s>x%d" % ("+" if plan else "", kern, te, ra, ",T" if sw else "", n_mt) + ("*%d" % n_nt if n_nt > 1 else "")
+
+    def chain(te, ra):                                       # lines 698-718, the same for both kernels once the re-split is taken out
+        for t, r in ((17, 2), (16, 2), (8, 2)):
+            if te == t and ra == 2:
+                return t, r
+        return (17, 1) if te == 17 else (16, 1) if te == 16 else (8, 1)
+
+    launches, texts, reduce, max_blocks = [], [], [], 1
+    L = len(p["npad"])
+    for j, (ne, na) in enumerate(_lins(p), 1):
+        wide, narrow_in, ra, te, n_mt, n_nt = _heb_tiles(ne, na)
+        ksplit, rps, _ = _heb_model(ne, na, rows, kn["dw_ksplit"])
+        mine, plan = [], ""
+        if narrow_in:
+            stream = next_stream(float(ne * na))
+            plan = name_launch(plan, heb_name, te[0], 2, True, 1, 1)
+            mine.append([heb_name, 1 if te[0] == 1 else 2 if te[0] == 2 else 4, 2, 1, 1, 1, 0, stream, 0])
+        elif wide:
+            col = 0
+            for part in range(2):
+                if n_mt[part] == 0:
+                    continue
+                stream = next_stream(float(n_mt[part] * te[part] * 16 * na))
+                t = te[part]
+                resplit = t == 17 and ra == 2 and not fp32 and heb171
+                if not resplit:
+                    plan = name_launch(plan, heb_name, t, ra, False, n_mt[part], n_nt)
+                    mine.append([heb_name, *chain(t, ra), 0, n_mt[part], n_nt, col, stream, 0])
+                else:
+                    plan = name_launch(plan, heb_name, 17, 1, False, n_mt[part], 2 * n_nt)
+                    mine.append([heb_name, 17, 1, 0, n_mt[part], 2 * n_nt, col, stream, 0])
+                col += n_mt[part] * t * 16
+        else:
+            stream = next_stream(float(ne * na))
+            wave_tiles = ((ne + 63) // 64) * ((na + 63) // 64)
+            plan = "dw tiles=%d" % wave_tiles
+            mine.append(["dw", 0, 0, 0, 0, 0, 0, stream, wave_tiles])
+        launches.append(mine)
+        texts.append(plan + " ksplit=%d rps=%d" % (ksplit, rps) + (" tm" if p["spill_tm"][j] else " rm"))
+        reduce.append([-1 if j < L else 1, ne if narrow_in else 0, na if narrow_in else 0])
+        max_blocks = max(max_blocks, min((ne * na + 255) // 256, 2048))
+    return launches, texts, reduce, max_blocks
+
+
+def _check_flushes(net, p, rp, seen=None):
+    """Every flush of the run plan `rp` against _flush_model, launch for launch and character for character; every launch names the
+    instantiation it runs (a valid index into HEB_FORMS whose entry is its te, ra, swapped -- nothing falls through to a default);
+    no Linear's K-splits outgrow the slab plan_engine sized for it.  Returns the number of flushes checked."""
+    assert rp["launch_fields"] == LAUNCH_FIELDS and rp["reduce_fields"] == ["sign", "tr_cols", "tr_ld"]
+    kn = _knobs(net["tuning"])
+    two = bool(rp["overlap"]) and kn["flush_streams"] >= 2
+    lins = _lins(p)
+    # the slabs: one region per Linear j >= 1, back to back
+    off = 0
+    for j, (slab_off, slab_floats, splits) in enumerate(p["slabs"]):
+        if j == 0:
+            assert (slab_off, slab_floats, splits) == (0, 0, 0)
+            continue
+        ne, na = lins[j - 1]
+        assert slab_off == off and slab_floats == splits * (ne * na + ne), (net, j)
+        assert splits == _heb_model(ne, na, p["half_slots"] * p["Bpad"], kn["dw_ksplit"])[2]
+        off += slab_floats
+    assert off == p["slab_floats"] and len(p["slabs"]) == len(lins) + 1
+    models = {}
+    for fl in rp["flushes"]:
+        rows = fl["rows"]
+        if rows not in models:
+            models[rows] = _flush_model(p, net["tuning"], rows, two)
+        launches, texts, reduce, max_blocks = models[rows]
+        assert fl["two_streams"] == int(two) and fl["max_blocks"] == max_blocks and fl["reduce"] == reduce, (net, fl)
+        assert fl["text"] == texts, (net, fl["text"], texts)
+        assert [[l[:1] + l[2:] for l in lin] for lin in fl["launches"]] == launches, (net, fl["launches"], launches)
+        for j, (lin, (ksplit, rps, cap)) in enumerate(zip(fl["launches"], fl["lin"]), 1):
+            ne, na = lins[j - 1]
+            assert ksplit * (ne * na + ne) <= p["slabs"][j][1], (net, j, ksplit)
+            for l in map(lambda row: dict(zip(LAUNCH_FIELDS, row)), lin):
+                assert l["stream"] in ((0, 1) if two else (0,)), (net, l)
+                if l["family"] == "dw":
+                    assert l["form"] == -1 and len(lin) == 1
+                else:
+                    assert 0 <= l["form"] < len(HEB_FORMS) and HEB_FORMS[l["form"]] == (l["te"], l["ra"], l["swapped"]), (net, l)
+                    assert l["family"] == ("heb" if kn["heb_fp32"] else "heb7")
+                if seen is not None:
+                    seen.add((l["family"], l["form"]))
+                    seen.add("stream %d" % l["stream"])
+    return len(models)
 
 
 # ---- the sweep ----------------------------------------------------------------------------------------------------------------------------------
@@ -277,7 +405,7 @@ def test_every_run_plan_is_sound(sweep):
 
 
 def test_no_flush_needs_more_splits_than_the_slabs_hold(sweep):
-    """ensure_spill sizes a Linear's slabs by the `ksplit_cap` of a flush of a whole ring part; every flush of every run fits them."""
+    """plan_engine sizes a Linear's slabs by the `ksplit_cap` of a flush of a whole ring part; every flush of every run fits them."""
     n = 0
     for net, run, p, rp in sweep:
         flushing = [it for it in rp["items"] if it[FIELDS.index("flush")]]
@@ -293,6 +421,94 @@ def test_no_flush_needs_more_splits_than_the_slabs_hold(sweep):
                 assert cap == _heb_model(ne, na, p["half_slots"] * p["Bpad"], dwk)[2]
                 n += 1
     assert n >= 10000, n
+
+
+def test_the_library_plans_the_flushes_the_launcher_chose(sweep):
+    """The planned flush of every Hebbian segment of the sweep is what flush_spill used to decide while launching."""
+    n, seen = 0, set()
+    for net, run, p, rp in sweep:
+        assert len(rp["flushes"]) == sum(1 for it in rp["items"] if it[FIELDS.index("flush")])
+        n += _check_flushes(net, p, rp, seen)
+    families = {s[0] for s in seen if isinstance(s, tuple)}
+    print("flush sweep: %d distinct flushes, launches seen %s" % (n, sorted(map(str, seen))))
+    assert n >= 1000 and families == {"heb7", "dw"} and {"stream 0", "stream 1"} <= seen, (n, seen)
+
+
+# Directed shapes: each row a net (latent sizes, read-out) whose Linears j >= 1 take the plans named behind it
+FLUSH_NETS = [
+    ([16, 256, 256], 272),            # 16->256 <1,2,T>; 256->256 <16,2>; 256->272 <17,2> (heb171=1: <17,1> x 2 activation groups)
+    ([32, 256, 128, 128], 272),       # 32->256 <2,2,T>; 256->128 <8,2> (et <= 8); 128->128 <8,1>; 128->272 <17,1>
+    ([64, 256, 128], 256),            # 64->256 <4,2,T>; 256->128 <8,2>; 128->256 <16,1>
+    ([128, 256], 528),                # 256->528 = 17 + 16 tiles: two launches
+    ([128, 256], 304),                # 19 tiles: a ragged group of 17 (2 x 17 > 19)
+    ([128, 256], 240),                # 15 tiles on <16,2> (et <= 16)
+    ([512, 256], 784),                # 512->256: an input of 32 tiles, two activation groups; 256->784 = 17 + 16 + 16
+    ([32, 48, 100], 60),              # the streaming kernel
+]
+FLUSH_TUNINGS = [None, "heb_fp32=1", "heb171=1", "heb171=1,heb_fp32=1", "flush_streams=1", "no_overlap=1", "dw_ksplit=7", "dw_ksplit=7,heb_fp32=1"]
+
+
+def test_directed_flush_shapes_reach_every_plan():
+    """Every instantiation in both families, every branch of the tiling, the re-split, one and two streams, serial flushes and a forced
+    split count -- each asserted as seen, so the sweep cannot shrink unnoticed.  A ring of three parts of 4 slots and a window of 10
+    steps: segments of 4, 4 and 2 steps, two distinct flushes per run."""
+    seen, hit = set(), set()
+    run = dict(T=10, t_begin=0, n_steps=10, acc_begin=0, acc_end=10, update_x=1, xopt_kind=SGD, noise_mode=1, loss_kind=LOSS_BERNOULLI)
+    for sizes, n_out in FLUSH_NETS:
+        for extra in FLUSH_TUNINGS:
+            net = dict(sizes=sizes, n_out=n_out, batch=64, tuning="wide=1,slot_cap=12" + ("," + extra if extra else ""))
+            p, rp = plan(**net), run_plan(run=run, **net)
+            kn = _knobs(net["tuning"])
+            assert rp["overlap"] == int("no_overlap" not in net["tuning"])
+            assert _check_flushes(net, p, rp, seen) == (2 if rp["overlap"] else 1)
+            for fl in rp["flushes"]:
+                streams = {l[LAUNCH_FIELDS.index("stream")] for lin in fl["launches"] for l in lin}
+                if kn["flush_streams"] == 1 or not rp["overlap"]:
+                    assert streams == {0} and not fl["two_streams"]
+                    hit.add("flush_streams=1" if rp["overlap"] else "no_overlap=1")
+                for (ne, na), lin, text, (_, _, cap) in zip(_lins(p), fl["launches"], fl["text"], fl["lin"]):
+                    rows = [dict(zip(LAUNCH_FIELDS, l)) for l in lin]
+                    et = ne // 16
+                    if [(l["te"], l["n_mt"]) for l in rows] == [(17, et % 16), (16, (et - 17 * (et % 16)) // 16)]:
+                        hit.add("17 + 16")
+                    if len(rows) == 1 and rows[0]["te"] == 17 and rows[0]["n_mt"] * 17 > et:
+                        hit.add("ragged 17")
+                    if rows[0]["te"] == 8 and et <= 8:
+                        hit.add("et <= 8")
+                    if rows[0]["te"] == 16 and 8 < et <= 16 and not rows[0]["swapped"]:
+                        hit.add("et <= 16")
+                    if rows[0]["family"] != "dw" and not rows[0]["swapped"] and na // 16 > 16 and rows[0]["n_nt"] == na // 256:
+                        hit.add("input wider than 16 tiles")
+                    if rows[0]["swapped"]:
+                        hit.add("swapped %d" % (na // 16))
+                        assert (rows[0]["te"], rows[0]["n_mt"], rows[0]["n_nt"], rows[0]["col0"]) == (na // 16, 1, 1, 0)
+                    if rows[0]["family"] == "dw":
+                        hit.add("dw")
+                    if kn["heb171"] and not kn["heb_fp32"] and text.startswith("heb7<17,1>x1*2 "):
+                        assert na == 256 and (rows[0]["te"], rows[0]["ra"], rows[0]["n_nt"]) == (17, 1, 2)      # no flag: the launch itself
+                        hit.add("heb171=1")
+                    if kn["heb171"] and kn["heb_fp32"] and text.startswith("heb<17,2>x1 "):
+                        hit.add("heb171=1 leaves the fp32 form alone")
+                    if kn["dw_ksplit"] == 7 and rows[0]["family"] != "dw" and cap == 7:       # (the splits asked for; _check_flushes holds ksplit, rps to them)
+                        hit.add("dw_ksplit=7")
+    want_hit = {"17 + 16", "ragged 17", "et <= 8", "et <= 16", "input wider than 16 tiles", "swapped 1", "swapped 2", "swapped 4", "dw",
+                "heb171=1", "heb171=1 leaves the fp32 form alone", "flush_streams=1", "no_overlap=1", "dw_ksplit=7"}
+    print("directed flush shapes: %s" % sorted(hit))
+    assert hit == want_hit, (want_hit - hit, hit - want_hit)
+    want_seen = {(fam, i) for fam in ("heb7", "heb") for i in range(len(HEB_FORMS))} | {("dw", -1), "stream 0", "stream 1"}
+    assert seen == want_seen, (want_seen - seen, seen - want_seen)
+
+
+def test_the_learning_calls_flush_text():
+    """cfg-M's learning call: 784 x 256 as one group of 17 tiles and two of 16, 256 x 256 on <16,2>, 256 x 32 with the operands swapped."""
+    run = dict(T=5000, t_begin=0, n_steps=5000, acc_begin=1000, acc_end=5000, update_x=1, xopt_kind=SGD, noise_mode=1, loss_kind=LOSS_BERNOULLI)
+    rp = run_plan(run=run, **CFG_M)
+    for fl in rp["flushes"]:
+        ks = [k for k, _, _ in fl["lin"]]
+        rps = [r for _, r, _ in fl["lin"]]
+        assert fl["text"] == ["heb7<2,2,T>x1 ksplit=%d rps=%d tm" % (ks[0], rps[0]), "heb7<16,2>x1 ksplit=%d rps=%d tm" % (ks[1], rps[1]),
+                              "heb7<17,2>x1+heb7<16,2>x2 ksplit=%d rps=%d tm" % (ks[2], rps[2])]
+        assert fl["two_streams"] == 1 and [[l[LAUNCH_FIELDS.index("stream")] for l in lin] for lin in fl["launches"]] == [[0], [1], [0, 1]]
 
 
 @pytest.mark.parametrize("dw_ksplit", [0, 7])
