@@ -326,6 +326,39 @@ int mcpc_hist_accumulate(int device, const float* rec, int32_t B, int32_t width,
                          int32_t transform, const float* edges, int32_t n_bins, int32_t pool, int64_t* counts, int accumulate,
                          void* stream);
 
+/* Streaming JOINT histograms of recorded steps: integer counts of pairs of columns of one or two record rings, the joint density a sum
+ * or a marginal cannot show (two modes of a posterior, the banana of a ReLU pair; the reference bins the class-plane projection of a
+ * probe in 2-D: figure_2.py, posterior_non_linear_model).  csrc/mcpc_hist2d.h.
+ * rec_x and rec_y are record buffers as mcpc_run writes them (or derived records: mcpc_probe_records, mcpc_prediction_errors),
+ * [records][B][width_x] and [records][B][width_y] fp32; they may be the same pointer.  Records first + k*stride, k = 0..n-1, are taken of
+ * both.  pairs is a HOST pointer to n_pairs x 2 int32 column indices, a column of rec_x then a column of rec_y; a column may repeat, and a
+ * pair may name one column of one record twice.  edges_x and edges_y are HOST pointers to nx + 1 and ny + 1 fp32 values, finite and
+ * strictly ascending.  Pairs and edges are validated before any device work and reach the kernel by value in the launch arguments
+ * (2.2 KiB).  transform_x / transform_y are MCPC_MOM_IDENTITY or MCPC_MOM_SIGMOID, per axis.
+ * Each axis is classified exactly as mcpc_hist_accumulate classifies a value (order-preserving keys, NaN by its bits, -0.0 as +0.0, the
+ * last bin closed, +-inf in over / under): class 0..n-1 the bins, then under, over, nan.  counts is int64 device memory,
+ *   pool = 0:  counts [B][n_pairs][nx + 3][ny + 3]
+ *   pool = 1:  counts [n_pairs][nx + 3][ny + 3], summed over the chains
+ * the row index the x class and the column index the y class.  Every (chain, pair) grid of a fresh call sums to n (n * B pooled), and a
+ * marginal of a grid is what mcpc_hist_accumulate counts for that column with the same edges.
+ * accumulate = 0 overwrites counts, accumulate != 0 adds.  Counts are integers: the result depends neither on the launch shape, nor on
+ * how the caller chunks the records, nor on the order of pairs (a permuted list gives the permuted grids).  Counters live in LDS for the
+ * length of a workgroup and reach counts once, by plain stores where a workgroup owns its grids and by 64-bit integer atomics
+ * otherwise (an overwriting call zeroes counts first on the same stream).  Nothing outside counts is written; the library allocates
+ * nothing.  Stateless, asynchronous on `stream`, no engine needed, all offsets 64-bit.
+ * n = 0 reads nothing: it zeroes counts when accumulate = 0 and does nothing otherwise.
+ * MCPC_EINVAL, checked before any HIP call: counts, pairs or an edge pointer NULL, rec_x or rec_y NULL with n > 0, B, width_x or width_y
+ * < 1, stride < 1, first < 0, n < 0, n_pairs outside 1..MCPC_HIST2D_MAX_PAIRS, a column index out of range, nx or ny outside
+ * 1..MCPC_HIST2D_MAX_BINS, more than MCPC_HIST2D_MAX_CELLS cells, pool not 0 or 1, an unknown transform, edges not finite or not
+ * strictly ascending. */
+#define MCPC_HIST2D_MAX_BINS  128      /* per axis */
+#define MCPC_HIST2D_MAX_CELLS 12288    /* (nx + 3) * (ny + 3) at most: one grid's u32 counters stay in LDS (48 KiB) */
+#define MCPC_HIST2D_MAX_PAIRS 128      /* per call */
+int mcpc_hist2d_accumulate(int device, const float* rec_x, int32_t width_x, const float* rec_y, int32_t width_y, int32_t B,
+                           int32_t first, int32_t stride, int32_t n, int32_t transform_x, int32_t transform_y,
+                           const int32_t* pairs, int32_t n_pairs, const float* edges_x, int32_t nx, const float* edges_y, int32_t ny,
+                           int32_t pool, int64_t* counts, int accumulate, void* stream);
+
 /* Streaming lagged products of recorded steps: the raw material of the autocorrelation function, the integrated autocorrelation time
  * and the effective sample size of a Langevin call, whose samples are strongly autocorrelated (csrc/mcpc_acov.h).  The first reducer
  * whose result depends on the ORDER of the records and that carries state from call to call.
@@ -430,6 +463,17 @@ int64_t mcpc_roll_workspace_bytes(int32_t B, int32_t width, int32_t n);
 int mcpc_probe_accumulate(int device, const float* rec, int32_t B, int32_t width, int32_t first, int32_t stride, int32_t n,
                           const float* W, const float* bias, int32_t n_classes, int32_t link, double* psum, double* psumsq,
                           int64_t* votes, double* entsum, int accumulate, void* stream);
+
+/* The probe as a derived record: the link values mcpc_probe_accumulate forms, written out instead of summed.  out is fp32 device
+ * memory [n][B][n_classes], contiguous; row k belongs to record first + k*stride and out[k][c][i] is p_i of chain c, bitwise what the
+ * accumulating entry adds for that sample (one kernel, csrc/mcpc_probe.h), NaN propagation included.  out has the layout of a record
+ * buffer: every stateless reducer takes it as `rec` (mcpc_hist_accumulate, mcpc_hist2d_accumulate, mcpc_cov_accumulate, ...), and an
+ * identity-link probe on it is a projection of the class probabilities.  Nothing is summed, so the records are dealt out over
+ * workgroups.  Stateless, asynchronous on `stream`, no engine needed, all offsets 64-bit.  n = 0 writes nothing and needs no device.
+ * MCPC_EINVAL, checked before any HIP call: W or out NULL, rec NULL with n > 0, B < 1, width < 1, stride < 1, first < 0, n < 0,
+ * n_classes outside 1..MCPC_PROBE_MAX_CLASSES, an unknown link. */
+int mcpc_probe_records(int device, const float* rec, int32_t B, int32_t width, int32_t first, int32_t stride, int32_t n,
+                       const float* W, const float* bias, int32_t n_classes, int32_t link, float* out, void* stream);
 
 /* The k smallest squared distances from every query row into a reference set, by brute force on the device (csrc/mcpc_knn.h): the hot
  * path of the nearest-neighbour KL estimator between two sample clouds (the reference asks two scipy KD-trees: figure_5.py,

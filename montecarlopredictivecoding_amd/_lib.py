@@ -19,6 +19,7 @@ NOISE_NONE, NOISE_PHILOX, NOISE_EXTERNAL = 0, 1, 2
 ENERGY_NONE, ENERGY_LAST, ENERGY_ALL = 0, 1, 2
 MOM_IDENTITY, MOM_SIGMOID = 0, 1
 HIST_MAX_BINS = 256
+HIST2D_MAX_BINS, HIST2D_MAX_CELLS, HIST2D_MAX_PAIRS = 128, 12288, 128
 ACOV_MAX_LAG = 64
 PROBE_MAX_CLASSES = 64
 PROBE_IDENTITY, PROBE_SIGMOID, PROBE_SOFTMAX = 0, 1, 2
@@ -110,6 +111,9 @@ SYMBOLS = {
                                       C.c_void_p]),
     "mcpc_hist_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_void_p, C.c_int, C.c_void_p]),
+    "mcpc_hist2d_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_float), C.c_int32,
+                                         C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_void_p, C.c_int, C.c_void_p]),
     "mcpc_acov_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcpc_roll_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -118,6 +122,8 @@ SYMBOLS = {
     "mcpc_roll_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "mcpc_probe_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                         C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "mcpc_probe_records": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mcpc_knn_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                       C.c_void_p, C.c_int64, C.c_void_p]),
     "mcpc_knn_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),

@@ -17,6 +17,7 @@
 #include "mcpc_moments.h"
 #include "mcpc_cov.h"
 #include "mcpc_hist.h"
+#include "mcpc_hist2d.h"
 #include "mcpc_acov.h"
 #include "mcpc_roll.h"
 #include "mcpc_probe.h"
@@ -1373,11 +1374,8 @@ int mcpc_hist_accumulate(int device, const float* rec, int32_t B, int32_t width,
     const int kVec = (E % 4 == 0 && (uintptr_t)w.r0 % 16 == 0) ? 4 : 1;
     const HistPlan plan = hist_plan(E, width, pool, n, n_bins, kVec);
     HistParams P{};
-    for (int i = 0; i < kHistTable; ++i) P.key[i] = i < n_bins ? hist_key(edges[i]) : 0xffffffffu;
-    P.key_hi = hist_key(edges[n_bins]);
+    P.top = hist_key_table(edges, n_bins, P.key, kHistTable, &P.key_hi);
     P.n_bins = n_bins;
-    P.top = 1;
-    while (2 * P.top <= n_bins - 1) P.top *= 2;
     P.TV = plan.TV; P.n = n; P.seg = plan.seg; P.width = width; P.pool = pool;
     P.exclusive = (!pool && plan.segments == 1) ? 1 : 0;
     P.accumulate = accumulate ? 1 : 0;
@@ -1497,6 +1495,93 @@ int mcpc_probe_accumulate(int device, const float* rec, int32_t B, int32_t width
     P.B = B; P.width = width; P.n = n; P.C = n_classes; P.accumulate = accumulate ? 1 : 0;
     P.psum = psum; P.psumsq = psumsq; P.votes = votes; P.entsum = entsum;
     probe_dispatch(link, P, stream);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+int mcpc_probe_records(int device, const float* rec, int32_t B, int32_t width, int32_t first, int32_t stride, int32_t n, const float* W,
+                       const float* bias, int32_t n_classes, int32_t link, float* out, void* stream_) {
+    if (!W) return fail(MCPC_EINVAL, "probe records: W is null");
+    if (!out) return fail(MCPC_EINVAL, "probe records: out is null");
+    if (link != MCPC_PROBE_IDENTITY && link != MCPC_PROBE_SIGMOID && link != MCPC_PROBE_SOFTMAX)
+        return fail(MCPC_EINVAL, "probe records: unknown link %d", link);
+    if (const int rc = check_shape("probe records", B, width)) return rc;
+    if (const int rc = check_window("probe records", rec, first, stride, n)) return rc;
+    if (n_classes < 1 || n_classes > MCPC_PROBE_MAX_CLASSES)
+        return fail(MCPC_EINVAL, "probe records: n_classes=%d outside 1..%d", n_classes, MCPC_PROBE_MAX_CLASSES);
+    if (n == 0) return MCPC_OK;                                   // no row to write
+    HIP_TRY(hipSetDevice(device));
+    ProbeParams P{};
+    const RecWindow w = rec_window(rec, (int64_t)B * width, first, stride, n);
+    P.rec = w.r0; P.W = W; P.bias = bias; P.row_step = w.row_step;
+    P.B = B; P.width = width; P.n = n; P.C = n_classes; P.out = out;
+    probe_dispatch<true>(link, P, (hipStream_t)stream_);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+int mcpc_hist2d_accumulate(int device, const float* rec_x, int32_t width_x, const float* rec_y, int32_t width_y, int32_t B, int32_t first,
+                           int32_t stride, int32_t n, int32_t transform_x, int32_t transform_y, const int32_t* pairs, int32_t n_pairs,
+                           const float* edges_x, int32_t nx, const float* edges_y, int32_t ny, int32_t pool, int64_t* counts,
+                           int accumulate, void* stream_) {
+    if (!counts) return fail(MCPC_EINVAL, "hist2d: counts is null");
+    if (!edges_x) return fail(MCPC_EINVAL, "hist2d: edges_x is null");
+    if (!edges_y) return fail(MCPC_EINVAL, "hist2d: edges_y is null");
+    if (!pairs) return fail(MCPC_EINVAL, "hist2d: pairs is null");
+    if (B < 1) return fail(MCPC_EINVAL, "hist2d: B=%d, must be at least 1", B);
+    if (width_x < 1) return fail(MCPC_EINVAL, "hist2d: width_x=%d, must be at least 1", width_x);
+    if (width_y < 1) return fail(MCPC_EINVAL, "hist2d: width_y=%d, must be at least 1", width_y);
+    if (const int rc = check_window("hist2d", rec_x, first, stride, n)) return rc;
+    if (n > 0 && !rec_y) return fail(MCPC_EINVAL, "hist2d: rec_y is null with n=%d", n);
+    if (n_pairs < 1 || n_pairs > MCPC_HIST2D_MAX_PAIRS)
+        return fail(MCPC_EINVAL, "hist2d: n_pairs=%d outside 1..%d", n_pairs, MCPC_HIST2D_MAX_PAIRS);
+    if (nx < 1 || nx > MCPC_HIST2D_MAX_BINS) return fail(MCPC_EINVAL, "hist2d: nx=%d outside 1..%d", nx, MCPC_HIST2D_MAX_BINS);
+    if (ny < 1 || ny > MCPC_HIST2D_MAX_BINS) return fail(MCPC_EINVAL, "hist2d: ny=%d outside 1..%d", ny, MCPC_HIST2D_MAX_BINS);
+    if ((nx + 3) * (ny + 3) > MCPC_HIST2D_MAX_CELLS)
+        return fail(MCPC_EINVAL, "hist2d: (nx + 3) * (ny + 3) = %d cells, more than %d", (nx + 3) * (ny + 3), MCPC_HIST2D_MAX_CELLS);
+    if (pool != 0 && pool != 1) return fail(MCPC_EINVAL, "hist2d: pool=%d, must be 0 or 1", pool);
+    if (const int rc = check_transform("hist2d", transform_x)) return rc;
+    if (const int rc = check_transform("hist2d", transform_y)) return rc;
+    for (int i = 0; i < n_pairs; ++i) {
+        if (pairs[2 * i] < 0 || pairs[2 * i] >= width_x)
+            return fail(MCPC_EINVAL, "hist2d: pair %d: x column %d outside 0..%d", i, pairs[2 * i], width_x - 1);
+        if (pairs[2 * i + 1] < 0 || pairs[2 * i + 1] >= width_y)
+            return fail(MCPC_EINVAL, "hist2d: pair %d: y column %d outside 0..%d", i, pairs[2 * i + 1], width_y - 1);
+    }
+    for (int axis = 0; axis < 2; ++axis) {
+        const float* edges = axis ? edges_y : edges_x;
+        const char* name = axis ? "edges_y" : "edges_x";
+        for (int i = 0; i <= (axis ? ny : nx); ++i) {
+            if (!std::isfinite(edges[i])) return fail(MCPC_EINVAL, "hist2d: %s[%d] is not finite", name, i);
+            if (i > 0 && !(edges[i - 1] < edges[i]))
+                return fail(MCPC_EINVAL, "hist2d: %s are not strictly ascending at %d (%.9g, then %.9g)", name, i, (double)edges[i - 1],
+                            (double)edges[i]);
+        }
+    }
+    if (n == 0 && accumulate) return MCPC_OK;                     // nothing to add
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(device));
+    const Hist2dPlan plan = hist2d_plan(B, width_x, width_y, n_pairs, nx, ny, pool, n > 0 ? n : 1);
+    const size_t out_bytes = (size_t)plan.slots * plan.cells * sizeof(int64_t);
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(counts, 0, out_bytes, stream));
+        return MCPC_OK;
+    }
+    const RecWindow wx = rec_window(rec_x, (int64_t)B * width_x, first, stride, n);
+    const RecWindow wy = rec_window(rec_y, (int64_t)B * width_y, first, stride, n);
+    Hist2dParams P{};
+    P.top_x = hist_key_table(edges_x, nx, P.key_x, kHist2dTable, &P.hi_x);
+    P.top_y = hist_key_table(edges_y, ny, P.key_y, kHist2dTable, &P.hi_y);
+    P.nx = nx; P.ny = ny;
+    for (int i = 0; i < n_pairs; ++i) { P.col[i][0] = pairs[2 * i]; P.col[i][1] = pairs[2 * i + 1]; }
+    P.n_pairs = n_pairs; P.B = B; P.wx = width_x; P.wy = width_y; P.G = plan.G; P.GL = plan.GL; P.n = n; P.seg = plan.seg;
+    P.chains_per = plan.chains_per; P.pool = pool;
+    P.exclusive = (!pool && plan.segments == 1) ? 1 : 0;
+    P.accumulate = accumulate ? 1 : 0;
+    P.slots = plan.slots; P.groups = plan.groups; P.step_x = wx.row_step; P.step_y = wy.row_step;
+    // workgroups that share a grid add into it with integer atomics: an overwriting call starts them from zero
+    if (!P.exclusive && !accumulate) HIP_TRY(hipMemsetAsync(counts, 0, out_bytes, stream));
+    hist2d_launch(transform_x, transform_y, wx.r0, wy.r0, P, plan, counts, stream);
     HIP_TRY(hipGetLastError());
     return MCPC_OK;
 }

@@ -67,6 +67,33 @@ inline uint32_t hist_key(float v) {
     return hist_key_bits(b);
 }
 
+// The search table of n_bins + 1 validated edges, shared with mcpc_hist2d.h: key[i] = hist_key(edges[i]) for i < n_bins and 0xffffffff
+// up to `cap` (above every non-NaN key), *key_hi = hist_key(edges[n_bins]); returns the first step of the search, the largest power of
+// two <= max(n_bins - 1, 1).
+inline int32_t hist_key_table(const float* edges, int32_t n_bins, uint32_t* key, int32_t cap, uint32_t* key_hi) {
+    for (int32_t i = 0; i < cap; ++i) key[i] = i < n_bins ? hist_key(edges[i]) : 0xffffffffu;
+    *key_hi = hist_key(edges[n_bins]);
+    int32_t top = 1;
+    while (2 * top <= n_bins - 1) top *= 2;
+    return top;
+}
+
+// One step of the branch-free binary search over the table: what `lo` advances by.  Callers interleave the steps of several values so
+// that their table reads are in flight together.
+__host__ __device__ __forceinline__ int32_t hist_search_step(const uint32_t* table, int32_t lo, int32_t step, uint32_t kv) {
+    return (table[lo + step] <= kv) ? step : 0;
+}
+
+// The column of a value with bits `b` and key `kv` whose search ended at `lo`: the bin, or under / over / nan.
+__host__ __device__ __forceinline__ int32_t hist_column(int32_t lo, uint32_t b, uint32_t kv, uint32_t key_lo, uint32_t key_hi,
+                                                        int32_t n_bins) {
+    int32_t col = lo;
+    col = kv < key_lo ? n_bins : col;
+    col = kv > key_hi ? n_bins + 1 : col;
+    col = (b & 0x7fffffffu) > 0x7f800000u ? n_bins + 2 : col;
+    return col;
+}
+
 // The host's plan: depends on E, width, pool, n and n_bins alone (and the result on none of it).
 struct HistPlan {
     int32_t TV, seg, segments;
@@ -134,14 +161,11 @@ __global__ __launch_bounds__(kHistThreads) void mcpc_hist_kernel(const float* __
         }
         for (int32_t step = P.top; step > 0; step >>= 1) {
 #pragma unroll
-            for (int i = 0; i < N; ++i) lo[i] += (table[lo[i] + step] <= kv[i]) ? step : 0;
+            for (int i = 0; i < N; ++i) lo[i] += hist_search_step(table, lo[i], step, kv[i]);
         }
 #pragma unroll
         for (int i = 0; i < N; ++i) {
-            int32_t col = lo[i];
-            col = kv[i] < key_lo ? P.n_bins : col;
-            col = kv[i] > key_hi ? P.n_bins + 1 : col;
-            col = (b[i] & 0x7fffffffu) > 0x7f800000u ? P.n_bins + 2 : col;
+            const int32_t col = hist_column(lo[i], b[i], kv[i], key_lo, key_hi, P.n_bins);
             atomicAdd(&cnt[col * TE + (i % kVec) * TV + lane], 1u);
         }
     };

@@ -32,6 +32,12 @@
 // and argmax go across the Cpad lanes by xor-butterflies.
 // Accumulators are read and written once per call.  Few chains (128 chains x 16 lanes = 32 waves) leave the kernel latency-bound on
 // the record loop; that is accepted as it is for moments -- parallelism over the records would reorder the sums.
+//
+// The probe as a derived record (include/mcpc.h: mcpc_probe_records) is the SAME kernel with kRecords set: the logit loop, the link and
+// the butterflies are the code above, and the link value p_i goes to out[j][c][i] (fp32, the layout of a record) instead of into the
+// sums, so that out holds bitwise what the accumulating form adds.  Nothing is ordered there, so the blocks of kProbeInFlight samples
+// are dealt out over gridDim.y as well (block b, b + gridDim.y, ... per workgroup; about kProbeRecordWaves waves in all), and few
+// chains no longer leave the launch latency-bound.  The accumulating form is gridDim.y = 1 of the same loop.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -43,6 +49,7 @@ namespace mcpc {
 
 constexpr int kProbeInFlight = 8;       // samples per block: their loads are in flight together, their logit chains are independent
 constexpr int kProbeKTile = 64;         // columns of W staged through LDS at a time
+constexpr int kProbeRecordWaves = 4096; // mcpc_probe_records: waves a launch is sized for (256 CUs x 16)
 
 static_assert(MCPC_PROBE_MAX_CLASSES == 64, "a chain's classes are the lanes of at most one wave");
 
@@ -57,6 +64,7 @@ struct ProbeParams {
     double* psumsq;         // [B][C] or null
     int64_t* votes;         // [B][C + 1]
     double* entsum;         // [B] (softmax)
+    float* out;             // kRecords: [n][B][C], the link values themselves
 };
 
 template <int kCpad>
@@ -66,8 +74,8 @@ __device__ __forceinline__ float probe_sum(float v) {
     return v;
 }
 
-// kLink: MCPC_PROBE_IDENTITY / _SIGMOID / _SOFTMAX
-template <int kCpad, int kLink>
+// kLink: MCPC_PROBE_IDENTITY / _SIGMOID / _SOFTMAX; kRecords: write the link values to P.out instead of reducing them
+template <int kCpad, int kLink, bool kRecords>
 __global__ __launch_bounds__(64) void mcpc_probe_kernel(const ProbeParams P) {
     constexpr int U = kProbeInFlight, KT = kProbeKTile;
     __shared__ float wt[KT * kCpad];
@@ -81,6 +89,7 @@ __global__ __launch_bounds__(64) void mcpc_probe_kernel(const ProbeParams P) {
     const bool resident = width <= KT;                      // W is staged once
     const int32_t n_piece = (width + kCpad - 1) / kCpad;
     const int32_t n_block = (n + U - 1) / U;
+    const int32_t b_first = kRecords ? (int32_t)blockIdx.y : 0, b_step = kRecords ? (int32_t)gridDim.y : 1;
 
     auto stage = [&](int32_t k0) {                          // wt[kk][ii] = W[ii][k0 + kk], 0 outside
         for (int idx = lane; idx < KT * kCpad; idx += 64) {
@@ -96,15 +105,15 @@ __global__ __launch_bounds__(64) void mcpc_probe_kernel(const ProbeParams P) {
         const int32_t k = pc * kCpad + i < width ? pc * kCpad + i : width - 1;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int32_t j = b * U + u < n ? b * U + u : n - 1;
-            dst[u] = row[(int64_t)j * P.row_step + k];
+            const int64_t j = (int64_t)b * U + u < n ? (int64_t)b * U + u : (int64_t)n - 1;
+            dst[u] = row[j * P.row_step + k];
         }
     };
 
     double s = 0.0, q = 0.0, ent = 0.0;
     int64_t vote = 0, n_nan = 0;
-    const bool sq = P.psumsq != nullptr;
-    if (own && P.accumulate) {
+    const bool sq = !kRecords && P.psumsq != nullptr;
+    if (!kRecords && own && P.accumulate) {
         s = P.psum[c * C + i];
         if (sq) q = P.psumsq[c * C + i];
         vote = P.votes[c * (C + 1) + i];
@@ -120,8 +129,8 @@ __global__ __launch_bounds__(64) void mcpc_probe_kernel(const ProbeParams P) {
         __syncthreads();
     }
     float cur[U], nxt[U];
-    load(0, 0, cur);                                        // n >= 1: the host launches nothing for n = 0
-    for (int32_t b = 0; b < n_block; ++b) {
+    load(b_first, 0, cur);                                  // n >= 1: the host launches nothing for n = 0
+    for (int32_t b = b_first; b < n_block; b += b_step) {
         double z[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) z[u] = b0;
@@ -133,7 +142,7 @@ __global__ __launch_bounds__(64) void mcpc_probe_kernel(const ProbeParams P) {
                 __syncthreads();
             }
             const bool more = pc + 1 < n_piece;
-            load(more ? b : b + 1, more ? pc + 1 : 0, nxt);     // (behind the last block: its last sample again, not used)
+            load(more ? b : b + b_step, more ? pc + 1 : 0, nxt);    // (behind the last block: its last sample again, not used)
             const float* wk = wt + (k0 % KT) * kCpad + i;
 #pragma unroll
             for (int jj = 0; jj < kCpad; ++jj) {
@@ -168,8 +177,10 @@ __global__ __launch_bounds__(64) void mcpc_probe_kernel(const ProbeParams P) {
                         arg = oa;
                     }
                 }
-                if (bad) n_nan += 1;
-                else if (arg == i) vote += 1;
+                if constexpr (!kRecords) {
+                    if (bad) n_nan += 1;
+                    else if (arg == i) vote += 1;
+                }
                 float p;
                 if constexpr (kLink == MCPC_PROBE_IDENTITY) {
                     p = v;
@@ -181,17 +192,23 @@ __global__ __launch_bounds__(64) void mcpc_probe_kernel(const ProbeParams P) {
                     const float e = i < C ? expf(d) : 0.0f;
                     const float S = probe_sum<kCpad>(e);
                     p = e / S;
-                    const float h = logf(S) - probe_sum<kCpad>(i < C ? p * d : 0.0f);
-                    ent = ent + (double)h;
+                    if constexpr (!kRecords) {
+                        const float h = logf(S) - probe_sum<kCpad>(i < C ? p * d : 0.0f);
+                        ent = ent + (double)h;
+                    }
                 }
-                const double pd = (double)p;
-                s = s + pd;
-                if (sq) q = q + pd * pd;
+                if constexpr (kRecords) {
+                    if (own) P.out[((int64_t)(b * U + u) * P.B + c) * C + i] = p;
+                } else {
+                    const double pd = (double)p;
+                    s = s + pd;
+                    if (sq) q = q + pd * pd;
+                }
             }
         }
     }
 
-    if (own) {
+    if (!kRecords && own) {
         P.psum[c * C + i] = s;
         if (sq) P.psumsq[c * C + i] = q;
         P.votes[c * (C + 1) + i] = vote;
@@ -202,23 +219,37 @@ __global__ __launch_bounds__(64) void mcpc_probe_kernel(const ProbeParams P) {
     }
 }
 
-template <int kCpad>
+// The record form's gridDim.y: blocks of kProbeInFlight samples per chain group, a plain host function of the shape.
+inline int32_t probe_record_rows(int64_t chain_groups, int32_t n) {
+    const int64_t n_block = ((int64_t)n + kProbeInFlight - 1) / kProbeInFlight;
+    int64_t gy = (kProbeRecordWaves + chain_groups - 1) / chain_groups;
+    if (gy > n_block) gy = n_block;
+    if (gy > 65535) gy = 65535;
+    return (int32_t)(gy < 1 ? 1 : gy);
+}
+
+template <int kCpad, bool kRecords>
 inline void probe_launch(int link, const ProbeParams& P, hipStream_t stream) {
-    const dim3 grid((unsigned)(((int64_t)P.B + 64 / kCpad - 1) / (64 / kCpad))), block(64);
-    if (link == MCPC_PROBE_SOFTMAX) hipLaunchKernelGGL((mcpc_probe_kernel<kCpad, MCPC_PROBE_SOFTMAX>), grid, block, 0, stream, P);
-    else if (link == MCPC_PROBE_SIGMOID) hipLaunchKernelGGL((mcpc_probe_kernel<kCpad, MCPC_PROBE_SIGMOID>), grid, block, 0, stream, P);
-    else hipLaunchKernelGGL((mcpc_probe_kernel<kCpad, MCPC_PROBE_IDENTITY>), grid, block, 0, stream, P);
+    const int64_t gx = ((int64_t)P.B + 64 / kCpad - 1) / (64 / kCpad);
+    const dim3 grid((unsigned)gx, kRecords ? (unsigned)probe_record_rows(gx, P.n) : 1u), block(64);
+    if (link == MCPC_PROBE_SOFTMAX)
+        hipLaunchKernelGGL((mcpc_probe_kernel<kCpad, MCPC_PROBE_SOFTMAX, kRecords>), grid, block, 0, stream, P);
+    else if (link == MCPC_PROBE_SIGMOID)
+        hipLaunchKernelGGL((mcpc_probe_kernel<kCpad, MCPC_PROBE_SIGMOID, kRecords>), grid, block, 0, stream, P);
+    else
+        hipLaunchKernelGGL((mcpc_probe_kernel<kCpad, MCPC_PROBE_IDENTITY, kRecords>), grid, block, 0, stream, P);
 }
 
 // Cpad: C rounded up to a power of two
+template <bool kRecords = false>
 inline void probe_dispatch(int link, const ProbeParams& P, hipStream_t stream) {
-    if (P.C <= 1) probe_launch<1>(link, P, stream);
-    else if (P.C <= 2) probe_launch<2>(link, P, stream);
-    else if (P.C <= 4) probe_launch<4>(link, P, stream);
-    else if (P.C <= 8) probe_launch<8>(link, P, stream);
-    else if (P.C <= 16) probe_launch<16>(link, P, stream);
-    else if (P.C <= 32) probe_launch<32>(link, P, stream);
-    else probe_launch<64>(link, P, stream);
+    if (P.C <= 1) probe_launch<1, kRecords>(link, P, stream);
+    else if (P.C <= 2) probe_launch<2, kRecords>(link, P, stream);
+    else if (P.C <= 4) probe_launch<4, kRecords>(link, P, stream);
+    else if (P.C <= 8) probe_launch<8, kRecords>(link, P, stream);
+    else if (P.C <= 16) probe_launch<16, kRecords>(link, P, stream);
+    else if (P.C <= 32) probe_launch<32, kRecords>(link, P, stream);
+    else probe_launch<64, kRecords>(link, P, stream);
 }
 
 }  // namespace mcpc

@@ -720,6 +720,108 @@ def probe_accumulate(rec, first, stride, n, W, bias, link, psum, psumsq, votes, 
                                       stream))
 
 
+def probe_records(rec, first, stride, n, W, bias, link, out=None):
+    """The linear probe ``link(W r + bias)`` of records ``rec[first + j * stride]``, j < n, as a derived record (include/mcpc.h:
+    mcpc_probe_records): fp32 ``[n, B, C]`` on the device of ``rec``, row j the link values of record ``first + j * stride``, bitwise
+    what ``probe_accumulate`` adds for that sample.  ``rec``, ``W``, ``bias``, ``link`` as ``probe_accumulate`` takes them.  ``out``:
+    a contiguous fp32 ``[n, B, C]`` tensor to fill, or None to allocate one.  The result has the layout of a record buffer: every
+    stateless reducer takes it as ``rec``, and an identity-link probe on it projects the class probabilities.  On the current torch
+    stream."""
+    lib = L.load()
+    if link not in _PROBE_LINKS:
+        raise ValueError(f"link: expected 'identity', 'sigmoid' or 'softmax', got {link!r}")
+    device, (R, B, width) = _check_records(rec)
+    first, stride, n = int(first), int(stride), int(n)
+    _check_last_record(R, first, stride, n)
+    if not isinstance(W, torch.Tensor) or W.dim() != 2:
+        raise TypeError("W: expected a torch.Tensor [C, width]")
+    n_classes = int(W.shape[0])
+    if not 1 <= n_classes <= L.PROBE_MAX_CLASSES:
+        raise ValueError(f"W: {n_classes} classes, expected 1..{L.PROBE_MAX_CLASSES}")
+    _check_tensor(W, (n_classes, width), device, "W")
+    if bias is not None:
+        _check_tensor(bias, (n_classes,), device, "bias")
+    if out is None:
+        out = torch.empty(max(n, 0), B, n_classes, dtype=torch.float32, device=device)
+    _check_tensor(out, (max(n, 0), B, n_classes), device, "out")
+    if n == 0:                                     # an empty tensor has no address to hand over
+        return out
+    stream = _current_stream(device)
+    L.check(lib.mcpc_probe_records(device.index or 0, _ptr(rec), B, width, first, stride, n, _ptr(W), _ptr(bias), n_classes,
+                                   _PROBE_LINKS[link], _ptr(out), stream))
+    return out
+
+
+def _hist2d_edges(edges, name):
+    e = torch.as_tensor(edges)
+    if e.device.type != "cpu" or e.dtype != torch.float32 or e.dim() != 1:
+        raise TypeError(f"{name}: expected a 1-D fp32 CPU tensor or array")
+    e = e.contiguous()
+    if not 1 <= e.numel() - 1 <= L.HIST2D_MAX_BINS:
+        raise ValueError(f"{name}: {e.numel()} values, expected 2..{L.HIST2D_MAX_BINS + 1} (1..{L.HIST2D_MAX_BINS} bins)")
+    return e
+
+
+def hist2d_accumulate(rec_x, rec_y, first, stride, n, pairs, edges_x, edges_y, counts, transforms=("identity", "identity"), pool=False,
+                      accumulate=True):
+    """Count the pairs ``(rec_x[k][c][px], rec_y[k][c][py])`` of records ``k = first + j * stride``, j < n, into the int64 joint
+    histograms ``counts`` on the device (include/mcpc.h: mcpc_hist2d_accumulate).  ``rec_x`` / ``rec_y``: contiguous fp32
+    ``[records, B, width_x]`` / ``[records, B, width_y]`` of equally many records and chains; they may be the same tensor.  ``pairs``: a
+    sequence of ``(px, py)`` column indices, any number (more than ``L.HIST2D_MAX_PAIRS`` are split over several library calls).
+    ``edges_x`` / ``edges_y``: 1-D fp32 CPU tensors or arrays of ``nx + 1`` / ``ny + 1`` finite, strictly ascending values, at most
+    ``L.HIST2D_MAX_BINS`` bins each and ``(nx + 3) * (ny + 3) <= L.HIST2D_MAX_CELLS``.  ``counts``: contiguous int64
+    ``[B, pairs, nx + 3, ny + 3]``, or ``[pairs, nx + 3, ny + 3]`` with ``pool=True``: per axis the bins, then under, over, nan, each
+    decided as ``hist_accumulate`` decides it.  ``transforms``: per axis "identity" or "sigmoid".  ``accumulate=False`` overwrites.
+    Counts are integers: exact, however the records are chunked over calls and the pairs are ordered.  On the current torch stream."""
+    lib = L.load()
+    transforms = tuple(transforms)
+    if len(transforms) != 2 or any(t not in _MOM_TRANSFORMS for t in transforms):
+        raise ValueError(f"transforms: expected two of 'identity' or 'sigmoid', got {transforms!r}")
+    device, (R, B, wx) = _check_records(rec_x)
+    if not isinstance(rec_y, torch.Tensor) or rec_y.dim() != 3:
+        raise TypeError("rec_y: expected a torch.Tensor [records, B, width]")
+    _check_tensor(rec_y, (R, B, rec_y.shape[2]), device, "rec_y")
+    wy = int(rec_y.shape[2])
+    first, stride, n = int(first), int(stride), int(n)
+    _check_last_record(R, first, stride, n)
+    pairs = [(int(a), int(b)) for a, b in pairs]
+    if not pairs:
+        raise ValueError("pairs: expected at least one (x column, y column)")
+    for k, (a, b) in enumerate(pairs):
+        if not (0 <= a < wx and 0 <= b < wy):
+            raise ValueError(f"pairs[{k}] = {(a, b)}: outside the records' columns (0..{wx - 1}, 0..{wy - 1})")
+    ex, ey = _hist2d_edges(edges_x, "edges_x"), _hist2d_edges(edges_y, "edges_y")
+    nx, ny = ex.numel() - 1, ey.numel() - 1
+    if (nx + 3) * (ny + 3) > L.HIST2D_MAX_CELLS:
+        raise ValueError(f"edges: (nx + 3) * (ny + 3) = {(nx + 3) * (ny + 3)} cells, more than {L.HIST2D_MAX_CELLS}")
+    if not isinstance(counts, torch.Tensor):
+        raise TypeError(f"counts: expected a torch.Tensor, got {type(counts)}")
+    grid = (len(pairs), nx + 3, ny + 3)
+    _check_tensor(counts, grid if pool else (B,) + grid, device, "counts", torch.int64)
+    stream = _current_stream(device)
+    xf = [_MOM_TRANSFORMS[t] for t in transforms]
+    fptr = C.POINTER(C.c_float)
+
+    def call(some, into):
+        flat = (C.c_int32 * (2 * len(some)))(*[v for p in some for v in p])
+        L.check(lib.mcpc_hist2d_accumulate(device.index or 0, _ptr(rec_x), wx, _ptr(rec_y), wy, B, first, stride, n, xf[0], xf[1], flat,
+                                           len(some), C.cast(ex.data_ptr(), fptr), nx, C.cast(ey.data_ptr(), fptr), ny,
+                                           1 if pool else 0, _ptr(into), 1 if accumulate else 0, stream))
+    if len(pairs) <= L.HIST2D_MAX_PAIRS:
+        call(pairs, counts)
+        return
+    # more pairs than a launch carries: a call per group of them; pooled, a group's grids are contiguous in counts, per chain they are
+    # not, and the group counts into a buffer of its own that is added (or copied) into its columns
+    for p0 in range(0, len(pairs), L.HIST2D_MAX_PAIRS):
+        some = pairs[p0:p0 + L.HIST2D_MAX_PAIRS]
+        if pool:
+            call(some, counts[p0:p0 + len(some)])
+        else:
+            part = counts[:, p0:p0 + len(some)].contiguous()
+            call(some, part)
+            counts[:, p0:p0 + len(some)] = part
+
+
 def knn_workspace_bytes(nq, nr, d, k) -> int:
     """Bytes of device workspace ``knn_accumulate`` needs for ``nq`` queries into ``nr`` reference rows of ``d`` coordinates, ``k`` kept."""
     lib = L.load()

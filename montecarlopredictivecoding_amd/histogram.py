@@ -41,37 +41,38 @@ def result_bytes(columns, edges, B: int, pooled: bool) -> int:
     return 8 * sum(w * (len(e) + 2) for (_, w), e in zip(columns, edges)) * (1 if pooled else B)
 
 
-def _edges(name, bins, rng):
-    """The fp32 edges of block ``name``: ``bins`` an int with ``rng = (lo, hi)``, or a sequence of edges."""
+def _edges(name, bins, rng, who="mcpc_histogram", max_bins=MAX_BINS):
+    """The fp32 edges of block ``name``: ``bins`` an int with ``rng = (lo, hi)``, or a sequence of edges.  ``who`` opens the messages and
+    ``max_bins`` bounds the bins (``mcpc_histogram2d`` parses each axis here too)."""
     if isinstance(bins, bool):
-        raise ValueError(f"mcpc_histogram: bins of {name!r} must be an int or a sequence of edges, got {bins!r}")
+        raise ValueError(f"{who}: bins of {name!r} must be an int or a sequence of edges, got {bins!r}")
     if isinstance(bins, (int, np.integer)):
-        if not 1 <= bins <= MAX_BINS:
-            raise ValueError(f"mcpc_histogram: bins={bins} of {name!r}, must be 1..{MAX_BINS}")
+        if not 1 <= bins <= max_bins:
+            raise ValueError(f"{who}: bins={bins} of {name!r}, must be 1..{max_bins}")
         if rng is None:
-            raise ValueError(f"mcpc_histogram: bins={bins} of {name!r} needs range=(lo, hi): the range is never taken from the data (a "
+            raise ValueError(f"{who}: bins={bins} of {name!r} needs range=(lo, hi): the range is never taken from the data (a "
                              "streaming pass cannot know the extremes)")
         try:
             lo, hi = (float(v) for v in rng)
         except (TypeError, ValueError):
-            raise ValueError(f"mcpc_histogram: range of {name!r} must be (lo, hi), got {rng!r}") from None
+            raise ValueError(f"{who}: range of {name!r} must be (lo, hi), got {rng!r}") from None
         if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
-            raise ValueError(f"mcpc_histogram: range of {name!r} must be finite with lo < hi, got {(lo, hi)!r}")
+            raise ValueError(f"{who}: range of {name!r} must be finite with lo < hi, got {(lo, hi)!r}")
         e64 = np.linspace(lo, hi, int(bins) + 1)
     else:
         try:
             e64 = np.asarray(bins, dtype=np.float64)
         except (TypeError, ValueError):
-            raise ValueError(f"mcpc_histogram: bins of {name!r} must be an int or a sequence of edges, got {bins!r}") from None
-        if e64.ndim != 1 or not 2 <= e64.size <= MAX_BINS + 1:
-            raise ValueError(f"mcpc_histogram: edges of {name!r}: expected a 1-D sequence of 2..{MAX_BINS + 1} values, got shape "
+            raise ValueError(f"{who}: bins of {name!r} must be an int or a sequence of edges, got {bins!r}") from None
+        if e64.ndim != 1 or not 2 <= e64.size <= max_bins + 1:
+            raise ValueError(f"{who}: edges of {name!r}: expected a 1-D sequence of 2..{max_bins + 1} values, got shape "
                              f"{e64.shape}")
     with np.errstate(over="ignore"):
         e32 = e64.astype(np.float32)
     if not np.isfinite(e32).all():
-        raise ValueError(f"mcpc_histogram: edges of {name!r} are not finite in fp32")
+        raise ValueError(f"{who}: edges of {name!r} are not finite in fp32")
     if not (np.diff(e32) > 0).all():
-        raise ValueError(f"mcpc_histogram: edges of {name!r} are not strictly ascending in fp32 (they are rounded to fp32: the fp32 "
+        raise ValueError(f"{who}: edges of {name!r} are not strictly ascending in fp32 (they are rounded to fp32: the fp32 "
                          "edges are the edges)")
     return e32
 

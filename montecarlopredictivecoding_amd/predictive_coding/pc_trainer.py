@@ -269,6 +269,11 @@ class PCTrainer(object):
         self.mcpc_errors = None
         self.mcpc_last_errors = None
         self.mcpc_errors_max_bytes = 2 << 30
+        # x=(layer, units), y=(layer, units) | probe=dict(layer, linear | weight, bias, link), project=None | [2, C], bins=int | (nx, ny) |
+        # (edges_x, edges_y), range=(lo, hi) | ((lo, hi), (lo, hi)), pool=None | "chains" -> histogram2d.Histogram2D
+        self.mcpc_histogram2d = None
+        self.mcpc_last_histogram2d = None
+        self.mcpc_histogram2d_max_bytes = 2 << 30
 
     # ---- getters & setters (reference :268-461) -------------------------------------------------------
     def get_T(self) -> int:

@@ -24,9 +24,9 @@ from typing import Any, Callable, Optional
 import torch
 
 from .. import _lib as L
-from .. import autocovariance, chain_energies, cloud, covariance, errors, histogram, moments, probe, rolling
-from ..engine import (acov_accumulate, cov_accumulate, cov_workspace_bytes, hist_accumulate, moments_accumulate, probe_accumulate,
-                      roll_accumulate, roll_workspace_bytes)
+from .. import autocovariance, chain_energies, cloud, covariance, errors, histogram, histogram2d, moments, probe, rolling
+from ..engine import (acov_accumulate, cov_accumulate, cov_workspace_bytes, hist2d_accumulate, hist_accumulate, moments_accumulate,
+                      probe_accumulate, probe_records, roll_accumulate, roll_workspace_bytes)
 
 
 @dataclass
@@ -349,6 +349,48 @@ class ErrorsReducer(Reducer):
                              sumsq={k: None if v is None else v.to(md) for k, v in self.sumsq.items()}, covariance=pcov)
 
 
+class Histogram2DReducer(Reducer):
+    """``mcpc_histogram2d``: int64 joint counts by ``hist2d_accumulate``.  Units form: straight out of the ring rows of the one or two
+    layers.  Probe form: the slice's samples go through ``probe_records`` twice -- the link values of the probe, then their projection
+    onto the plane, two derived records as long as the longest slice's samples -- and the plane's two coordinates are the one pair."""
+    attr = "mcpc_last_histogram2d"
+
+    def __init__(self, spec, call):
+        super().__init__(spec, call)
+        self.layers, self.reads_out = spec.layers, False
+
+    def step_bytes(self, B):
+        if self.spec.probe is None:
+            return 0
+        return -(-4 * B * (self.spec.probe.C + 2) // self.spec.stride)   # the derived records of a step's share of the samples
+
+    def start(self, B, dev, S):
+        super().start(B, dev, S)
+        spec = self.spec
+        grid = (len(spec.pairs), len(spec.edges_x) + 2, len(spec.edges_y) + 2)
+        self.counts = self.zeros(*(grid if spec.pooled else (B,) + grid), dtype=torch.int64)
+        if spec.probe is not None:
+            rows = spec.max_samples(S)
+            self.w, self.b = spec.probe.on(dev)
+            self.plane = torch.from_numpy(spec.project.copy()).to(dev)
+            self.p = torch.empty(rows, B, spec.probe.C, dtype=torch.float32, device=dev)
+            self.xy = torch.empty(rows, B, 2, dtype=torch.float32, device=dev)
+
+    def add(self, first, cnt, t0, view):
+        spec = self.spec
+        kw = dict(pool=spec.pooled, accumulate=True)
+        if spec.probe is None:
+            hist2d_accumulate(view.x[spec.x_layer], view.x[spec.y_layer], first, spec.stride, cnt, spec.pairs, spec.edges_x,
+                              spec.edges_y, self.counts, **kw)
+            return
+        probe_records(view.x[spec.probe.layer], first, spec.stride, cnt, self.w, self.b, spec.probe.link, out=self.p[:cnt])
+        probe_records(self.p, 0, 1, cnt, self.plane, None, "identity", out=self.xy[:cnt])
+        hist2d_accumulate(self.xy, self.xy, 0, 1, cnt, spec.pairs, spec.edges_x, spec.edges_y, self.counts, **kw)
+
+    def result(self):
+        return histogram2d.from_counts(self.spec, self.B, self.counts, self.call.model_device)
+
+
 @dataclass(frozen=True)
 class Request:
     """One row of ``REQUESTS``."""
@@ -386,6 +428,8 @@ REQUESTS = (
     Request("mcpc_errors", "errors", errors, "prediction errors are evaluated out of the fused HIP loop's record ring only",
             lambda tr, net, plan: (len(net.sizes), net.n_out, net.sizes, plan["B"], plan["loss"].kind != L.LOSS_NONE,
                                    tr.mcpc_errors_max_bytes), ErrorsReducer),
+    Request("mcpc_histogram2d", "histogram2d", histogram2d, "joint histograms are counted by the fused HIP loop only",
+            _columns("mcpc_histogram2d_max_bytes"), Histogram2DReducer),
 )
 
 

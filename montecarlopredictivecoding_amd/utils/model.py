@@ -397,6 +397,53 @@ def get_posterior_class_probabilities(gen_pc, config, trainers, loader, classifi
     return Probe.cat(parts), torch.cat(labels, dim=0)
 
 
+def get_posterior_class_density(gen_pc, config, trainers, loader, classifier, layer=0, link="softmax", bins=40, range=(-1, 1), project=None,
+                                pool=None):
+    """The joint density of a linear classifier's class probabilities on a latent layer, projected onto a plane, per batch of
+    ``loader`` (the reference's figure_2.py, ``posterior_non_linear_model``: panels 2c and 2d): MAP call with ``trainers[0]``, then an
+    MCPC call with ``trainers[1]`` started from the MAP state (the protocol of ``get_posterior_class_probabilities``), over the steps
+    from ``config["mixing"]`` on; the call itself applies the classifier to every sample of the layer, projects the link values with
+    ``project`` (fp32 ``[2, C]``; None = the regular C-gon of ``proba_to_coordinate``) and bins the two coordinates jointly on the device
+    (``PCTrainer.mcpc_histogram2d``): no trajectory is recorded.  ``bins`` / ``range`` as the request takes them.  ``classifier``: an
+    ``nn.Linear`` on the layer, or a module that holds exactly one.  Returns one ``histogram2d.Histogram2D`` over all data in the
+    loader's order, one grid per datum (``Histogram2D.cat`` of the batches; with ``pool="chains"`` the batches' pooled grids merged).
+    The loader's labels are not consulted."""
+    from ..histogram2d import Histogram2D
+    if len(trainers) != 2:
+        raise NotImplementedError
+    linears = [m for m in classifier.modules() if isinstance(m, torch.nn.Linear)]
+    if len(linears) != 1:
+        raise ValueError("get_posterior_class_density: the classifier must be an nn.Linear or hold exactly one, it holds {}".format(
+            len(linears)))
+    device = next(gen_pc.parameters()).device
+    input_size = len(gen_pc[0].bias)
+    pc_trainer, mcpc_trainer = trainers
+    parts = []
+    saved = mcpc_trainer.mcpc_histogram2d
+    mcpc_trainer.mcpc_histogram2d = dict(begin=int(config["mixing"]), stride=1, probe=dict(layer=layer, linear=linears[0], link=link),
+                                         project=project, bins=bins, range=range, pool=pool)
+    try:
+        for data, _ in loader:
+            pseudo_input = torch.zeros(data.shape[0], input_size, device=device)
+            data = data.to(device)
+            kw = dict(inputs=pseudo_input, loss_fn=config["loss_fn"],
+                      loss_fn_kwargs={"_target": data, "_var": config["input_var"]},
+                      is_log_progress=False, is_return_results_every_t=False, is_checking_after_callback_after_t=False)
+            pc_trainer.train_on_batch(**kw)
+            mcpc_trainer.train_on_batch(callback_after_t=random_step, callback_after_t_kwargs={"_pc_trainer": mcpc_trainer},
+                                        is_sample_x_at_batch_start=False, **kw)
+            parts.append(mcpc_trainer.mcpc_last_histogram2d)
+    finally:
+        mcpc_trainer.mcpc_histogram2d = saved
+    if pool is None:
+        density = Histogram2D.cat(parts)
+    else:
+        density = parts[0]
+        for part in parts[1:]:
+            density = density.merge(part)
+    return density
+
+
 def get_posterior_cloud(gen_pc, config, trainers, loader, layer=2, units=None, loss_fn=None):
     """The posterior samples themselves of a few units of one latent layer, per batch of ``loader``: MAP call with ``trainers[0]``,
     then an MCPC call with ``trainers[1]`` started from the MAP state (the protocol of ``get_posterior_ess``), over the steps from
