@@ -123,7 +123,7 @@ struct GemmScale { int a_exp; int mode; int fixed_b; int run; int short_k; int s
 #endif
 
 #ifdef MCPC_EXP_NOSPLIT    // timing experiment only (wrong results): the B planes of block 0 serve every block (no LDS reads, no split)
-#define MCPC_EXP_SPLIT8(a_, b_) bs[0]
+#define MCPC_EXP_SPLIT8(a_, b_) bs
 #else
 #define MCPC_EXP_SPLIT8(a_, b_) b_planes<PS>(a_, b_, bscale)
 #endif
@@ -134,7 +134,7 @@ struct GemmScale { int a_exp; int mode; int fixed_b; int run; int short_k; int s
 // sub-steps (k, G0), (k, G1) of 4 x 2 MFMAs each, and the fragments of sub-step u + 2 travel while u and u + 1 compute -- the distance
 // of a whole k-block -- in THREE rotating half-sets of 16 VGPRs: sub-step u reads set u mod 3, the request for u + 2 goes into the set
 // u - 1 has just freed.  Static register names need the rotation unrolled over three k-blocks.
-// (Two chain tiles per fragment -- CTT = 2 -- were measured in rounds 4 and 5 and dropped: profiles/r04_k1_bounds.txt, r05_k1_decomp.txt.)
+// (Two chain tiles per fragment -- 32 chains per workgroup -- were measured in rounds 4 and 5 and dropped: profiles/r04_k1_bounds.txt, r05_k1_decomp.txt.)
 //
 // b_exp: 2^b_exp scales this lane's chain row (gemm_row_exp below, or the caller's fixed exponent).
 // MM: with the a_m b_m term (2^-22 of the leading one).  GEMMs of at most kShortK k-blocks (K <= 64) keep it: there are too few terms there
@@ -142,10 +142,9 @@ struct GemmScale { int a_exp; int mode; int fixed_b; int run; int short_k; int s
 // 2.6e-8 with it; fp32 MFMA chain 1.0e-7 / 2.1e-8).  From K = 96 on the term changes neither figure (profiles/r05_f16x4_study.txt) and longer
 // GEMMs run THREE MFMAs per product.
 constexpr int kShortK = 2;
-template <int NT, int NTT, int CTT, int NW, bool MM, bool PS = false>
-__device__ __forceinline__ void gemm_fixed(f32x4 (&acc)[NTT][CTT], const gu32x4* __restrict__ A, const int (&aoff)[NTT], int nkb, int kw,
+template <int NT, int NTT, int NW, bool MM, bool PS = false>
+__device__ __forceinline__ void gemm_fixed(f32x4 (&acc)[NTT], const gu32x4* __restrict__ A, const int (&aoff)[NTT], int nkb, int kw,
                                            const float* B, int ldb, int lane, frag_t (&pre)[NTT], const float* zeros, int b_exp) {
-    static_assert(CTT == 1, "one chain tile per workgroup (two were measured and dropped in rounds 4 and 5: DESIGN.md section 4)");
     constexpr int N0 = NT < 2 ? NT : 2, N1 = NT - N0;            // tiles of group 0 / group 1
     if (nkb <= 0) return;
     const int c = lane & 15, g = lane >> 4;
@@ -161,15 +160,15 @@ __device__ __forceinline__ void gemm_fixed(f32x4 (&acc)[NTT][CTT], const gu32x4*
 #pragma unroll
     for (int t = 0; t < NT; ++t) voff[t] = (uint32_t)(aoff[t] + lane) * 16u;
     const char __attribute__((address_space(1)))* const Ab = (const char __attribute__((address_space(1)))*)A;
-    f32x4 bC[CTT][2];
-    frag_t bs[CTT];
+    f32x4 bC[2];
+    frag_t bs;
     frag_t s0[2], s1[2], s2[2];                                   // the three half-sets
     const int last = nkb - 1;
 #define MCPC_LOAD_B(k_)                                                                             \
     do {                                                                                            \
         const float* const src_ = (k_) < last ? bp + (k_) * kKB : bp_last;     /* never conditional */ \
-        bC[0][0] = *reinterpret_cast<const f32x4*>(src_);                                           \
-        bC[0][1] = *reinterpret_cast<const f32x4*>(src_ + 4);                                       \
+        bC[0] = *reinterpret_cast<const f32x4*>(src_);                                              \
+        bC[1] = *reinterpret_cast<const f32x4*>(src_ + 4);                                          \
     } while (0)
     // fragments of group G_ (0 / 1) of block k_ (clamped) into half-set s_
 #define MCPC_LOAD_HALF(s_, G_, k_)                                                                  \
@@ -181,34 +180,34 @@ __device__ __forceinline__ void gemm_fixed(f32x4 (&acc)[NTT][CTT], const gu32x4*
             s_[i].m = *(const gu32x4*)(Ak_ + voff[2 * (G_) + i] + 1024u);                           \
         }                                                                                           \
     } while (0)
-    // the four products of group G_ x chain tile ct_ out of half-set s_, small terms first; consecutive MFMAs alternate between the
-    // group's (at most two) accumulators of that chain tile
-#define MCPC_M4(s_, G_, ct_, ap_, bp_)                                                              \
+    // the four products of group G_ out of half-set s_, small terms first; consecutive MFMAs alternate between the group's (at most
+    // two) accumulators
+#define MCPC_M4(s_, G_, ap_, bp_)                                                                   \
     _Pragma("unroll") for (int i = 0; i < ((G_) ? N1 : N0); ++i)                                    \
-        acc[2 * (G_) + i][ct_] = mfma4(s_[i].ap_, bs[ct_].bp_, acc[2 * (G_) + i][ct_])
+        acc[2 * (G_) + i] = mfma4(s_[i].ap_, bs.bp_, acc[2 * (G_) + i])
 #ifdef MCPC_EXP_HALFMFMA   // timing experiment only (wrong results): two of the four products
-#define MCPC_SUB(s_, G_, ct_)                                                                       \
-    do { MCPC_M4(s_, G_, ct_, m, h); MCPC_M4(s_, G_, ct_, h, h); } while (0)
+#define MCPC_SUB(s_, G_)                                                                            \
+    do { MCPC_M4(s_, G_, m, h); MCPC_M4(s_, G_, h, h); } while (0)
 #else
-#define MCPC_SUB(s_, G_, ct_)                                                                       \
-    do { if constexpr (MM) { MCPC_M4(s_, G_, ct_, m, m); }                                           \
-         MCPC_M4(s_, G_, ct_, m, h); MCPC_M4(s_, G_, ct_, h, m); MCPC_M4(s_, G_, ct_, h, h); } while (0)
+#define MCPC_SUB(s_, G_)                                                                            \
+    do { if constexpr (MM) { MCPC_M4(s_, G_, m, m); }                                               \
+         MCPC_M4(s_, G_, m, h); MCPC_M4(s_, G_, h, m); MCPC_M4(s_, G_, h, h); } while (0)
 #endif
-#define MCPC_SPLIT1(ct_) bs[ct_] = b_planes<PS>(bC[ct_][0], bC[ct_][1], bscale)
+#define MCPC_SPLIT1() bs = b_planes<PS>(bC[0], bC[1], bscale)
     // One k-block: the chain tile's planes are read by both sub-steps, so the next block's split goes into a second copy beside
     // (k, G1) and is moved over at the end of the block (8 v_mov)
 #define MCPC_BLOCK1(sa_, sb_, sc_, k_)                                                              \
     do {                                                                                            \
         __builtin_amdgcn_sched_barrier(0);                                                          \
         MCPC_LOAD_HALF(sc_, 0, (k_) + 1);                                                           \
-        MCPC_SUB(sa_, 0, 0);                                                                        \
+        MCPC_SUB(sa_, 0);                                                                           \
         __builtin_amdgcn_sched_barrier(0);                                                          \
         MCPC_LOAD_HALF(sa_, 1, (k_) + 1);                                                           \
-        const frag_t bsn_ = MCPC_EXP_SPLIT8(bC[0][0], bC[0][1]);   /* (k + 1): read at the head of this block */ \
-        MCPC_SUB(sb_, 1, 0);                                                                        \
+        const frag_t bsn_ = MCPC_EXP_SPLIT8(bC[0], bC[1]);         /* (k + 1): read at the head of this block */ \
+        MCPC_SUB(sb_, 1);                                                                           \
         __builtin_amdgcn_sched_barrier(0);                                                          \
         MCPC_LOAD_B((k_) + 2);                                                                      \
-        bs[0] = bsn_;                                                                               \
+        bs = bsn_;                                                                                  \
     } while (0)
 #define MCPC_BLOCK(sa_, sb_, sc_, k_) MCPC_BLOCK1(sa_, sb_, sc_, k_)
     // The LAST block of a GEMM requests, reads and splits nothing: there is no next block.  (Until round 5 every block ran MCPC_BLOCK1 with
@@ -217,8 +216,8 @@ __device__ __forceinline__ void gemm_fixed(f32x4 (&acc)[NTT][CTT], const gu32x4*
 #define MCPC_BLOCK_LAST(sa_, sb_)                                                                   \
     do {                                                                                            \
         __builtin_amdgcn_sched_barrier(0);                                                          \
-        MCPC_SUB(sa_, 0, 0);                                                                        \
-        MCPC_SUB(sb_, 1, 0);                                                                        \
+        MCPC_SUB(sa_, 0);                                                                           \
+        MCPC_SUB(sb_, 1);                                                                           \
     } while (0)
     // block 0 arrives in `pre`: tiles 0, 1 -> set 0, tiles 2, 3 -> set 1
 #pragma unroll
@@ -228,7 +227,7 @@ __device__ __forceinline__ void gemm_fixed(f32x4 (&acc)[NTT][CTT], const gu32x4*
     MCPC_LOAD_B(0);
     // (the exponent may still be on its way from LDS -- the row word of the in-place kernel -- : first used here, behind the B reads)
     const float bscale = pow2i(b_exp);
-    MCPC_SPLIT1(0);
+    MCPC_SPLIT1();
     MCPC_LOAD_B(1);
     int k = 0;
     // steady state: three k-blocks per round (the rotation's period) while a block FOLLOWS the round; then up to two more full blocks and
@@ -269,7 +268,7 @@ __device__ __forceinline__ void gemm_fixed(f32x4 (&acc)[NTT][CTT], const gu32x4*
 // registers, longer ones refill a slot as soon as its MFMAs are issued.  Per accumulator the MFMAs are those of gemm_fixed, in its order
 // ([a_m b_m,] a_m b_h, a_h b_m, a_h b_h per block, blocks ascending): bitwise the same sums.
 template <int NT, int NTT, bool MM, bool PS = false>
-__device__ __forceinline__ void gemm_deep(f32x4 (&acc)[NTT][1], const gu32x4* __restrict__ A, const int (&aoff)[NTT], int nkb, int kw,
+__device__ __forceinline__ void gemm_deep(f32x4 (&acc)[NTT], const gu32x4* __restrict__ A, const int (&aoff)[NTT], int nkb, int kw,
                                           const float* B, int ldb, int lane, frag_t (&pre)[NTT], const float* zeros, int b_exp) {
     static_assert(NT == 1 || NT == 2, "one or two tiles");
     static_assert(NTT == 4, "four fragment slots");
@@ -297,7 +296,7 @@ __device__ __forceinline__ void gemm_deep(f32x4 (&acc)[NTT][1], const gu32x4* __
         b1 = *reinterpret_cast<const f32x4*>(src_ + 4);                                             \
     } while (0)
 #define MCPC_DM(j_, ap_, bp_)                                                                       \
-    _Pragma("unroll") for (int i = 0; i < NT; ++i) acc[i][0] = mfma4(f[j_][i].ap_, bs.bp_, acc[i][0])
+    _Pragma("unroll") for (int i = 0; i < NT; ++i) acc[i] = mfma4(f[j_][i].ap_, bs.bp_, acc[i])
 #define MCPC_DSUB(j_)                                                                               \
     do { if constexpr (MM) { MCPC_DM(j_, m, m); }                                                   \
          MCPC_DM(j_, m, h); MCPC_DM(j_, h, m); MCPC_DM(j_, h, h); } while (0)
@@ -370,31 +369,29 @@ __device__ __forceinline__ int gemm_row_exp(const float* B, int ldb, int nkb, in
 }
 
 // un-scale accumulators that are in units of 2^(a_exp + b_exp) (exact)
-template <int NTT, int CTT>
-__device__ __forceinline__ void gemm_unscale(f32x4 (&acc)[NTT][CTT], int a_exp, int b_exp) {
+template <int NTT>
+__device__ __forceinline__ void gemm_unscale(f32x4 (&acc)[NTT], int a_exp, int b_exp) {
     const float un = pow2i(-a_exp) * pow2i(-b_exp);
 #pragma unroll
-    for (int i = 0; i < NTT; ++i)
-#pragma unroll
-        for (int ct = 0; ct < CTT; ++ct) acc[i][ct] = acc[i][ct] * un;
+    for (int i = 0; i < NTT; ++i) acc[i] = acc[i] * un;
 }
 
 // nt (wave-uniform, 1..NTT) selects a straight-line instantiation: no per-tile branches in the loop
-template <int N, int NTT, int CTT, int NW, bool MM>
-__device__ __forceinline__ void gemm_dispatch(f32x4 (&acc)[NTT][CTT], const gu32x4* __restrict__ A, const int (&aoff)[NTT], int nt, int nkb, int kw,
+template <int N, int NTT, int NW, bool MM>
+__device__ __forceinline__ void gemm_dispatch(f32x4 (&acc)[NTT], const gu32x4* __restrict__ A, const int (&aoff)[NTT], int nt, int nkb, int kw,
                                               const float* B, int ldb, int lane, frag_t (&pre0)[NTT], const float* zeros, int b_exp) {
     if constexpr (N >= NTT) {
-        gemm_fixed<NTT, NTT, CTT, NW, MM>(acc, A, aoff, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
+        gemm_fixed<NTT, NTT, NW, MM>(acc, A, aoff, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
     } else {
-        if (nt == N) gemm_fixed<N, NTT, CTT, NW, MM>(acc, A, aoff, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
-        else gemm_dispatch<N + 1, NTT, CTT, NW, MM>(acc, A, aoff, nt, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
+        if (nt == N) gemm_fixed<N, NTT, NW, MM>(acc, A, aoff, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
+        else gemm_dispatch<N + 1, NTT, NW, MM>(acc, A, aoff, nt, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
     }
 }
 // kw: valid k width of the B rows (a multiple of 16, 32 (nkb - 1) < kw <= 32 nkb); zeros: 16 floats of LDS that stay zero for the launch.
 // gs: see GemmScale.  GS_FRESH: acc must be zero on entry and holds the true sums on return.  GS_ACCUM: acc carries earlier chunks in units
 // of 2^(a_exp + gs.run) and stays scaled; gs.run is updated (a smaller exponent rescales acc first: exact).
-template <int NTT, int CTT, int NW>
-__device__ __forceinline__ void gemm_tiles(f32x4 (&acc)[NTT][CTT], const void* A, const int (&aoff)[NTT], int nt, int nkb, int kw,
+template <int NTT, int NW>
+__device__ __forceinline__ void gemm_tiles(f32x4 (&acc)[NTT], const void* A, const int (&aoff)[NTT], int nt, int nkb, int kw,
                                            const float* B, int ldb, int lane, frag_t (&pre0)[NTT], const float* zeros, GemmScale& gs) {
 #ifdef MCPC_EXP_NOROWEXP    // timing experiment only (wrong results): no pre-pass over the row, a constant exponent
     int b_exp = gs.scan ? 8 : gs.fixed_b;
@@ -406,9 +403,7 @@ __device__ __forceinline__ void gemm_tiles(f32x4 (&acc)[NTT][CTT], const void* A
             if (b_exp < gs.run) {                       // this chunk's row is larger than any before: bring the sum down to its units
                 const float f = pow2i(b_exp - gs.run);
 #pragma unroll
-                for (int i = 0; i < NTT; ++i)
-#pragma unroll
-                    for (int ct = 0; ct < CTT; ++ct) acc[i][ct] = acc[i][ct] * f;
+                for (int i = 0; i < NTT; ++i) acc[i] = acc[i] * f;
             } else {
                 b_exp = gs.run;                         // a smaller row joins in the units the sum is already in
             }
@@ -416,16 +411,16 @@ __device__ __forceinline__ void gemm_tiles(f32x4 (&acc)[NTT][CTT], const void* A
         gs.run = b_exp;
     }
     const bool mm = gs.short_k >= 0 ? gs.short_k != 0 : nkb <= kShortK;
-    if (mm && nkb <= kShortK) gemm_dispatch<1, NTT, CTT, NW, true>(acc, (const gu32x4*)A, aoff, nt, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
-    else gemm_dispatch<1, NTT, CTT, NW, false>(acc, (const gu32x4*)A, aoff, nt, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
-    if (gs.mode == GS_FRESH) gemm_unscale<NTT, CTT>(acc, gs.a_exp, b_exp);
+    if (mm && nkb <= kShortK) gemm_dispatch<1, NTT, NW, true>(acc, (const gu32x4*)A, aoff, nt, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
+    else gemm_dispatch<1, NTT, NW, false>(acc, (const gu32x4*)A, aoff, nt, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
+    if (gs.mode == GS_FRESH) gemm_unscale<NTT>(acc, gs.a_exp, b_exp);
 }
 
 // GEMM of the unified-wave kernel: fresh accumulators, the row's exponent from its producers' word (or a constant), un-scaled on return;
 // one or two tiles on the deep fragment stream (gemm_deep: `pre` = four (block, tile) slots), three or four on the rotation of gemm_fixed
 // (`pre` = block 0 of every tile).  ps (wave-uniform): the B operand is already in planes (the Bernoulli read-out's error: headf_planes).
 template <int NTT>
-__device__ __forceinline__ void gemm_tiles_u(f32x4 (&acc)[NTT][1], const void* A, const int (&aoff)[NTT], int nt, int nkb, int kw,
+__device__ __forceinline__ void gemm_tiles_u(f32x4 (&acc)[NTT], const void* A, const int (&aoff)[NTT], int nt, int nkb, int kw,
                                              const float* B, int ldb, int lane, frag_t (&pre)[NTT], const float* zeros, int a_exp, int b_exp,
                                              int short_k, bool ps) {
     const bool mm = (short_k >= 0 ? short_k != 0 : nkb <= kShortK) && nkb <= kShortK;
@@ -433,8 +428,8 @@ __device__ __forceinline__ void gemm_tiles_u(f32x4 (&acc)[NTT][1], const void* A
     if (ps) {                       // (long contractions only: never with the fourth product)
         if (nt == 1) gemm_deep<1, NTT, false, true>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
         else if (nt == 2) gemm_deep<2, NTT, false, true>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
-        else if (nt == 3) gemm_fixed<3, NTT, 1, 8, false, true>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
-        else gemm_fixed<4, NTT, 1, 8, false, true>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
+        else if (nt == 3) gemm_fixed<3, NTT, 8, false, true>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
+        else gemm_fixed<4, NTT, 8, false, true>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
     } else if (nt == 1) {
         if (mm) gemm_deep<1, NTT, true>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
         else gemm_deep<1, NTT, false>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
@@ -442,13 +437,13 @@ __device__ __forceinline__ void gemm_tiles_u(f32x4 (&acc)[NTT][1], const void* A
         if (mm) gemm_deep<2, NTT, true>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
         else gemm_deep<2, NTT, false>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
     } else if (nt == 3) {
-        if (mm) gemm_fixed<3, NTT, 1, 8, true>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
-        else gemm_fixed<3, NTT, 1, 8, false>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
+        if (mm) gemm_fixed<3, NTT, 8, true>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
+        else gemm_fixed<3, NTT, 8, false>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
     } else {
-        if (mm) gemm_fixed<4, NTT, 1, 8, true>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
-        else gemm_fixed<4, NTT, 1, 8, false>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
+        if (mm) gemm_fixed<4, NTT, 8, true>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
+        else gemm_fixed<4, NTT, 8, false>(acc, Ag, aoff, nkb, kw, B, ldb, lane, pre, zeros, b_exp);
     }
-    gemm_unscale<NTT, 1>(acc, a_exp, b_exp);
+    gemm_unscale<NTT>(acc, a_exp, b_exp);
 }
 
 // request the fragments of k-block 0 of a phase's GEMM (issued one phase early: weights do not depend on any barrier)

@@ -1,7 +1,7 @@
 // MCPC kernels for gfx950 (MI355X).  See DESIGN.md for the data layout and the per-kernel rooflines.
 //
 // K1  mcpc_steps_kernel   fused Langevin / PC inference steps, persistent over n_steps:
-//                         one workgroup = kCT chains, all layers, weights streamed from L2 in
+//                         one workgroup = 16 chains (one MFMA column tile), all layers, weights streamed from L2 in
 //                         MFMA-fragment order, state in HBM/L2 (padded), activations/errors in LDS.
 //                         replaces reference pc_trainer.py:733-918 + utils/model.py:35-44 per step.
 // K3  mcpc_dw_kernel      Hebbian sums  G[u][i] = sum_r E[r][u] * A[r][i]  over spilled (error,
@@ -15,7 +15,7 @@
 namespace mcpc {
 
 constexpr int kMaxLatent = MCPC_MAX_LATENT;
-constexpr int kCT = 32;           // max chains per workgroup = 2 MFMA column tiles of 16 (CTT = 1 or 2)
+constexpr int kBatchPad = 32;     // the batch is padded to a multiple of this (plan_engine: Bpad); a workgroup owns 16 chains = one MFMA column tile
 constexpr int kWaves = 4;         // waves per workgroup of the default variant; kMaxWaves bounds the LDS scratch
 constexpr int kMaxWaves = 8;
 constexpr int kThreads = kWaves * 64;
@@ -216,9 +216,12 @@ __device__ __forceinline__ f32x4 splat(float v) { f32x4 r = {v, v, v, v}; return
 // into pa/pb, ahead of the phase's GEMM.  Branch-free on purpose: the entry type only selects ADDRESSES, every slot
 // issues the same three loads (one streamed, one cached, one LDS).  With a load inside an `if` hipcc joins the
 // branches behind an `s_waitcnt vmcnt(0)`, which serialised the slots at full HBM latency each.
+// CTT, here and in the epilogues below, is always 1 (one MFMA column tile of 16 chains per workgroup; two were measured and dropped in
+// rounds 4 and 5).  The parameter and a one-trip `ct` loop are left in the functions whose compiled code changes without the loop
+// (profiles/ctt_removal_asm.txt); everything else knows one tile only.
 template <int CTT, int NW, int NTW>
 __device__ __forceinline__ void issue_epilogue_loads(const KParams& P, const KPhase& ph, const float* lds, int nt, int wave,
-                                                     int lane, int chain0, f32x4 (&pa)[NTW][CTT], f32x4 (&pb)[NTW][CTT]) {
+                                                     int lane, int chain0, f32x4 (&pa)[NTW], f32x4 (&pb)[NTW]) {
     const KLayer& Ly = P.layer[ph.layer];
     const int c = lane & 15, q = lane >> 4;
     const bool is_head = ph.type == PH_HEADF, is_bwd = ph.type == PH_BWD;
@@ -244,8 +247,8 @@ __device__ __forceinline__ void issue_epilogue_loads(const KParams& P, const KPh
             const f32x4 va = ld4s(baseA + (size_t)(chain0 + cl) * strideA + uA);
             const f32x4 vg = ld4(baseB + (size_t)(chain0 + cl) * strideB + u0);
             const f32x4 ve = ld4(lds + Ly.lds_e + cl * Ly.ld + (is_bwd ? u0 : 4 * q));
-            pa[i][ct] = va;
-            pb[i][ct] = is_bwd ? (mu1 ? (va - vg) * ecoef : ve) : vg;
+            pa[i] = va;
+            pb[i] = is_bwd ? (mu1 ? (va - vg) * ecoef : ve) : vg;
         }
     }
 }
@@ -338,8 +341,8 @@ __device__ __forceinline__ unsigned long long mcpc_stamp() {
 // ---- FWD epilogue: prediction errors, energies, activations to LDS, spills, trajectory records -------
 template <int CTT, int NW, int NTW, int ACT, bool WRITE_FX = true>
 __device__ __forceinline__ float fwd_epilogue(const KParams& P, const KPhase& ph, float* lds, int nt, int wave, int lane,
-                                              int chain0, const f32x4 (&acc)[NTW][CTT], const f32x4 (&pa)[NTW][CTT],
-                                              const f32x4 (&pb)[NTW][CTT], int slot, int rec_idx) {
+                                              int chain0, const f32x4 (&acc)[NTW], const f32x4 (&pa)[NTW],
+                                              const f32x4 (&pb)[NTW], int slot, int rec_idx) {
     const KLayer& Ly = P.layer[ph.layer];
     const int c = lane & 15, q = lane >> 4;
     const int l = ph.layer, npad = Ly.npad, n = Ly.n, ld = Ly.ld, B = P.B, Bpad = P.Bpad;
@@ -356,17 +359,15 @@ __device__ __forceinline__ float fwd_epilogue(const KParams& P, const KPhase& ph
 #pragma unroll
     for (int i = 0; i < NTW; ++i) {
         if (i >= nt) continue;
-        f32x4 a[CTT], xa[CTT], xb[CTT];
-#pragma unroll
-        for (int ct = 0; ct < CTT; ++ct) { a[ct] = acc[i][ct]; xa[ct] = pa[i][ct]; xb[ct] = pb[i][ct]; }
+        const f32x4 a = acc[i], xa = pa[i], xb = pb[i];
         const int u0 = 16 * (ph.tile0 + wave + NW * i) + 4 * q;
 #pragma unroll
         for (int ct = 0; ct < CTT; ++ct) {
             const int cl = 16 * ct + c, chain = chain0 + cl;
             const bool live = chain < B;
-            const f32x4 x = xa[ct];
+            const f32x4 x = xa;
             f32x4 d;                                              // x - mu
-            const f32x4 e = pc_error4(x, a[ct] + xb[ct], ecoef, d);
+            const f32x4 e = pc_error4(x, a + xb, ecoef, d);
             const f32x4 fx = act4<ACT>(x);
             if constexpr (WRITE_FX) st4(fx_lds + cl * ld + u0, fx);   // in-place variant: FX_l is written by the x update
             if (l > 0) st4(e_lds + cl * ld + u0, e);
@@ -397,8 +398,8 @@ __device__ __forceinline__ float fwd_epilogue(const KParams& P, const KPhase& ph
 // ---- HEADF epilogue: read-out, loss error e_o into the LDS chunk, loss value, spills, output records ----
 template <int CTT, int NW, int NTW>
 __device__ __forceinline__ float headf_epilogue(const KParams& P, const KPhase& ph, float* lds, int nt, int wave, int lane,
-                                                int chain0, const f32x4 (&acc)[NTW][CTT], const f32x4 (&pa)[NTW][CTT],
-                                                const f32x4 (&pb)[NTW][CTT], int slot, int rec_idx, bool do_energy) {
+                                                int chain0, const f32x4 (&acc)[NTW], const f32x4 (&pa)[NTW],
+                                                const f32x4 (&pb)[NTW], int slot, int rec_idx, bool do_energy) {
     const KHead& H = P.head;
     const int c = lane & 15, q = lane >> 4;
     const int npad = H.npad, n = H.n, ld = ph.out_ld, B = P.B, Bpad = P.Bpad, mask_start = H.mask_start, kind = H.loss_kind;
@@ -413,19 +414,17 @@ __device__ __forceinline__ float headf_epilogue(const KParams& P, const KPhase& 
 #pragma unroll
     for (int i = 0; i < NTW; ++i) {
         if (i >= nt) continue;
-        f32x4 a[CTT], xa[CTT], xb[CTT];
-#pragma unroll
-        for (int ct = 0; ct < CTT; ++ct) { a[ct] = acc[i][ct]; xa[ct] = pa[i][ct]; xb[ct] = pb[i][ct]; }
+        const f32x4 a = acc[i], xa = pa[i], xb = pb[i];
         const int ut = ph.tile0 + wave + NW * i;
         const int u0 = 16 * ut + 4 * q;
 #pragma unroll
         for (int ct = 0; ct < CTT; ++ct) {
             const int cl = 16 * ct + c, chain = chain0 + cl;
             const bool live = chain < B;
-            const f32x4 o = a[ct] + xb[ct];
+            const f32x4 o = a + xb;
             f32x4 e = splat(0.f);
             if (kind != MCPC_LOSS_NONE) {
-                const f32x4 y = xa[ct];
+                const f32x4 y = xa;
                 MCPC_READOUT_LOSS4(e, o, y, kind, do_energy, inv_var, lsum, live && (u0 + r) >= mask_start && (u0 + r) < n, true);
             }
             st4(eo_lds + cl * ld + (u0 - 16 * ph.tile0), e);
@@ -442,8 +441,8 @@ __device__ __forceinline__ float headf_epilogue(const KParams& P, const KPhase& 
 //   else (Adam, external noise, gradients-only) behind wave-uniform branches.
 template <int CTT, int NW, int NTW, int ACT, int MODE, bool FXOUT = false>
 __device__ __forceinline__ void bwd_epilogue(const KParams& P, const KPhase& ph, int nt, int wave, int lane, int chain0,
-                                             const f32x4 (&acc)[NTW][CTT], const f32x4 (&pa)[NTW][CTT],
-                                             const f32x4 (&pb)[NTW][CTT], int s, int t, float* lds = nullptr) {
+                                             const f32x4 (&acc)[NTW], const f32x4 (&pa)[NTW],
+                                             const f32x4 (&pb)[NTW], int s, int t, float* lds = nullptr) {
     const KLayer& Ly = P.layer[ph.layer];
     const int c = lane & 15, q = lane >> 4;
     const int l = ph.layer, npad = Ly.npad, n = Ly.n, B = P.B;
@@ -455,15 +454,13 @@ __device__ __forceinline__ void bwd_epilogue(const KParams& P, const KPhase& ph,
 #pragma unroll
     for (int i = 0; i < NTW; ++i) {
         if (i >= nt) continue;
-        f32x4 a[CTT], xa[CTT], xb[CTT];
-#pragma unroll
-        for (int ct = 0; ct < CTT; ++ct) { a[ct] = acc[i][ct]; xa[ct] = pa[i][ct]; xb[ct] = pb[i][ct]; }
+        const f32x4 a = acc[i], xa = pa[i], xb = pb[i];
         const int u0 = 16 * (ph.tile0 + wave + NW * i) + 4 * q;
 #pragma unroll
         for (int ct = 0; ct < CTT; ++ct) {
             const int chain = chain0 + 16 * ct + c;
             const size_t row = (size_t)chain * npad + u0;
-            const f32x4 x = xa[ct], e = xb[ct], back = a[ct];
+            const f32x4 x = xa, e = xb, back = a;
             const f32x4 g = x_grad4<ACT>(x, e, back, sign);
             f32x4 xn;
             if constexpr (MODE == 0) {
@@ -504,8 +501,8 @@ __device__ __forceinline__ void bwd_epilogue(const KParams& P, const KPhase& ph,
 
 template <int CTT, int NW, int NTW, int ACT, bool FXOUT = false>
 __device__ __forceinline__ void bwd_epilogue_mode(const KParams& P, const KPhase& ph, int nt, int wave, int lane, int chain0,
-                                                  const f32x4 (&acc)[NTW][CTT], const f32x4 (&pa)[NTW][CTT],
-                                                  const f32x4 (&pb)[NTW][CTT], int s, int t, int mode, float* lds = nullptr) {
+                                                  const f32x4 (&acc)[NTW], const f32x4 (&pa)[NTW],
+                                                  const f32x4 (&pb)[NTW], int s, int t, int mode, float* lds = nullptr) {
     if (mode == 2) bwd_epilogue<CTT, NW, NTW, ACT, 2, FXOUT>(P, ph, nt, wave, lane, chain0, acc, pa, pb, s, t, lds);
     else if (mode == 1) bwd_epilogue<CTT, NW, NTW, ACT, 1, FXOUT>(P, ph, nt, wave, lane, chain0, acc, pa, pb, s, t, lds);
     else bwd_epilogue<CTT, NW, NTW, ACT, 0, FXOUT>(P, ph, nt, wave, lane, chain0, acc, pa, pb, s, t, lds);
@@ -515,14 +512,15 @@ __device__ __forceinline__ void bwd_epilogue_mode(const KParams& P, const KPhase
 #define MCPC_BARRIER_WAVES_PER_EU 1      // one workgroup per CU, no spilled VGPRs (256 + 112 AGPRs): 129 us per step at cfg-M; 2 (two workgroups
                                          // per CU, one's GEMMs covering the other's epilogues, 72 VGPRs spilled to scratch): 147 us (round 4)
 #endif
-template <int CTT, int NW>
+template <int CTT, int NW>       // CTT: part of the symbol, always 1 (one MFMA column tile of 16 chains); handed on only to the epilogues that still take it
 __global__ __launch_bounds__(NW * 64, MCPC_BARRIER_WAVES_PER_EU) void mcpc_steps_kernel(const KParams P) {
+    static_assert(CTT == 1, "part of the symbol: one chain tile per workgroup");
     constexpr int NTW = 16 / NW;     // unit tiles per wave per phase (a phase hands out 16 tiles)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int chain0 = blockIdx.x * (16 * CTT);
+    const int chain0 = blockIdx.x * 16;
     const int L = P.L;
     // fused fast paths of the x update (wave-uniform, fixed for the launch)
     const int upd_mode = (P.update_x && P.xopt == MCPC_XOPT_SGD)
@@ -561,11 +559,9 @@ __global__ __launch_bounds__(NW * 64, MCPC_BARRIER_WAVES_PER_EU) void mcpc_steps
         float* red = lds + P.lds_red + (s & 1) * (kMaxLatent + 1) * NW;
         if (do_energy && lane <= kMaxLatent) red[lane * NW + wave] = 0.f;
 
-        f32x4 accb[NTW][CTT];
+        f32x4 accb[NTW];
 #pragma unroll
-        for (int i = 0; i < NTW; ++i)
-#pragma unroll
-            for (int ct = 0; ct < CTT; ++ct) accb[i][ct] = splat(0.f);
+        for (int i = 0; i < NTW; ++i) accb[i] = splat(0.f);
         int accb_run = kRunNone, accb_aexp = 0;            // the units accb is in (mcpc_gemm_f16.h: GemmScale)
 
 #pragma unroll 1
@@ -597,17 +593,15 @@ __global__ __launch_bounds__(NW * 64, MCPC_BARRIER_WAVES_PER_EU) void mcpc_steps
                 STAMP(12);
                 continue;
             }
-            f32x4 acc[NTW][CTT], pa[NTW][CTT], pb[NTW][CTT];
+            f32x4 acc[NTW], pa[NTW], pb[NTW];
             const KLayer& Ly = P.layer[ph.layer];
             // ---- accumulators; the epilogue's operands are requested by `prologue`, which the GEMM
             //      invokes after its last fragment load (or which runs directly when there is no GEMM)
 #pragma unroll
-            for (int i = 0; i < NTW; ++i)
-#pragma unroll
-                for (int ct = 0; ct < CTT; ++ct) {
-                    acc[i][ct] = (ph.flags & PHF_ACC_FROM_B) ? accb[i][ct] : splat(0.f);
-                    pa[i][ct] = splat(0.f); pb[i][ct] = splat(0.f);
-                }
+            for (int i = 0; i < NTW; ++i) {
+                acc[i] = (ph.flags & PHF_ACC_FROM_B) ? accb[i] : splat(0.f);
+                pa[i] = splat(0.f); pb[i] = splat(0.f);
+            }
             STAMP_T(0, ph.type);
             // ---- GEMM ------------------------------------------------------------------------------------
             // operands of the epilogue (x, targets: streamed; bias, E: L2/LDS) are requested ahead of the GEMM.
@@ -618,18 +612,16 @@ __global__ __launch_bounds__(NW * 64, MCPC_BARRIER_WAVES_PER_EU) void mcpc_steps
                 const int hb_exp = ph.type == PH_HEADB ? headb_fixed_exp(P.head.loss_kind, y_bounded) : kScaleAuto;
                 GemmScale gs{load_wexp(P.wexp, ph.a_lin), ph.type == PH_HEADB ? GS_ACCUM : GS_FRESH, hb_exp, accb_run,
                              ph.type == PH_HEADB ? (P.head.npad <= kShortK * kKB ? 1 : 0) : -1, hb_exp == kScaleAuto ? 1 : 0};
-                gemm_tiles<NTW, CTT, NW>(acc, ph.A, aoff, nt, ph.nkb, ph.kw, lds + ph.b_lds, ph.ldb, lane, pre0, lds + P.lds_zero, gs);
+                gemm_tiles<NTW, NW>(acc, ph.A, aoff, nt, ph.nkb, ph.kw, lds + ph.b_lds, ph.ldb, lane, pre0, lds + P.lds_zero, gs);
                 if (ph.type == PH_HEADB) { accb_run = gs.run; accb_aexp = gs.a_exp; }
             } else if ((ph.flags & PHF_ACC_FROM_B) && ph.type != PH_HEADB && accb_run != kRunNone) {
-                gemm_unscale<NTW, CTT>(acc, accb_aexp, accb_run);       // the complete back-projection of the read-out error, handed to BWD_{L-1}
+                gemm_unscale<NTW>(acc, accb_aexp, accb_run);       // the complete back-projection of the read-out error, handed to BWD_{L-1}
             }
             // the next phase's first weight fragments travel while this phase's epilogue runs
             if (has_next) prefetch_first_blocks<NW, NTW>(ph_next, wave, lane, nt_next, aoff_next, pre0_next);
             if (ph.flags & PHF_ACC_TO_B) {
 #pragma unroll
-                for (int i = 0; i < NTW; ++i)
-#pragma unroll
-                    for (int ct = 0; ct < CTT; ++ct) accb[i][ct] = acc[i][ct];
+                for (int i = 0; i < NTW; ++i) accb[i] = acc[i];
             }
             STAMP_T(1, ph.type);
             // ---- epilogue --------------------------------------------------------------------------------

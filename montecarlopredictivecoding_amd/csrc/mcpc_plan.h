@@ -77,7 +77,7 @@ struct Knobs {
     int stagger = 0;          // barrier kernel: start cycles of the second workgroup of a CU
     int no_lean = 0;          // 1: the in-place kernel's E waves use the generic epilogues everywhere (A/B, parity tests)
     int no_ybits = 0;         // 1: 0/1 targets are read as fp32 like any other target (A/B, parity tests)
-    int overlay16 = 0;        // 1: 16-chain plans share the LDS of the ring and the E_l like 32-chain plans do (A/B, parity tests)
+    int overlay16 = 0;        // 1: the ring and the E_l share their LDS, as the 32-chain plans of rounds 1-3 did (A/B, parity tests)
     int no_xl = 0;            // 1: 16-chain plans keep the state and the per-step constants in global memory even when the LDS has the room (A/B, parity tests)
     int rr = 1;               // 0: shards of more 16-chain units than CUs run as one launch in hardware rounds instead of the round schedule (plan_rounds)
     int rr_qmax = 100;        // round schedule: most steps per launch in stretches without Hebbian accumulation
@@ -267,7 +267,7 @@ inline int plan_lds_ws2(const EnginePlan& e, StepPlan& p) {
     if (e.has_head) {
         // fewest chunks of at most 16 tiles whose ring of two still fits; chunks equalised; ring of three if that fits too
         const int ht = std::max(e.out_pad / 16, 1);
-        const int span = kWs2Pairs * ws2_nt<1>();     // tiles a table entry hands out
+        const int span = kWs2Pairs * kWs2NTW;     // tiles a table entry hands out
         auto ring_of = [&](int hc, int nb) { return nb * CT * (hc * 16 + kLdPad); };
         // (+ tail: what is added behind the operand regions below -- a plan that close to the limit takes a smaller chunk or ring here
         // instead of failing the final size check)
@@ -333,7 +333,7 @@ inline int plan_lds_ws2(const EnginePlan& e, StepPlan& p) {
 // the previous step's readers of E_l: dep_g <- last back-projection GEMM, dep_se <- last BWD entry.
 inline void build_phases_ws2(const EnginePlan& e, StepPlan& p) {
     const int L = e.L;
-    const int span = kWs2Pairs * ws2_nt<1>();     // tiles per table entry
+    const int span = kWs2Pairs * kWs2NTW;     // tiles per table entry
     auto tiles = [&](int l) { return e.npad[l] / 16; };
     enum { REF_LAST_BWD = -1000, REF_LAST_FWD = -2000, REF_LAST_HB = -3000, REF_LAST_BWD_GEMM = -4000, REF_LAST_BWD_ANY = -5000 };   // symbolic deps
     auto fwd_entries = [&](int l, std::vector<KPhase>& out) {
@@ -830,7 +830,7 @@ inline int plan_engine(const mcpc_net_desc& d, int n_cu, size_t total_mem, Engin
     const Knobs& kn = e.knobs;
     e.L = d.n_latent;
     e.has_head = d.n_out > 0;
-    e.Bpad = (d.batch + kCT - 1) / kCT * kCT;
+    e.Bpad = (d.batch + kBatchPad - 1) / kBatchPad * kBatchPad;
     e.ws = kn.ws == 0 ? 0 : 2;
     e.nw = e.ws == 2 ? 2 * kWs2Pairs : kWaves;
     for (int l = 0; l < e.L; ++l) e.npad[l] = pad16(d.sizes[l]);
@@ -838,7 +838,7 @@ inline int plan_engine(const mcpc_net_desc& d, int n_cu, size_t total_mem, Engin
     // The back-projection of the read-out error is accumulated in registers over the whole read-out: 16 tiles per workgroup
     // (a last latent layer of up to 256 units) in both kernels (cap_ws2 = 4 GEMM waves x 4 tiles, cap_bar = 4 waves x 4 tiles).
     const int last_tiles = e.has_head ? e.npad[e.L - 1] / 16 : 0;
-    const int cap_ws2 = kWs2Pairs * ws2_nt<1>(), cap_bar = kNT * kWaves;
+    const int cap_ws2 = kWs2Pairs * kWs2NTW, cap_bar = kNT * kWaves;
     // The layer-wise kernels (mcpc_steps_lw.h) know neither limit: tuning ws=4 takes them for every run, wide=1 where the checks below fail
     e.lw = kn.ws == 4;
     if (!e.lw && (last_tiles > std::max(cap_ws2, cap_bar) || (last_tiles > cap_bar && e.ws != 2))) {

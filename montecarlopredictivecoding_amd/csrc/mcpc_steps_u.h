@@ -89,39 +89,39 @@ __device__ __forceinline__ void u_energy_row(const KParams& P, const float* lds,
 // the epilogue of a row, straight from the accumulators (mcpc_ws2_lean.h, REG = true).  PLAIN: the caller passes slot = rec_idx = -1 and
 // do_energy = false as literals -- after inlining, the spill, record and energy code of the epilogues is gone from that instantiation.
 template <bool MIX, bool PLAIN>
-__device__ __forceinline__ void u_epilogue(const KParams& P, const KPhase& ph, float* lds, int nt, const LeanLane<1>& LL, int slot, int rec_idx,
-                                           bool do_energy, int t, int s_tab, float* rx, unsigned row_gen, const f32x4 (&acc)[kUNT][1],
-                                           f32x4 (&e0acc)[1], bool e0_in_regs, bool& e0_dirty, float& en_acc, bool ybin, bool hplanes, bool lean_adam,
+__device__ __forceinline__ void u_epilogue(const KParams& P, const KPhase& ph, float* lds, int nt, const LeanLane& LL, int slot, int rec_idx,
+                                           bool do_energy, int t, int s_tab, float* rx, unsigned row_gen, const f32x4 (&acc)[kUNT],
+                                           f32x4& e0acc, bool e0_in_regs, bool& e0_dirty, float& en_acc, bool ybin, bool hplanes, bool lean_adam,
                                            int upd_mode, int lane, bool yw_glob, const uint32_t (&ywreg)[kUNT]) {
-    constexpr int CTT = 1, NW = kUWaves, NTW = kUNT;
+    constexpr int NW = kUWaves, NTW = kUNT;
     int dead = 0;
     const int act = P.layer[ph.layer].act;
     if (ph.type == PH_FWD) {
         float esum;
         if (!PLAIN && ph.layer == 0 && slot >= 0) e0_dirty = true;
-        if (act == MCPC_ACT_RELU) esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_RELU, true, true>(P, ph, lds, nt, 0, LL, slot, rec_idx, nullptr, 0, P.err, dead, e0acc, e0_in_regs, rx, row_gen, acc);
-        else if (act == MCPC_ACT_TANH) esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_TANH, true, true>(P, ph, lds, nt, 0, LL, slot, rec_idx, nullptr, 0, P.err, dead, e0acc, e0_in_regs, rx, row_gen, acc);
-        else esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, true, true>(P, ph, lds, nt, 0, LL, slot, rec_idx, nullptr, 0, P.err, dead, e0acc, e0_in_regs, rx, row_gen, acc);
+        if (act == MCPC_ACT_RELU) esum = lean_fwd<1, NW, NTW, MCPC_ACT_RELU, true, true>(P, ph, lds, nt, 0, LL, slot, rec_idx, nullptr, 0, P.err, dead, e0acc, e0_in_regs, rx, row_gen, acc);
+        else if (act == MCPC_ACT_TANH) esum = lean_fwd<1, NW, NTW, MCPC_ACT_TANH, true, true>(P, ph, lds, nt, 0, LL, slot, rec_idx, nullptr, 0, P.err, dead, e0acc, e0_in_regs, rx, row_gen, acc);
+        else esum = lean_fwd<1, NW, NTW, MCPC_ACT_IDENTITY, true, true>(P, ph, lds, nt, 0, LL, slot, rec_idx, nullptr, 0, P.err, dead, e0acc, e0_in_regs, rx, row_gen, acc);
         if (do_energy) { esum = wave_sum(esum); if (lane == ph.layer) en_acc += esum; }
     } else if (ph.type == PH_HEADF) {
         float lsum;
-        if (ybin && yw_glob) lsum = lean_headf<CTT, NW, NTW, true, true, true, true>(P, ph, lds, nt, 0, LL, slot, rec_idx, do_energy, nullptr, 0, P.err, dead, true, rx, acc, row_gen, hplanes, ywreg);
-        else if (ybin) lsum = lean_headf<CTT, NW, NTW, true, true, true>(P, ph, lds, nt, 0, LL, slot, rec_idx, do_energy, nullptr, 0, P.err, dead, true, rx, acc, row_gen, hplanes);
-        else lsum = lean_headf<CTT, NW, NTW, true, false, true>(P, ph, lds, nt, 0, LL, slot, rec_idx, do_energy, nullptr, 0, P.err, dead, false, rx, acc, row_gen, hplanes);
+        if (ybin && yw_glob) lsum = lean_headf<1, NW, NTW, true, true, true, true>(P, ph, lds, nt, 0, LL, slot, rec_idx, do_energy, nullptr, 0, P.err, dead, true, rx, acc, row_gen, hplanes, ywreg);
+        else if (ybin) lsum = lean_headf<1, NW, NTW, true, true, true>(P, ph, lds, nt, 0, LL, slot, rec_idx, do_energy, nullptr, 0, P.err, dead, true, rx, acc, row_gen, hplanes);
+        else lsum = lean_headf<1, NW, NTW, true, false, true>(P, ph, lds, nt, 0, LL, slot, rec_idx, do_energy, nullptr, 0, P.err, dead, false, rx, acc, row_gen, hplanes);
         if (do_energy) { lsum = wave_sum(lsum); if (lane == kMaxLatent) en_acc += lsum; }
     } else if (ph.type == PH_BWD) {
         if (lean_adam) {
-            if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, false, true, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, s_tab, rx, row_gen, acc);
-            else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, false, true, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, s_tab, rx, row_gen, acc);
-            else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, false, true, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, s_tab, rx, row_gen, acc);
+            if (act == MCPC_ACT_RELU) lean_bwd<1, NW, NTW, MCPC_ACT_RELU, false, true, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, s_tab, rx, row_gen, acc);
+            else if (act == MCPC_ACT_TANH) lean_bwd<1, NW, NTW, MCPC_ACT_TANH, false, true, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, s_tab, rx, row_gen, acc);
+            else lean_bwd<1, NW, NTW, MCPC_ACT_IDENTITY, false, true, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, s_tab, rx, row_gen, acc);
         } else if (upd_mode == 2) {
-            if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, true, false, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, 0, rx, row_gen, acc);
-            else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, true, false, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, 0, rx, row_gen, acc);
-            else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, true, false, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, 0, rx, row_gen, acc);
+            if (act == MCPC_ACT_RELU) lean_bwd<1, NW, NTW, MCPC_ACT_RELU, true, false, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, 0, rx, row_gen, acc);
+            else if (act == MCPC_ACT_TANH) lean_bwd<1, NW, NTW, MCPC_ACT_TANH, true, false, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, 0, rx, row_gen, acc);
+            else lean_bwd<1, NW, NTW, MCPC_ACT_IDENTITY, true, false, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, 0, rx, row_gen, acc);
         } else {
-            if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, false, false, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, 0, rx, row_gen, acc);
-            else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, false, false, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, 0, rx, row_gen, acc);
-            else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, false, false, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, 0, rx, row_gen, acc);
+            if (act == MCPC_ACT_RELU) lean_bwd<1, NW, NTW, MCPC_ACT_RELU, false, false, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, 0, rx, row_gen, acc);
+            else if (act == MCPC_ACT_TANH) lean_bwd<1, NW, NTW, MCPC_ACT_TANH, false, false, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, 0, rx, row_gen, acc);
+            else lean_bwd<1, NW, NTW, MCPC_ACT_IDENTITY, false, false, true, true>(P, ph, lds, nt, 0, LL, t, nullptr, 0, P.err, dead, 0, rx, row_gen, acc);
         }
     }
 }
@@ -129,7 +129,7 @@ __device__ __forceinline__ void u_epilogue(const KParams& P, const KPhase& ph, f
 template <bool MIX>
 __global__ __launch_bounds__(kUThreads, 2) void mcpc_steps_u_kernel(const KParams P) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int CTT = 1, NW = kUWaves, NTW = kUNT;
+    constexpr int NW = kUWaves, NTW = kUNT;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -147,20 +147,20 @@ __global__ __launch_bounds__(kUThreads, 2) void mcpc_steps_u_kernel(const KParam
     float* const rx = lds + P.lds_rowexp;
     for (int l = 0; l < L; ++l) {
         const KLayer& Ly = P.layer[l];
-        if (Ly.act == MCPC_ACT_RELU) ws2_fill_fx<MCPC_ACT_RELU>(Ly, lds, chain0, tid, 16, true, rx, rowexp_fx(l));
-        else if (Ly.act == MCPC_ACT_TANH) ws2_fill_fx<MCPC_ACT_TANH>(Ly, lds, chain0, tid, 16, true, rx, rowexp_fx(l));
-        else ws2_fill_fx<MCPC_ACT_IDENTITY>(Ly, lds, chain0, tid, 16, true, rx, rowexp_fx(l));
+        if (Ly.act == MCPC_ACT_RELU) ws2_fill_fx<MCPC_ACT_RELU>(Ly, lds, chain0, tid, true, rx, rowexp_fx(l));
+        else if (Ly.act == MCPC_ACT_TANH) ws2_fill_fx<MCPC_ACT_TANH>(Ly, lds, chain0, tid, true, rx, rowexp_fx(l));
+        else ws2_fill_fx<MCPC_ACT_IDENTITY>(Ly, lds, chain0, tid, true, rx, rowexp_fx(l));
     }
-    ws2_fill_constants(P, lds, chain0, tid, 16);
+    ws2_fill_constants(P, lds, chain0, tid);
     __syncthreads();
 
     const bool clk_wave = P.clk != nullptr && blockIdx.x == 0 && w == 0;
     unsigned long long clk_c0 = 0, clk_w0 = 0;
     if (clk_wave) { clk_c0 = __builtin_amdgcn_s_memtime(); clk_w0 = __builtin_amdgcn_s_memrealtime(); }
-    LeanLane<CTT> LL;
+    LeanLane LL;
     LL.c = c; LL.q = q;
-    LL.chain[0] = (uint32_t)(chain0 + c); LL.lrow[0] = (uint32_t)c;
-    LL.livem[0] = chain0 + c < P.B ? ~0u : 0u;
+    LL.chain = (uint32_t)(chain0 + c); LL.lrow = (uint32_t)c;
+    LL.livem = chain0 + c < P.B ? ~0u : 0u;
     const bool has_head = P.has_head != 0;
     const bool ybin = has_head && *P.head.y_binary != 0;
     const bool y_bounded = has_head && *P.head.y_bounded != 0;      // (headb_fixed_exp: the bound target lies in [-1, 2])
@@ -171,9 +171,8 @@ __global__ __launch_bounds__(kUThreads, 2) void mcpc_steps_u_kernel(const KParam
     const bool no_loss = has_head && P.head.loss_kind == MCPC_LOSS_NONE;
     const bool e0_in_regs = P.layer[0].ntiles <= NW;
     bool e0_dirty = false;
-    f32x4 e0acc[CTT];
-    e0acc[0] = splat(0.f);
-    if (e0_in_regs && t_first + P.n_steps > P.acc_begin && t_first < P.acc_end) lean_load_e0<CTT>(P, w, LL, e0acc);
+    f32x4 e0acc = splat(0.f);
+    if (e0_in_regs && t_first + P.n_steps > P.acc_begin && t_first < P.acc_end) lean_load_e0(P, w, LL, e0acc);
 
     // the exponents the packed weights were scaled by (one per Linear), once: lane j of a VGPR holds Linear j's -- a v_readlane per GEMM
     // where a scalar load from device memory sat in front of every GEMM's first block (its latency exposed: the exponent is needed at once)
@@ -212,9 +211,9 @@ __global__ __launch_bounds__(kUThreads, 2) void mcpc_steps_u_kernel(const KParam
             const int nt = nt_next;
             const int pn = p + 1 < n_ent ? p + 1 : 0;
             if (pn != 0 || s + 1 < P.n_steps) ph_next = load_phase(tab, pn);
-            f32x4 acc[NTW][CTT];
+            f32x4 acc[NTW];
 #pragma unroll
-            for (int i = 0; i < NTW; ++i) acc[i][0] = splat(0.f);
+            for (int i = 0; i < NTW; ++i) acc[i] = splat(0.f);
             STAMP(0);
             // level boundary: what this level reads is complete, what it writes is no longer read
             if (ph.flags & PHF_SYNC) {
@@ -233,7 +232,7 @@ __global__ __launch_bounds__(kUThreads, 2) void mcpc_steps_u_kernel(const KParam
                 for (int i = 0; i < NTW; ++i) {
                     const int tile = ph.tile0 + ph.rot * (i < nt ? i : 0);
                     ywreg[i] = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t*>(
-                        (gbytes_t)P.head.ybits + mul24(LL.chain[0], 4u * (uint32_t)P.head.ywords) + 4u * (uint32_t)(tile >> 1));
+                        (gbytes_t)P.head.ybits + mul24(LL.chain, 4u * (uint32_t)P.head.ywords) + 4u * (uint32_t)(tile >> 1));
                 }
             }
             if (live && (ph.flags & PHF_WS_GEMM) && ph.nkb > 0) {
@@ -276,13 +275,13 @@ __global__ __launch_bounds__(kUThreads, 2) void mcpc_steps_u_kernel(const KParam
     // every wave's last x update is in LDS (and its partial energy sums)
     u_barrier();
     if (energy_prev && w == 0) u_energy_row(P, lds, P.n_steps - 1, t_first + P.n_steps - 1, unit, lane, L, has_head);
-    lean_store_x<CTT, NW>(P, lds, w, LL);                       // the state of this wave's tiles goes back to global memory
+    lean_store_x<1, NW>(P, lds, w, LL);                       // the state of this wave's tiles goes back to global memory
     spill_max_publish(P.spillmax, lds + P.lds_spillmax, lane);
     if (clk_wave && lane == 0) {
         atomicAdd(P.clk, __builtin_amdgcn_s_memtime() - clk_c0);
         atomicAdd(P.clk + 1, __builtin_amdgcn_s_memrealtime() - clk_w0);
     }
-    if (e0_in_regs && e0_dirty) lean_flush_e0<CTT>(P, w, LL, e0acc);
+    if (e0_in_regs && e0_dirty) lean_flush_e0(P, w, LL, e0acc);
 #ifdef MCPC_STAMPS
     if (lane == 0 && P.dbg != nullptr)
         for (int i = 0; i < 16; ++i) P.dbg[((size_t)blockIdx.x * kUWaves + w) * 16 + i] = st_sum[i];

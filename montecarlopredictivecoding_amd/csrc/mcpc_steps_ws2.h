@@ -46,7 +46,7 @@ constexpr int kWs2NT = MCPC_WS2_SPAN / kWs2Pairs;   // unit tiles per pair per t
 #ifndef MCPC_WS2_NT16
 #define MCPC_WS2_NT16 kWs2NT
 #endif
-template <int CTT> constexpr int ws2_nt() { return MCPC_WS2_NT16; }
+constexpr int kWs2NTW = MCPC_WS2_NT16;
 constexpr int kWs2Threads = 2 * kWs2Pairs * 64;
 static_assert(kWs2Pairs == 4 || kWs2Pairs == 8, "4 or 8 pairs");
 
@@ -135,10 +135,10 @@ __device__ __forceinline__ void ws2_prefetch(const KPhase& ph, int k, int lane, 
 }
 
 template <int ACT>
-__device__ __forceinline__ void ws2_fill_fx(const KLayer& Ly, float* lds, int chain0, int tid, int ct_rows, bool keep_x,
+__device__ __forceinline__ void ws2_fill_fx(const KLayer& Ly, float* lds, int chain0, int tid, bool keep_x,
                                             float* lds_rowexp = nullptr, int row_id = 0) {
     const int qpr = Ly.npad / 4;                            // quads per row
-    for (int idx = tid; idx < ct_rows * qpr; idx += kWs2Threads) {
+    for (int idx = tid; idx < 16 * qpr; idx += kWs2Threads) {
         const int r = idx / qpr, u0 = 4 * (idx - r * qpr);
         const f32x4 x = ld4s(Ly.x + (size_t)(chain0 + r) * Ly.npad + u0);
         const f32x4 fx = act4<ACT>(x);
@@ -151,7 +151,7 @@ __device__ __forceinline__ void ws2_fill_fx(const KLayer& Ly, float* lds, int ch
 
 // KParams::xl: what the epilogues of a launch read over and over and nobody else writes -- biases, the mu_1 rows and the bit-packed
 // target rows of the workgroup's chains -- copied to LDS once (the state rows X_l: ws2_fill_fx)
-__device__ __forceinline__ void ws2_fill_constants(const KParams& P, float* lds, int chain0, int tid, int ct_rows) {
+__device__ __forceinline__ void ws2_fill_constants(const KParams& P, float* lds, int chain0, int tid) {
     for (int l = 1; l < P.L; ++l) {
         const KLayer& Ly = P.layer[l];
         for (int i = tid; i < Ly.npad / 4; i += kWs2Threads) st4(lds + Ly.lds_bias + 4 * i, ld4(Ly.bias + 4 * i));
@@ -159,7 +159,7 @@ __device__ __forceinline__ void ws2_fill_constants(const KParams& P, float* lds,
     {
         const KLayer& Ly = P.layer[0];
         const int qpr = Ly.npad / 4;
-        for (int idx = tid; idx < ct_rows * qpr; idx += kWs2Threads) {
+        for (int idx = tid; idx < 16 * qpr; idx += kWs2Threads) {
             const int r = idx / qpr, u0 = 4 * (idx - r * qpr);
             st4(lds + Ly.lds_bias + r * Ly.ld + u0, ld4(P.mu1 + (size_t)(chain0 + r) * Ly.npad + u0));
         }
@@ -169,7 +169,7 @@ __device__ __forceinline__ void ws2_fill_constants(const KParams& P, float* lds,
         for (int i = tid; i < H.npad / 4; i += kWs2Threads) st4(lds + H.lds_bias + 4 * i, ld4(H.bias + 4 * i));
         if (H.lds_yw >= 0) {
             uint32_t* const yw = reinterpret_cast<uint32_t*>(lds + H.lds_yw);
-            for (int idx = tid; idx < ct_rows * H.ywords; idx += kWs2Threads) {
+            for (int idx = tid; idx < 16 * H.ywords; idx += kWs2Threads) {
                 const int r = idx / H.ywords, w = idx - r * H.ywords;
                 yw[idx] = H.ybits[(size_t)(chain0 + r) * H.ywords + w];
             }
@@ -191,8 +191,8 @@ __device__ __forceinline__ float* vreg(float* s) {
 // HEADF epilogue of the E waves: headf_epilogue (mcpc_kernels.h) with its uniforms in VGPRs
 template <int CTT, int NW, int NTW>
 __device__ __forceinline__ float ws2_headf_epilogue(const KParams& P, const KPhase& ph, float* lds, int nt, int wave, int lane,
-                                                    int chain0, const f32x4 (&acc)[NTW][CTT], const f32x4 (&pa)[NTW][CTT],
-                                                    const f32x4 (&pb)[NTW][CTT], int slot, int rec_idx, bool do_energy) {
+                                                    int chain0, const f32x4 (&acc)[NTW], const f32x4 (&pa)[NTW],
+                                                    const f32x4 (&pb)[NTW], int slot, int rec_idx, bool do_energy) {
     const KHead& H = P.head;
     const int c = lane & 15, q = lane >> 4;
     const int kind = H.loss_kind;
@@ -212,10 +212,10 @@ __device__ __forceinline__ float ws2_headf_epilogue(const KParams& P, const KPha
         for (int ct = 0; ct < CTT; ++ct) {
             const int cl = 16 * ct + c, chain = chain0 + cl;
             const bool live = chain < B;
-            const f32x4 o = acc[i][ct] + pb[i][ct];
+            const f32x4 o = acc[i] + pb[i];
             f32x4 e = splat(0.f);
             if (kind != MCPC_LOSS_NONE) {
-                const f32x4 y = pa[i][ct];
+                const f32x4 y = pa[i];
                 MCPC_READOUT_LOSS4(e, o, y, kind, do_energy, inv_var, lsum, live && (u0 + r) >= mask_start && (u0 + r) < n, true);
             }
             st4(lds + eo_off + cl * ld + (u0 - tile0x16), e);
@@ -233,7 +233,7 @@ __device__ __forceinline__ float ws2_headf_epilogue(const KParams& P, const KPha
 // One definition serves every instantiation (mcpc_steps_ws2_kernel.inc: launch bounds, LDS declaration, the body's macros), included
 // once per kernel name with WS2_KERNEL_TEMPLATE / WS2_KERNEL_NAME / WS2_MODE set.
 // The GENERIC kernel: every decision of a launch is a run-time value of KParams (WS2_MODE = Ws2Generic).
-#define WS2_KERNEL_TEMPLATE template <int CTT, bool MIX = false>
+#define WS2_KERNEL_TEMPLATE template <int CTT, bool MIX = false>           // CTT: part of the symbol, always 1; the body hands it on only to the epilogues and loops that still take it
 #define WS2_KERNEL_NAME mcpc_steps_ws2_kernel
 #define WS2_MODE Ws2Generic
 #include "mcpc_steps_ws2_kernel.inc"
@@ -241,7 +241,7 @@ __device__ __forceinline__ float ws2_headf_epilogue(const KParams& P, const KPha
 // the paths not taken and the SGPR spills they cause are gone; the floating-point operations and their order are the generic kernel's.
 // A kernel of its own name, so that a trace tells the instantiations apart and the generic kernel's two symbols stay what they were.
 // The instantiations the library holds are listed ONCE, in kWs2Specs below; ws2_select_mode (mcpc_api.hip) picks one per launch.
-#define WS2_KERNEL_TEMPLATE template <class MODE, int CTT, bool MIX = false>
+#define WS2_KERNEL_TEMPLATE template <class MODE, int CTT, bool MIX = false>      // CTT: as above
 #define WS2_KERNEL_NAME mcpc_steps_ws2_spec_kernel
 #define WS2_MODE MODE
 #include "mcpc_steps_ws2_kernel.inc"

@@ -1,17 +1,17 @@
 // Body of a workgroup of the in-place wave-specialised step kernel: included as the body of mcpc_steps_ws2_kernel (WS2_BLOCK =
 // blockIdx.x: the kernels of the plain schedule compile exactly as they did as stand-alone kernels) and twice inside
-// mcpc_steps_ws2_mixed_kernel (one block per workgroup form).  Expects: CTT, MIX, P, lds, WS2_BLOCK, WS2_NBLOCKS, and WS2_MODE: the
+// mcpc_steps_ws2_mixed_kernel (one block per workgroup form).  Expects: CTT (always 1), MIX, P, lds, WS2_BLOCK, WS2_NBLOCKS, and WS2_MODE: the
 // launch's compile-time mode (mcpc_ws2_lean.h: Ws2Mode) -- a field other than kModeDyn replaces the run-time test below by its value.
     using M = WS2_MODE;
-    constexpr int NW = kWs2Pairs, NTW = ws2_nt<CTT>();
+    constexpr int NW = kWs2Pairs, NTW = kWs2NTW;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool is_g = wave8 < kWs2Pairs;                   // waves 0..NW-1 and NW..2NW-1 both spread evenly over the 4 SIMDs
     const int k = wave8 & (kWs2Pairs - 1);                 // pair id
     const int c = lane & 15, q = lane >> 4;
-    const int unit = MIX ? P.wg_list[WS2_BLOCK] : (int)WS2_BLOCK;             // pair of chain tiles (CTT = 2) or single tile
-    const int chain0 = unit * (16 * CTT);
+    const int unit = MIX ? P.wg_list[WS2_BLOCK] : (int)WS2_BLOCK;             // the workgroup's MFMA column tile of 16 chains
+    const int chain0 = unit * 16;
     // first step of this unit in this launch (round schedule: a unit takes part in m of the k launches of a cycle and carries the
     // number it has already run)
     const int t_first = MIX ? P.t0 + P.wg_rel[WS2_BLOCK] * P.rr_q : P.t0;
@@ -31,22 +31,22 @@
     const bool lean_adam = M::UPD != kModeDyn ? M::UPD == WS2_UPD_ADAM : P.update_x && P.xopt == MCPC_XOPT_ADAM && P.noise_mode == MCPC_NOISE_NONE;
     const bool lean = M::UPD != kModeDyn || ((upd_mode != 0 || lean_adam) && chain0 < P.B && P.lean_ok);       // (padding chains of a last workgroup: LeanLane::livem)
     // the lean epilogues of a plan with the room keep the state (and what else they read every step) in LDS for the whole launch
-    const bool xl = M::XL != kModeDyn ? M::XL != 0 : CTT == 1 && lean && P.xl != 0;
+    const bool xl = M::XL != kModeDyn ? M::XL != 0 : lean && P.xl != 0;
     // lean epilogues keep the exponent of every B row they write (mcpc_kernels.h: rowexp_track): the GEMM waves then scan no row
 #ifdef MCPC_EXP_NOLEAN
     const bool rowexp = false;
 #else
-    const bool rowexp = M::ROWEXP != kModeDyn ? M::ROWEXP != 0 : CTT == 1 && lean;
+    const bool rowexp = M::ROWEXP != kModeDyn ? M::ROWEXP != 0 : lean;
 #endif
     float* const rx = rowexp ? lds + P.lds_rowexp : nullptr;
     // f(x_l) of the state the launch starts from; afterwards the x updates keep FX_l current
     for (int l = 0; l < L; ++l) {
         const KLayer& Ly = P.layer[l];
-        if (M::act(Ly.act) == MCPC_ACT_RELU) ws2_fill_fx<MCPC_ACT_RELU>(Ly, lds, chain0, tid, 16 * CTT, xl, rx, rowexp_fx(l));
-        else if (M::act(Ly.act) == MCPC_ACT_TANH) ws2_fill_fx<MCPC_ACT_TANH>(Ly, lds, chain0, tid, 16 * CTT, xl, rx, rowexp_fx(l));
-        else ws2_fill_fx<MCPC_ACT_IDENTITY>(Ly, lds, chain0, tid, 16 * CTT, xl, rx, rowexp_fx(l));
+        if (M::act(Ly.act) == MCPC_ACT_RELU) ws2_fill_fx<MCPC_ACT_RELU>(Ly, lds, chain0, tid, xl, rx, rowexp_fx(l));
+        else if (M::act(Ly.act) == MCPC_ACT_TANH) ws2_fill_fx<MCPC_ACT_TANH>(Ly, lds, chain0, tid, xl, rx, rowexp_fx(l));
+        else ws2_fill_fx<MCPC_ACT_IDENTITY>(Ly, lds, chain0, tid, xl, rx, rowexp_fx(l));
     }
-    if (xl) ws2_fill_constants(P, lds, chain0, tid, 16 * CTT);
+    if (xl) ws2_fill_constants(P, lds, chain0, tid);
     __syncthreads();                                       // the only barrier
 
     if (is_g) {
@@ -73,11 +73,9 @@
 #endif
         for (int s = 0; s < P.n_steps; ++s) {
             const int base = s * n_ent;
-            f32x4 accb[NTW][CTT];                       // back-projection of the read-out error: 16 tiles over the pairs
+            f32x4 accb[NTW];                       // back-projection of the read-out error: 16 tiles over the pairs
 #pragma unroll
-            for (int i = 0; i < NTW; ++i)
-#pragma unroll
-                for (int ct = 0; ct < CTT; ++ct) accb[i][ct] = splat(0.f);
+            for (int i = 0; i < NTW; ++i) accb[i] = splat(0.f);
             int accb_run = kRunNone, accb_aexp = 0;      // the units accb is in (mcpc_gemm_f16.h: GemmScale); per lane = per chain
 #pragma unroll 1
             for (;;) {
@@ -91,11 +89,9 @@
                 const bool is_headb = ph.type == PH_HEADB;
                 const bool works = true;                                            // (only such entries are visited)
                 const bool stores = !is_headb;
-                f32x4 acc[NTW][CTT];
+                f32x4 acc[NTW];
 #pragma unroll
-                for (int i = 0; i < NTW; ++i)
-#pragma unroll
-                    for (int ct = 0; ct < CTT; ++ct) acc[i][ct] = splat(0.f);
+                for (int i = 0; i < NTW; ++i) acc[i] = splat(0.f);
                 STAMP(0);
 #ifdef MCPC_STAMPS_ENTRY
                 const unsigned long long ge0 = mcpc_stamp();
@@ -115,17 +111,15 @@
                             const int fixed_b = hb_word ? rowexp_read(rx, ph.b_row, c) : hb_exp;
                             GemmScale gs{load_wexp(P.wexp, ph.a_lin), GS_ACCUM, fixed_b, accb_run,
                                          P.head.npad <= kShortK * kKB ? 1 : 0, (hb_exp == kScaleAuto && !hb_word) ? 1 : 0};
-                            gemm_tiles<NTW, CTT, NW>(accb, ph.A, aoff, nt, ph.nkb, ph.kw, lds + ph.b_lds, ph.ldb, lane, pre0, lds + P.lds_zero, gs);
+                            gemm_tiles<NTW, NW>(accb, ph.A, aoff, nt, ph.nkb, ph.kw, lds + ph.b_lds, ph.ldb, lane, pre0, lds + P.lds_zero, gs);
                             accb_run = gs.run; accb_aexp = gs.a_exp;
                         }
                         STAMP(2);
                     } else {
                         if (handoff) {
 #pragma unroll
-                            for (int i = 0; i < NTW; ++i)
-#pragma unroll
-                                for (int ct = 0; ct < CTT; ++ct) acc[i][ct] = accb[i][ct];     // one entry covers all of accb
-                            if (accb_run != kRunNone) gemm_unscale<NTW, CTT>(acc, accb_aexp, accb_run);      // (the hand-off entry has no GEMM of its own)
+                            for (int i = 0; i < NTW; ++i) acc[i] = accb[i];     // one entry covers all of accb
+                            if (accb_run != kRunNone) gemm_unscale<NTW>(acc, accb_aexp, accb_run);      // (the hand-off entry has no GEMM of its own)
                         }
                         if (nt > 0 && ph.nkb > 0 MCPC_EXP_GEMM_GATE) {
                             // the row's exponent: from its producers' word (lean epilogues), else scanned by gemm_tiles
@@ -133,7 +127,7 @@
                             const bool has_word = rowexp && ph.b_row >= 0;
                             const int fixed_b = has_word ? rowexp_read(rx, ph.b_row, c) : kScaleAuto;
                             GemmScale gs{load_wexp(P.wexp, ph.a_lin), GS_FRESH, fixed_b, kRunNone, -1, has_word ? 0 : 1};
-                            gemm_tiles<NTW, CTT, NW>(acc, ph.A, aoff, nt, ph.nkb, ph.kw, lds + ph.b_lds, ph.ldb, lane, pre0, lds + P.lds_zero, gs);
+                            gemm_tiles<NTW, NW>(acc, ph.A, aoff, nt, ph.nkb, ph.kw, lds + ph.b_lds, ph.ldb, lane, pre0, lds + P.lds_zero, gs);
                         }
                         STAMP(3);
                     }
@@ -162,8 +156,7 @@
                     for (int i = 0; i < NTW; ++i) {
                         if (i >= ntw) continue;
                         const int col = col0 + 16 * (kk + NW * i) + 4 * q;
-#pragma unroll
-                        for (int ct = 0; ct < CTT; ++ct) st4(out + (16 * ct + c) * ph.out_ld + col, acc[i][ct]);
+                        st4(out + c * ph.out_ld + col, acc[i]);
                     }
                 }
                 if (lane == 0) ws_publish(&sync->prog_g[k], base + p + 1);
@@ -194,23 +187,25 @@
     const bool clk_wave = P.clk != nullptr && WS2_BLOCK == 0 && k == 0;
     unsigned long long clk_c0 = 0, clk_w0 = 0;
     if (clk_wave) { clk_c0 = __builtin_amdgcn_s_memtime(); clk_w0 = __builtin_amdgcn_s_memrealtime(); }
-    LeanLane<CTT> LL;
+    LeanLane LL;
     LL.c = c; LL.q = q;
+    // (CTT is 1.  The one-trip `ct` loops left in this body and in the epilogues are the ones without which the compiled kernels change:
+    // profiles/ctt_removal_asm.txt)
 #pragma unroll
     for (int ct = 0; ct < CTT; ++ct) {
-        LL.chain[ct] = (uint32_t)(chain0 + 16 * ct + c); LL.lrow[ct] = (uint32_t)(16 * ct + c);
+        LL.chain = (uint32_t)(chain0 + 16 * ct + c); LL.lrow = (uint32_t)(16 * ct + c);
         const bool live = chain0 + 16 * ct + c < P.B;
-        LL.livem[ct] = live ? ~0u : 0u;
+        LL.livem = live ? ~0u : 0u;
     }
     // 0/1 targets are read bit-packed (a wave-uniform flag the library set when the target was bound)
     const bool ybin = M::HEAD != kModeDyn ? M::HEAD == WS2_HEAD_BERNOULLI_BITS : lean && P.has_head && *P.head.y_binary != 0;
     // sum_t e_1 of this launch in registers (lean path, top layer of at most one tile per wave, rot == 0 for FWD entries)
     const bool e0_in_regs = lean && P.layer[0].ntiles <= NW;
     bool e0_dirty = false;
-    f32x4 e0acc[CTT];
+    f32x4 e0acc;
 #pragma unroll
-    for (int ct = 0; ct < CTT; ++ct) e0acc[ct] = splat(0.f);
-    if (e0_in_regs && (M::SPILL != kModeDyn ? M::SPILL != WS2_SPILL_OFF : t_first + P.n_steps > P.acc_begin && t_first < P.acc_end)) lean_load_e0<CTT>(P, k, LL, e0acc);   // (a launch that accumulates)
+    for (int ct = 0; ct < CTT; ++ct) e0acc = splat(0.f);
+    if (e0_in_regs && (M::SPILL != kModeDyn ? M::SPILL != WS2_SPILL_OFF : t_first + P.n_steps > P.acc_begin && t_first < P.acc_end)) lean_load_e0(P, k, LL, e0acc);   // (a launch that accumulates)
     STAMP_DECL
     for (int s = 0; s < P.n_steps; ++s) {
         const int t = t_first + s;
@@ -250,11 +245,9 @@
                             for (int w = 0; w < kWs2Pairs; ++w) v += (double)red[lane * kMaxWaves + w];
                         }
                         const int erow = (P.energy_mode == MCPC_ENERGY_ALL) ? t : 0;
-                        // a row has one slot per 16-chain tile: a 32-chain workgroup writes the slot of its first tile and
-                        // clears the other (a 16-chain workgroup may have written it for the same step of an earlier call)
-                        double* const ep = P.epart + ((size_t)erow * P.epart_slots + (size_t)unit * CTT) * (kMaxLatent + 1) + lane;
+                        // a row has one slot per 16-chain tile, and a workgroup is one such tile: every slot has exactly one writer
+                        double* const ep = P.epart + ((size_t)erow * P.epart_slots + (size_t)unit) * (kMaxLatent + 1) + lane;
                         ep[0] = v;
-                        if (CTT == 2) ep[kMaxLatent + 1] = 0.0;
                     }
                 }
                 continue;
@@ -284,12 +277,12 @@
                 if (ph.type == PH_FWD) {
                     float esum;
                     if (ph.layer == 0 && M::spills(slot)) e0_dirty = true;
-                    if constexpr (CTT == 1) {
-                        if (xl) {
-                            if (act == MCPC_ACT_RELU) esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_RELU, true, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
-                            else if (act == MCPC_ACT_TANH) esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_TANH, true, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
-                            else esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, true, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
-                        }
+                    // (two `if`s here and a `done` flag in the read-out entry, not if / else: the generic kernel compiles to other code with the
+                    // plain form, like the one-trip `ct` loops that are left -- profiles/ctt_removal_asm.txt)
+                    if (xl) {
+                        if (act == MCPC_ACT_RELU) esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_RELU, true, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
+                        else if (act == MCPC_ACT_TANH) esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_TANH, true, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
+                        else esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, true, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
                     }
                     if (!xl) {
                     if (act == MCPC_ACT_RELU) esum = lean_fwd<CTT, NW, NTW, MCPC_ACT_RELU, false, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, pg, need, P.err, dead, e0acc, e0_in_regs, rx, (unsigned)(s + 1));
@@ -300,36 +293,28 @@
                 } else if (ph.type == PH_HEADF) {
                     float lsum;
                     bool done = false;
-                    if constexpr (CTT == 1) {
-                        if (xl) {
-                            if (ybin) lsum = lean_headf<CTT, NW, NTW, true, true, false, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, do_energy, pg, need, P.err, dead, true, rx);
-                            else lsum = lean_headf<CTT, NW, NTW, true, false, false, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, do_energy, pg, need, P.err, dead, false, rx);
-                            done = true;
-                        }
+                    if (xl) {
+                        if (ybin) lsum = lean_headf<CTT, NW, NTW, true, true, false, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, do_energy, pg, need, P.err, dead, true, rx);
+                        else lsum = lean_headf<CTT, NW, NTW, true, false, false, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, do_energy, pg, need, P.err, dead, false, rx);
+                        done = true;
                     }
                     if (!done) lsum = lean_headf<CTT, NW, NTW, false, false, false, false, M>(P, ph, lds, nt, kk, LL, slot, rec_idx, do_energy, pg, need, P.err, dead, ybin, rx);
                     if (do_energy) { lsum = wave_sum(lsum); if (lane == kMaxLatent) en_acc += lsum; }
                 } else if (ph.type == PH_BWD) {
-                    bool done = false;
-                    if constexpr (CTT == 1) {
-                        if (xl) {
-                            done = true;
-                            if (lean_adam) {
-                                if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, false, true, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
-                                else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, false, true, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
-                                else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, false, true, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
-                            } else if (upd_mode == 2) {
-                                if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, true, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
-                                else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, true, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
-                                else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, true, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
-                            } else {
-                                if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, false, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
-                                else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, false, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
-                                else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, false, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
-                            }
+                    if (xl) {
+                        if (lean_adam) {
+                            if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, false, true, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
+                            else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, false, true, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
+                            else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, false, true, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
+                        } else if (upd_mode == 2) {
+                            if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, true, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
+                            else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, true, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
+                            else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, true, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
+                        } else {
+                            if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, false, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
+                            else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, false, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
+                            else lean_bwd<CTT, NW, NTW, MCPC_ACT_IDENTITY, false, false, true, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, 0, rx, (unsigned)(s + 1));
                         }
-                    }
-                    if (done) {
                     } else if (lean_adam) {
                         if (act == MCPC_ACT_RELU) lean_bwd<CTT, NW, NTW, MCPC_ACT_RELU, false, true, false, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
                         else if (act == MCPC_ACT_TANH) lean_bwd<CTT, NW, NTW, MCPC_ACT_TANH, false, true, false, false, M>(P, ph, lds, nt, kk, LL, t, pg, need, P.err, dead, s_tab, rx, (unsigned)(s + 1));
@@ -352,11 +337,9 @@
                 continue;
             }
 #endif
-            f32x4 acc[NTW][CTT], pa[NTW][CTT], pb[NTW][CTT];
+            f32x4 acc[NTW], pa[NTW], pb[NTW];
 #pragma unroll
-            for (int i = 0; i < NTW; ++i)
-#pragma unroll
-                for (int ct = 0; ct < CTT; ++ct) { acc[i][ct] = splat(0.f); pa[i][ct] = splat(0.f); pb[i][ct] = splat(0.f); }
+            for (int i = 0; i < NTW; ++i) { acc[i] = splat(0.f); pa[i] = splat(0.f); pb[i] = splat(0.f); }
             const KLayer& Ly = P.layer[ph.layer];
             STAMP(8);
             // operands of the epilogue travel while the partner still computes
@@ -378,7 +361,7 @@
                 for (int i = 0; i < NTW; ++i) {
                     const int col = col0 + 16 * (kk + NW * (i < nt ? i : 0)) + 4 * q;     // unused slots re-read slot 0
 #pragma unroll
-                    for (int ct = 0; ct < CTT; ++ct) acc[i][ct] = ld4(src + (16 * ct + c) * ph.out_ld + col);
+                    for (int ct = 0; ct < CTT; ++ct) acc[i] = ld4(src + (16 * ct + c) * ph.out_ld + col);
                 }
             }
 #ifdef MCPC_EXP_NOEPI   // timing experiment only (wrong results): E waves skip the epilogue arithmetic and stores
@@ -406,15 +389,13 @@
 #endif
         }
     }
-    if constexpr (CTT == 1) {
-        if (xl) lean_store_x<CTT, NW>(P, lds, k, LL);          // the state of this wave's tiles goes back to global memory
-    }
+    if (xl) lean_store_x<CTT, NW>(P, lds, k, LL);              // the state of this wave's tiles goes back to global memory
     if constexpr (M::SPILL != WS2_SPILL_OFF) spill_max_publish(P.spillmax, lds + P.lds_spillmax, lane);  // what this workgroup spilled at most, per tensor (every E wave, when it is through)
     if (clk_wave && lane == 0) {
         atomicAdd(P.clk, __builtin_amdgcn_s_memtime() - clk_c0);
         atomicAdd(P.clk + 1, __builtin_amdgcn_s_memrealtime() - clk_w0);
     }
-    if (e0_in_regs && e0_dirty) lean_flush_e0<CTT>(P, k, LL, e0acc);      // (FWD entries have rot == 0: this wave's tile is k)
+    if (e0_in_regs && e0_dirty) lean_flush_e0(P, k, LL, e0acc);      // (FWD entries have rot == 0: this wave's tile is k)
 #ifdef MCPC_STAMPS
     if (lane == 0 && P.dbg != nullptr)
         for (int i = 0; i < 16; ++i) P.dbg[((size_t)WS2_BLOCK * 8 + wave8) * 16 + i] = st_sum[i];

@@ -7,7 +7,7 @@
 // switched off the E waves alone needed 35 us of a 94 us step.  The generic epilogues (mcpc_kernels.h) spend much of
 // their instruction count on things these paths do not need:
 //   * 64-bit per-lane addresses for every access   -> wave-uniform base (SGPR pair) + one 32-bit byte offset per lane:
-//     a row offset per chain tile computed once per entry (v_mul_u32_u24), one v_add per tile;
+//     a row offset computed once per entry (v_mul_u32_u24), one v_add per tile;
 //   * per-element `live` / padding / mask predicates -> padded units and partial loss masks are handled by a wave-uniform branch on
 //     the one tile that has them; padding CHAINS (the last workgroup of a batch that is not a multiple of 16) cost one per-lane mask:
 //     they evolve like any chain, and their energy terms are dropped by a select, their spills ANDed with 0, their records skipped
@@ -101,12 +101,11 @@ struct Ws2Mode {
 using Ws2Generic = Ws2Mode<>;
 
 // per-lane constants of an E wave, fixed for the launch
-template <int CTT>
 struct LeanLane {
     int c, q;
-    uint32_t chain[CTT];       // global row (chain) of this lane in chain tile ct
-    uint32_t lrow[CTT];        // 16 ct + c: row inside the workgroup's LDS images
-    uint32_t livem[CTT];       // ~0u / 0u
+    uint32_t chain;            // global row (chain) of this lane
+    uint32_t lrow;             // c: row inside the workgroup's LDS images
+    uint32_t livem;            // ~0u / 0u: the chain lies inside the batch / is a padding chain
 };
 __device__ __forceinline__ f32x4 mask4(f32x4 v, uint32_t m) {
     f32x4 r;
@@ -116,63 +115,59 @@ __device__ __forceinline__ f32x4 mask4(f32x4 v, uint32_t m) {
 }
 
 // tiles of this wave in an entry: tile(i) = tile0 + kk + NW i, i < nt
+// CTT is always 1 (mcpc_kernels.h: issue_epilogue_loads): the one-trip `ct` loops left below are those the compiled code depends on
 
 // ---- FWD entry (layer l): e_l = c_l (x_l - mu_l), energies, E_l -> LDS, Hebbian spills ------------------------------
 // mu_l = acc (from G, in LDS at out_lds) + bias for l >= 1; the constant mu_1 row for l == 0 (no GEMM).
 // e0acc: Linear 0 sees a constant input, so only sum_t e_1 is needed for its Hebbian sums; when the top layer has at most
 // one tile per wave (n_1 <= 64) the running sum is held in registers for the whole launch (lean_load_e0 / lean_flush_e0)
 // instead of a global read-modify-write in every step.
-// REG (unified-wave kernel, mcpc_steps_u.h): the wave computed the block itself -- it arrives in registers (racc[i][ct], zeros when the entry has
+// REG (unified-wave kernel, mcpc_steps_u.h): the wave computed the block itself -- it arrives in registers (racc[i], zeros when the entry has
 // no GEMM), nothing is waited for and nothing is read from out_lds.
 template <int CTT, int NW, int NTW, int ACT, bool XL = false, bool REG = false, class M = Ws2Generic>
-__device__ __forceinline__ float lean_fwd(const KParams& P, const KPhase& ph, float* lds, int nt, int kk, const LeanLane<CTT>& L,
+__device__ __forceinline__ float lean_fwd(const KParams& P, const KPhase& ph, float* lds, int nt, int kk, const LeanLane& L,
                                           int slot, int rec_idx, const int* prog_g, int need, int* err, int& dead,
-                                          f32x4 (&e0acc)[CTT], bool e0_in_regs, float* rx = nullptr, unsigned row_gen = 0u,
-                                          const f32x4 (*racc)[CTT] = nullptr) {
+                                          f32x4& e0acc, bool e0_in_regs, float* rx = nullptr, unsigned row_gen = 0u,
+                                          const f32x4* racc = nullptr) {
     if (nt <= 0) return 0.f;                  // (a layer with fewer tiles than waves: nothing to load, nothing to wait for)
     const int tstep = REG ? ph.rot : NW;      // tile(i) = tile0 + kk + tstep i: the unified-wave kernel's rows carry their own stride (kk = 0)
     const KLayer& Ly = P.layer[ph.layer];
     const int l = ph.layer;
     const bool has_gemm = (ph.flags & PHF_WS_GEMM) && ph.nkb > 0;
     const uint32_t npad4 = 4u * (uint32_t)Ly.npad;
-    uint32_t rowb[CTT], lrowb[CTT], orowb[CTT];
+    uint32_t rowb, lrowb, orowb;
 #pragma unroll
     for (int ct = 0; ct < CTT; ++ct) {
-        rowb[ct] = mul24(L.chain[ct], npad4) + 16u * L.q;
-        lrowb[ct] = mul24(L.lrow[ct], 4u * (uint32_t)Ly.ld) + 16u * L.q;
-        orowb[ct] = mul24(L.lrow[ct], 4u * (uint32_t)ph.out_ld) + 16u * L.q;
+        rowb = mul24(L.chain, npad4) + 16u * L.q;
+        lrowb = mul24(L.lrow, 4u * (uint32_t)Ly.ld) + 16u * L.q;
+        orowb = mul24(L.lrow, 4u * (uint32_t)ph.out_ld) + 16u * L.q;
     }
-    f32x4 xv[NTW][CTT], bv[NTW][CTT];
+    f32x4 xv[NTW], bv[NTW];
     const float* const bsrc = l == 0 ? P.mu1 : Ly.bias;                  // mu1: a row per chain; bias: one row
 #pragma unroll
     for (int i = 0; i < NTW; ++i) {
         const uint32_t tb = 64u * (uint32_t)(ph.tile0 + kk + tstep * (i < nt ? i : 0));     // unused slots repeat slot 0
-#pragma unroll
-        for (int ct = 0; ct < CTT; ++ct) {
-            if constexpr (XL) {
-                xv[i][ct] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(lds + Ly.lds_x) + lrowb[ct] + tb);
-                bv[i][ct] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(lds + Ly.lds_bias) + (l == 0 ? lrowb[ct] : 16u * L.q) + tb);
-                (void)bsrc;
-            } else {
+        if constexpr (XL) {
+            xv[i] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(lds + Ly.lds_x) + lrowb + tb);
+            bv[i] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(lds + Ly.lds_bias) + (l == 0 ? lrowb : 16u * L.q) + tb);
+            (void)bsrc;
+        } else {
 #if defined(MCPC_EXP_NOX) || defined(MCPC_EXP_NOELOAD)       // timing experiment only (wrong results): the state is neither loaded nor stored
-            xv[i][ct] = splat(0.5f);
+        xv[i] = splat(0.5f);
 #else
-            xv[i][ct] = gld4s(Ly.x, rowb[ct] + tb);
+        xv[i] = gld4s(Ly.x, rowb + tb);
 #endif
 #ifdef MCPC_EXP_NOELOAD   // timing experiment only (wrong results): no operand loads at all in the E waves
-            bv[i][ct] = splat(0.25f); (void)bsrc;
+        bv[i] = splat(0.25f); (void)bsrc;
 #else
-            bv[i][ct] = gld4(bsrc, (l == 0 ? rowb[ct] : 16u * L.q) + tb);
+        bv[i] = gld4(bsrc, (l == 0 ? rowb : 16u * L.q) + tb);
 #endif
-            }
         }
     }
-    f32x4 av[NTW][CTT];
+    f32x4 av[NTW];
     if constexpr (REG) {
 #pragma unroll
-        for (int i = 0; i < NTW; ++i)
-#pragma unroll
-            for (int ct = 0; ct < CTT; ++ct) av[i][ct] = racc[i][ct];
+        for (int i = 0; i < NTW; ++i) av[i] = racc[i];
         (void)has_gemm; (void)prog_g; (void)need; (void)err; (void)dead; (void)orowb;
     } else if (has_gemm) {
         ws_wait_one(prog_g, need, err, dead);
@@ -180,14 +175,11 @@ __device__ __forceinline__ float lean_fwd(const KParams& P, const KPhase& ph, fl
 #pragma unroll
         for (int i = 0; i < NTW; ++i) {
             const uint32_t tb = 64u * (uint32_t)(ph.tile0 + kk + tstep * (i < nt ? i : 0));
-#pragma unroll
-            for (int ct = 0; ct < CTT; ++ct) av[i][ct] = *reinterpret_cast<const f32x4*>(src + orowb[ct] + tb);
+            av[i] = *reinterpret_cast<const f32x4*>(src + orowb + tb);
         }
     } else {
 #pragma unroll
-        for (int i = 0; i < NTW; ++i)
-#pragma unroll
-            for (int ct = 0; ct < CTT; ++ct) av[i][ct] = splat(0.f);
+        for (int i = 0; i < NTW; ++i) av[i] = splat(0.f);
     }
     const float ecoef = Ly.ecoef;
     char* const e_lds = reinterpret_cast<char*>(lds + Ly.lds_e);
@@ -206,33 +198,33 @@ __device__ __forceinline__ float lean_fwd(const KParams& P, const KPhase& ph, fl
         const uint32_t tb = 64u * (uint32_t)tile;
 #pragma unroll
         for (int ct = 0; ct < CTT; ++ct) {
-            const f32x4 x = xv[i][ct];
+            const f32x4 x = xv[i];
             f32x4 d;                                                      // x - mu
-            const f32x4 e = pc_error4(x, av[i][ct] + bv[i][ct], ecoef, d);
-            if (l > 0) { *reinterpret_cast<f32x4*>(e_lds + lrowb[ct] + tb) = e; rmx = absmax4(rmx, e); }
+            const f32x4 e = pc_error4(x, av[i] + bv[i], ecoef, d);
+            if (l > 0) { *reinterpret_cast<f32x4*>(e_lds + lrowb + tb) = e; rmx = absmax4(rmx, e); }
             if (M::spills(slot)) {
 #ifdef MCPC_EXP_SPILL_LINEAR      // timing experiment only (rows permuted inside the workgroup's block): one contiguous KiB per store
-                const uint32_t sb = mul24(L.chain[ct] - (uint32_t)L.c, npad4) + 1024u * (uint32_t)tile + 16u * (uint32_t)(L.c + 16 * L.q);
+                const uint32_t sb = mul24(L.chain - (uint32_t)L.c, npad4) + 1024u * (uint32_t)tile + 16u * (uint32_t)(L.c + 16 * L.q);
 #else
-                const uint32_t sb = rowb[ct] + tb;
+                const uint32_t sb = rowb + tb;
 #endif
                 // tile-major image: (chain's row tile, unit tile) is one contiguous KiB, lane (c, q) its float4 number c + 16 q
-                const uint32_t sb_tm = mul24(L.chain[ct] - (uint32_t)L.c, npad4) + 1024u * (uint32_t)tile + 16u * (uint32_t)(L.c + 16 * L.q);
-                spill_st4(spill_a, img_bytes, Ly.spill_a_tm ? sb_tm : sb, mask4(act4<ACT>(x), L.livem[ct]), sys);
-                amx = absmax4(amx, mask4(act4<ACT>(x), L.livem[ct]));
-                if (l > 0) { spill_st4(spill_e, img_bytes, Ly.spill_e_tm ? sb_tm : sb, mask4(e, L.livem[ct]), sys); emx = absmax4(emx, mask4(e, L.livem[ct])); }
-                else if (e0_in_regs) e0acc[ct] = e0acc[ct] + e;                          // (one tile per wave: i == 0 only)
-                else gst4s(spill_e, rowb[ct] + tb, gld4s(spill_e, rowb[ct] + tb) + e);   // Linear 0: only sum_t e_1 is needed
+                const uint32_t sb_tm = mul24(L.chain - (uint32_t)L.c, npad4) + 1024u * (uint32_t)tile + 16u * (uint32_t)(L.c + 16 * L.q);
+                spill_st4(spill_a, img_bytes, Ly.spill_a_tm ? sb_tm : sb, mask4(act4<ACT>(x), L.livem), sys);
+                amx = absmax4(amx, mask4(act4<ACT>(x), L.livem));
+                if (l > 0) { spill_st4(spill_e, img_bytes, Ly.spill_e_tm ? sb_tm : sb, mask4(e, L.livem), sys); emx = absmax4(emx, mask4(e, L.livem)); }
+                else if (e0_in_regs) e0acc = e0acc + e;                          // (one tile per wave: i == 0 only)
+                else gst4s(spill_e, rowb + tb, gld4s(spill_e, rowb + tb) + e);   // Linear 0: only sum_t e_1 is needed
             }
-            if (rec != nullptr && L.livem[ct]) st_unpadded(rec, (int)L.chain[ct], Ly.n, 16 * tile + 4 * L.q, x);
-            esum += L.livem[ct] ? pc_energy4(d, ecoef) : 0.f;                  // (a select, not a product: whatever a padding chain holds)
+            if (rec != nullptr && L.livem) st_unpadded(rec, (int)L.chain, Ly.n, 16 * tile + 4 * L.q, x);
+            esum += L.livem ? pc_energy4(d, ecoef) : 0.f;                  // (a select, not a product: whatever a padding chain holds)
         }
     }
     if (M::spills(slot)) {
         spill_track(lds + P.lds_spillmax, spill_id_a(l), amx, L.c + 16 * L.q);
         if (l > 0) spill_track(lds + P.lds_spillmax, spill_id_e(l), emx, L.c + 16 * L.q);
     }
-    if (CTT == 1 && M::has_rx(rx) && ph.o_row >= 0) rowexp_track(rx, ph.o_row, L.c, rmx, row_gen);
+    if (M::has_rx(rx) && ph.o_row >= 0) rowexp_track(rx, ph.o_row, L.c, rmx, row_gen);
     return esum;
 }
 
@@ -240,35 +232,31 @@ __device__ __forceinline__ float lean_fwd(const KParams& P, const KPhase& ph, fl
 // before the step loop and WRITTEN back after it: every chain's sum is then one sequential fp32 chain over its steps, whatever the
 // launches a call is cut into (plain segments, the cycles of the round schedule) -- adding a launch's partial sum to the global
 // value instead made the result depend on where the launches end.
-template <int CTT>
-__device__ __forceinline__ void lean_load_e0(const KParams& P, int kk, const LeanLane<CTT>& L, f32x4 (&e0acc)[CTT]) {
+__device__ __forceinline__ void lean_load_e0(const KParams& P, int kk, const LeanLane& L, f32x4& e0acc) {
     const KLayer& Ly = P.layer[0];
     if (kk >= Ly.ntiles) return;
     const uint32_t npad4 = 4u * (uint32_t)Ly.npad;
-#pragma unroll
-    for (int ct = 0; ct < CTT; ++ct) e0acc[ct] = gld4s(Ly.spill_e, mul24(L.chain[ct], npad4) + 16u * L.q + 64u * (uint32_t)kk);
+    e0acc = gld4s(Ly.spill_e, mul24(L.chain, npad4) + 16u * L.q + 64u * (uint32_t)kk);
 }
-template <int CTT>
-__device__ __forceinline__ void lean_flush_e0(const KParams& P, int kk, const LeanLane<CTT>& L, const f32x4 (&e0acc)[CTT]) {
+__device__ __forceinline__ void lean_flush_e0(const KParams& P, int kk, const LeanLane& L, const f32x4& e0acc) {
     const KLayer& Ly = P.layer[0];
     if (kk >= Ly.ntiles) return;
     const uint32_t npad4 = 4u * (uint32_t)Ly.npad;
-#pragma unroll
-    for (int ct = 0; ct < CTT; ++ct) gst4s(Ly.spill_e, mul24(L.chain[ct], npad4) + 16u * L.q + 64u * (uint32_t)kk, e0acc[ct]);
+    gst4s(Ly.spill_e, mul24(L.chain, npad4) + 16u * L.q + 64u * (uint32_t)kk, e0acc);
 }
 
 // XL: after the step loop every E wave writes the state rows of its tiles back (the tiles its BWD entries updated: tile = kk + NW i
 // of every layer; FWD and BWD entries of a layer hand out tiles alike, rot == 0, chunk starts multiples of NW)
 template <int CTT, int NW>
-__device__ __forceinline__ void lean_store_x(const KParams& P, const float* lds, int kk, const LeanLane<CTT>& L) {
+__device__ __forceinline__ void lean_store_x(const KParams& P, const float* lds, int kk, const LeanLane& L) {
     for (int l = 0; l < P.L; ++l) {
         const KLayer& Ly = P.layer[l];
         const uint32_t npad4 = 4u * (uint32_t)Ly.npad;
         for (int tile = kk; tile < Ly.ntiles; tile += NW) {
 #pragma unroll
             for (int ct = 0; ct < CTT; ++ct) {
-                const uint32_t lb = mul24(L.lrow[ct], 4u * (uint32_t)Ly.ld) + 16u * L.q + 64u * (uint32_t)tile;
-                gst4s(Ly.x, mul24(L.chain[ct], npad4) + 16u * L.q + 64u * (uint32_t)tile,
+                const uint32_t lb = mul24(L.lrow, 4u * (uint32_t)Ly.ld) + 16u * L.q + 64u * (uint32_t)tile;
+                gst4s(Ly.x, mul24(L.chain, npad4) + 16u * L.q + 64u * (uint32_t)tile,
                       *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(lds + Ly.lds_x) + lb));
             }
         }
@@ -281,9 +269,9 @@ __device__ __forceinline__ void lean_store_x(const KParams& P, const float* lds,
 // in front of the wait for the partner's block -- the generic epilogue loads them behind it, one L2/HBM round trip exposed
 // per x update (s_tab: row of the bias-correction table).
 template <int CTT, int NW, int NTW, int ACT, bool NOISE, bool ADAM = false, bool XL = false, bool REG = false, class M = Ws2Generic>
-__device__ __forceinline__ void lean_bwd(const KParams& P, const KPhase& ph, float* lds, int nt, int kk, const LeanLane<CTT>& L,
+__device__ __forceinline__ void lean_bwd(const KParams& P, const KPhase& ph, float* lds, int nt, int kk, const LeanLane& L,
                                          int t, const int* prog_g, int need, int* err, int& dead, int s_tab = 0, float* rx = nullptr,
-                                         unsigned row_gen = 0u, const f32x4 (*racc)[CTT] = nullptr) {
+                                         unsigned row_gen = 0u, const f32x4* racc = nullptr) {
     static_assert(!(NOISE && ADAM), "Adam with the fused kick takes the generic epilogue");
     if (nt <= 0) return;
     const int tstep = REG ? ph.rot : NW;
@@ -291,16 +279,16 @@ __device__ __forceinline__ void lean_bwd(const KParams& P, const KPhase& ph, flo
     const int l = ph.layer, n = Ly.n;
     const bool from_g = ((ph.flags & PHF_WS_GEMM) && ph.nkb > 0) || (ph.flags & PHF_WS2_HANDOFF);
     const uint32_t npad4 = 4u * (uint32_t)Ly.npad;
-    uint32_t rowb[CTT], lrowb[CTT], orowb[CTT];
+    uint32_t rowb, lrowb, orowb;
 #pragma unroll
     for (int ct = 0; ct < CTT; ++ct) {
-        rowb[ct] = mul24(L.chain[ct], npad4) + 16u * L.q;
-        lrowb[ct] = mul24(L.lrow[ct], 4u * (uint32_t)Ly.ld) + 16u * L.q;
-        orowb[ct] = mul24(L.lrow[ct], 4u * (uint32_t)ph.out_ld) + 16u * L.q;
+        rowb = mul24(L.chain, npad4) + 16u * L.q;
+        lrowb = mul24(L.lrow, 4u * (uint32_t)Ly.ld) + 16u * L.q;
+        orowb = mul24(L.lrow, 4u * (uint32_t)ph.out_ld) + 16u * L.q;
     }
     const float ecoef = Ly.ecoef;
-    f32x4 xv[NTW][CTT], ev[NTW][CTT];
-    f32x4 mv[ADAM ? NTW : 1][CTT], vv[ADAM ? NTW : 1][CTT];
+    f32x4 xv[NTW], ev[NTW];
+    f32x4 mv[ADAM ? NTW : 1], vv[ADAM ? NTW : 1];
     const char* const e_lds = reinterpret_cast<const char*>(lds + Ly.lds_e);
 #pragma unroll
     for (int i = 0; i < NTW; ++i) {
@@ -308,37 +296,35 @@ __device__ __forceinline__ void lean_bwd(const KParams& P, const KPhase& ph, flo
 #pragma unroll
         for (int ct = 0; ct < CTT; ++ct) {
             if constexpr (XL) {
-                xv[i][ct] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(lds + Ly.lds_x) + lrowb[ct] + tb);
+                xv[i] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(lds + Ly.lds_x) + lrowb + tb);
             } else {
 #if defined(MCPC_EXP_NOX) || defined(MCPC_EXP_NOELOAD)
-            xv[i][ct] = splat(0.5f);
+            xv[i] = splat(0.5f);
 #else
-            xv[i][ct] = gld4s(Ly.x, rowb[ct] + tb);
+            xv[i] = gld4s(Ly.x, rowb + tb);
 #endif
             }
             if constexpr (ADAM) {
                 // (moments are kept tile-major: one contiguous KiB per wave access, tile_major_offset in mcpc_kernels.h)
-                const uint32_t mb = (mul24(L.chain[ct] >> 4, (uint32_t)Ly.ntiles) + (uint32_t)(ph.tile0 + kk + tstep * (i < nt ? i : 0))) * 1024u + 16u * (uint32_t)(L.c + 16 * L.q);
-                mv[i][ct] = gld4s(Ly.m, mb);
-                vv[i][ct] = gld4s(Ly.v, mb);
+                const uint32_t mb = (mul24(L.chain >> 4, (uint32_t)Ly.ntiles) + (uint32_t)(ph.tile0 + kk + tstep * (i < nt ? i : 0))) * 1024u + 16u * (uint32_t)(L.c + 16 * L.q);
+                mv[i] = gld4s(Ly.m, mb);
+                vv[i] = gld4s(Ly.v, mb);
             }
 #ifdef MCPC_EXP_NOELOAD
-            if (l == 0) ev[i][ct] = (xv[i][ct] - splat(0.25f)) * ecoef;
+            if (l == 0) ev[i] = (xv[i] - splat(0.25f)) * ecoef;
 #else
             if (l == 0) {                                                               // e_1 = c_1 (x_1 - mu_1), mu_1 constant
-                if constexpr (XL) ev[i][ct] = (xv[i][ct] - *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(lds + Ly.lds_bias) + lrowb[ct] + tb)) * ecoef;
-                else ev[i][ct] = (xv[i][ct] - gld4(P.mu1, rowb[ct] + tb)) * ecoef;
+                if constexpr (XL) ev[i] = (xv[i] - *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(lds + Ly.lds_bias) + lrowb + tb)) * ecoef;
+                else ev[i] = (xv[i] - gld4(P.mu1, rowb + tb)) * ecoef;
             }
 #endif
-            else if constexpr (!ADAM) ev[i][ct] = *reinterpret_cast<const f32x4*>(e_lds + lrowb[ct] + tb);
+            else if constexpr (!ADAM) ev[i] = *reinterpret_cast<const f32x4*>(e_lds + lrowb + tb);
         }
     }
-    f32x4 av[NTW][CTT];
+    f32x4 av[NTW];
     if constexpr (REG) {       // (unified-wave kernel: the back-projection arrives in registers, zeros when there is none)
 #pragma unroll
-        for (int i = 0; i < NTW; ++i)
-#pragma unroll
-            for (int ct = 0; ct < CTT; ++ct) av[i][ct] = racc[i][ct];
+        for (int i = 0; i < NTW; ++i) av[i] = racc[i];
         (void)from_g; (void)prog_g; (void)need; (void)err; (void)dead; (void)orowb;
     } else if (from_g) {
         ws_wait_one(prog_g, need, err, dead);
@@ -346,14 +332,11 @@ __device__ __forceinline__ void lean_bwd(const KParams& P, const KPhase& ph, flo
 #pragma unroll
         for (int i = 0; i < NTW; ++i) {
             const uint32_t tb = 64u * (uint32_t)(ph.tile0 + kk + tstep * (i < nt ? i : 0));
-#pragma unroll
-            for (int ct = 0; ct < CTT; ++ct) av[i][ct] = *reinterpret_cast<const f32x4*>(src + orowb[ct] + tb);
+            av[i] = *reinterpret_cast<const f32x4*>(src + orowb + tb);
         }
     } else {
 #pragma unroll
-        for (int i = 0; i < NTW; ++i)
-#pragma unroll
-            for (int ct = 0; ct < CTT; ++ct) av[i][ct] = splat(0.f);
+        for (int i = 0; i < NTW; ++i) av[i] = splat(0.f);
     }
     const float sign = ph.sign, lr = P.lr, nscale = P.noise_scale;
     const uint64_t seed = P.seed, step = P.step_base + (uint64_t)t, chain_base = P.chain_base;
@@ -367,20 +350,20 @@ __device__ __forceinline__ void lean_bwd(const KParams& P, const KPhase& ph, flo
         const bool pad_tile = 16 * tile + 16 > n;                  // wave-uniform: only the last tile of a ragged layer
 #pragma unroll
         for (int ct = 0; ct < CTT; ++ct) {
-            const f32x4 x = xv[i][ct], back = av[i][ct];
+            const f32x4 x = xv[i], back = av[i];
             f32x4 e;
             if constexpr (ADAM) {         // (the error rows are read here, not held across the wait: registers go to m and v)
-                if (l == 0) e = ev[i][ct];
-                else e = *reinterpret_cast<const f32x4*>(e_lds + lrowb[ct] + tb);
+                if (l == 0) e = ev[i];
+                else e = *reinterpret_cast<const f32x4*>(e_lds + lrowb + tb);
             } else {
-                e = ev[i][ct];
+                e = ev[i];
             }
             const f32x4 g = x_grad4<ACT>(x, e, back, sign);
             f32x4 xn;
             if constexpr (ADAM) {
-                f32x4 m = mv[i][ct], v = vv[i][ct];
+                f32x4 m = mv[i], v = vv[i];
                 adam_moments4(m, v, g, P.omb1, P.beta2, P.omb2);
-                const uint32_t mb = (mul24(L.chain[ct] >> 4, (uint32_t)Ly.ntiles) + (uint32_t)tile) * 1024u + 16u * (uint32_t)(L.c + 16 * L.q);
+                const uint32_t mb = (mul24(L.chain >> 4, (uint32_t)Ly.ntiles) + (uint32_t)tile) * 1024u + 16u * (uint32_t)(L.c + 16 * L.q);
                 gst4s(Ly.m, mb, m);
                 gst4s(Ly.v, mb, v);
                 xn = adam_x4(x, m, v, P.adam_coef[2 * s_tab], P.adam_coef[2 * s_tab + 1], P.eps);
@@ -388,21 +371,21 @@ __device__ __forceinline__ void lean_bwd(const KParams& P, const KPhase& ph, flo
                 xn = x - g * lr;
             }
             if constexpr (NOISE)
-                xn = xn + normals4(seed, step, (uint32_t)l, (uint32_t)(chain_base + (uint64_t)L.chain[ct]), (uint32_t)(4 * tile + L.q)) * nscale;
+                xn = xn + normals4(seed, step, (uint32_t)l, (uint32_t)(chain_base + (uint64_t)L.chain), (uint32_t)(4 * tile + L.q)) * nscale;
             if (pad_tile) zero_padded4(xn, 16 * tile + 4 * L.q, n);
             if constexpr (XL) {
-                *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(lds + Ly.lds_x) + lrowb[ct] + tb) = xn;
+                *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(lds + Ly.lds_x) + lrowb + tb) = xn;
             } else {
 #ifndef MCPC_EXP_NOX
-            gst4s(Ly.x, rowb[ct] + tb, xn);
+            gst4s(Ly.x, rowb + tb, xn);
 #endif
             }
             const f32x4 fxn = act4<ACT>(xn);
-            *reinterpret_cast<f32x4*>(fx_lds + lrowb[ct] + tb) = fxn;                // the next step's GEMMs read f(x_new) from FX_l
+            *reinterpret_cast<f32x4*>(fx_lds + lrowb + tb) = fxn;                // the next step's GEMMs read f(x_new) from FX_l
             rmx = absmax4(rmx, fxn);
         }
     }
-    if (CTT == 1 && M::has_rx(rx) && ph.o_row >= 0) rowexp_track(rx, ph.o_row, L.c, rmx, row_gen);
+    if (M::has_rx(rx) && ph.o_row >= 0) rowexp_track(rx, ph.o_row, L.c, rmx, row_gen);
 }
 
 // ---- HEADF entry (read-out chunk): out = acc + bias, e_o = dL/dout -> ring slot (LDS), loss, spills, output records -----
@@ -410,9 +393,9 @@ __device__ __forceinline__ void lean_bwd(const KParams& P, const KPhase& ph, flo
 // choice, so that the 0/1 case holds no global load at all (see the note on loads under an `if` below).
 // YWG (with XL, YB, REG): the target words were requested from global memory by the caller, in front of the row's GEMM (ywreg[i])
 template <int CTT, int NW, int NTW, bool XL = false, bool YB = false, bool REG = false, bool YWG = false, class M = Ws2Generic>
-__device__ __forceinline__ float lean_headf(const KParams& P, const KPhase& ph, float* lds, int nt, int kk, const LeanLane<CTT>& L,
+__device__ __forceinline__ float lean_headf(const KParams& P, const KPhase& ph, float* lds, int nt, int kk, const LeanLane& L,
                                             int slot, int rec_idx, bool do_energy, const int* prog_g, int need, int* err, int& dead,
-                                            bool ybin, float* rx = nullptr, const f32x4 (*racc)[CTT] = nullptr, unsigned row_gen = 0u,
+                                            bool ybin, float* rx = nullptr, const f32x4* racc = nullptr, unsigned row_gen = 0u,
                                             bool planes_ok = false, const uint32_t* ywreg = nullptr) {
     if (nt <= 0) return 0.f;
     const int tstep = REG ? ph.rot : NW;
@@ -421,14 +404,14 @@ __device__ __forceinline__ float lean_headf(const KParams& P, const KPhase& ph, 
     const bool planes = REG && planes_ok;
     const int kind = M::loss_kind(H), n = H.n, mask_start = H.mask_start;
     const uint32_t npad4 = 4u * (uint32_t)H.npad;
-    uint32_t rowb[CTT], orowb[CTT];
+    uint32_t rowb, orowb;
 #pragma unroll
     for (int ct = 0; ct < CTT; ++ct) {
-        rowb[ct] = mul24(L.chain[ct], npad4) + 16u * L.q;
-        orowb[ct] = mul24(L.lrow[ct], 4u * (uint32_t)ph.out_ld) + 16u * L.q;
+        rowb = mul24(L.chain, npad4) + 16u * L.q;
+        orowb = mul24(L.lrow, 4u * (uint32_t)ph.out_ld) + 16u * L.q;
     }
-    f32x4 yv[NTW][CTT], bv[NTW];
-    uint32_t yw[NTW][CTT];                                   // ybin: the word of the bit-packed target that holds this lane's four units
+    f32x4 yv[NTW], bv[NTW];
+    uint32_t yw[NTW];                                        // ybin: the word of the bit-packed target that holds this lane's four units
     const uint32_t wrow4 = 4u * (uint32_t)H.ywords;
 #pragma unroll
     for (int i = 0; i < NTW; ++i) {
@@ -446,47 +429,44 @@ __device__ __forceinline__ float lean_headf(const KParams& P, const KPhase& ph, 
 #pragma unroll
         for (int ct = 0; ct < CTT; ++ct) {
             if constexpr (XL && YB && YWG) {
-                yv[i][ct] = splat(0.f);
-                yw[i][ct] = ywreg[i];                 // (i: a compile-time index after unrolling -- the caller's array stays in registers)
+                yv[i] = splat(0.f);
+                yw[i] = ywreg[i];                 // (i: a compile-time index after unrolling -- the caller's array stays in registers)
             } else if constexpr (XL && YB) {
-                yv[i][ct] = splat(0.f);
-                yw[i][ct] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(lds + H.lds_yw) + mul24(L.lrow[ct], wrow4) + 4u * (uint32_t)(tile >> 1));
+                yv[i] = splat(0.f);
+                yw[i] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(lds + H.lds_yw) + mul24(L.lrow, wrow4) + 4u * (uint32_t)(tile >> 1));
             } else if constexpr (XL) {
                 // (an fp32 target is read from its tile-major image: one contiguous KiB per wave access, like Adam's moments)
                 const bool has_y = kind != MCPC_LOSS_NONE;
-                yv[i][ct] = gld4s(has_y ? H.ytile : H.bias,
-                                  has_y ? (mul24(L.chain[ct] >> 4, (uint32_t)H.ntiles) + (uint32_t)tile) * 1024u + 16u * (uint32_t)(L.c + 16 * L.q) : 16u * L.q + tb);
-                yw[i][ct] = 0u;
+                yv[i] = gld4s(has_y ? H.ytile : H.bias,
+                              has_y ? (mul24(L.chain >> 4, (uint32_t)H.ntiles) + (uint32_t)tile) * 1024u + 16u * (uint32_t)(L.c + 16 * L.q) : 16u * L.q + tb);
+                yw[i] = 0u;
             } else {
             // Branch-free on purpose (a load under an `if` makes hipcc join the paths behind `s_waitcnt vmcnt(0)`, which here
             // would also wait for every spill store still in flight): both loads are always issued; the one that is not
             // needed reads a harmless hot address (the bias row again / the word array, which always exists).
 #if defined(MCPC_EXP_NOY) || defined(MCPC_EXP_NOELOAD)        // (timing experiment only, wrong results: targets are not loaded)
-            yv[i][ct] = splat(0.f); yw[i][ct] = 0u;
+            yv[i] = splat(0.f); yw[i] = 0u;
 #else
             const bool fp32_y = kind != MCPC_LOSS_NONE && !ybin;
-            yv[i][ct] = gld4s(fp32_y ? H.y : H.bias, fp32_y ? rowb[ct] + tb : 16u * L.q + tb);
-            yw[i][ct] = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t*>(
-                (gbytes_t)H.ybits + mul24(L.chain[ct], wrow4) + 4u * (uint32_t)(tile >> 1));
+            yv[i] = gld4s(fp32_y ? H.y : H.bias, fp32_y ? rowb + tb : 16u * L.q + tb);
+            yw[i] = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t*>(
+                (gbytes_t)H.ybits + mul24(L.chain, wrow4) + 4u * (uint32_t)(tile >> 1));
 #endif
             }
         }
     }
     char* const eo = reinterpret_cast<char*>(lds + ph.out_lds);
-    f32x4 av[NTW][CTT];
+    f32x4 av[NTW];
     if constexpr (REG) {
 #pragma unroll
-        for (int i = 0; i < NTW; ++i)
-#pragma unroll
-            for (int ct = 0; ct < CTT; ++ct) av[i][ct] = racc[i][ct];
+        for (int i = 0; i < NTW; ++i) av[i] = racc[i];
         (void)prog_g; (void)err; (void)dead;
     } else {
         ws_wait_one(prog_g, need, err, dead);
 #pragma unroll
         for (int i = 0; i < NTW; ++i) {
             const uint32_t cb = 64u * (uint32_t)(kk + tstep * (i < nt ? i : 0));               // column inside the chunk
-#pragma unroll
-            for (int ct = 0; ct < CTT; ++ct) av[i][ct] = *reinterpret_cast<const f32x4*>(eo + orowb[ct] + cb);
+            av[i] = *reinterpret_cast<const f32x4*>(eo + orowb + cb);
         }
     }
     const float inv_var = H.inv_var;
@@ -503,12 +483,12 @@ __device__ __forceinline__ float lean_headf(const KParams& P, const KPhase& ph, 
         const bool inside = 16 * tile >= mask_start && 16 * tile + 16 <= n;        // wave-uniform: every unit of the tile counts
 #pragma unroll
         for (int ct = 0; ct < CTT; ++ct) {
-            const f32x4 o = av[i][ct] + bv[i];
+            const f32x4 o = av[i] + bv[i];
             f32x4 e = splat(0.f);
             if (kind != MCPC_LOSS_NONE) {
-                f32x4 y = yv[i][ct];
+                f32x4 y = yv[i];
                 if (ybin) {                                     // units 16 tile + 4 q .. + 3: a nibble of the word
-                    const uint32_t nib = yw[i][ct] >> (16u * (uint32_t)(tile & 1) + 4u * (uint32_t)L.q);
+                    const uint32_t nib = yw[i] >> (16u * (uint32_t)(tile & 1) + 4u * (uint32_t)L.q);
                     y.x = (float)(nib & 1u); y.y = (float)((nib >> 1) & 1u); y.z = (float)((nib >> 2) & 1u); y.w = (float)((nib >> 3) & 1u);
                 }
                 // a padding chain's error is computed like any chain's; only its share of the loss is dropped (livem)
@@ -516,10 +496,10 @@ __device__ __forceinline__ float lean_headf(const KParams& P, const KPhase& ph, 
                 float ev[4];
                 const int u0 = 16 * tile + 4 * L.q;
                 if (kind == MCPC_LOSS_GAUSSIAN) {
-                    MCPC_LOSS_GAUSSIAN4(ev, ov, yy, inv_var, lsum, inside || ((u0 + r) >= mask_start && (u0 + r) < n), L.livem[ct])
+                    MCPC_LOSS_GAUSSIAN4(ev, ov, yy, inv_var, lsum, inside || ((u0 + r) >= mask_start && (u0 + r) < n), L.livem)
                 } else if (do_energy) {       // (a tile whose every unit counts: a wave-uniform branch instead of a select per unit)
-                    if (inside) { MCPC_LOSS_BERNOULLI_ENERGY4(ev, ov, yy, lsum, true, L.livem[ct]) }
-                    else { MCPC_LOSS_BERNOULLI_ENERGY4(ev, ov, yy, lsum, (u0 + r) >= mask_start && (u0 + r) < n, L.livem[ct]) }
+                    if (inside) { MCPC_LOSS_BERNOULLI_ENERGY4(ev, ov, yy, lsum, true, L.livem) }
+                    else { MCPC_LOSS_BERNOULLI_ENERGY4(ev, ov, yy, lsum, (u0 + r) >= mask_start && (u0 + r) < n, L.livem) }
                 } else {
                     MCPC_LOSS_BERNOULLI_GRAD4(ev, ov, yy, inside || ((u0 + r) >= mask_start && (u0 + r) < n))
                 }
@@ -532,30 +512,30 @@ __device__ __forceinline__ float lean_headf(const KParams& P, const KPhase& ph, 
                 const float sc = pow2i(headb_fixed_exp(MCPC_LOSS_BERNOULLI, true));
                 split2_pair(f32x2{e.x, e.y}, sc, h0, m0);
                 split2_pair(f32x2{e.z, e.w}, sc, h1, m1);
-                char* const gp = eo + (orowb[ct] - 16u * L.q) + cb + 32u * (uint32_t)(L.q >> 1) + 8u * (uint32_t)(L.q & 1);
+                char* const gp = eo + (orowb - 16u * L.q) + cb + 32u * (uint32_t)(L.q >> 1) + 8u * (uint32_t)(L.q & 1);
                 *reinterpret_cast<uint2*>(gp) = make_uint2(h0, h1);
                 *reinterpret_cast<uint2*>(gp + 16) = make_uint2(m0, m1);
             } else {
-                *reinterpret_cast<f32x4*>(eo + orowb[ct] + cb) = e;
+                *reinterpret_cast<f32x4*>(eo + orowb + cb) = e;
             }
             rmx = absmax4(rmx, e);
 #ifdef MCPC_EXP_SPILL_LINEAR
-            if (M::spills(slot)) spill_st4(spill, (uint32_t)P.Bpad * npad4, mul24(L.chain[ct] - (uint32_t)L.c, npad4) + 1024u * (uint32_t)tile + 16u * (uint32_t)(L.c + 16 * L.q), mask4(e, L.livem[ct]), M::spill_sys(P));
+            if (M::spills(slot)) spill_st4(spill, (uint32_t)P.Bpad * npad4, mul24(L.chain - (uint32_t)L.c, npad4) + 1024u * (uint32_t)tile + 16u * (uint32_t)(L.c + 16 * L.q), mask4(e, L.livem), M::spill_sys(P));
 #else
             if (M::spills(slot)) {
                 spill_st4(spill, (uint32_t)P.Bpad * npad4,
-                          H.spill_tm ? mul24(L.chain[ct] - (uint32_t)L.c, npad4) + 1024u * (uint32_t)tile + 16u * (uint32_t)(L.c + 16 * L.q) : rowb[ct] + tb,
-                          mask4(e, L.livem[ct]), M::spill_sys(P));
-                omx = absmax4(omx, mask4(e, L.livem[ct]));
+                          H.spill_tm ? mul24(L.chain - (uint32_t)L.c, npad4) + 1024u * (uint32_t)tile + 16u * (uint32_t)(L.c + 16 * L.q) : rowb + tb,
+                          mask4(e, L.livem), M::spill_sys(P));
+                omx = absmax4(omx, mask4(e, L.livem));
             }
 #endif
-            if (rec != nullptr && L.livem[ct]) st_unpadded(rec, (int)L.chain[ct], H.n, 16 * tile + 4 * L.q, o);
+            if (rec != nullptr && L.livem) st_unpadded(rec, (int)L.chain, H.n, 16 * tile + 4 * L.q, o);
         }
     }
     if (M::spills(slot)) spill_track(lds + P.lds_spillmax, kSpillIdEo, omx, L.c + 16 * L.q);
     // (a ring slot is reused inside a step: its generation is the entry, `need` = entries completed so far)
     // (the unified-wave kernel keeps the whole e_o row in LDS: its chunks of one step combine under the step's generation)
-    if (CTT == 1 && M::has_rx(rx) && ph.o_row >= 0) rowexp_track(rx, ph.o_row, L.c, rmx, REG ? row_gen : (unsigned)need);
+    if (M::has_rx(rx) && ph.o_row >= 0) rowexp_track(rx, ph.o_row, L.c, rmx, REG ? row_gen : (unsigned)need);
     return lsum;
 }
 
