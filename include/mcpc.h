@@ -585,6 +585,41 @@ int mcpc_prediction_errors(mcpc_engine* e, const float* inputs, const float* con
                            double loss_var, int32_t mask_start, float* const* err, float* const* pred, float* err_out, float* pred_out,
                            int32_t max_rows, void* stream);
 
+/* Ancestral samples of the generative model, drawn on the device: x_1 ~ N(mu_1, 1/c_1), x_2 ~ N(mu_2(x_1), 1/c_2), ..., the read-out (the
+ * reference's utils.training_evaluation.sample_pc, which draws on the CPU and runs nn.Linear in torch).  A ROW is one sample; row i has
+ * the global id g = sample_base + i.  n is independent of the engine's batch, as the rows of mcpc_chain_energies are; rows are processed
+ * in chunks of max_rows (0 = default 16384; rounded up to a multiple of 64) through the scratch of mcpc_chain_energies (shared).
+ * Latent layer j = 0 .. n_latent - 1, in this order:
+ *   mu_j = f(x_{j-1}) W_j^T + b_j   mu_0 from `inputs` ([n][n_in], NULL = zeros).  The step kernels' own GEMM on the engine's packed
+ *                                   weights: bitwise what mcpc_prediction_errors writes as pred[j] for the same x_{j-1}.
+ *   x_j  = mu_j + s_j * z           z = the engine's normals for (seed, step, layer j, chain (uint32)g, group u / 4): exactly what
+ *                                   mcpc_philox_normals(device, seed, step, j, sample_base, n, n_j, ...) returns;
+ *                                   s_j = (float)(1 / sqrt((double)ecoef_j)); s_j * z and the sum are two fp32 roundings (no fma).
+ * The prior is the one the energy c * 0.5 (x - mu)^2 implies, variance 1 / c: what unclamped Langevin sampling converges to.  The
+ * reference's sample_pc ignores a custom coefficient (mean + randn); with the default ecoef = 1 the two agree.  Padded units stay zero.
+ * Read-out (n_out > 0): o = f(x_{L-1}) W_L^T + b_L, bitwise pred_out, written to `out` as
+ *   MCPC_SAMPLE_HIDDEN   o (loss_kind and loss_var are not consulted)
+ *   MCPC_SAMPLE_MEAN     MCPC_LOSS_BERNOULLI: sigmoid_f(o), the library's own (MCPC_MOM_SIGMOID);  MCPC_LOSS_GAUSSIAN: o
+ *   MCPC_SAMPLE_DRAW     MCPC_LOSS_BERNOULLI: u < sigmoid_f(o) ? 1.f : 0.f with u = (r >> 8) * 2^-24, r the raw Philox word of (seed, step,
+ *                        layer n_latent, g, unit): the raw != 0 stream of mcpc_philox_normals for layer n_latent;
+ *                        MCPC_LOSS_GAUSSIAN: o + (float)sqrt(loss_var) * z, two roundings, z the normals of layer n_latent.
+ * x_out: NULL, or n_latent pointers, each NULL or unpadded [n][n_j]; out: [n][n_out] or NULL -- the layout of a record: every stateless
+ * reducer of this header takes them as `rec`.  Only the Linears below the last destination asked for are launched.  Destinations need
+ * 4-byte alignment; one that is 16-byte aligned with a width that is a multiple of 4 is written with 16-byte stores.  Nothing is written
+ * beyond row n or unit n_j.  A sample depends on (seed, step, g), the weights and its input row alone: not on n, max_rows, on how a
+ * caller splits [sample_base, sample_base + n) over calls or devices, or on the engine's form.  The engine's state, sums and bound
+ * pointers are untouched; no target is needed.  Asynchronous on `stream` but for the growth of the scratch.  n = 0 launches nothing.
+ * MCPC_EINVAL, before any launch: null engine, n < 0, sample_base + n > 2^32 (the generator's chain word is 32 bits), max_rows < 0,
+ * unknown readout or loss_kind, out on an engine without a read-out, out and every x_out[j] NULL, and for a wanted `out`: MEAN or DRAW
+ * with MCPC_LOSS_NONE, DRAW / Gaussian with loss_var <= 0.  (An ecoef_j <= 0 never reaches the call: mcpc_create refuses it.)
+ * MCPC_ESTATE: parameters of a Linear the call runs not bound. */
+#define MCPC_SAMPLE_HIDDEN 0   /* the read-out as it is: logits / means (sample_pc(is_return_hidden=True)) */
+#define MCPC_SAMPLE_MEAN   1   /* Bernoulli: sigmoid_f(o), the library's own; Gaussian: o */
+#define MCPC_SAMPLE_DRAW   2   /* a draw from the sensory distribution */
+int mcpc_sample_prior(mcpc_engine* e, const float* inputs, int64_t n, uint64_t seed, uint64_t step, uint64_t sample_base,
+                      int32_t loss_kind, double loss_var, int32_t readout, float* const* x_out, float* out, int32_t max_rows,
+                      void* stream);
+
 /* Synchronise `stream` and report device-side faults of the runs issued so far (the wave-specialised step kernel
  * bounds every intra-workgroup wait; a wait that runs out is recorded instead of hanging the GPU).
  * Returns MCPC_ESTATE if the last results must not be used.  The only call besides create/destroy that

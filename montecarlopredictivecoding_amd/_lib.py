@@ -24,6 +24,7 @@ ACOV_MAX_LAG = 64
 PROBE_MAX_CLASSES = 64
 PROBE_IDENTITY, PROBE_SIGMOID, PROBE_SOFTMAX = 0, 1, 2
 KNN_MAX_DIM, KNN_MAX_K = 32, 4
+SAMPLE_HIDDEN, SAMPLE_MEAN, SAMPLE_DRAW = 0, 1, 2
 
 # MCPC_LIB: developer override to load a diagnostic build (e.g. libmcpc_stamps.so) or a `make variant` A/B library; a library that
 # reports exp=1 (built with a timing-experiment switch: wrong results on purpose) is refused unless MCPC_ALLOW_EXP=1
@@ -134,6 +135,8 @@ SYMBOLS = {
                                       C.c_void_p, C.c_int32, C.c_void_p]),
     "mcpc_prediction_errors": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_int32,
                                          C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "mcpc_sample_prior": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_double, C.c_int32,
+                                    C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_void_p]),
     "mcpc_query": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                              C.POINTER(C.c_int32)]),
     "mcpc_step_kernel_name": (C.c_char_p, [C.c_void_p]),

@@ -26,6 +26,7 @@
 #include "mcpc_plan.h"
 #include "mcpc_chain_energy.h"
 #include "mcpc_pred_err.h"
+#include "mcpc_ancestral.h"
 
 using namespace mcpc;
 
@@ -1857,6 +1858,84 @@ int mcpc_prediction_errors(mcpc_engine* e, const float* inputs, const float* con
         }
         hipLaunchKernelGGL(mcpc_pe_kernel, dim3(padded / kLwChains, e->pe_njobs), dim3(kLwThreads), 0, stream, P);
     });
+}
+
+int mcpc_sample_prior(mcpc_engine* e, const float* inputs, int64_t n, uint64_t seed, uint64_t step, uint64_t sample_base, int32_t loss_kind,
+                      double loss_var, int32_t readout, float* const* x_out, float* out, int32_t max_rows, void* stream_) {
+    static const char pre[] = "sample prior: ";
+    if (!e) return fail(MCPC_EINVAL, "%snull engine", pre);
+    if (n < 0) return fail(MCPC_EINVAL, "%sn=%lld, must not be negative", pre, (long long)n);
+    constexpr uint64_t kChains = 1ull << 32;            // the Philox chain word is 32 bits
+    if (sample_base > kChains || (uint64_t)n > kChains - sample_base)
+        return fail(MCPC_EINVAL, "%ssample_base=%llu + n=%lld passes 2^32 (the generator's chain word is 32 bits)", pre,
+                    (unsigned long long)sample_base, (long long)n);
+    if (max_rows < 0) return fail(MCPC_EINVAL, "%smax_rows=%d, must not be negative (0 = default)", pre, max_rows);
+    if (readout != MCPC_SAMPLE_HIDDEN && readout != MCPC_SAMPLE_MEAN && readout != MCPC_SAMPLE_DRAW)
+        return fail(MCPC_EINVAL, "%sunknown readout %d", pre, readout);
+    if (const int rc = check_loss_kind(pre, loss_kind)) return rc;
+    const int L = e->L;
+    if (out && !e->has_head) return fail(MCPC_EINVAL, "%sout needs a read-out Linear (n_out > 0)", pre);
+    // the Linears to run: up to the read-out, or to the last latent layer asked for
+    int last = out ? L : -1;
+    if (!out && x_out)
+        for (int l = 0; l < L; ++l)
+            if (x_out[l]) last = l;
+    if (last < 0) return fail(MCPC_EINVAL, "%snothing is asked for (every destination is null)", pre);
+    if (out && readout != MCPC_SAMPLE_HIDDEN) {
+        if (loss_kind == MCPC_LOSS_NONE) return fail(MCPC_EINVAL, "%sthe mean or a draw of the read-out needs a loss (loss_kind is MCPC_LOSS_NONE)", pre);
+        if (readout == MCPC_SAMPLE_DRAW && loss_kind == MCPC_LOSS_GAUSSIAN && !(loss_var > 0.0))
+            return fail(MCPC_EINVAL, "%sloss_var=%g, must be positive", pre, loss_var);
+    }
+    // (every ecoef is positive: mcpc_create refuses an engine with another one, so 1 / sqrt(ecoef) below is finite)
+    for (int j = 0; j <= last; ++j)
+        if (!e->lin[j].bound)
+            return fail(MCPC_ESTATE, "%sLinear %d has no bound parameters (mcpc_bind_params + mcpc_params_changed first)", pre, j);
+    if (n == 0) return MCPC_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(e->d.device));
+    // the chunk: a multiple of the 64-row tile, no longer than the call; the scratch and the job table are the evaluators'
+    const int64_t want = max_rows > 0 ? max_rows : kCeDefaultRows;
+    const int chunk = (int)(std::min<int64_t>((want + kLwChains - 1) / kLwChains, (n + kLwChains - 1) / kLwChains) * kLwChains);
+    if (const int rc = ce_ensure_scratch(e, chunk, 0u, stream)) return rc;
+    free_completed_retired(e);
+    int mode = kSpLogits;
+    if (readout == MCPC_SAMPLE_MEAN && loss_kind == MCPC_LOSS_BERNOULLI) mode = kSpSigmoid;
+    if (readout == MCPC_SAMPLE_DRAW) mode = loss_kind == MCPC_LOSS_BERNOULLI ? kSpBernoulli : kSpGaussian;
+    const Lin& l0 = e->lin[0];
+    const int n_in = e->d.n_in;
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        const int rows = (int)std::min<int64_t>(chunk, n - r0);
+        const int padded = (rows + kLwChains - 1) / kLwChains * kLwChains;
+        // mu_1 of the chunk's inputs, by the runs' and the evaluators' own kernel, in the scratch no launch of this call reads as x_0
+        hipLaunchKernelGGL(mcpc_mu1_kernel, dim3(grid_for((size_t)padded * e->npad[0])), dim3(256), 0, stream,
+                           inputs ? inputs + (size_t)r0 * n_in : nullptr, l0.W, l0.bias, e->ce_x[0], rows, n_in, e->d.sizes[0], padded, e->npad[0]);
+        for (int j = 0; j <= last; ++j) {
+            const bool head = j == L;
+            SpParams P{};
+            P.fx_in = j > 0 ? e->ce_fx[j - 1] : nullptr;
+            P.fx_out = j < last ? e->ce_fx[j] : nullptr;
+            P.Wf = j > 0 ? e->lin[j].Wf : nullptr;
+            P.bias = j > 0 ? e->lin[j].bias_pad : nullptr;
+            P.mu1 = e->ce_x[0];
+            P.wexp = e->wexp;
+            P.jobs = e->ce_jobs + e->ce_finish.first[j];
+            P.seed = seed; P.step = step; P.g0 = sample_base + (uint64_t)r0;
+            P.kw = j > 0 ? e->npad[j - 1] : 0;
+            P.npad = head ? e->out_pad : e->npad[j];
+            P.n = head ? e->d.n_out : e->d.sizes[j];
+            P.act = head ? 0 : e->d.acts[j];
+            P.rows = rows;
+            P.mode = head ? mode : kSpLatent;
+            P.scale = head ? (mode == kSpGaussian ? (float)std::sqrt(loss_var) : 1.0f) : (float)(1.0 / std::sqrt((double)e->d.ecoef[j]));
+            float* const base = head ? out : (x_out ? x_out[j] : nullptr);
+            // (a chunk starts at a multiple of kLwChains rows: r0 * n floats keeps the 16-byte alignment where n % 4 == 0)
+            P.dst = base ? base + (size_t)r0 * P.n : nullptr;
+            P.vec = base && P.n % 4 == 0 && ((uintptr_t)base & 15u) == 0;
+            hipLaunchKernelGGL(mcpc_sp_kernel, dim3(padded / kLwChains, e->ce_finish.count[j]), dim3(kLwThreads), 0, stream, P);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
 }
 
 int mcpc_query(const mcpc_engine* e, int32_t* lds_bytes, int32_t* chains_per_wg, int32_t* n_workgroups, int32_t* spill_slots) {

@@ -340,6 +340,37 @@ class Engine:
                                                  pred_out, int(max_rows), self._stream()))
         return res
 
+    # ---- ancestral samples ---------------------------------------------------------------------------
+    def sample_prior(self, n: int, seed: int, step: int = 0, sample_base: int = 0, inputs: Optional[torch.Tensor] = None, loss=None,
+                     var=None, readout="hidden", latents=False, out: Optional[torch.Tensor] = None, max_rows: int = 0):
+        """``n`` ancestral samples of the generative model: ``x_1 ~ N(mu_1, 1/c_1)``, ``x_2 ~ N(mu_2(x_1), 1/c_2)``, ..., the read-out
+        (include/mcpc.h: mcpc_sample_prior).  Sample ``i`` has the global id ``sample_base + i``; its values depend on ``(seed, step,
+        id)``, the bound weights and its row of ``inputs`` (``[n, n_in]``, None = zeros) alone -- not on ``n``, ``max_rows`` or the
+        engine's batch.  ``readout``: "hidden" (logits / means), "mean" (sigmoid for ``loss="bernoulli"``), "draw" (0/1 for
+        "bernoulli"; mean + sqrt(``var``) * normal for "gaussian"), or None (no read-out).  ``latents``: False, True (every layer) or the
+        layer indices to return.  Returns ``(out or None, [x_l or None])``, contiguous fp32 ``[n, width]`` on the engine's device -- the
+        layout of a record with ``B = n``.  ``out``: a tensor to fill with the read-out.  The normals are ``philox_normals(seed, step,
+        layer, sample_base, n, n_l, device)``.  On the current torch stream."""
+        n, loss_kind, loss_var, code, layers, want_out = check_sample_prior(self.L, self.n_out, n, sample_base, loss, var, readout, latents,
+                                                                            max_rows)
+        if inputs is not None:
+            _check_tensor(inputs, (n, self.n_in), self.device, "inputs")
+        if not want_out:
+            if out is not None:
+                raise ValueError("out: given with readout=None")
+        elif out is None:
+            out = torch.empty(n, self.n_out, dtype=torch.float32, device=self.device)
+        else:
+            _check_tensor(out, (n, self.n_out), self.device, "out")
+        xs = [None] * self.L
+        arr = (C.c_void_p * self.L)()
+        for l in layers:
+            xs[l] = torch.empty(n, self.sizes[l], dtype=torch.float32, device=self.device)
+            arr[l] = xs[l].data_ptr()
+        L.check(self._lib.mcpc_sample_prior(self._h, _ptr(inputs), n, int(seed), int(step), int(sample_base), loss_kind, loss_var, code, arr,
+                                            _ptr(out), int(max_rows), self._stream()))
+        return out, xs
+
     # ---- parameter gradients ---------------------------------------------------------------------
     def read_param_grads(self, j: int, dW: torch.Tensor, db: Optional[torch.Tensor], scale=1.0, accumulate=False):
         n_out, n_in = self.lin_shape(j)
@@ -413,6 +444,41 @@ class Engine:
         g = C.c_float()
         L.check(self._lib.mcpc_last_shader_clock_ghz(self._h, C.byref(g)))
         return g.value
+
+
+def check_sample_prior(n_latent, n_out, n, sample_base=0, loss=None, var=None, readout="hidden", latents=False, max_rows=0):
+    """The argument checks of ``Engine.sample_prior`` for a network of ``n_latent`` layers and ``n_out`` outputs; no device is needed.
+    Returns (n, loss_kind, loss_var, readout code, the latent layers wanted, whether the read-out is)."""
+    n, sample_base = int(n), int(sample_base)
+    if n < 0:
+        raise ValueError(f"n={n}, must not be negative")
+    if sample_base < 0 or sample_base + n > 1 << 32:
+        raise ValueError(f"sample_base={sample_base} with n={n}: sample ids are 32 bits (sample_base + n <= 2^32)")
+    if int(max_rows) < 0:
+        raise ValueError(f"max_rows={max_rows}, must not be negative (0 = default)")
+    if readout not in _SAMPLE_READOUTS:
+        raise ValueError(f"readout={readout!r}, expected 'hidden', 'mean', 'draw' or None")
+    if loss not in (None, "bernoulli", "gaussian"):
+        raise ValueError(f"loss: expected None, 'bernoulli' or 'gaussian', got {loss!r}")
+    if latents is True:
+        layers = tuple(range(n_latent))
+    elif latents is False or latents is None:
+        layers = ()
+    else:
+        layers = tuple(sorted(set(int(l) for l in latents)))
+    for l in layers:
+        if not 0 <= l < n_latent:
+            raise ValueError(f"layer index {l} out of range 0..{n_latent - 1}")
+    want_out = readout is not None and n_out > 0           # (a network that ends in a PCLayer has no read-out to return)
+    if not want_out and not layers:
+        raise ValueError("nothing is asked for: no read-out and no latent layer")
+    if want_out and readout != "hidden" and loss is None:
+        raise ValueError(f"readout={readout!r} needs a loss ('bernoulli' or 'gaussian')")
+    if loss == "gaussian" and want_out and readout == "draw":
+        if var is None or not float(var) > 0.0:
+            raise ValueError(f"var: a draw of the Gaussian read-out needs a positive variance, got {var!r}")
+    loss_var = float(var) if var is not None else 1.0
+    return n, _LOGLIK_LOSSES.get(loss, L.LOSS_NONE), loss_var, _SAMPLE_READOUTS[readout], layers, want_out
 
 
 def debug_poison_lds(device, word=0x7FA00000):
@@ -868,6 +934,7 @@ def knn_accumulate(q, ref, k, best, accumulate=False, workspace=None):
 
 
 _LOGLIK_LOSSES = {"bernoulli": L.LOSS_BERNOULLI, "gaussian": L.LOSS_GAUSSIAN}
+_SAMPLE_READOUTS = {None: L.SAMPLE_HIDDEN, "hidden": L.SAMPLE_HIDDEN, "mean": L.SAMPLE_MEAN, "draw": L.SAMPLE_DRAW}
 
 
 def loglik_workspace_bytes(n_data, n_samp, width) -> int:

@@ -1043,6 +1043,41 @@ class PCTrainer(object):
             eng.sync_check()
         return {k: v[0].to(plan["model_device"]) for k, v in res.items()}
 
+    def mcpc_sample_prior(self, n, seed=0, step=0, sample_base=0, loss_fn: typing.Callable = None, loss_fn_kwargs: dict = {},
+                          readout="hidden", latents=False):
+        """``n`` ancestral samples of the model -- ``x_1 ~ N(mu_1, 1/c_1)``, ``x_2 ~ N(mu_2(x_1), 1/c_2)``, ..., the read-out -- drawn on
+        the device from a zero pseudo-input (Engine.sample_prior; no step is run, no state or gradient changes).  Sample ``i`` is a
+        function of ``(seed, step, sample_base + i)`` and the parameters alone.  ``readout``: "hidden", "mean" or "draw" under the
+        read-out distribution ``loss_fn`` names (``fe_fn`` with ``_var``, ``bernoulli_fn``; a ``_target`` is not needed), or None;
+        ``latents``: False, True or layer indices.  Returns ``(out or None, [x_l or None])``, fp32 ``[n, width]`` on the model's device.
+        The engine is one the trainer's calls already made for this model where there is one, else a small one.  A model or loss the
+        fused loop does not express raises NotImplementedError."""
+        net, why = recognise.describe_model(self._model)
+        if net is None:
+            raise NotImplementedError("mcpc_sample_prior: outside what the HIP engine expresses ({})".format(why))
+        model_device = net.linears[0].weight.device
+        kw = dict(loss_fn_kwargs)
+        if loss_fn is not None and "_target" not in kw:
+            kw["_target"] = torch.zeros(1, net.n_out, device=model_device)      # (the loss is recognised by its kind alone)
+        plan, why = self._plan(torch.zeros(1, net.n_in, device=model_device), loss_fn, kw, False, False, None, None, {}, {}, False, False)
+        if plan is None:
+            raise NotImplementedError("mcpc_sample_prior: outside what the HIP engine expresses ({})".format(why))
+        net, loss = plan["net"], plan["loss"]
+        # an engine of this model whatever its batch (a sample does not depend on it), most recently used first
+        tuning = os.environ.get("MCPC_TUNING")
+        eng = next((e for key, e in reversed(_ENGINES.items()) if key == (net.key(e.batch, plan["device"]), tuning)), None)
+        if eng is None:
+            eng = self._engine_for(dict(plan, B=64))
+        loss_name = {L.LOSS_GAUSSIAN: "gaussian", L.LOSS_BERNOULLI: "bernoulli"}.get(loss.kind)
+        with _few_cpu_threads(plan["staged"]):
+            self._sync_params(eng, net, plan=plan)
+            out, xs = eng.sample_prior(n, seed, step=step, sample_base=sample_base, loss=loss_name,
+                                       var=loss.var if loss.kind == L.LOSS_GAUSSIAN else None, readout=readout, latents=latents,
+                                       max_rows=self.mcpc_chain_energies_max_rows)
+            eng.sync_check()
+        to = plan["model_device"]
+        return (None if out is None else out.to(to)), [None if x is None else x.to(to) for x in xs]
+
     def mcpc_state_probe(self, spec):
         """The probe of ``spec`` (a dict as ``mcpc_probe`` takes; ``begin`` and ``stride`` are not consulted) on the CURRENT x of its
         layer -- what a MAP call leaves -- through the kernel of the sampled probe (engine.probe_accumulate with one record): the

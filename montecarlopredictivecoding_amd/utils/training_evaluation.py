@@ -87,6 +87,39 @@ def sample_pc(num_samples, model, config, use_cuda=False, is_return_hidden=False
     return temp.detach()
 
 
+def sample_pc_device(num_samples, model, config, use_cuda=False, is_return_hidden=False, seed=0, step=0, sample_base=0,
+                     return_latents=False):
+    """``sample_pc`` on the device (``PCTrainer.mcpc_sample_prior``; include/mcpc.h: mcpc_sample_prior): the same ancestral pass with
+    the normals of the step kernels' Philox stream instead of torch's CPU generator and every Linear on the engine's packed weights.
+    Sample ``i`` is a function of ``(seed, step, sample_base + i)`` and the parameters alone, so chunks drawn with an advancing
+    ``sample_base`` are the bits of one draw; ``torch.manual_seed`` does not reach it.  ``config["loss_fn"]`` / ``config["input_var"]``
+    choose the read-out draw as in ``sample_pc``; ``is_return_hidden`` returns the read-out as it is.  A PCLayer's noise has the variance
+    ``1 / c`` of its energy coefficient ``c`` (``sample_pc`` adds unit noise whatever ``c``; with the default ``c = 1`` the two agree).
+    Returns fp32 ``[num_samples, n_out]`` on the model's device -- Bernoulli draws are fp32 0/1 where the reference returns doubles --
+    or, with ``return_latents``, ``(that, [x_l])``.  A model the engine does not express raises NotImplementedError; without a HIP
+    device, MCPCLibraryError."""
+    from ..engine import check_sample_prior
+    from ..predictive_coding import recognise
+    from ..utils.model import bernoulli_fn, fe_fn
+    net, why = recognise.describe_model(model)
+    if net is None:
+        raise NotImplementedError("sample_pc_device: outside what the HIP engine expresses ({})".format(why))
+    if net.n_in != config["input_size"]:
+        raise ValueError("sample_pc_device: config['input_size']={} but the model takes {} inputs".format(config["input_size"], net.n_in))
+    if net.n_out == 0:
+        raise NotImplementedError("sample_pc_device: the model ends in a PCLayer, there is no read-out to sample "
+                                  "(PCTrainer.mcpc_sample_prior(latents=True) returns its layers)")
+    loss_fn = None if is_return_hidden or config["loss_fn"] not in (fe_fn, bernoulli_fn) else config["loss_fn"]
+    kw = {"_var": config["input_var"]} if loss_fn is fe_fn else {}
+    readout = "hidden" if loss_fn is None else "draw"
+    check_sample_prior(len(net.sizes), net.n_out, num_samples, sample_base, {None: None, fe_fn: "gaussian", bernoulli_fn: "bernoulli"}[loss_fn],
+                       kw.get("_var"), readout, bool(return_latents))
+    trainer = pc.PCTrainer(model, update_p_at="never", plot_progress_at=[])
+    out, xs = trainer.mcpc_sample_prior(num_samples, seed=seed, step=step, sample_base=sample_base, loss_fn=loss_fn, loss_fn_kwargs=kw,
+                                        readout=readout, latents=bool(return_latents))
+    return (out, xs) if return_latents else out
+
+
 def get_mse_rec(gen_pc, config, dataloader, use_cuda):
     """Masked-reconstruction error: infer (MAP) from the bottom half of each image, score the top half."""
     import torch
@@ -195,7 +228,8 @@ def get_marginal_likelihood(gen_pc, config, dataloader, use_cuda, n_samples=5000
     return marginal_likelihood_from_logits(logits, dataloader)
 
 
-def get_marginal_likelihood_per_datum(gen_pc, config, dataloader, use_cuda, n_samples=5000, sample_chunk=None, clamp=20.0):
+def get_marginal_likelihood_per_datum(gen_pc, config, dataloader, use_cuda, n_samples=5000, sample_chunk=None, clamp=20.0, sampler="torch",
+                                      seed=0):
     """``get_marginal_likelihood`` per datum, in fp64 on the device, for both read-outs: a ``likelihood.LogLikelihood`` over the loader's
     data, in the loader's order -- ``.log_p`` per datum, ``.ess`` (the effective sample size of its importance weights),
     ``.n_samples``; ``.mean()`` is the reference's scalar.  The data are gathered onto the model's device once.  The prior samples are
@@ -203,7 +237,10 @@ def get_marginal_likelihood_per_datum(gen_pc, config, dataloader, use_cuda, n_sa
     generator exactly as ``get_marginal_likelihood`` does (the same seed gives the same samples); otherwise they are drawn
     ``sample_chunk`` at a time and the state is accumulated over the chunks, so ``n_samples`` is not bounded by memory.
     ``bernoulli_fn`` reads the samples' read-outs as logits, ``fe_fn`` as means of a Gaussian of variance ``config["input_var"]``;
-    both are clamped to ``+-clamp`` as the reference clamps (``math.inf``: not at all)."""
+    both are clamped to ``+-clamp`` as the reference clamps (``math.inf``: not at all).
+    ``sampler="device"`` draws every chunk with ``sample_pc_device(..., is_return_hidden=True, seed=seed, sample_base=s0)`` instead: the
+    samples are then the same bits whatever ``sample_chunk`` is (only the accumulation's documented rounding bound remains), no normal
+    is drawn on the CPU, and the torch generator is not consumed by the draws."""
     import torch
     from ..likelihood import log_likelihood
     from ..utils.model import bernoulli_fn, fe_fn
@@ -217,10 +254,16 @@ def get_marginal_likelihood_per_datum(gen_pc, config, dataloader, use_cuda, n_sa
     chunk = n_samples if sample_chunk is None else int(sample_chunk)
     if n_samples < 1 or chunk < 1:
         raise ValueError(f"n_samples={n_samples} and sample_chunk={sample_chunk!r} must be at least 1")
+    if sampler not in ("torch", "device"):
+        raise ValueError(f"sampler={sampler!r}, expected 'torch' or 'device'")
     device = next(gen_pc.parameters()).device
     data, state = None, None
     for s0 in range(0, n_samples, chunk):
-        outputs = sample_pc(min(chunk, n_samples - s0), gen_pc, config, use_cuda=use_cuda, is_return_hidden=True)
+        if sampler == "device":
+            outputs = sample_pc_device(min(chunk, n_samples - s0), gen_pc, config, use_cuda=use_cuda, is_return_hidden=True, seed=seed,
+                                       sample_base=s0)
+        else:
+            outputs = sample_pc(min(chunk, n_samples - s0), gen_pc, config, use_cuda=use_cuda, is_return_hidden=True)
         if data is None:
             # after the first draw, as get_marginal_likelihood walks its loader: a DataLoader's iterator takes a seed from the torch generator
             data = torch.cat([d.to(device).to(torch.float32).reshape(d.shape[0], -1) for d, _ in dataloader])
