@@ -1,4 +1,9 @@
-// Host side of libmcpc.so: the C ABI declared in include/mcpc.h.
+// Host side of libmcpc.so: the C ABI declared in include/mcpc.h, in four translation units.
+//   mcpc_api.hip (this one)   the engine's life cycle and bindings, mcpc_run and its executor with every step kernel, the three evaluators
+//                             that share kernels and scratch with the runs, RCCL, the normals, the query, debug and profiling entries
+//   mcpc_flush.hip            the Hebbian flush of the Linears j >= 1 (flush_spill) and its kernels
+//   mcpc_records.hip          the stateless reducers over recorded states (int device, no engine) and their kernels
+//   mcpc_build_info.hip       mcpc_abi_version, mcpc_build_info: the one unit that is compiled with the provenance defines
 // Allocation, weight packing, launch orchestration (step segments + Hebbian flushes); no torch.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -13,117 +18,18 @@
 #include <vector>
 
 #include "mcpc_build.h"
+#include "mcpc_engine.h"
+// every kernel this unit launches: the barrier step kernel and the small kernels, the in-place, unified-wave and layer-wise step
+// kernels, the evaluators
 #include "mcpc_kernels.h"
-#include "mcpc_moments.h"
-#include "mcpc_cov.h"
-#include "mcpc_hist.h"
-#include "mcpc_hist2d.h"
-#include "mcpc_acov.h"
-#include "mcpc_roll.h"
-#include "mcpc_probe.h"
-#include "mcpc_knn.h"
-#include "mcpc_loglik.h"
-#include "mcpc_plan.h"
+#include "mcpc_steps_ws2.h"
+#include "mcpc_steps_u.h"
+#include "mcpc_steps_lw.h"
 #include "mcpc_chain_energy.h"
 #include "mcpc_pred_err.h"
 #include "mcpc_ancestral.h"
 
 using namespace mcpc;
-
-#define HIP_TRY(expr)                                                                            \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e != hipSuccess) return fail(MCPC_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-
-static inline int grid_for(size_t n, int block = 256) { return (int)std::min<size_t>((n + block - 1) / block, 4096); }
-
-// An engine is its plan (mcpc_plan.h: what plan_engine decided from the descriptor and the device) and the device state built from it
-struct mcpc_engine : EnginePlan {
-    mcpc_net_desc d{};
-    ncclComm_t comm = nullptr;      // mcpc_comm_init: the shards' communicator (RCCL), one rank per engine
-    int comm_ranks = 0;
-    float* x[kMaxLatent]{};
-    float* m[kMaxLatent]{};
-    float* v[kMaxLatent]{};
-    float* e0sum = nullptr;
-    float* mu1 = nullptr;
-    float* ypad = nullptr;
-    float* ytile = nullptr;         // tile-major copy of ypad (KHead::ytile)
-    uint32_t* ybits = nullptr;      // bit-packed copy of a 0/1 target (see mcpc_pack_target_bits_kernel)
-    int* y_binary = nullptr;        // device flag: the bound target is exactly 0/1 everywhere
-    int ywords = 0;
-    bool target_bound = false;
-    // host copy of the three flag words (target_flags_on_host): requested by mcpc_bind_target behind its kernels; engines that may take a
-    // specialised instantiation of the in-place kernel only
-    int* y_flags_host = nullptr;    // pinned
-    hipEvent_t y_flags_ev = nullptr;
-    bool y_flags_pending = false;
-    const float* inputs = nullptr;
-    // Hebbian spill ring (EnginePlan::slots in parts of half_slots): the flush of one part runs on `aux` while the step kernel fills another
-    hipStream_t aux = nullptr;
-    hipEvent_t ev_steps[kMaxRingParts] = {}, ev_flush[kMaxRingParts] = {};
-    hipStream_t spacer = nullptr;   // never used: see ensure_spill
-    hipStream_t aux3 = nullptr;     // second low-priority stream of the overlapped flush: the GEMMs of a flush alternate between the two,
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // so that the tail of one launch is filled by the next (same-stream kernels serialise)
-    bool flush_pending[kMaxRingParts] = {};
-    float* spill_a[kMaxLatent]{};
-    float* spill_e[kMaxLatent]{};
-    float* spill_eo = nullptr;
-    float* slab = nullptr;          // EnginePlan::slab_floats floats
-    // energies
-    double* epart = nullptr;
-    size_t epart_rows = 0;
-    float* adam_coef = nullptr;     // device table [steps][2]; grown buffers are retired, never freed under a running kernel
-    size_t adam_cap = 0;
-    float* adam_host[2] = {nullptr, nullptr};     // pinned staging, double-buffered: a run never rewrites a table whose upload may be pending
-    size_t adam_host_cap[2] = {0, 0};
-    hipEvent_t adam_ev[2] = {nullptr, nullptr};
-    int adam_next = 0;
-    struct Retired { void* p; hipEvent_t ev; };
-    std::vector<Retired> retired;   // device buffers replaced by larger ones while earlier launches may still use them: each carries an event
-                                    // recorded on the stream at retirement and is freed by the first later run that finds the event complete
-    bool spill_ready = false;       // the spill ring, its stream/events and the slabs exist (allocated by the first accumulating run)
-    int* err = nullptr;             // device error word written by the kernels
-    int* wexp = nullptr;            // [kMaxLatent + 1] per Linear: the power of two its packed weights are scaled by (mcpc_wexp_kernel)
-    unsigned* spillmax = nullptr;   // [kMaxRingParts][kSpillTensors]: per ring part, the largest |value| per spilled tensor of the segment
-                                    // that filled it (bit patterns; written by the step kernels, read by the Hebbian GEMMs of that part)
-    // layer-wise kernels (mcpc_steps_lw.h): state, activations and errors of all chains in global memory, two launches per step
-    float* lw_fx[kMaxLatent]{};     // f(x_l) [Bpad][npad_l]
-    float* lw_err[kMaxLatent]{};    // e_l, l >= 1
-    float* lw_err_o = nullptr;      // e_o [Bpad][out_pad]
-    LwJob* lw_jobs = nullptr;       // device copy of lw_table
-    unsigned long long* clk = nullptr;   // profiling: {shader cycles, 100 MHz ticks} of one wave per launch (KParams::clk)
-    float* dummy = nullptr;         // 4 KiB of zeros (KParams::dummy)
-    int* rr_tab = nullptr;          // device copy of rr_host (round schedule)
-    // per-chain energies (mcpc_chain_energy.h): the evaluator's own scratch, allocated by the first mcpc_chain_energies and grown by a
-    // call that asks for a larger chunk (the old buffers are retired, like every buffer launches in the stream may still use)
-    float* ce_x[kMaxLatent]{};      // x_l    [ce_rows][npad_l]
-    float* ce_fx[kMaxLatent]{};     // f(x_l) [ce_rows][npad_l]
-    float* ce_mu1 = nullptr;        // mu_1 of the call's inputs [Bpad][npad_0]
-    double* ce_part = nullptr;      // [job][ce_rows]
-    LwJob* ce_jobs = nullptr;       // device copy of the job table (ce_job_table)
-    int ce_njobs = 0, ce_nhead = 0;
-    CeFinish ce_finish{};
-    int ce_rows = 0;                // rows the scratch holds (a multiple of kLwChains)
-    // prediction errors (mcpc_pred_err.h) share that scratch; their job table is ce_table filtered to the Linears of the last call
-    std::vector<LwJob> ce_table;    // host copy of ce_jobs
-    LwJob* pe_jobs = nullptr;       // device copy of pe_job_table(ce_table, pe_want)
-    unsigned pe_want = 0;
-    int pe_njobs = 0;
-    RunPlan run_plan;               // the schedule of the last mcpc_run (plan_run); kept for its storage: no allocation per run
-    // diagnostics, host strings set while launching (no device work): what the last mcpc_run and each Linear's last flush launched
-    std::string last_step;                       // mcpc_last_step_kernel_name
-    std::string last_flush[kMaxLatent + 1];      // mcpc_last_flush_plan, per Linear j >= 1
-    // profiling
-    bool profiling = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;   // HIP events around every launch of the step kernel
-    size_t events_used = 0;
-    double prof_steps = 0;          // whole-shard steps covered by the bracketed launches
-#ifdef MCPC_STAMPS
-    unsigned long long* dbg = nullptr;
-#endif
-};
 
 namespace {
 
@@ -315,19 +221,6 @@ int launch_lw_steps(mcpc_engine* e, const mcpc_run_desc* r, const KParams& P, in
 
 extern "C" {
 
-int mcpc_abi_version(void) { return MCPC_ABI_VERSION; }
-
-const char* mcpc_build_info(void) {
-    // exp: the umbrella of mcpc_build.h, and -- should a switch ever be added without being listed there -- any -DMCPC_EXP / MCPC_HEB_EXP
-    // in the flags the Makefile recorded
-    static const bool exp = MCPC_TIMING_BUILD != 0 || std::strstr(MCPC_BUILD_FLAGS, "MCPC_EXP") != nullptr ||
-                            std::strstr(MCPC_BUILD_FLAGS, "MCPC_HEB_EXP") != nullptr;
-    static char buf[1024];
-    static const int n = std::snprintf(buf, sizeof buf, "libmcpc abi=%d arch=gfx950 csrc=%s commit=%s exp=%d stamps=%d flags=[%s]",
-                                       MCPC_ABI_VERSION, MCPC_BUILD_CSRC_SHA, MCPC_BUILD_COMMIT, exp ? 1 : 0, MCPC_STAMPS_BUILD, MCPC_BUILD_FLAGS);
-    (void)n;
-    return buf;
-}
 const char* mcpc_last_error(void) { return g_err.c_str(); }
 
 int mcpc_create(const mcpc_net_desc* d, mcpc_engine** out) {
@@ -539,30 +432,6 @@ int mcpc_store_adam_state(mcpc_engine* e, float* const* m, float* const* v, void
 
 namespace {
 
-// The tiled Hebbian kernels, family (HEB_F16, HEB_FP32: mcpc_plan.h) x form (kHebForms: mcpc_hebbian.h): every instantiation the
-// library holds, with its dynamic LDS.  A planned launch names its entry; nothing else chooses a kernel.
-struct HebKernel { void (*fn)(HebArgs); int lds_bytes; bool attr_set[16]; };      // (attr_set: per device)
-#define MCPC_HEB7_ROW(te, ra, sw) {mcpc_heb7_kernel<te, ra, sw>, heb7_lds_bytes(te), {false}},
-#define MCPC_HEB_ROW(te, ra, sw) {mcpc_heb_kernel<te, ra, sw>, heb_lds_bytes(te, ra), {false}},
-HebKernel g_heb_kernels[2][kNumHebForms] = {{MCPC_HEB_FORMS(MCPC_HEB7_ROW)}, {MCPC_HEB_FORMS(MCPC_HEB_ROW)}};
-#undef MCPC_HEB7_ROW
-#undef MCPC_HEB_ROW
-
-int launch_heb(const FlushLaunch& l, const HebArgs& a, hipStream_t stream) {
-    if ((l.family != HEB_F16 && l.family != HEB_FP32) || l.form < 0 || l.form >= kNumHebForms)
-        return fail(MCPC_ESTATE, "internal: no Hebbian kernel %s<%d,%d%s> (form %d)", heb_family_name(l.family), l.te, l.ra, l.swapped ? ",T" : "", l.form);
-    HebKernel& k = g_heb_kernels[l.family][l.form];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev >= 0 && dev < 16 && !k.attr_set[dev]) {
-        if (hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds_bytes) != hipSuccess)
-            return fail(MCPC_EHIP, "hipFuncSetAttribute failed for the Hebbian kernel");
-        k.attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(k.fn, dim3(a.n_mt * a.n_nt * a.ksplit), dim3(kHebThreads), k.lds_bytes, stream, a);
-    return 0;
-}
-
 // Allocated by the first run that accumulates Hebbian sums (inference-only engines never pay for it): the spill ring, the
 // slabs of the split-K partial sums (sized by plan_engine), the low-priority stream and events of the overlapped flush.
 int ensure_spill(mcpc_engine* e, hipStream_t stream) {
@@ -612,47 +481,6 @@ int ensure_spill(mcpc_engine* e, hipStream_t stream) {
     return 0;
 }
 
-// One Hebbian flush, as planned (mcpc_plan.h: plan_flush): fold the spilled steps from slot `slot0` on into the gradient sums of every
-// Linear j >= 1.  Every Linear has its own slab region, so the GEMMs of a flush are independent launches and ONE reduction launch
-// follows them.  An overlapped flush spreads them over two low-priority streams (`stream` and aux3); the reduction joins them.
-int flush_spill(mcpc_engine* e, const FlushPlan& f, int slot0, hipStream_t stream, int part) {
-    const unsigned* const smax = e->spillmax + (size_t)part * kSpillTensors;      // largest |value| per spilled tensor of this segment
-    if (f.two_streams && !e->aux3) return fail(MCPC_ESTATE, "internal: a flush planned for two streams on an engine that has one");
-    hipStream_t const streams[2] = {stream, f.two_streams ? e->aux3 : stream};
-    if (f.two_streams) { HIP_TRY(hipEventRecord(e->ev_fork, stream)); HIP_TRY(hipStreamWaitEvent(e->aux3, e->ev_fork, 0)); }
-    ReduceJobs jobs{};
-    for (int j = 1; j < e->L + e->has_head; ++j) {
-        const Lin& ln = e->lin[j];
-        const LinFlush& lf = f.lin[j];
-        const int ne = ln.out_pad, na = ln.in_pad;
-        const float* E = (j < e->L ? e->spill_e[j] : e->spill_eo) + (size_t)slot0 * e->Bpad * ne;
-        const float* A = e->spill_a[j - 1] + (size_t)slot0 * e->Bpad * na;
-        const unsigned* const e_max = smax + (j < e->L ? spill_id_e(j) : kSpillIdEo), * const a_max = smax + spill_id_a(j - 1);
-        float* slab = e->slab + ln.slab_off;
-        float* slab_b = slab + (size_t)lf.ksplit * ne * na;
-        for (int i = 0; i < lf.n_launch; ++i) {
-            const FlushLaunch& l = lf.launch[i];
-            if (l.family == HEB_DW) {
-                hipLaunchKernelGGL(mcpc_dw_kernel, dim3((l.wave_tiles + 3) / 4, lf.ksplit), dim3(256), 0, streams[l.stream], E, A, slab, slab_b,
-                                   f.rows, ne, na, lf.rps);
-                continue;
-            }
-            // (swapped: the transposed product -- the activations take the E slot, the errors the A slot; slab = [split][na][ne])
-            const bool sw = l.swapped;
-            const HebArgs a{sw ? A : E, sw ? E : A, slab, slab_b, f.rows, sw ? na : ne, sw ? ne : na, lf.rps, l.n_mt, l.n_nt, lf.ksplit, l.col0,
-                            sw ? a_max : e_max, sw ? e_max : a_max};
-            if (const int rc = launch_heb(l, a, streams[l.stream])) return rc;
-        }
-        e->last_flush[j] = lf.text;
-        jobs.job[jobs.n_jobs++] = ReduceJob{slab, ln.G, ne * na, lf.ksplit, lf.sign, lf.tr_cols, lf.tr_ld};
-        jobs.job[jobs.n_jobs++] = ReduceJob{slab_b, ln.Gb, ne, lf.ksplit, lf.sign, 0, 0};
-    }
-    if (f.two_streams) { HIP_TRY(hipEventRecord(e->ev_join, e->aux3)); HIP_TRY(hipStreamWaitEvent(stream, e->ev_join, 0)); }
-    if (jobs.n_jobs > 0)
-        hipLaunchKernelGGL(mcpc_reduce_jobs_kernel, dim3(f.max_blocks, jobs.n_jobs), dim3(256), 0, stream, jobs);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
 
 }  // namespace
 
@@ -1224,463 +1052,6 @@ int mcpc_box_muller(int device, const uint32_t* a, const uint32_t* b, int64_t n,
     return MCPC_OK;
 }
 
-namespace {
-// The record window of the accumulate entries: records first, first + stride, ... (n of them) of a ring `rec` whose rows hold B x width
-// floats.  The checks they share; `who`, the entry's name, opens every message.
-int check_shape(const char* who, int32_t B, int32_t width) {
-    if (B < 1) return fail(MCPC_EINVAL, "%s: B=%d, must be at least 1", who, B);
-    if (width < 1) return fail(MCPC_EINVAL, "%s: width=%d, must be at least 1", who, width);
-    return 0;
-}
-int check_window(const char* who, const void* rec, int32_t first, int32_t stride, int32_t n) {
-    if (stride < 1) return fail(MCPC_EINVAL, "%s: stride=%d, must be at least 1", who, stride);
-    if (first < 0) return fail(MCPC_EINVAL, "%s: first=%d, must not be negative", who, first);
-    if (n < 0) return fail(MCPC_EINVAL, "%s: n=%d, must not be negative", who, n);
-    if (n > 0 && !rec) return fail(MCPC_EINVAL, "%s: rec is null with n=%d", who, n);
-    return 0;
-}
-int check_transform(const char* who, int32_t xf) {
-    return xf != MCPC_MOM_IDENTITY && xf != MCPC_MOM_SIGMOID ? fail(MCPC_EINVAL, "%s: unknown transform %d", who, xf) : 0;
-}
-// The window itself: the row length E, the first record, the distance between two records.
-// All offsets in 64 bits: (first + k * stride) * E passes 2^31 elements at the shapes the step kernels are built for.
-struct RecWindow { int64_t E; const float* r0; int64_t row_step; };
-RecWindow rec_window(const float* rec, int64_t E, int32_t first, int32_t stride, int32_t n) {
-    return {E, n > 0 ? rec + (int64_t)first * E : rec, (int64_t)stride * E};
-}
-}  // namespace
-
-int mcpc_moments_accumulate(int device, const float* rec, int64_t row_elems, int32_t first, int32_t stride, int32_t n, int32_t transform,
-                            double* sum, double* sumsq, int accumulate, void* stream_) {
-    if (!sum) return fail(MCPC_EINVAL, "moments: sum is null");
-    if (row_elems < 1) return fail(MCPC_EINVAL, "moments: row_elems=%lld, must be at least 1", (long long)row_elems);
-    if (const int rc = check_window("moments", rec, first, stride, n)) return rc;
-    if (const int rc = check_transform("moments", transform)) return rc;
-    if (n == 0 && accumulate) return MCPC_OK;                     // nothing to add
-    HIP_TRY(hipSetDevice(device));
-    const RecWindow w = rec_window(rec, row_elems, first, stride, n);
-    const uintptr_t align = (uintptr_t)w.r0 | (uintptr_t)sum | (uintptr_t)sumsq;
-    if (row_elems % 4 == 0 && align % 16 == 0)
-        mom_dispatch<4>(transform, w.r0, w.E, w.row_step, n, sum, sumsq, accumulate, (hipStream_t)stream_);
-    else
-        mom_dispatch<1>(transform, w.r0, w.E, w.row_step, n, sum, sumsq, accumulate, (hipStream_t)stream_);
-    HIP_TRY(hipGetLastError());
-    return MCPC_OK;
-}
-
-// shared argument checks of the two covariance entry points; fills the plan
-static int cov_check_shape(int32_t B, const int32_t* widths, int32_t n_blocks, int32_t pool, CovPlan& plan) {
-    if (n_blocks < 1 || n_blocks > kCovMaxBlocks) return fail(MCPC_EINVAL, "cov: n_blocks=%d outside 1..%d", n_blocks, kCovMaxBlocks);
-    if (!widths) return fail(MCPC_EINVAL, "cov: widths is null");
-    if (B < 1) return fail(MCPC_EINVAL, "cov: B=%d, must be at least 1", B);
-    if (pool != 0 && pool != 1) return fail(MCPC_EINVAL, "cov: pool=%d, must be 0 or 1", pool);
-    int64_t D = 0;
-    for (int b = 0; b < n_blocks; ++b) {
-        if (widths[b] < 1) return fail(MCPC_EINVAL, "cov: widths[%d]=%d, must be at least 1", b, widths[b]);
-        D += (widths[b] + 15) / 16 * 16;
-    }
-    if (D > 32768) return fail(MCPC_EINVAL, "cov: %lld padded columns, at most 32768", (long long)D);
-    plan = cov_plan(B, widths, n_blocks, pool);
-    // one workgroup of 64 lanes per job, and a grid holds fewer than 2^32 threads
-    if ((int64_t)plan.groups * plan.npairs >= (1LL << 26))
-        return fail(MCPC_EINVAL, "cov: %lld jobs (chain groups x blocks of tile pairs), a launch holds fewer than %lld", (long long)plan.groups * plan.npairs, 1LL << 26);
-    return MCPC_OK;
-}
-
-int64_t mcpc_cov_workspace_bytes(int32_t B, const int32_t* widths, int32_t n_blocks, int32_t pool) {
-    CovPlan plan;
-    if (cov_check_shape(B, widths, n_blocks, pool, plan)) return -1;
-    return pool ? (int64_t)plan.groups * plan.Dpad * plan.Dpad * (int64_t)sizeof(double) : 0;
-}
-
-int mcpc_cov_accumulate(int device, const float* const* rec, const int32_t* widths, const int32_t* transforms, int32_t n_blocks, int32_t B,
-                        int32_t first, int32_t stride, int32_t n, int32_t pool, double* outer, int accumulate, void* workspace,
-                        int64_t workspace_bytes, void* stream_) {
-    CovPlan plan;
-    if (const int rc = cov_check_shape(B, widths, n_blocks, pool, plan)) return rc;
-    if (!outer) return fail(MCPC_EINVAL, "cov: outer is null");
-    if (const int rc = check_window("cov", rec, first, stride, n)) return rc;
-    bool any_sig = false;
-    for (int b = 0; b < n_blocks; ++b) {
-        const int32_t xf = transforms ? transforms[b] : MCPC_MOM_IDENTITY;
-        if (xf != MCPC_MOM_IDENTITY && xf != MCPC_MOM_SIGMOID) return fail(MCPC_EINVAL, "cov: unknown transform %d of block %d", xf, b);
-        any_sig = any_sig || xf == MCPC_MOM_SIGMOID;
-    }
-    for (int b = 0; n > 0 && b < n_blocks; ++b)
-        if (!rec[b]) return fail(MCPC_EINVAL, "cov: rec[%d] is null with n=%d", b, n);
-    const int64_t need = pool ? (int64_t)plan.groups * plan.Dpad * plan.Dpad * (int64_t)sizeof(double) : 0;
-    if (n > 0 && pool) {
-        if (!workspace) return fail(MCPC_EINVAL, "cov: workspace is null with pool=1 (mcpc_cov_workspace_bytes: %lld bytes)", (long long)need);
-        if (workspace_bytes < need)
-            return fail(MCPC_EINVAL, "cov: workspace of %lld bytes is too small, %lld needed", (long long)workspace_bytes, (long long)need);
-    }
-    if (n == 0 && accumulate) return MCPC_OK;                     // nothing to add
-    hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipSetDevice(device));
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(outer, 0, (size_t)(pool ? 1 : B) * plan.D * plan.D * sizeof(double), stream));
-        return MCPC_OK;
-    }
-    CovParams P{};
-    int32_t tile = 0, col = 0;
-    for (int b = 0; b <= kCovMaxBlocks; ++b) {
-        P.tile0[b] = tile; P.col0[b] = col;
-        if (b < n_blocks) {
-            P.rec[b] = rec[b]; P.width[b] = widths[b]; P.xf[b] = transforms ? transforms[b] : MCPC_MOM_IDENTITY;
-            tile += (widths[b] + 15) / 16; col += widths[b];
-        }
-    }
-    P.n_blocks = n_blocks; P.NT = plan.NT; P.NB = plan.NB; P.npairs = plan.npairs; P.D = plan.D; P.Dpad = plan.Dpad;
-    P.B = B; P.first = first; P.stride = stride; P.n = n; P.gs = plan.gs; P.accumulate = accumulate ? 1 : 0;
-    P.out = pool ? (double*)workspace : outer;
-    const dim3 grid((unsigned)((int64_t)plan.groups * plan.npairs)), block(64);
-    if (pool) {
-        if (any_sig) hipLaunchKernelGGL((mcpc_cov_kernel<true, true>), grid, block, 0, stream, P);
-        else hipLaunchKernelGGL((mcpc_cov_kernel<true, false>), grid, block, 0, stream, P);
-        const int64_t total = (int64_t)plan.D * plan.D;
-        hipLaunchKernelGGL(mcpc_cov_finish_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 2048)), dim3(256), 0, stream, P,
-                           (const double*)workspace, plan.groups, outer);
-    } else {
-        if (any_sig) hipLaunchKernelGGL((mcpc_cov_kernel<false, true>), grid, block, 0, stream, P);
-        else hipLaunchKernelGGL((mcpc_cov_kernel<false, false>), grid, block, 0, stream, P);
-    }
-    HIP_TRY(hipGetLastError());
-    return MCPC_OK;
-}
-
-int mcpc_hist_accumulate(int device, const float* rec, int32_t B, int32_t width, int32_t first, int32_t stride, int32_t n, int32_t transform,
-                         const float* edges, int32_t n_bins, int32_t pool, int64_t* counts, int accumulate, void* stream_) {
-    if (!counts) return fail(MCPC_EINVAL, "hist: counts is null");
-    if (!edges) return fail(MCPC_EINVAL, "hist: edges is null");
-    if (const int rc = check_shape("hist", B, width)) return rc;
-    if (const int rc = check_window("hist", rec, first, stride, n)) return rc;
-    if (n_bins < 1 || n_bins > MCPC_HIST_MAX_BINS) return fail(MCPC_EINVAL, "hist: n_bins=%d outside 1..%d", n_bins, MCPC_HIST_MAX_BINS);
-    if (pool != 0 && pool != 1) return fail(MCPC_EINVAL, "hist: pool=%d, must be 0 or 1", pool);
-    if (const int rc = check_transform("hist", transform)) return rc;
-    for (int i = 0; i <= n_bins; ++i) {
-        if (!std::isfinite(edges[i])) return fail(MCPC_EINVAL, "hist: edges[%d] is not finite", i);
-        if (i > 0 && !(edges[i - 1] < edges[i]))
-            return fail(MCPC_EINVAL, "hist: edges are not strictly ascending at %d (%.9g, then %.9g)", i, (double)edges[i - 1], (double)edges[i]);
-    }
-    if (n == 0 && accumulate) return MCPC_OK;                     // nothing to add
-    hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipSetDevice(device));
-    const RecWindow w = rec_window(rec, (int64_t)B * width, first, stride, n);
-    const int64_t E = w.E, ncol = n_bins + 3;
-    const size_t out_bytes = (size_t)(pool ? (int64_t)width : E) * ncol * sizeof(int64_t);
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(counts, 0, out_bytes, stream));
-        return MCPC_OK;
-    }
-    const int kVec = (E % 4 == 0 && (uintptr_t)w.r0 % 16 == 0) ? 4 : 1;
-    const HistPlan plan = hist_plan(E, width, pool, n, n_bins, kVec);
-    HistParams P{};
-    P.top = hist_key_table(edges, n_bins, P.key, kHistTable, &P.key_hi);
-    P.n_bins = n_bins;
-    P.TV = plan.TV; P.n = n; P.seg = plan.seg; P.width = width; P.pool = pool;
-    P.exclusive = (!pool && plan.segments == 1) ? 1 : 0;
-    P.accumulate = accumulate ? 1 : 0;
-    P.E = E; P.row_step = w.row_step; P.tiles = plan.tiles; P.period = plan.period; P.splits = plan.splits;
-    // workgroups that share a destination add into it with integer atomics: an overwriting call starts them from zero
-    if (!P.exclusive && !accumulate) HIP_TRY(hipMemsetAsync(counts, 0, out_bytes, stream));
-    if (kVec == 4) hist_launch<4>(transform, w.r0, P, plan, counts, stream);
-    else hist_launch<1>(transform, w.r0, P, plan, counts, stream);
-    HIP_TRY(hipGetLastError());
-    return MCPC_OK;
-}
-
-int mcpc_acov_accumulate(int device, const float* rec, int32_t B, int32_t width, int32_t first, int32_t stride, int32_t n, int32_t transform,
-                         int32_t max_lag, int64_t n_seen, double* lagged, double* sum, float* window, float* head, void* stream_) {
-    if (max_lag < 0 || max_lag > MCPC_ACOV_MAX_LAG) return fail(MCPC_EINVAL, "acov: max_lag=%d outside 0..%d", max_lag, MCPC_ACOV_MAX_LAG);
-    if (!lagged) return fail(MCPC_EINVAL, "acov: lagged is null");
-    if (!sum) return fail(MCPC_EINVAL, "acov: sum is null");
-    if (max_lag > 0 && !window) return fail(MCPC_EINVAL, "acov: window is null with max_lag=%d", max_lag);
-    if (max_lag > 0 && !head) return fail(MCPC_EINVAL, "acov: head is null with max_lag=%d", max_lag);
-    if (const int rc = check_shape("acov", B, width)) return rc;
-    if (const int rc = check_window("acov", rec, first, stride, n)) return rc;
-    if (n_seen < 0) return fail(MCPC_EINVAL, "acov: n_seen=%lld, must not be negative", (long long)n_seen);
-    if (const int rc = check_transform("acov", transform)) return rc;
-    if (n == 0 && n_seen > 0) return MCPC_OK;                     // nothing to add
-    hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipSetDevice(device));
-    const RecWindow w = rec_window(rec, (int64_t)B * width, first, stride, n);
-    if (n == 0) {                                                 // a stream that starts empty
-        HIP_TRY(hipMemsetAsync(lagged, 0, (size_t)w.E * (max_lag + 1) * sizeof(double), stream));
-        HIP_TRY(hipMemsetAsync(sum, 0, (size_t)w.E * sizeof(double), stream));
-        return MCPC_OK;
-    }
-    AcovParams P{};
-    P.rec = w.r0; P.E = w.E; P.row_step = w.row_step; P.n_seen = n_seen; P.n = n; P.K = max_lag;
-    P.lagged = lagged; P.sum = sum; P.window = window; P.head = head;
-    acov_dispatch(transform, P, stream);
-    HIP_TRY(hipGetLastError());
-    return MCPC_OK;
-}
-
-static int roll_check_shape(int32_t B, int32_t width, int32_t n) {
-    if (const int rc = check_shape("roll", B, width)) return rc;
-    if (n < 0) return fail(MCPC_EINVAL, "roll: n=%d, must not be negative", n);
-    if (roll_groups((int64_t)B * width, 1) >= kRollMaxGroups)
-        return fail(MCPC_EINVAL, "roll: B * width = %lld is more than one launch holds", (long long)B * width);
-    return MCPC_OK;
-}
-
-int64_t mcpc_roll_workspace_bytes(int32_t B, int32_t width, int32_t n) {
-    if (roll_check_shape(B, width, n)) return -1;
-    // a chunk of n samples emits at most n rows, and the scalar form has the most workgroups
-    return roll_groups((int64_t)B * width, 1) * (int64_t)n * 4 * (int64_t)sizeof(double);
-}
-
-int mcpc_roll_accumulate(int device, const float* rec, int32_t B, int32_t width, int32_t first, int32_t stride, int32_t n, int32_t transform,
-                         int32_t window, int32_t every, int64_t n_seen, double* s1, double* s2, float* hist, double* out_elem,
-                         double* out_pool, void* workspace, void* stream_) {
-    if (window < 2) return fail(MCPC_EINVAL, "roll: window=%d, must be at least 2", window);
-    if (every < 1) return fail(MCPC_EINVAL, "roll: every=%d, must be at least 1", every);
-    if (!s1) return fail(MCPC_EINVAL, "roll: s1 is null");
-    if (!s2) return fail(MCPC_EINVAL, "roll: s2 is null");
-    if (!hist) return fail(MCPC_EINVAL, "roll: hist is null");
-    if (!out_elem && !out_pool) return fail(MCPC_EINVAL, "roll: out_elem and out_pool are both null");
-    if (const int rc = roll_check_shape(B, width, n)) return rc;
-    if (const int rc = check_window("roll", rec, first, stride, n)) return rc;      // (n: checked with the shape already)
-    if (n_seen < 0) return fail(MCPC_EINVAL, "roll: n_seen=%lld, must not be negative", (long long)n_seen);
-    if (const int rc = check_transform("roll", transform)) return rc;
-    RollParams P{};
-    P.rows = roll_rows(n_seen, n, window, every, &P.emit0);
-    if (out_pool && P.rows > 0 && !workspace)
-        return fail(MCPC_EINVAL, "roll: workspace is null with out_pool set (mcpc_roll_workspace_bytes: %lld bytes)",
-                    (long long)mcpc_roll_workspace_bytes(B, width, n));
-    if (n == 0 && n_seen > 0) return MCPC_OK;                     // nothing to add
-    hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipSetDevice(device));
-    const RecWindow w = rec_window(rec, (int64_t)B * width, first, stride, n);
-    if (n == 0) {                                                 // a stream that starts empty
-        HIP_TRY(hipMemsetAsync(s1, 0, (size_t)w.E * sizeof(double), stream));
-        HIP_TRY(hipMemsetAsync(s2, 0, (size_t)w.E * sizeof(double), stream));
-        return MCPC_OK;
-    }
-    P.rec = w.r0; P.E = w.E; P.row_step = w.row_step; P.n_seen = n_seen; P.n = n; P.W = window; P.every = every;
-    P.slot0 = (int32_t)(n_seen % window);
-    P.s1 = s1; P.s2 = s2; P.hist = hist; P.out_elem = out_elem; P.part = (double*)workspace;
-    if (roll_vec(P) == 4) roll_launch<4>(transform, P, out_pool, stream);
-    else roll_launch<1>(transform, P, out_pool, stream);
-    HIP_TRY(hipGetLastError());
-    return MCPC_OK;
-}
-
-int mcpc_probe_accumulate(int device, const float* rec, int32_t B, int32_t width, int32_t first, int32_t stride, int32_t n, const float* W,
-                          const float* bias, int32_t n_classes, int32_t link, double* psum, double* psumsq, int64_t* votes, double* entsum,
-                          int accumulate, void* stream_) {
-    if (!W) return fail(MCPC_EINVAL, "probe: W is null");
-    if (!psum) return fail(MCPC_EINVAL, "probe: psum is null");
-    if (!votes) return fail(MCPC_EINVAL, "probe: votes is null");
-    if (link != MCPC_PROBE_IDENTITY && link != MCPC_PROBE_SIGMOID && link != MCPC_PROBE_SOFTMAX)
-        return fail(MCPC_EINVAL, "probe: unknown link %d", link);
-    if (link == MCPC_PROBE_SOFTMAX && !entsum) return fail(MCPC_EINVAL, "probe: entsum is null with the softmax link");
-    if (const int rc = check_shape("probe", B, width)) return rc;
-    if (const int rc = check_window("probe", rec, first, stride, n)) return rc;
-    if (n_classes < 1 || n_classes > MCPC_PROBE_MAX_CLASSES)
-        return fail(MCPC_EINVAL, "probe: n_classes=%d outside 1..%d", n_classes, MCPC_PROBE_MAX_CLASSES);
-    if (n == 0 && accumulate) return MCPC_OK;                     // nothing to add
-    hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipSetDevice(device));
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(psum, 0, (size_t)B * n_classes * sizeof(double), stream));
-        if (psumsq) HIP_TRY(hipMemsetAsync(psumsq, 0, (size_t)B * n_classes * sizeof(double), stream));
-        HIP_TRY(hipMemsetAsync(votes, 0, (size_t)B * (n_classes + 1) * sizeof(int64_t), stream));
-        if (link == MCPC_PROBE_SOFTMAX) HIP_TRY(hipMemsetAsync(entsum, 0, (size_t)B * sizeof(double), stream));
-        return MCPC_OK;
-    }
-    ProbeParams P{};
-    const RecWindow w = rec_window(rec, (int64_t)B * width, first, stride, n);
-    P.rec = w.r0; P.W = W; P.bias = bias; P.row_step = w.row_step;
-    P.B = B; P.width = width; P.n = n; P.C = n_classes; P.accumulate = accumulate ? 1 : 0;
-    P.psum = psum; P.psumsq = psumsq; P.votes = votes; P.entsum = entsum;
-    probe_dispatch(link, P, stream);
-    HIP_TRY(hipGetLastError());
-    return MCPC_OK;
-}
-
-int mcpc_probe_records(int device, const float* rec, int32_t B, int32_t width, int32_t first, int32_t stride, int32_t n, const float* W,
-                       const float* bias, int32_t n_classes, int32_t link, float* out, void* stream_) {
-    if (!W) return fail(MCPC_EINVAL, "probe records: W is null");
-    if (!out) return fail(MCPC_EINVAL, "probe records: out is null");
-    if (link != MCPC_PROBE_IDENTITY && link != MCPC_PROBE_SIGMOID && link != MCPC_PROBE_SOFTMAX)
-        return fail(MCPC_EINVAL, "probe records: unknown link %d", link);
-    if (const int rc = check_shape("probe records", B, width)) return rc;
-    if (const int rc = check_window("probe records", rec, first, stride, n)) return rc;
-    if (n_classes < 1 || n_classes > MCPC_PROBE_MAX_CLASSES)
-        return fail(MCPC_EINVAL, "probe records: n_classes=%d outside 1..%d", n_classes, MCPC_PROBE_MAX_CLASSES);
-    if (n == 0) return MCPC_OK;                                   // no row to write
-    HIP_TRY(hipSetDevice(device));
-    ProbeParams P{};
-    const RecWindow w = rec_window(rec, (int64_t)B * width, first, stride, n);
-    P.rec = w.r0; P.W = W; P.bias = bias; P.row_step = w.row_step;
-    P.B = B; P.width = width; P.n = n; P.C = n_classes; P.out = out;
-    probe_dispatch<true>(link, P, (hipStream_t)stream_);
-    HIP_TRY(hipGetLastError());
-    return MCPC_OK;
-}
-
-int mcpc_hist2d_accumulate(int device, const float* rec_x, int32_t width_x, const float* rec_y, int32_t width_y, int32_t B, int32_t first,
-                           int32_t stride, int32_t n, int32_t transform_x, int32_t transform_y, const int32_t* pairs, int32_t n_pairs,
-                           const float* edges_x, int32_t nx, const float* edges_y, int32_t ny, int32_t pool, int64_t* counts,
-                           int accumulate, void* stream_) {
-    if (!counts) return fail(MCPC_EINVAL, "hist2d: counts is null");
-    if (!edges_x) return fail(MCPC_EINVAL, "hist2d: edges_x is null");
-    if (!edges_y) return fail(MCPC_EINVAL, "hist2d: edges_y is null");
-    if (!pairs) return fail(MCPC_EINVAL, "hist2d: pairs is null");
-    if (B < 1) return fail(MCPC_EINVAL, "hist2d: B=%d, must be at least 1", B);
-    if (width_x < 1) return fail(MCPC_EINVAL, "hist2d: width_x=%d, must be at least 1", width_x);
-    if (width_y < 1) return fail(MCPC_EINVAL, "hist2d: width_y=%d, must be at least 1", width_y);
-    if (const int rc = check_window("hist2d", rec_x, first, stride, n)) return rc;
-    if (n > 0 && !rec_y) return fail(MCPC_EINVAL, "hist2d: rec_y is null with n=%d", n);
-    if (n_pairs < 1 || n_pairs > MCPC_HIST2D_MAX_PAIRS)
-        return fail(MCPC_EINVAL, "hist2d: n_pairs=%d outside 1..%d", n_pairs, MCPC_HIST2D_MAX_PAIRS);
-    if (nx < 1 || nx > MCPC_HIST2D_MAX_BINS) return fail(MCPC_EINVAL, "hist2d: nx=%d outside 1..%d", nx, MCPC_HIST2D_MAX_BINS);
-    if (ny < 1 || ny > MCPC_HIST2D_MAX_BINS) return fail(MCPC_EINVAL, "hist2d: ny=%d outside 1..%d", ny, MCPC_HIST2D_MAX_BINS);
-    if ((nx + 3) * (ny + 3) > MCPC_HIST2D_MAX_CELLS)
-        return fail(MCPC_EINVAL, "hist2d: (nx + 3) * (ny + 3) = %d cells, more than %d", (nx + 3) * (ny + 3), MCPC_HIST2D_MAX_CELLS);
-    if (pool != 0 && pool != 1) return fail(MCPC_EINVAL, "hist2d: pool=%d, must be 0 or 1", pool);
-    if (const int rc = check_transform("hist2d", transform_x)) return rc;
-    if (const int rc = check_transform("hist2d", transform_y)) return rc;
-    for (int i = 0; i < n_pairs; ++i) {
-        if (pairs[2 * i] < 0 || pairs[2 * i] >= width_x)
-            return fail(MCPC_EINVAL, "hist2d: pair %d: x column %d outside 0..%d", i, pairs[2 * i], width_x - 1);
-        if (pairs[2 * i + 1] < 0 || pairs[2 * i + 1] >= width_y)
-            return fail(MCPC_EINVAL, "hist2d: pair %d: y column %d outside 0..%d", i, pairs[2 * i + 1], width_y - 1);
-    }
-    for (int axis = 0; axis < 2; ++axis) {
-        const float* edges = axis ? edges_y : edges_x;
-        const char* name = axis ? "edges_y" : "edges_x";
-        for (int i = 0; i <= (axis ? ny : nx); ++i) {
-            if (!std::isfinite(edges[i])) return fail(MCPC_EINVAL, "hist2d: %s[%d] is not finite", name, i);
-            if (i > 0 && !(edges[i - 1] < edges[i]))
-                return fail(MCPC_EINVAL, "hist2d: %s are not strictly ascending at %d (%.9g, then %.9g)", name, i, (double)edges[i - 1],
-                            (double)edges[i]);
-        }
-    }
-    if (n == 0 && accumulate) return MCPC_OK;                     // nothing to add
-    hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipSetDevice(device));
-    const Hist2dPlan plan = hist2d_plan(B, width_x, width_y, n_pairs, nx, ny, pool, n > 0 ? n : 1);
-    const size_t out_bytes = (size_t)plan.slots * plan.cells * sizeof(int64_t);
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(counts, 0, out_bytes, stream));
-        return MCPC_OK;
-    }
-    const RecWindow wx = rec_window(rec_x, (int64_t)B * width_x, first, stride, n);
-    const RecWindow wy = rec_window(rec_y, (int64_t)B * width_y, first, stride, n);
-    Hist2dParams P{};
-    P.top_x = hist_key_table(edges_x, nx, P.key_x, kHist2dTable, &P.hi_x);
-    P.top_y = hist_key_table(edges_y, ny, P.key_y, kHist2dTable, &P.hi_y);
-    P.nx = nx; P.ny = ny;
-    for (int i = 0; i < n_pairs; ++i) { P.col[i][0] = pairs[2 * i]; P.col[i][1] = pairs[2 * i + 1]; }
-    P.n_pairs = n_pairs; P.B = B; P.wx = width_x; P.wy = width_y; P.G = plan.G; P.GL = plan.GL; P.n = n; P.seg = plan.seg;
-    P.chains_per = plan.chains_per; P.pool = pool;
-    P.exclusive = (!pool && plan.segments == 1) ? 1 : 0;
-    P.accumulate = accumulate ? 1 : 0;
-    P.slots = plan.slots; P.groups = plan.groups; P.step_x = wx.row_step; P.step_y = wy.row_step;
-    // workgroups that share a grid add into it with integer atomics: an overwriting call starts them from zero
-    if (!P.exclusive && !accumulate) HIP_TRY(hipMemsetAsync(counts, 0, out_bytes, stream));
-    hist2d_launch(transform_x, transform_y, wx.r0, wy.r0, P, plan, counts, stream);
-    HIP_TRY(hipGetLastError());
-    return MCPC_OK;
-}
-
-static int knn_check_shape(int64_t nq, int64_t nr, int32_t d, int32_t k) {
-    if (d < 1 || d > MCPC_KNN_MAX_DIM) return fail(MCPC_EINVAL, "knn: d=%d outside 1..%d", d, MCPC_KNN_MAX_DIM);
-    if (k < 1 || k > MCPC_KNN_MAX_K) return fail(MCPC_EINVAL, "knn: k=%d outside 1..%d", k, MCPC_KNN_MAX_K);
-    if (nq < 0 || nq > MCPC_KNN_MAX_ROWS) return fail(MCPC_EINVAL, "knn: nq=%lld outside 0..%lld", (long long)nq, (long long)MCPC_KNN_MAX_ROWS);
-    if (nr < 0 || nr > MCPC_KNN_MAX_ROWS) return fail(MCPC_EINVAL, "knn: nr=%lld outside 0..%lld", (long long)nr, (long long)MCPC_KNN_MAX_ROWS);
-    return MCPC_OK;
-}
-
-int64_t mcpc_knn_workspace_bytes(int64_t nq, int64_t nr, int32_t d, int32_t k) {
-    if (knn_check_shape(nq, nr, d, k)) return -1;
-    const KnnGeometry g = knn_geometry(nq, nr, d, k);
-    return g.n_splits * nq * g.kt * (int64_t)sizeof(float);
-}
-
-int mcpc_knn_accumulate(int device, const float* q, int64_t nq, const float* ref, int64_t nr, int32_t d, int32_t k, float* best,
-                        int32_t accumulate, void* workspace, int64_t workspace_bytes, void* stream_) {
-    if (const int rc = knn_check_shape(nq, nr, d, k)) return rc;
-    if (nq > 0 && !q) return fail(MCPC_EINVAL, "knn: q is null with nq=%lld", (long long)nq);
-    if (nq > 0 && !best) return fail(MCPC_EINVAL, "knn: best is null with nq=%lld", (long long)nq);
-    if (nr > 0 && !ref) return fail(MCPC_EINVAL, "knn: ref is null with nr=%lld", (long long)nr);
-    const KnnGeometry g = knn_geometry(nq, nr, d, k);
-    const int64_t need = g.n_splits * nq * g.kt * (int64_t)sizeof(float);
-    if (need > 0) {
-        if (!workspace) return fail(MCPC_EINVAL, "knn: workspace is null (mcpc_knn_workspace_bytes: %lld bytes)", (long long)need);
-        if (workspace_bytes < need)
-            return fail(MCPC_EINVAL, "knn: workspace of %lld bytes is too small, %lld needed", (long long)workspace_bytes, (long long)need);
-    }
-    if (nq == 0 || (nr == 0 && accumulate)) return MCPC_OK;      // nothing to write, or nothing to add
-    hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipSetDevice(device));
-    KnnParams P{};
-    P.q = q; P.ref = ref; P.nq = nq; P.nr = nr; P.d = d; P.k = k;
-    P.tiles_per_split = g.tiles_per_split; P.n_tiles = g.n_tiles; P.n_splits = g.n_splits;
-    P.part = (float*)workspace; P.best = best; P.accumulate = accumulate ? 1 : 0;
-    knn_dispatch(g, P, stream);
-    HIP_TRY(hipGetLastError());
-    return MCPC_OK;
-}
-
-static int loglik_check_shape(int64_t n_data, int64_t n_samp, int32_t width) {
-    if (width < 1) return fail(MCPC_EINVAL, "loglik: width=%d, must be at least 1", width);
-    if (n_data < 0 || n_data > MCPC_LOGLIK_MAX_ROWS)
-        return fail(MCPC_EINVAL, "loglik: n_data=%lld outside 0..%lld", (long long)n_data, (long long)MCPC_LOGLIK_MAX_ROWS);
-    if (n_samp < 0 || n_samp > MCPC_LOGLIK_MAX_ROWS)
-        return fail(MCPC_EINVAL, "loglik: n_samp=%lld outside 0..%lld", (long long)n_samp, (long long)MCPC_LOGLIK_MAX_ROWS);
-    return MCPC_OK;
-}
-
-int64_t mcpc_loglik_workspace_bytes(int64_t n_data, int64_t n_samp, int32_t width) {
-    if (loglik_check_shape(n_data, n_samp, width)) return -1;
-    return loglik_workspace_doubles(loglik_plan(n_data, n_samp, width), n_data, n_samp) * (int64_t)sizeof(double);
-}
-
-int mcpc_loglik_accumulate(int device, const float* y, int64_t n_data, const float* out, int64_t n_samp, int32_t width,
-                           int32_t loss_kind, double loss_var, double clamp, double* state, int32_t accumulate, void* workspace,
-                           int64_t workspace_bytes, void* stream_) {
-    if (const int rc = loglik_check_shape(n_data, n_samp, width)) return rc;
-    if (loss_kind != MCPC_LOSS_BERNOULLI && loss_kind != MCPC_LOSS_GAUSSIAN)
-        return fail(MCPC_EINVAL, "loglik: loss_kind=%d, expected MCPC_LOSS_GAUSSIAN (%d) or MCPC_LOSS_BERNOULLI (%d)", loss_kind,
-                    MCPC_LOSS_GAUSSIAN, MCPC_LOSS_BERNOULLI);
-    if (loss_kind == MCPC_LOSS_GAUSSIAN && !(loss_var > 0.0)) return fail(MCPC_EINVAL, "loglik: loss_var=%g, must be positive", loss_var);
-    if (!(clamp > 0.0)) return fail(MCPC_EINVAL, "loglik: clamp=%g, must be positive (+inf: none)", clamp);
-    if (n_data > 0 && !y) return fail(MCPC_EINVAL, "loglik: y is null with n_data=%lld", (long long)n_data);
-    if (n_data > 0 && !state) return fail(MCPC_EINVAL, "loglik: state is null with n_data=%lld", (long long)n_data);
-    if (n_samp > 0 && !out) return fail(MCPC_EINVAL, "loglik: out is null with n_samp=%lld", (long long)n_samp);
-    const LoglikPlan g = loglik_plan(n_data, n_samp, width);
-    const int64_t need = loglik_workspace_doubles(g, n_data, n_samp) * (int64_t)sizeof(double);
-    if (need > 0) {
-        if (!workspace) return fail(MCPC_EINVAL, "loglik: workspace is null (mcpc_loglik_workspace_bytes: %lld bytes)", (long long)need);
-        if (workspace_bytes < need)
-            return fail(MCPC_EINVAL, "loglik: workspace of %lld bytes is too small, %lld needed", (long long)workspace_bytes, (long long)need);
-    }
-    if (n_data == 0 || (n_samp == 0 && accumulate)) return MCPC_OK;      // nothing to write, or nothing to add
-    hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipSetDevice(device));
-    LoglikParams P{};
-    P.y = y; P.o = out; P.n_data = n_data; P.n_samp = n_samp; P.width = width;
-    P.gauss = loss_kind == MCPC_LOSS_GAUSSIAN ? 1 : 0;
-    P.accumulate = accumulate ? 1 : 0;
-    P.vec = (width % 4 == 0 && (uintptr_t)y % 16 == 0 && (uintptr_t)out % 16 == 0) ? 1 : 0;
-    P.clamp = clamp;
-    if (P.gauss) {
-        P.half_inv_var = 0.5 / loss_var;
-        P.cst = 0.5 * (double)width * log(2.0 * M_PI * loss_var);
-    }
-    P.tiles_per_group = g.tiles_per_group; P.n_stiles = g.n_stiles; P.groups = g.groups; P.ndpad = g.n_dtiles * 16;
-    P.part = (double*)workspace;
-    P.a = P.part + g.groups * P.ndpad * 4;
-    P.b = P.a + n_data;
-    P.state = state;
-    loglik_dispatch(g, P, stream);
-    HIP_TRY(hipGetLastError());
-    return MCPC_OK;
-}
 
 namespace {
 // The front the two evaluators share (mcpc_chain_energies, mcpc_prediction_errors).  What a call reads and launches over:

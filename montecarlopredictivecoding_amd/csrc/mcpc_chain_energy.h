@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "mcpc_step_math.h"
+#include "mcpc_steps_lw.h"      // the layer-wise forward tile (lw_job_gemm) and its job table
 
 namespace mcpc {
 
@@ -141,10 +142,7 @@ __global__ __launch_bounds__(kLwThreads) void mcpc_ce_kernel(const CeParams Q) {
     }
 }
 
-struct CeFinish {
-    int first[kMaxLatent + 1], count[kMaxLatent + 1];      // the jobs of Linear j in the table ([L]: the read-out), contiguous and ascending
-};
-
+// (CeFinish -- the jobs of Linear j in the table, contiguous and ascending -- is kept by the engine: mcpc_types.h)
 // out[row_base + row][:] = {loss, E_1..E_L, 0.., overall}
 __global__ __launch_bounds__(256) void mcpc_ce_finish_kernel(const double* __restrict__ part, double* __restrict__ out, const CeFinish F, int L,
                                                              int with_loss, int rows, int chunk, size_t row_base) {

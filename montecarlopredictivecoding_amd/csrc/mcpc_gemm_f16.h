@@ -36,11 +36,10 @@
 // zero-filled at launch and never written (KParams::lds_zero) instead of from behind their row -- so the excess products are exact
 // zeros WHATEVER the LDS holds behind the row (round 3's NaN: DESIGN section 8, tests/test_gpu_lds_poison.py).
 #pragma once
+#include "mcpc_types.h"       // kKB (k-depth of one fragment block), kFragBlock (u32x4 units per tile and k-block)
 
 namespace mcpc {
 
-constexpr int kKB = 32;                 // k-depth of one fragment block
-constexpr int kFragBlock = 2 * 64;      // u32x4 units per (tile, k-block): two fp16 planes of 64 lanes
 struct frag_t { u32x4 h, m; };          // one k-block of one tile as seen by a lane
 
 __device__ __forceinline__ frag_t frag_zero() { frag_t f; f.h = f.m = u32x4{0u, 0u, 0u, 0u}; return f; }

@@ -18,53 +18,22 @@
 //   * wave w owns activation tiles RA w .. RA w + RA - 1 against all TE error tiles: TE x RA accumulators (136 VGPRs at
 //     17 x 2), TE + RA LDS reads per TE x RA MFMAs;
 //   * bias sums (column sums of E) are taken from the LDS panel by the VALU (one thread per column), not by extra MFMAs.
+//
+// The kernels only: their arguments, forms and LDS sizes -- what the planner needs -- are in mcpc_heb_forms.h.  mcpc_reduce_jobs_kernel and
+// mcpc_dw_kernel are not templates, so ONE translation unit includes this header: mcpc_flush.hip.
 #pragma once
 
+#include "mcpc_types.h"
+#include "mcpc_gemm_f16.h"       // split2_pair, mfma4, scale_exp_for_max, pow2i
+#include "mcpc_heb_forms.h"
+
 namespace mcpc {
-
-constexpr int kHebKB = 32;           // spilled rows per stage
-constexpr int kHebThreads = 512;
-
-struct HebArgs {
-    const float* E;                  // [rows][ne]   spilled errors (row stride ne: padded width)
-    const float* A;                  // [rows][na]   spilled activations
-    float* slab;                     // [ksplit][ne][na]
-    float* slab_b;                   // [ksplit][ne]
-    int rows, ne, na;                // rows % 32 == 0; ne, na multiples of 16
-    int rows_per_split;              // multiple of 32
-    int n_mt, n_nt, ksplit;          // error-tile groups, activation-tile groups, K splits: grid = n_mt * n_nt * ksplit workgroups
-    int e_col_base;                  // first E column of this launch (a Linear may be covered by launches of different TE)
-    const unsigned* e_max;           // mcpc_heb7_kernel: bit pattern of the largest |value| in the E image of this segment, and in the A image:
-    const unsigned* a_max;           //   the powers of two its fp16 operands are scaled by (written by the step kernels: KParams::spillmax)
-};
 
 #ifndef MCPC_HEB_LD_AUX
 #define MCPC_HEB_LD_AUX 0          // cache policy of the spill reads (0 plain, 1 sc0, 2 nt, 16 sc1, 18 nt sc1): the learning call runs
                                    // within 0.2 us per step of itself with any of them (scripts/lib_ab.sh), so the reads are not what
                                    // costs the step kernel beside it its L2 hits (0.82 against 0.95-0.99 without a flush)
 #endif
-#ifndef MCPC_HEB_LDS_PAD
-#define MCPC_HEB_LDS_PAD 16        // floats added to a 256-float panel row in LDS (0: the linear image of round 2, for A/B runs)
-#endif
-constexpr int heb_lds_stride(int row_floats) { return row_floats == 256 ? row_floats + MCPC_HEB_LDS_PAD : row_floats; }
-// dynamic LDS of mcpc_heb_kernel<TE, RA, *>: two stages of both panels (host side: the launch, mcpc_api.hip)
-constexpr int heb_lds_bytes(int te, int ra) { return 2 * kHebKB * (heb_lds_stride(16 * te) + heb_lds_stride(16 * 8 * ra)) * (int)sizeof(float); }
-
-// The <TE, RA, SWAPPED> forms BOTH tiled kernels are instantiated for, listed once: the planner resolves every launch of a flush to an
-// index into this list (mcpc_plan.h: plan_flush), the executor's kernel table is built from it (mcpc_api.hip).
-#define MCPC_HEB_FORMS(X) X(17, 2, false) X(17, 1, false) X(16, 2, false) X(16, 1, false) X(8, 2, false) X(8, 1, false) \
-                          X(1, 2, true) X(2, 2, true) X(4, 2, true)
-struct HebForm { int te, ra; bool swapped; };
-#define MCPC_HEB_FORM_ROW(te, ra, sw) {te, ra, sw},
-constexpr HebForm kHebForms[] = {MCPC_HEB_FORMS(MCPC_HEB_FORM_ROW)};
-#undef MCPC_HEB_FORM_ROW
-constexpr int kNumHebForms = (int)(sizeof(kHebForms) / sizeof(kHebForms[0]));
-constexpr int heb_form_index(int te, int ra, bool swapped) {            // -1: no such instantiation
-    for (int i = 0; i < kNumHebForms; ++i)
-        if (kHebForms[i].te == te && kHebForms[i].ra == ra && kHebForms[i].swapped == swapped) return i;
-    return -1;
-}
-
 __device__ __forceinline__ void heb_glds16(const float* gsrc, float* lds_dst) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
                                      (__attribute__((address_space(3))) void*)lds_dst, 16, 0, MCPC_HEB_LD_AUX);
@@ -241,12 +210,6 @@ __global__ __launch_bounds__(kHebThreads, 2) void mcpc_heb_kernel(const HebArgs 
 //     coalesced float4 loads -- and writes one dword per unit and plane: k-slot pair (2c, 2c+1) = rows (c, 16 + c).  The MFMA's k order
 //     is free as long as both operands use it, and with the 80-byte unit stride the 32 lanes of a ds_write_b32 group hit 32 different
 //     banks (no conflicts), as do the 16 lanes of the operand's ds_read_b128.
-constexpr int kHeb7KB = 32;            // spilled rows per stage = K of one bf16 MFMA = two row tiles
-constexpr int kHeb7LD = 40;            // bf16 elements between the rows of two units in an LDS plane: 32 of data + 8 of padding (80 B)
-// dynamic LDS of mcpc_heb7_kernel<TE, *, *>: two plane buffers + the bias sums + every wave's transpose scratch for one activation tile
-// (2 row tiles x 4 x 17 float4) (host side: the launch, mcpc_api.hip)
-constexpr int heb7_lds_bytes(int te) { return 2 * 2 * 16 * te * kHeb7LD * 2 + 16 * te * (int)sizeof(float) + 8 * 2 * 272 * (int)sizeof(float); }
-
 // SWAPPED: the launch computes the TRANSPOSED product for a Linear with a narrow input (the E slot holds its activations, the A slot
 // its errors); the bias sums (column sums of the errors) then come from the A operand, and the reduction writes the slab back transposed.
 template <int TE, int RA, bool SWAPPED = false>
@@ -497,21 +460,6 @@ __global__ __launch_bounds__(kHebThreads, 2) void mcpc_heb7_kernel(const HebArgs
     }
 }
 
-// ---- fixed-order slab reduction for every Linear of a flush in ONE launch ---------------------------------------------
-struct ReduceJob {
-    const float* slab;     // [ksplit][n]
-    float* dst;            // [n]
-    int n, ksplit;
-    float sign;
-    int tr_cols, tr_ld;    // tr_cols > 0: the slab holds the transposed matrix [n / tr_cols][tr_cols]; element idx goes to
-                           // dst[(idx % tr_cols) * tr_ld + idx / tr_cols]
-};
-constexpr int kMaxReduceJobs = 2 * (kMaxLatent + 1);
-struct ReduceJobs {
-    ReduceJob job[kMaxReduceJobs];
-    int n_jobs;
-};
-
 // dst[i] += sign * sum_k slab[k][i]; k ascending in groups of 8 independent loads -> bitwise reproducible.  blockIdx.y = job.
 // Short vectors with many splits (bias slabs) take the wide form: the block's 4 waves each sum every 4th split of the same
 // 64 elements, partial sums added in wave order through LDS.
@@ -549,6 +497,100 @@ __global__ __launch_bounds__(256) void mcpc_reduce_jobs_kernel(const ReduceJobs 
         for (; k < jb.ksplit; ++k) s += __builtin_nontemporal_load(jb.slab + (size_t)k * n + idx);
         const size_t di = jb.tr_cols > 0 ? (idx % jb.tr_cols) * (size_t)jb.tr_ld + idx / jb.tr_cols : idx;
         jb.dst[di] += jb.sign * s;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The first K3, kept for the Linears the tiled kernels above do not take (FlushLaunch::family == HEB_DW): split-K Hebbian GEMM.  slab[ks][u][i] = sum_{r in split ks} E[r][u] * A[r][i].
+// Operands are row-major [rows][npad]; each lane loads 16 B = 4 consecutive columns of one row and
+// feeds component j to MFMA tile j whose rows/cols are the columns {base + 4*lane16 + j}: the
+// column permutation lives only in the epilogue index, loads stay 256 B-contiguous per row.
+// Wave tile = 64 x 64 outputs (4x4 MFMA tiles), one wave tile per wave, 4 waves per workgroup.
+__global__ __launch_bounds__(256, 2) void mcpc_dw_kernel(const float* __restrict__ E, const float* __restrict__ A,
+                                                      float* __restrict__ slab, float* __restrict__ slab_b,
+                                                      int rows, int ne, int na, int rows_per_split) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int tiles_a = (na + 63) / 64, tiles_e = (ne + 63) / 64;
+    const int wt = blockIdx.x * 4 + wave;
+    if (wt >= tiles_a * tiles_e) return;
+    const int te = wt / tiles_a, ta = wt % tiles_a;
+    const int m = lane & 15, q = lane >> 4;
+    const int ue = 64 * te + 4 * m, ua = 64 * ta + 4 * m;      // this lane's 4 columns of E / A
+    const bool ve = ue < ne, va = ua < na;
+    const bool with_bias = (ta == 0);                           // wave-uniform: these waves also sum E's columns
+    const int r0 = blockIdx.y * rows_per_split;
+    const int r1 = min(rows, r0 + rows_per_split);
+    if (r0 >= r1) return;
+    f32x4 acc[4][4], accb[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        accb[i] = splat(0.f);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = splat(0.f);
+    }
+    const f32x4 z = splat(0.f);
+    const float* Ep = E + (size_t)q * ne + ue;
+    const float* Ap = A + (size_t)q * na + ua;
+    // one block = 16 spilled rows = 4 MFMA k-steps; operands of block b+1 are requested before the 64 MFMAs
+    // of block b (two named register sets, steady-state loop free of conditional loads)
+    f32x4 eA[4], aA[4], eB[4], aB[4];
+#define DW_LOAD(e_, a_, r_)                                                                     \
+    do {                                                                                        \
+        _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                         \
+            e_[k] = ve ? ld4s(Ep + (size_t)((r_) + 4 * k) * ne) : z;                            \
+            a_[k] = va ? ld4s(Ap + (size_t)((r_) + 4 * k) * na) : z;                            \
+        }                                                                                       \
+    } while (0)
+#define DW_COMPUTE(e_, a_)                                                                      \
+    do {                                                                                        \
+        _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                         \
+            const float ev[4] = {e_[k].x, e_[k].y, e_[k].z, e_[k].w};                           \
+            const float av[4] = {a_[k].x, a_[k].y, a_[k].z, a_[k].w};                           \
+            _Pragma("unroll") for (int i = 0; i < 4; ++i)                                       \
+                _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(ev[i], av[j], acc[i][j]); \
+            if (with_bias) {                                                                    \
+                _Pragma("unroll") for (int i = 0; i < 4; ++i) accb[i] = mfma16(ev[i], 1.0f, accb[i]); \
+            }                                                                                   \
+        }                                                                                       \
+    } while (0)
+    const int nblk = (r1 - r0) / 16;      // rows_per_split and rows are multiples of 16
+    DW_LOAD(eA, aA, r0);
+    int b = 0;
+    for (; b + 2 < nblk; b += 2) {
+        DW_LOAD(eB, aB, r0 + 16 * (b + 1));
+        __builtin_amdgcn_sched_barrier(0);
+        DW_COMPUTE(eA, aA);
+        __builtin_amdgcn_sched_barrier(0);
+        DW_LOAD(eA, aA, r0 + 16 * (b + 2));
+        __builtin_amdgcn_sched_barrier(0);
+        DW_COMPUTE(eB, aB);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if (nblk - b == 2) {
+        DW_LOAD(eB, aB, r0 + 16 * (b + 1));
+        DW_COMPUTE(eA, aA);
+        DW_COMPUTE(eB, aB);
+    } else {
+        DW_COMPUTE(eA, aA);
+    }
+#undef DW_LOAD
+#undef DW_COMPUTE
+    // C layout of tile (i,j): row 4q+reg -> E column 64te + 4(4q+reg) + i ; col m -> A column 64ta + 4m + j
+    float* out = slab + (size_t)blockIdx.y * ne * na;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const int u = 64 * te + 4 * (4 * q + reg) + i;
+            if (u < ne && va) {
+                f32x4 v;
+                v.x = acc[i][0][reg]; v.y = acc[i][1][reg]; v.z = acc[i][2][reg]; v.w = acc[i][3][reg];
+                st4(out + (size_t)u * na + ua, v);
+            }
+            // bias partial: every column of accb[i] holds sum_r E[r][u]; column 0 (m == 0) writes it
+            if (with_bias && m == 0 && u < ne) slab_b[(size_t)blockIdx.y * ne + u] = accb[i][reg];
+        }
     }
 }
 

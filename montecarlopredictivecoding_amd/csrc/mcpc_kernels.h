@@ -4,213 +4,17 @@
 //                         one workgroup = 16 chains (one MFMA column tile), all layers, weights streamed from L2 in
 //                         MFMA-fragment order, state in HBM/L2 (padded), activations/errors in LDS.
 //                         replaces reference pc_trainer.py:733-918 + utils/model.py:35-44 per step.
-// K3  mcpc_dw_kernel      Hebbian sums  G[u][i] = sum_r E[r][u] * A[r][i]  over spilled (error,
-//                         activation) rows, split-K with deterministic slab reduction.
-//                         replaces the parameter part of overall.backward(), pc_trainer.py:862.
+// and the small kernels around it: weight packing, target images, padding, mu_1, Linear 0's Hebbian sums, energy reduction, gradient
+// export, the normals.  (K3, the Hebbian flush of the Linears j >= 1, is a translation unit of its own: mcpc_hebbian.h, mcpc_flush.hip.)
+// The parameter structs, table entries and tile shapes these kernels and the host agree on are in mcpc_types.h; the other step-kernel
+// forms (mcpc_steps_ws2.h, mcpc_steps_u.h, mcpc_steps_lw.h) build on this header.  Non-template kernels are defined here, so ONE
+// translation unit includes it: mcpc_api.hip.
 #pragma once
-#include "mcpc_device.h"
-#include "../../include/mcpc.h"
+#include "mcpc_types.h"
 #include "mcpc_step_math.h"
+#include "mcpc_gemm_f16.h"
 
 namespace mcpc {
-
-constexpr int kMaxLatent = MCPC_MAX_LATENT;
-constexpr int kBatchPad = 32;     // the batch is padded to a multiple of this (plan_engine: Bpad); a workgroup owns 16 chains = one MFMA column tile
-constexpr int kWaves = 4;         // waves per workgroup of the default variant; kMaxWaves bounds the LDS scratch
-constexpr int kMaxWaves = 8;
-constexpr int kThreads = kWaves * 64;
-constexpr int kNT = 4;            // unit tiles per wave per phase with 4 waves (2 with 8 waves): a phase hands out 16 tiles
-constexpr int kChunkTiles = 16;   // read-out units processed per chunk = 256
-constexpr int kLdPad = 4;         // LDS row padding (floats)
-constexpr int kEnergyCols = kMaxLatent + 2;   // loss, E_1..E_L(max), overall
-
-struct KLayer {
-    float* x;              // state [Bpad][npad]
-    float* m;              // Adam exp_avg    [Bpad][npad]
-    float* v;              // Adam exp_avg_sq [Bpad][npad]
-    float* xgrad;          // gradients-only mode: [B][n] (unpadded, caller's tensor)
-    float* rec;            // trajectory records [rec_count][B][n] (unpadded) or null
-    float* spill_e;        // l>=1: [slots][Bpad][npad] errors;  l==0: running sum of e_1 [Bpad][npad]
-    float* spill_a;        // [slots][Bpad][npad] activations f(x_l)
-    int spill_e_tm, spill_a_tm;   // 1: that image is TILE-MAJOR (spill_offset): what the fp16 Hebbian kernel reads (mcpc_heb7_kernel); 0: row-major
-    const float* ext_noise;// [n_steps][B][n] or null
-    const f32x4* Wf;       // l>=1: packed forward weights of Linear l  [ntiles][nkb_in][64]
-    const f32x4* Wb;       // l>=1: packed backward weights of Linear l [ntiles(l-1)][ntiles][64]
-    const float* bias;     // l>=1: padded bias [npad]
-    int n, npad, ntiles;   // units, padded to 16, npad/16
-    int act;
-    float ecoef;
-    int lds_a, lds_e;      // float offsets of FX_l / E_l in LDS
-    int ld;                // LDS row stride (floats) = npad + kLdPad
-    int lds_x;             // KParams::xl: float offset of the state rows X_l (row stride ld)
-    int lds_bias;          // KParams::xl: float offset of the bias row [npad] (l >= 1) / of the mu_1 rows (l == 0, row stride ld)
-};
-
-struct KHead {
-    const f32x4* Wf;       // [ntiles][nkb_in][64]
-    const f32x4* Wb;       // [ntiles(L-1)][ntiles][64]
-    const float* bias;     // [npad]
-    const float* y;        // padded target [Bpad][npad]
-    const float* ytile;    // the same image tile-major (tile_major_offset): what the lean read-out epilogue reads of an fp32 target
-    const uint32_t* ybits; // the same bit-packed, [Bpad][ywords] (bit u & 31 of word u >> 5 = y[chain][u]); valid iff *y_binary
-    const int* y_binary;   // device flag set by mcpc_bind_target: every target value is exactly 0.0f or 1.0f
-    const int* y_bounded;  // device flag set by mcpc_bind_target: every target value lies in [-1, 2] (headb_fixed_exp)
-    int ywords;            // words per chain = ceil(npad / 32)
-    float* rec_out;        // [rec_count][B][n] or null
-    float* spill_e;        // [slots][Bpad][npad]
-    int spill_tm;          // 1: tile-major (see KLayer::spill_e_tm)
-    int n, npad, ntiles;
-    int loss_kind;
-    float inv_var;
-    int mask_start;
-    int lds_eo;            // float offset of the read-out error chunk
-    int ld;                // its row stride = kChunkTiles*16 + kLdPad
-    int lds_bias;          // KParams::xl: float offset of the bias row [npad]
-    int lds_yw;            // KParams::xl: float offset of the bit-packed target rows [chains][ywords]; < 0 (unified-wave kernel, a plan without
-                           // the room): they stay in global memory
-};
-
-// One entry of the per-step phase table (built on the host, identical for every step):
-//   [prologue loads] -> acc = (from accb | 0) -> GEMM over nkb k-blocks -> [acc -> accb] -> epilogue -> [barrier]
-enum : int { PH_FWD = 0, PH_HEADF = 1, PH_HEADB = 2, PH_BWD = 3, PH_ENERGY = 4, PH_NOP = 5 };   // (PH_NOP: unified-wave kernel, a row without work)
-enum : int { PHF_ACC_FROM_B = 1, PHF_ACC_TO_B = 2, PHF_SYNC = 4, PHF_MU1 = 8 };
-struct KPhase {
-    const void* A;         // packed weight fragments of this GEMM (unused when nkb == 0): layout of the GEMM core in use
-    int type;              // PH_*
-    int layer;             // FWD: layer whose prediction error is produced; BWD: layer whose x is updated
-    int tile0, ntiles;     // output unit tiles of the phase; wave w owns tiles tile0 + w + 4 i
-    int a_tile_stride;     // 16-byte units between the fragments of consecutive output tiles
-    int a_off0;            // 16-byte offset of the first k-block of the k-window
-    int nkb;               // k-blocks of kKB (0: no GEMM -- top-layer pass, update without back-projection)
-    int kw;                // valid k width of the B rows (a multiple of 16 in (32 (nkb - 1), 32 nkb]): B lanes beyond it read as zeros
-    int b_lds, ldb;        // B operand: LDS float offset and row stride
-    int flags;             // PHF_*
-    float sign;            // BWD: g = e + sign * f'(x) * back
-    int out_lds, out_ld;   // HEADF: LDS offset / row stride of the e_o chunk this phase writes
-    int dep_e, dep_g;      // wave-specialised kernels: entry whose completion by all E / all G waves must precede (-1: none;
-                           // in-place variant: an index above the entry's own refers to the previous step)
-    int a_lin;             // Linear whose packed weights A points into: KParams::wexp[a_lin] is the exponent they were scaled by
-    int rot;               // in-place variant: pair k owns tiles tile0 + ((k + rot) & 3) + 4 i (balances uneven chunks);
-                           // unified-wave kernel: the tile stride of a wave's row -- its tiles are tile0 + rot i, i < ntiles
-    int dep_se;            // in-place variant: entry all E waves must have passed before this entry's block is STORED (its
-                           // LDS rows are still read by their epilogues); dep_g is waited for at the same point
-    int next_g;            // in-place variant: the next entry (cyclic) in which the GEMM waves have work -- they visit no other
-    int b_row, o_row;      // in-place variant: id of the B operand's / of the produced operand's row-exponent words (KParams::lds_rowexp;
-                           // -1: none -- the GEMM wave scans the row itself)
-};
-
-// Phase descriptors are fetched through the constant address space: wave-uniform s_load_* on the scalar cache.
-// (Through a generic pointer hipcc emits a vector load + readfirstlane and an `s_waitcnt vmcnt(0)` that drains the
-// weight-fragment prefetch at every phase boundary, and keeps the descriptor in scratch.)
-__device__ __forceinline__ KPhase load_phase(const KPhase* tbl, int p) {
-    typedef __attribute__((address_space(4))) const int cint;
-    cint* w = (cint*)(tbl + p);
-    union { KPhase ph; int v[sizeof(KPhase) / 4]; } u;
-#pragma unroll
-    for (int i = 0; i < (int)(sizeof(KPhase) / 4); ++i) u.v[i] = w[i];
-    return u.ph;
-}
-
-struct KParams {
-    KLayer layer[kMaxLatent];
-    KHead head;
-    const KPhase* phases;  // [n_phases] in device memory
-    const int* wexp;       // [kMaxLatent + 1]: per Linear, the power of two its packed weights are scaled by (mcpc_wexp_kernel)
-    unsigned* spillmax;    // [kSpillTensors] bit patterns of the largest |value| spilled per tensor in this Hebbian segment (null: no spill):
-                           // the fp16 Hebbian GEMM scales its operands by powers of two taken from them (mcpc_hebbian.h)
-    int lds_spillmax;      // LDS float offset of the workgroup's own maxima (kSpillTensors words, zero at launch)
-    int n_phases;
-    int stagger_cycles;    // workgroups >= 256 (the second resident on a CU) start this many cycles late
-    const float* mu1;      // prediction of the top latent layer [Bpad][npad_0] (inputs W0^T + b0)
-    const float* adam_coef;// [n_steps][2]: -step_size = -lr/(1-b1^t), sqrt(1-b2^t)
-    double* epart;         // [energy rows][nWG][kEnergyCols] per-workgroup partial sums
-    int L, has_head;
-    int B, Bpad;
-    int T, t0, n_steps;
-    int xopt, update_x;
-    float lr, beta2, omb1, omb2, eps;
-    int noise_mode;
-    float noise_scale;     // sqrt(noise_var*lr)
-    uint64_t seed, step_base, chain_base;
-    int acc_begin, acc_end, spill_t0;   // spill slot of step t = t - spill_t0 when acc_begin <= t < acc_end
-    int energy_mode;
-    int rec_begin, rec_stride, rec_count;
-    int lds_red;           // float offset of the energy reduction scratch [2][kMaxLatent+1][kMaxWaves]
-    int lds_ws_sync;                 // wave-specialised kernel: float offset of the progress counters
-    int ws_prio;                     // 1: epilogue waves run at raised static priority
-    int* err;                        // device error word (bit 0/1: a progress-counter wait ran out)
-    // in-place kernel, round schedule (setup_rounds / run_round_cycle in mcpc_api.hip): workgroup -> 16-chain unit and the launches of
-    // the cycle that unit has already taken part in
-    const int* wg_list;              // [gridDim.x] unit index, or null: unit = blockIdx.x
-    const int* wg_rel;               // [gridDim.x] launches of this cycle the unit has already run, or null
-    int rr_q;                        // steps per launch of the cycle
-    int epart_slots;                 // in-place kernel: energy partials are indexed by 16-chain tile, this many per row
-    int lean_ok;                     // in-place kernel: every [Bpad][npad] image is < 4 GiB and Bpad < 2^24 (32-bit lane offsets)
-    const void* dummy;               // 4 KiB of valid device memory: what the branch-free fragment prefetch reads for entries without a GEMM
-    int xl;                          // in-place kernel, 16-chain plans whose LDS has the room: the state x_l, the biases, mu_1 and the bit-packed
-                                     // target of the workgroup's chains live in LDS for the whole launch (mcpc_ws2_lean.h: XL)
-    int spill_sys;                   // Hebbian spill stores at system scope (write-through): shards whose spill per step is far beyond the L2s
-    int lds_floats;                  // floats of dynamic LDS of this plan (cleared once per launch: see mcpc_gemm_f16.h, k ranges)
-    int g_first;                     // in-place variant: first table entry with work for the GEMM waves (-1: none)
-    int lds_rowexp;                  // float offset of kRowExpIds x 16 words: per B operand and chain row, (generation << 8) | biased exponent of
-                                     // the row's largest |value|, kept by the epilogue waves that WRITE the rows (rowexp_track below)
-    int lds_zero;                    // float offset of 16 floats of the plan that nothing writes after that: what the GEMM core's lanes beyond a
-                                     // ragged k range read (mcpc_gemm_f16.h)
-    unsigned long long* clk;         // profiling only (else null): [0] += shader cycles (s_memtime), [1] += 100 MHz wall ticks (s_memrealtime)
-                                     // of one wave of workgroup 0 over the launch -- their ratio is the shader clock under THIS load
-#ifdef MCPC_STAMPS
-    unsigned long long* dbg;   // diagnostic build only: [nwg][kWaves][16] cycle sums per phase
-#endif
-};
-
-// Layout of images only the epilogues read or write -- Adam's moments m_l, v_l, the tile-major copy of an fp32 target: TILE-MAJOR --
-// the 16 chains x 16 units a wave's float4 access covers are one contiguous KiB, in lane order, instead of sixteen 64-byte pieces of
-// sixteen rows.  A row-major access costs the CU's vector-memory path about 100 cycles per wave instruction, a contiguous one a
-// fraction of that, and that path is what the step kernel is bound by: the MAP warm-up (Adam on x) took 62.4 us
-// per step at cfg-M with row-major moments against 52.0 for SGD with the kick.
-// Float offset of units u0 .. u0+3 (u0 a multiple of 4) of `chain` in an image of npad-wide rows:
-__device__ __forceinline__ size_t tile_major_offset(int chain, int u0, int npad) {
-    return (((size_t)(chain >> 4) * (npad >> 4) + (u0 >> 4)) * 64 + (chain & 15) + 16 * ((u0 >> 2) & 3)) * 4;
-}
-
-// Float offset of units u0 .. u0+3 of `row` in a spilled image [rows][npad]: row-major, or tile-major (tile_major_offset) -- the layout in
-// which the float4-per-lane store of an epilogue wave (16 rows x 16 units) is one contiguous KiB and which mcpc_heb7_kernel reads.
-__device__ __forceinline__ size_t spill_offset(int tm, size_t row, int u0, int npad) {
-    return tm ? (((row >> 4) * (size_t)(npad >> 4) + (size_t)(u0 >> 4)) * 64 + (row & 15) + 16 * ((u0 >> 2) & 3)) * 4
-              : row * (size_t)npad + (size_t)u0;
-}
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-// ---- largest |value| per spilled tensor (for the Hebbian GEMM's operand scaling) ---------------------------------------------------------
-// tensor ids: activations A_l = l, errors E_l = kMaxLatent + l, read-out errors E_o = 2 kMaxLatent
-constexpr int kSpillTensors = 16;
-__host__ __device__ __forceinline__ int spill_id_a(int l) { return l; }
-__host__ __device__ __forceinline__ int spill_id_e(int l) { return kMaxLatent + l; }
-constexpr int kSpillIdEo = 2 * kMaxLatent;
-__device__ __forceinline__ float absmax4(float m, f32x4 v) {
-    return fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-}
-// the lanes' maxima over what an epilogue call spilled of one tensor -> the workgroup's running maximum of that tensor in LDS
-// (non-negative floats order like their bit patterns)
-__device__ __forceinline__ void spill_track(float* lds_max, int id, float lane_max, int lane) {
-    const float m = wave_max(lane_max);
-    if (lane == 0) atomicMax(reinterpret_cast<unsigned*>(lds_max) + id, __float_as_uint(m));
-}
-// a wave that has finished its steps adds the workgroup's maxima (as far as they are known) to the segment's
-__device__ __forceinline__ void spill_max_publish(unsigned* gmax, const float* lds_max, int lane) {
-    if (gmax != nullptr && lane < kSpillTensors) {
-        const unsigned bits = reinterpret_cast<const volatile unsigned*>(lds_max)[lane];
-        if (bits != 0u) atomicMax(gmax + lane, bits);
-    }
-}
-
-// streamed once per step (state, targets, spills): nontemporal, so the per-XCD L2 (4 MiB) keeps the
-// 2.2 MB of packed weights every workgroup re-reads instead of cycling 4 MB of chain data through it
-__device__ __forceinline__ f32x4 ld4s(const float* p) { return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p)); }
-__device__ __forceinline__ void st4s(float* p, f32x4 v) { __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p)); }
-__device__ __forceinline__ f32x4 splat(float v) { f32x4 r = {v, v, v, v}; return r; }
-
 
 // Request the operands of a phase's epilogue (x, targets: streamed from HBM/MALL; mu1, bias from L2; E from LDS)
 // into pa/pb, ahead of the phase's GEMM.  Branch-free on purpose: the entry type only selects ADDRESSES, every slot
@@ -257,9 +61,6 @@ __device__ __forceinline__ void issue_epilogue_loads(const KParams& P, const KPh
 // fp32 products on the fp16 matrix pipe with per-row power-of-two scaling (mcpc_gemm_f16.h): frag_t, kKB (k-depth of a fragment block),
 // kFragBlock (16-byte units per tile and block), frag_zero, load_frag, gemm_tiles, GemmScale, prefetch_first_blocks.  The B operand is read
 // from fp32 LDS rows.  (Rounds 1-2 ran v_mfma_f32_16x16x4_f32 here, rounds 3-4 six bf16 MFMAs per product: git history)
-}  // namespace mcpc
-#include "mcpc_gemm_f16.h"
-namespace mcpc {
 
 // the weights' exponent of a phase's Linear, through the constant address space (a wave-uniform s_load like the phase descriptors)
 __device__ __forceinline__ int load_wexp(const int* wexp, int lin) {
@@ -288,11 +89,7 @@ __device__ __forceinline__ bool headf_planes(int loss_kind, bool bounded, int ou
 // consumer's dependency on the producing entries is (the atomic precedes the wave's progress-counter store in LDS order), and it is
 // protected against the next generation's writers exactly as the rows are.  The exponent is the one gemm_row_exp computes (the field of
 // the maximum is the maximum of the fields; v_max skips NaN in both), so kernel forms with and without it agree bitwise.
-constexpr int kRowExpIds = 16;                         // FX_0..5, E_0..5, ring slots 0..3
-constexpr int kRowExpFloats = kRowExpIds * 16;
-__device__ __host__ __forceinline__ int rowexp_fx(int l) { return l; }
-__device__ __host__ __forceinline__ int rowexp_e(int l) { return kMaxLatent + l; }
-__device__ __host__ __forceinline__ int rowexp_ring(int r) { return 2 * kMaxLatent + r; }
+// (the ids of the words -- kRowExpIds, rowexp_fx / rowexp_e / rowexp_ring -- are the planner's too: mcpc_types.h)
 __device__ __forceinline__ void rowexp_track(float* lds_rowexp, int id, int row, float lane_max, unsigned gen) {
     atomicMax(reinterpret_cast<unsigned*>(lds_rowexp) + 16 * id + row, (gen << 8) | (__float_as_uint(lane_max) >> 23));
 }
@@ -797,100 +594,6 @@ __global__ void mcpc_mu1_kernel(const float* __restrict__ inputs, const float* _
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// K3: split-K Hebbian GEMM.  slab[ks][u][i] = sum_{r in split ks} E[r][u] * A[r][i].
-// Operands are row-major [rows][npad]; each lane loads 16 B = 4 consecutive columns of one row and
-// feeds component j to MFMA tile j whose rows/cols are the columns {base + 4*lane16 + j}: the
-// column permutation lives only in the epilogue index, loads stay 256 B-contiguous per row.
-// Wave tile = 64 x 64 outputs (4x4 MFMA tiles), one wave tile per wave, 4 waves per workgroup.
-__global__ __launch_bounds__(256, 2) void mcpc_dw_kernel(const float* __restrict__ E, const float* __restrict__ A,
-                                                      float* __restrict__ slab, float* __restrict__ slab_b,
-                                                      int rows, int ne, int na, int rows_per_split) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int tiles_a = (na + 63) / 64, tiles_e = (ne + 63) / 64;
-    const int wt = blockIdx.x * 4 + wave;
-    if (wt >= tiles_a * tiles_e) return;
-    const int te = wt / tiles_a, ta = wt % tiles_a;
-    const int m = lane & 15, q = lane >> 4;
-    const int ue = 64 * te + 4 * m, ua = 64 * ta + 4 * m;      // this lane's 4 columns of E / A
-    const bool ve = ue < ne, va = ua < na;
-    const bool with_bias = (ta == 0);                           // wave-uniform: these waves also sum E's columns
-    const int r0 = blockIdx.y * rows_per_split;
-    const int r1 = min(rows, r0 + rows_per_split);
-    if (r0 >= r1) return;
-    f32x4 acc[4][4], accb[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        accb[i] = splat(0.f);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = splat(0.f);
-    }
-    const f32x4 z = splat(0.f);
-    const float* Ep = E + (size_t)q * ne + ue;
-    const float* Ap = A + (size_t)q * na + ua;
-    // one block = 16 spilled rows = 4 MFMA k-steps; operands of block b+1 are requested before the 64 MFMAs
-    // of block b (two named register sets, steady-state loop free of conditional loads)
-    f32x4 eA[4], aA[4], eB[4], aB[4];
-#define DW_LOAD(e_, a_, r_)                                                                     \
-    do {                                                                                        \
-        _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                         \
-            e_[k] = ve ? ld4s(Ep + (size_t)((r_) + 4 * k) * ne) : z;                            \
-            a_[k] = va ? ld4s(Ap + (size_t)((r_) + 4 * k) * na) : z;                            \
-        }                                                                                       \
-    } while (0)
-#define DW_COMPUTE(e_, a_)                                                                      \
-    do {                                                                                        \
-        _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                         \
-            const float ev[4] = {e_[k].x, e_[k].y, e_[k].z, e_[k].w};                           \
-            const float av[4] = {a_[k].x, a_[k].y, a_[k].z, a_[k].w};                           \
-            _Pragma("unroll") for (int i = 0; i < 4; ++i)                                       \
-                _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(ev[i], av[j], acc[i][j]); \
-            if (with_bias) {                                                                    \
-                _Pragma("unroll") for (int i = 0; i < 4; ++i) accb[i] = mfma16(ev[i], 1.0f, accb[i]); \
-            }                                                                                   \
-        }                                                                                       \
-    } while (0)
-    const int nblk = (r1 - r0) / 16;      // rows_per_split and rows are multiples of 16
-    DW_LOAD(eA, aA, r0);
-    int b = 0;
-    for (; b + 2 < nblk; b += 2) {
-        DW_LOAD(eB, aB, r0 + 16 * (b + 1));
-        __builtin_amdgcn_sched_barrier(0);
-        DW_COMPUTE(eA, aA);
-        __builtin_amdgcn_sched_barrier(0);
-        DW_LOAD(eA, aA, r0 + 16 * (b + 2));
-        __builtin_amdgcn_sched_barrier(0);
-        DW_COMPUTE(eB, aB);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    if (nblk - b == 2) {
-        DW_LOAD(eB, aB, r0 + 16 * (b + 1));
-        DW_COMPUTE(eA, aA);
-        DW_COMPUTE(eB, aB);
-    } else {
-        DW_COMPUTE(eA, aA);
-    }
-#undef DW_LOAD
-#undef DW_COMPUTE
-    // C layout of tile (i,j): row 4q+reg -> E column 64te + 4(4q+reg) + i ; col m -> A column 64ta + 4m + j
-    float* out = slab + (size_t)blockIdx.y * ne * na;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const int u = 64 * te + 4 * (4 * q + reg) + i;
-            if (u < ne && va) {
-                f32x4 v;
-                v.x = acc[i][0][reg]; v.y = acc[i][1][reg]; v.z = acc[i][2][reg]; v.w = acc[i][3][reg];
-                st4(out + (size_t)u * na + ua, v);
-            }
-            // bias partial: every column of accb[i] holds sum_r E[r][u]; column 0 (m == 0) writes it
-            if (with_bias && m == 0 && u < ne) slab_b[(size_t)blockIdx.y * ne + u] = accb[i][reg];
-        }
-    }
-}
-
 // Linear 0 (constant input): G_W0[u][k] -= sum_chain esum[chain][u] * inputs[chain][k];  G_b0[u] -= sum_chain esum[chain][u].
 // One block per (unit u, column k) -- blockIdx.y == n_in is the bias -- 256 threads stride over the chains, partial sums
 // meet in a fixed-order LDS tree: bitwise reproducible.  (One thread per output looping over 6000 chains took 2.3 ms.)
@@ -986,10 +689,3 @@ __global__ void mcpc_box_muller_kernel(const uint32_t* __restrict__ a, const uin
 }
 
 }  // namespace mcpc
-
-#include "mcpc_steps_ws.h"
-#include "mcpc_ws2_lean.h"
-#include "mcpc_steps_ws2.h"
-#include "mcpc_steps_u.h"
-#include "mcpc_hebbian.h"
-#include "mcpc_steps_lw.h"

@@ -2,8 +2,8 @@
 // fallbacks, the LDS plans and step tables, the layer-wise job tables, the round schedule, the spill ring's size -- and what mcpc_run
 // decides before it launches: the schedule of a run (plan_run) and every launch of its Hebbian flushes (plan_flush).  Plain host code
 // that makes no HIP call, so it runs (and is tested: mcpc_debug_plan, tests/test_plan_host.py; mcpc_debug_run_plan,
-// tests/test_run_plan_host.py) without a device.  Included by mcpc_api.hip only, after the kernel headers whose constants and table
-// types it uses.
+// tests/test_run_plan_host.py) without a device.  It sees no kernel: the table types and tile shapes it plans with are in mcpc_types.h,
+// the GEMM core's k-block constants in mcpc_gemm_f16.h, the Hebbian kernels' forms in mcpc_heb_forms.h.
 #pragma once
 
 #include <algorithm>
@@ -13,21 +13,12 @@
 #include <string>
 #include <vector>
 
-#include "mcpc_kernels.h"
+#include "mcpc_gemm_f16.h"
+#include "mcpc_heb_forms.h"
+#include "mcpc_host.h"
+#include "mcpc_types.h"
 
 namespace mcpc {
-
-inline thread_local std::string g_err;      // mcpc_last_error
-
-inline int fail(int code, const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
 
 inline int pad16(int n) { return (n + 15) / 16 * 16; }
 inline int kblocks(int k_pad) { return (k_pad + kKB - 1) / kKB; }      // k-blocks of the GEMM core that cover k_pad (a multiple of 16)

@@ -19,20 +19,11 @@
 // fp32 accumulator per tile, un-scaled at the end.  Lanes whose eight k values lie beyond a k range that is not a multiple of 32 stage
 // zeros and load nothing (global rows are npad wide: what lies behind them is the next chain's row).
 #pragma once
+#include "mcpc_kernels.h"
 
 namespace mcpc {
 
-constexpr int kLwChains = 64;                       // chains per workgroup
-constexpr int kLwCTT = kLwChains / 16;              // chain tiles per wave
-constexpr int kLwWaves = 4;
-constexpr int kLwThreads = kLwWaves * 64;
-constexpr int kLwUTW = 2;                           // unit tiles per wave
-constexpr int kLwUnitTiles = kLwWaves * kLwUTW;     // unit tiles per workgroup (128 units)
-constexpr int kLwLd = kKB + 4;                      // floats per chain row of a staged k-block
-constexpr int kLwStageFloats = 2 * kLwChains * kLwLd;
-constexpr int kLwLdsBytes = (kLwStageFloats + kLwChains + kLwWaves + 2) * 4;     // staging, row exponents, energy partials, spill maxima
-
-struct LwJob { int layer; int ut0; };               // forward: Linear j (layer L = the read-out); backward: latent layer l; first unit tile
+// (the tile's shape -- kLwChains, kLwWaves, kLwUnitTiles, kLwLdsBytes, ... -- and LwJob are the planner's too: mcpc_types.h)
 
 struct LwParams {
     KParams P;                     // what the LDS-resident kernels take: layers, read-out, optimiser, noise, records (LDS offsets unused)

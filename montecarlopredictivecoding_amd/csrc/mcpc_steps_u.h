@@ -36,12 +36,14 @@
 // Only the lean paths run here (fused SGD update with or without the Philox kick, Adam without noise; state in LDS): mcpc_run picks this
 // kernel per run and keeps the in-place / barrier kernels for everything else.
 #pragma once
+#include "mcpc_kernels.h"
+#include "mcpc_steps_ws.h"      // the LDS-scoped fences of the level barrier
+#include "mcpc_steps_ws2.h"     // ws2_fill_fx, ws2_fill_constants: the launch's fill of the LDS images
+#include "mcpc_ws2_lean.h"      // the lean epilogues
 
 namespace mcpc {
 
-constexpr int kUWaves = 8;                      // waves per workgroup, all alike (two per SIMD)
-constexpr int kUNT = 4;                         // unit tiles per row (job) at most: the four fragment slots and accumulator tiles of a wave
-constexpr int kUThreads = kUWaves * 64;
+// (the workgroup's shape -- kUWaves, kUNT, kUThreads -- is the planner's too: mcpc_types.h)
 
 // request the first fragments of an upcoming row's GEMM (weights need no dependency), into the four slots the GEMM forms expect
 // (mcpc_gemm_f16.h: gemm_tiles_u): three or four tiles -- block 0 of every tile; one or two tiles -- the first 4 / nt blocks of each

@@ -18,6 +18,9 @@
 //   and, for read-out chunks only, "all G past dep_g" (chunk buffer no longer read).  Every other write-after-read
 //   hazard is implied by a read dependency -- see the table builder.
 #pragma once
+#include "mcpc_kernels.h"
+#include "mcpc_steps_ws.h"
+#include "mcpc_ws2_lean.h"
 
 namespace mcpc {
 
@@ -27,28 +30,10 @@ namespace mcpc {
 #define MCPC_EXP_GEMM_GATE
 #endif
 
-#ifndef MCPC_WS2_PAIRS
-#define MCPC_WS2_PAIRS 4
-#endif
-constexpr int kWs2Pairs = MCPC_WS2_PAIRS;          // (G, E) pairs per workgroup: 4 = one GEMM and one epilogue wave per SIMD.
-                                                   // (8 = two of each: measured 99 vs 95 us per step at cfg-M -- the two GEMM waves of a SIMD walk the
-                                                   // same table behind the same dependencies, so they stall together instead of filling each other's gaps)
-#ifndef MCPC_WS2_SPAN
-#define MCPC_WS2_SPAN 16
-#endif
+// (the workgroup's shape -- kWs2Pairs, kWs2NT, kWs2NTW, kWs2Threads and their build-time knobs -- is the planner's too: mcpc_types.h)
 #ifndef MCPC_WS2_WAVES_PER_EU
 #define MCPC_WS2_WAVES_PER_EU 2
 #endif
-constexpr int kWs2NT = MCPC_WS2_SPAN / kWs2Pairs;   // unit tiles per pair per table entry: an entry hands out 16 tiles
-// Tiles per pair and entry (build-time knob).  Measured: 6 (a third group of two tiles in the register rotation) and 5 against 4 --
-// 50.7 / 50.0 / 51.4 us per step at 4096 chains in round 2, 34.9 against 34.4 with the bf16x6 core in round 3: the hand-over count is
-// not what a step pays for, and the default stays 4 (one table layout; mcpc_gemm_f16.h's rotation is written for at most four).
-#ifndef MCPC_WS2_NT16
-#define MCPC_WS2_NT16 kWs2NT
-#endif
-constexpr int kWs2NTW = MCPC_WS2_NT16;
-constexpr int kWs2Threads = 2 * kWs2Pairs * 64;
-static_assert(kWs2Pairs == 4 || kWs2Pairs == 8, "4 or 8 pairs");
 
 // Diagnostic build variant -DMCPC_STAMPS -DMCPC_STAMPS_ENTRY=q: the 16 slots hold, per TABLE ENTRY p (p < 16),
 //   q = 1: cycles the G wave waits in front of / behind the GEMM of entry p (dep_e, dep_g, dep_se)

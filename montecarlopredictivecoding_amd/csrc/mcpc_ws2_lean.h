@@ -25,6 +25,8 @@
 // 12.5 us of a 96 us step in the Hebbian stretches of cfg-M (timing build without the stores: 78.5 us against 88.5 per step of a
 // learning call), and the x store / x loads of every step besides.
 #pragma once
+#include "mcpc_kernels.h"       // the barrier kernel's epilogues, row-exponent words, stamps
+#include "mcpc_steps_ws.h"      // progress counters and hand-off fences
 
 namespace mcpc {
 

@@ -7,12 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-#include "../montecarlopredictivecoding_amd/csrc/mcpc_device.h"
-namespace mcpc {
-constexpr int kMaxLatent = 6;
-__device__ __forceinline__ f32x4 splat(float v) { f32x4 r = {v, v, v, v}; return r; }
-}
-#include "../montecarlopredictivecoding_amd/csrc/mcpc_hebbian.h"
+#include "../montecarlopredictivecoding_amd/csrc/mcpc_hebbian.h"       // (includes what it uses: mcpc_types.h, mcpc_gemm_f16.h, mcpc_heb_forms.h)
 using namespace mcpc;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

@@ -243,7 +243,7 @@ def _args(text, name):
 
 def test_header_source_and_binding_agree_on_both_signatures():
     header = open(os.path.join(ROOT, "include", "mcpc.h")).read()
-    source = open(os.path.join(ROOT, "montecarlopredictivecoding_amd", "csrc", "mcpc_api.hip")).read()
+    source = open(os.path.join(ROOT, "montecarlopredictivecoding_amd", "csrc", "mcpc_records.hip")).read()       # the unit of the stateless reducers
     assert re.search(r"#define\s+MCPC_ABI_VERSION\s+4\b", header) and _lib.ABI_VERSION == 4
     ctype = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64}
     for name, count, res in (("mcpc_roll_accumulate", 18, C.c_int), ("mcpc_roll_workspace_bytes", 3, C.c_int64)):
