@@ -14,12 +14,8 @@
 // in the tile, on the number of rows or on how the caller chunks them.
 // The per-element arithmetic is pc_error4 / pc_energy4 / MCPC_READOUT_LOSS4 of mcpc_step_math.h.
 #pragma once
-
-#include <algorithm>
-#include <vector>
-
 #include "mcpc_step_math.h"
-#include "mcpc_steps_lw.h"      // the layer-wise forward tile (lw_job_gemm) and its job table
+#include "mcpc_lw_tile.h"       // the layer-wise forward tile (lw_job_gemm)
 
 namespace mcpc {
 
@@ -165,23 +161,6 @@ __global__ __launch_bounds__(256) void mcpc_ce_finish_kernel(const double* __res
     o[kEnergyCols - 1] = overall + loss;
 }
 
-// The job table (host): every (Linear, block of kLwUnitTiles unit tiles) once.  The read-out's jobs come first -- a call without a loss
-// launches the table from `n_head` on -- then the latent layers, longest contraction first (the long GEMMs of the launch start first);
-// the jobs of one Linear are contiguous with ascending first tile: the order mcpc_ce_finish_kernel adds them in.
-inline void ce_job_table(int L, const int* npad, int out_pad, std::vector<LwJob>& jobs, int& n_head, CeFinish& F) {
-    jobs.clear();
-    for (int j = 0; j <= kMaxLatent; ++j) F.first[j] = F.count[j] = 0;
-    auto emit = [&](int j, int tiles) {
-        F.first[j] = (int)jobs.size();
-        for (int ut = 0; ut < tiles; ut += kLwUnitTiles) jobs.push_back(LwJob{j, ut});
-        F.count[j] = (int)jobs.size() - F.first[j];
-    };
-    if (out_pad > 0) emit(L, out_pad / 16);
-    n_head = (int)jobs.size();
-    std::vector<int> order;
-    for (int j = 0; j < L; ++j) order.push_back(j);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return (a == 0 ? 0 : npad[a - 1]) > (b == 0 ? 0 : npad[b - 1]); });
-    for (int j : order) emit(j, npad[j] / 16);
-}
+// (the job table, ce_job_table, is built on the host: mcpc_plan.h)
 
 }  // namespace mcpc

@@ -1,9 +1,11 @@
 // The engine behind the C handle `mcpc_engine` (include/mcpc.h), and the few functions that cross a translation-unit boundary of
-// libmcpc.so.  Host declarations only: no kernel is defined here or in anything this header includes.
+// libmcpc.so (the step kernels' launchers have a header of their own: mcpc_step_forms.h).  Host declarations and small inline templates
+// only: no kernel is defined here or in anything this header includes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>          // types and prototypes only: the library is loaded with dlopen on first use (no link dependency)
 
+#include <algorithm>
 #include <string>
 #include <utility>
 #include <vector>
@@ -102,9 +104,56 @@ struct mcpc_engine : mcpc::EnginePlan {
 
 namespace mcpc {
 
+// ---- device buffers of an engine (retire, free_completed_retired: mcpc_api.hip) -----------------------------------------------------------
+template <typename T>
+int dmalloc(T*& p, size_t count) {
+    void* q = nullptr;
+    hipError_t err = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
+    if (err != hipSuccess) return fail(MCPC_ENOMEM, "hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(err));
+#ifdef MCPC_POISON_ALLOC      // diagnostic build: every fresh device allocation is filled with 0xFF bytes (NaN as fp32 / fp64, -1 as int), so that a
+                              // read of memory nobody initialised shows on every box, not only on one whose fresh pages are not zero
+    if (hipMemset(q, 0xFF, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return fail(MCPC_EHIP, "hipMemset (poison) failed");
+#endif
+    p = (T*)q;
+    return 0;
+}
+// A table the planner built, copied to the device
+template <typename T>
+int upload(T*& dev, const std::vector<T>& host, const char* what) {
+    if (const int rc = dmalloc(dev, host.size())) return rc;
+    if (hipMemcpy(dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return fail(MCPC_EHIP, "hipMemcpy of %s failed", what);
+    return 0;
+}
+// A buffer that launches already in the stream may still use is not freed but retired behind an event.
+void retire(mcpc_engine* e, void* p, hipStream_t stream);
+// The engine gives a buffer up (retired if there is one, the pointer cleared), and replaces it by one of `count` elements: nothing waits
+template <typename T>
+void give_up(mcpc_engine* e, T*& p, hipStream_t stream) { if (p) retire(e, (void*)p, stream); p = nullptr; }
+template <typename T>
+int regrow(mcpc_engine* e, T*& p, size_t count, hipStream_t stream) { give_up(e, p, stream); return dmalloc(p, count); }
+// A retired buffer is freed by a later run once its event has completed (never under a kernel that uses it)
+void free_completed_retired(mcpc_engine* e);
+
+// ---- what mcpc_run (mcpc_run.hip) shares with the evaluators (mcpc_eval.hip) and the layer-wise launcher (mcpc_steps_lw.hip) ---------------
+// mcpc_api.hip -- mu_1 = inputs W0^T + b0 into `dst` [padded][npad_0] for `rows` rows of inputs: one kernel for the runs and the evaluators,
+// so that all of them see the same bits
+void launch_mu1(const mcpc_engine* e, const float* inputs, float* dst, int rows, int padded, hipStream_t stream);
+// mcpc_run.hip -- the loss arguments of a run or of an evaluator call.  `pre` opens every message: "" for mcpc_run, "<entry>: " for an evaluator.
+int check_loss_kind(const char* pre, int32_t kind);
+int check_loss_values(const char* pre, const mcpc_engine* e, int32_t loss_kind, double loss_var, int32_t mask_start);
+int check_loss(const char* pre, const mcpc_engine* e, int32_t loss_kind, double loss_var, int32_t mask_start);
+// A launch window of a run: steps [t0, t0 + n), and the rows of the run's per-step tables (Adam coefficients, injected noise) it starts at
+inline void set_window(const mcpc_engine* e, const mcpc_run_desc* r, KParams& P, int t0, int n) {
+    P.t0 = t0; P.n_steps = n;
+    const size_t s0 = (size_t)(t0 - r->t_begin);
+    P.adam_coef = r->xopt_kind == MCPC_XOPT_ADAM ? e->adam_coef + 2 * s0 : nullptr;
+    if (r->noise_mode == MCPC_NOISE_EXTERNAL)
+        for (int l = 0; l < e->L; ++l) P.layer[l].ext_noise = r->ext_noise[l] + s0 * e->d.batch * e->d.sizes[l];
+}
+
 // mcpc_flush.hip -- one Hebbian flush, as planned (plan_flush): fold the spilled steps from slot `slot0` on into the gradient sums of
 // every Linear j >= 1, on `stream` (and the engine's second flush stream where the plan says so).  `part`: the ring part, whose
-// spilled maxima scale the fp16 operands.  Called by mcpc_run (mcpc_api.hip).
+// spilled maxima scale the fp16 operands.  Called by mcpc_run (mcpc_run.hip).
 int flush_spill(mcpc_engine* e, const FlushPlan& f, int slot0, hipStream_t stream, int part);
 
 }  // namespace mcpc

@@ -1,6 +1,6 @@
 // libmcpc.so, the Hebbian flush: the launches that fold a segment of spilled steps into the gradient sums of the Linears j >= 1, with
 // their kernels (mcpc_hebbian.h: the only unit that includes them).  What to launch was decided on the host (mcpc_plan.h: plan_flush);
-// mcpc_run (mcpc_api.hip) calls flush_spill once per accumulating segment.
+// mcpc_run (mcpc_run.hip) calls flush_spill once per accumulating segment.
 #include <hip/hip_runtime.h>
 
 #include "mcpc_engine.h"

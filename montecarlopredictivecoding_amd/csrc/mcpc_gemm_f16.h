@@ -140,7 +140,7 @@ struct GemmScale { int a_exp; int mode; int fixed_b; int run; int short_k; int s
 // for the rounding errors of the 22-bit operands to average out (K = 32: max 1.6e-7 / rms 3.1e-8 of sum |terms| without it against 1.2e-7 /
 // 2.6e-8 with it; fp32 MFMA chain 1.0e-7 / 2.1e-8).  From K = 96 on the term changes neither figure (profiles/r05_f16x4_study.txt) and longer
 // GEMMs run THREE MFMAs per product.
-constexpr int kShortK = 2;
+// (kShortK itself is the planner's too: mcpc_types.h)
 template <int NT, int NTT, int NW, bool MM, bool PS = false>
 __device__ __forceinline__ void gemm_fixed(f32x4 (&acc)[NTT], const gu32x4* __restrict__ A, const int (&aoff)[NTT], int nkb, int kw,
                                            const float* B, int ldb, int lane, frag_t (&pre)[NTT], const float* zeros, int b_exp) {

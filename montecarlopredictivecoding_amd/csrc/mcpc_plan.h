@@ -3,7 +3,7 @@
 // decides before it launches: the schedule of a run (plan_run) and every launch of its Hebbian flushes (plan_flush).  Plain host code
 // that makes no HIP call, so it runs (and is tested: mcpc_debug_plan, tests/test_plan_host.py; mcpc_debug_run_plan,
 // tests/test_run_plan_host.py) without a device.  It sees no kernel: the table types and tile shapes it plans with are in mcpc_types.h,
-// the GEMM core's k-block constants in mcpc_gemm_f16.h, the Hebbian kernels' forms in mcpc_heb_forms.h.
+// the Hebbian kernels' forms in mcpc_heb_forms.h.
 #pragma once
 
 #include <algorithm>
@@ -13,7 +13,6 @@
 #include <string>
 #include <vector>
 
-#include "mcpc_gemm_f16.h"
 #include "mcpc_heb_forms.h"
 #include "mcpc_host.h"
 #include "mcpc_types.h"
@@ -75,7 +74,7 @@ struct Knobs {
     int heb171 = 0;           // 1: the 17-tile group of a read-out on <17, 1> with twice the activation groups instead of <17, 2> (A/B)
     int heb_fp32 = 0;         // 1: the tiled Hebbian GEMM runs on the fp32 MFMA (mcpc_heb_kernel) instead of the fp16x6 form (A/B, parity tests)
     int spec = 1;             // 0: every launch of the in-place kernel takes its generic instantiation, never a specialised one (A/B, parity tests)
-    int spec_wait = 0;        // a run of at least this many steps waits for the host copy of the bound target's flags (mcpc_api.hip:
+    int spec_wait = 0;        // a run of at least this many steps waits for the host copy of the bound target's flags (mcpc_run.hip:
                               // target_flags_on_host); a shorter one specialises only if the copy has landed.  0, every candidate run
                               // waits: with a target bound in front of every call that won at every length from 4 steps up, and runs
                               // that only polled were 2 % behind the parent (profiles/spec_modes.txt section 7)
@@ -735,6 +734,25 @@ inline void lw_job_table(int L, const int* npad, int out_pad, std::vector<LwJob>
     std::stable_sort(border.begin(), border.end(), [&](int a, int b) { return bcost(a) > bcost(b); });
     for (int l : border)
         for (int ut = 0; ut < npad[l] / 16; ut += kLwUnitTiles) bwd.push_back(LwJob{l, ut});
+}
+
+// The evaluators' job table (mcpc_chain_energy.h; built by mcpc_eval.hip): every (Linear, block of kLwUnitTiles unit tiles) once.  The read-out's jobs come
+// first -- a call without a loss launches the table from `n_head` on -- then the latent layers, longest contraction first (the long GEMMs of the launch start first);
+// the jobs of one Linear are contiguous with ascending first tile: the order mcpc_ce_finish_kernel adds them in.
+inline void ce_job_table(int L, const int* npad, int out_pad, std::vector<LwJob>& jobs, int& n_head, CeFinish& F) {
+    jobs.clear();
+    for (int j = 0; j <= kMaxLatent; ++j) F.first[j] = F.count[j] = 0;
+    auto emit = [&](int j, int tiles) {
+        F.first[j] = (int)jobs.size();
+        for (int ut = 0; ut < tiles; ut += kLwUnitTiles) jobs.push_back(LwJob{j, ut});
+        F.count[j] = (int)jobs.size() - F.first[j];
+    };
+    if (out_pad > 0) emit(L, out_pad / 16);
+    n_head = (int)jobs.size();
+    std::vector<int> order;
+    for (int j = 0; j < L; ++j) order.push_back(j);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return (a == 0 ? 0 : npad[a - 1]) > (b == 0 ? 0 : npad[b - 1]); });
+    for (int j : order) emit(j, npad[j] / 16);
 }
 
 // Round schedule of the in-place kernel for a shard of U 16-chain units on C < U CUs.  One unit per CU is what the kernel is built

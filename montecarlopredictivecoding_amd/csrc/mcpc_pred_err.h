@@ -17,6 +17,8 @@
 // destination), per-element predicated stores otherwise.
 #pragma once
 
+#include <vector>
+
 #include "mcpc_chain_energy.h"
 
 namespace mcpc {

@@ -16,7 +16,7 @@
 //     synchronises; with a barrier on either side of a level no tile belongs to a wave;
 //   * every wave walks its OWN table (P.phases[w * n_rows + p]): a row is a JOB -- up to four consecutive unit tiles of one entry = one
 //     GEMM call + one epilogue call -- and the host deals a level's jobs to the eight waves by a cost model, longest first, with the grain
-//     of every entry chosen for the shortest makespan (mcpc_api.hip: build_phases_u);
+//     of every entry chosen for the shortest makespan (mcpc_plan.h: build_phases_u);
 //   * with a zero loss (reference utils/model.py:31-33 `zero_fn`: unclamped generation, figure_3.py:125-161) the read-out is dead code on
 //     every step whose output is not recorded: e_o = 0, so its back-projection vanishes and `out` is consumed by nothing.  Those steps skip
 //     the read-out rows and the back-projection GEMM -- the arithmetic of everything that IS computed is unchanged (the x update adds
@@ -38,7 +38,7 @@
 #pragma once
 #include "mcpc_kernels.h"
 #include "mcpc_steps_ws.h"      // the LDS-scoped fences of the level barrier
-#include "mcpc_steps_ws2.h"     // ws2_fill_fx, ws2_fill_constants: the launch's fill of the LDS images
+#include "mcpc_ws2_fill.h"      // ws2_fill_fx, ws2_fill_constants: the launch's fill of the LDS images
 #include "mcpc_ws2_lean.h"      // the lean epilogues
 
 namespace mcpc {

@@ -18,8 +18,11 @@
 //   and, for read-out chunks only, "all G past dep_g" (chunk buffer no longer read).  Every other write-after-read
 //   hazard is implied by a read dependency -- see the table builder.
 #pragma once
+#include "mcpc_host.h"           // the launchers at the end: HIP_TRY
 #include "mcpc_kernels.h"
+#include "mcpc_step_forms.h"     // Ws2Spec
 #include "mcpc_steps_ws.h"
+#include "mcpc_ws2_fill.h"       // ws2_fill_fx, ws2_fill_constants
 #include "mcpc_ws2_lean.h"
 
 namespace mcpc {
@@ -119,49 +122,6 @@ __device__ __forceinline__ void ws2_prefetch(const KPhase& ph, int k, int lane, 
     }
 }
 
-template <int ACT>
-__device__ __forceinline__ void ws2_fill_fx(const KLayer& Ly, float* lds, int chain0, int tid, bool keep_x,
-                                            float* lds_rowexp = nullptr, int row_id = 0) {
-    const int qpr = Ly.npad / 4;                            // quads per row
-    for (int idx = tid; idx < 16 * qpr; idx += kWs2Threads) {
-        const int r = idx / qpr, u0 = 4 * (idx - r * qpr);
-        const f32x4 x = ld4s(Ly.x + (size_t)(chain0 + r) * Ly.npad + u0);
-        const f32x4 fx = act4<ACT>(x);
-        st4(lds + Ly.lds_a + r * Ly.ld + u0, fx);
-        if (keep_x) st4(lds + Ly.lds_x + r * Ly.ld + u0, x);
-        // generation 0 of the row's exponent word (mcpc_kernels.h: rowexp_track; the words were zeroed with the plan)
-        if (lds_rowexp != nullptr && r < 16) rowexp_track(lds_rowexp, row_id, r, absmax4(0.f, fx), 0u);
-    }
-}
-
-// KParams::xl: what the epilogues of a launch read over and over and nobody else writes -- biases, the mu_1 rows and the bit-packed
-// target rows of the workgroup's chains -- copied to LDS once (the state rows X_l: ws2_fill_fx)
-__device__ __forceinline__ void ws2_fill_constants(const KParams& P, float* lds, int chain0, int tid) {
-    for (int l = 1; l < P.L; ++l) {
-        const KLayer& Ly = P.layer[l];
-        for (int i = tid; i < Ly.npad / 4; i += kWs2Threads) st4(lds + Ly.lds_bias + 4 * i, ld4(Ly.bias + 4 * i));
-    }
-    {
-        const KLayer& Ly = P.layer[0];
-        const int qpr = Ly.npad / 4;
-        for (int idx = tid; idx < 16 * qpr; idx += kWs2Threads) {
-            const int r = idx / qpr, u0 = 4 * (idx - r * qpr);
-            st4(lds + Ly.lds_bias + r * Ly.ld + u0, ld4(P.mu1 + (size_t)(chain0 + r) * Ly.npad + u0));
-        }
-    }
-    if (P.has_head) {
-        const KHead& H = P.head;
-        for (int i = tid; i < H.npad / 4; i += kWs2Threads) st4(lds + H.lds_bias + 4 * i, ld4(H.bias + 4 * i));
-        if (H.lds_yw >= 0) {
-            uint32_t* const yw = reinterpret_cast<uint32_t*>(lds + H.lds_yw);
-            for (int idx = tid; idx < 16 * H.ywords; idx += kWs2Threads) {
-                const int r = idx / H.ywords, w = idx - r * H.ywords;
-                yw[idx] = H.ybits[(size_t)(chain0 + r) * H.ywords + w];
-            }
-        }
-    }
-}
-
 // Uniform values the epilogue loops use over and over are parked in VGPRs: the E waves have ~100 registers to
 // spare but no SGPRs (hipcc re-loaded them from the kernel arguments inside the loops: s_load + s_waitcnt lgkmcnt(0),
 // a scalar-cache round trip per use).
@@ -212,7 +172,7 @@ __device__ __forceinline__ float ws2_headf_epilogue(const KParams& P, const KPha
     return lsum;
 }
 
-// MIX: the launch is one launch of a round-schedule cycle (setup_rounds, mcpc_api.hip) -- workgroups take their unit and the steps it
+// MIX: the launch is one launch of a round-schedule cycle (run_round_cycle, mcpc_run.hip) -- workgroups take their unit and the steps it
 // has already done from per-launch lists (KParams::wg_list / wg_rel).
 // (The body is a textual include: wrapped into a device function and inlined, the SAME code compiled about 1 % slower.)
 // One definition serves every instantiation (mcpc_steps_ws2_kernel.inc: launch bounds, LDS declaration, the body's macros), included
@@ -225,32 +185,28 @@ __device__ __forceinline__ float ws2_headf_epilogue(const KParams& P, const KPha
 // The same body with the launch's decisions fixed at compile time (MODE: a Ws2Mode, mcpc_ws2_lean.h): the branches, the live ranges of
 // the paths not taken and the SGPR spills they cause are gone; the floating-point operations and their order are the generic kernel's.
 // A kernel of its own name, so that a trace tells the instantiations apart and the generic kernel's two symbols stay what they were.
-// The instantiations the library holds are listed ONCE, in kWs2Specs below; ws2_select_mode (mcpc_api.hip) picks one per launch.
+// The instantiations the library holds are listed ONCE, each in the unit that holds it: the generic kernel in mcpc_steps_ws2.hip, the
+// specialised ones in mcpc_steps_ws2_spec.hip; ws2_select_mode (mcpc_run.hip) picks one per launch.
 #define WS2_KERNEL_TEMPLATE template <class MODE, int CTT, bool MIX = false>      // CTT: as above
 #define WS2_KERNEL_NAME mcpc_steps_ws2_spec_kernel
 #define WS2_MODE MODE
 #include "mcpc_steps_ws2_kernel.inc"
 
-// The hot set: what every script of the reference runs per step on a ReLU network with a Bernoulli read-out -- lean SGD with the fused
-// Philox kick, state and constants in LDS, row words, a bit-packed 0/1 target -- apart by whether the launch accumulates (its spill
-// stores then go out at system scope).
-template <int SPILL> using Ws2HotMode = Ws2Mode<WS2_UPD_SGD_PHILOX, 1, 1, SPILL, WS2_HEAD_BERNOULLI_BITS, MCPC_ACT_RELU>;
-// The MAP warm-up of the same networks: Adam on x without noise, nothing accumulated.
-using Ws2MapMode = Ws2Mode<WS2_UPD_ADAM, 1, 1, WS2_SPILL_OFF, WS2_HEAD_BERNOULLI_BITS, MCPC_ACT_RELU>;
-enum Ws2Spec { WS2_SPEC_GENERIC = 0, WS2_SPEC_HOT, WS2_SPEC_HOT_SPILL, WS2_SPEC_MAP, WS2_SPEC_COUNT };
+// ---- host side, for the two units that hold the instantiations ----------------------------------------------------------------------------
+// One entry per Ws2Spec (mcpc_step_forms.h) a unit holds; taking a kernel's address is what instantiates it there.
 struct Ws2SpecEntry { const void* fn[2]; const char* tag; };      // fn[MIX]; tag: what mcpc_last_step_kernel_name adds to the generic kernel's name
-#ifndef MCPC_EXP_NOLEAN
-static const Ws2SpecEntry kWs2Specs[WS2_SPEC_COUNT] = {
-    {{(const void*)mcpc_steps_ws2_kernel<1, false>, (const void*)mcpc_steps_ws2_kernel<1, true>}, "generic"},
-    {{(const void*)mcpc_steps_ws2_spec_kernel<Ws2HotMode<WS2_SPILL_OFF>, 1, false>, (const void*)mcpc_steps_ws2_spec_kernel<Ws2HotMode<WS2_SPILL_OFF>, 1, true>}, "hot"},
-    {{(const void*)mcpc_steps_ws2_spec_kernel<Ws2HotMode<WS2_SPILL_SYS>, 1, false>, (const void*)mcpc_steps_ws2_spec_kernel<Ws2HotMode<WS2_SPILL_SYS>, 1, true>}, "hot+spill"},
-    // (a spill that stays in the L2 -- a small shard, a narrow network: KParams::spill_sys == 0 -- keeps the generic kernel: the in-place
-    // kernel serves such shards only under tuning ws=2, and no measurement asked for an instantiation of their own)
-    {{(const void*)mcpc_steps_ws2_spec_kernel<Ws2MapMode, 1, false>, (const void*)mcpc_steps_ws2_spec_kernel<Ws2MapMode, 1, true>}, "map"},
-};
-#else       // (timing build without the lean epilogues: the generic kernel everywhere)
-static const Ws2SpecEntry kWs2Specs[WS2_SPEC_COUNT] = {
-    {{(const void*)mcpc_steps_ws2_kernel<1, false>, (const void*)mcpc_steps_ws2_kernel<1, true>}, "generic"}, {{nullptr, nullptr}, ""}, {{nullptr, nullptr}, ""}, {{nullptr, nullptr}, ""}};
-#endif
+inline hipError_t ws2_entry_allow_lds(const Ws2SpecEntry& s, bool mix, int bytes) {
+    return s.fn[mix] ? hipFuncSetAttribute(s.fn[mix], hipFuncAttributeMaxDynamicSharedMemorySize, bytes) : hipSuccess;
+}
+inline int ws2_entry_launch(const Ws2SpecEntry& s, bool mix, int nblocks, int lds_bytes, KParams& K, hipStream_t stream) {
+    void* args[] = {&K};
+    HIP_TRY(hipLaunchKernel(s.fn[mix], dim3(nblocks), dim3(kWs2Threads), args, lds_bytes, stream));
+    return 0;
+}
+// mcpc_steps_ws2_spec.hip: the specialised instantiations, reached by the launchers of mcpc_step_forms.h (mcpc_steps_ws2.hip) for spec >= 1
+bool ws2_specialised_built(int spec, bool mix);
+const char* ws2_specialised_tag(int spec);
+hipError_t ws2_specialised_allow_lds(bool mix, int bytes);
+int ws2_specialised_launch(int spec, bool mix, int nblocks, int lds_bytes, KParams& K, hipStream_t stream);
 
 }  // namespace mcpc

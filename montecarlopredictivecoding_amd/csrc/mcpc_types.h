@@ -133,7 +133,7 @@ struct KParams {
     int lds_ws_sync;                 // wave-specialised kernel: float offset of the progress counters
     int ws_prio;                     // 1: epilogue waves run at raised static priority
     int* err;                        // device error word (bit 0/1: a progress-counter wait ran out)
-    // in-place kernel, round schedule (setup_rounds / run_round_cycle in mcpc_api.hip): workgroup -> 16-chain unit and the launches of
+    // in-place kernel, round schedule (plan_rounds in mcpc_plan.h, run_round_cycle in mcpc_run.hip): workgroup -> 16-chain unit and the launches of
     // the cycle that unit has already taken part in
     const int* wg_list;              // [gridDim.x] unit index, or null: unit = blockIdx.x
     const int* wg_rel;               // [gridDim.x] launches of this cycle the unit has already run, or null
@@ -209,6 +209,7 @@ __device__ __forceinline__ f32x4 splat(float v) { f32x4 r = {v, v, v, v}; return
 // GEMM core (mcpc_gemm_f16.h)
 constexpr int kKB = 32;                 // k-depth of one fragment block
 constexpr int kFragBlock = 2 * 64;      // u32x4 units per (tile, k-block): two fp16 planes of 64 lanes
+constexpr int kShortK = 2;              // GEMMs of at most this many k-blocks (K <= 64) keep the fourth product a_m b_m
 
 // wave-specialised kernels (mcpc_steps_ws.h)
 enum : int { PHF_WS_GEMM = 16, PHF_WS_EPI = 32 };   // which role has work in a table entry

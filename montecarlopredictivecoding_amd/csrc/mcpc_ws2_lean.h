@@ -80,7 +80,7 @@ __device__ __forceinline__ void spill_st4(float* base, uint32_t image_bytes, uin
 // activations -- is a run-time value of KParams in the generic kernel, re-tested in every workgroup, table entry and tile loop; the
 // compiler keeps the union of all paths alive (294 spilled SGPRs).  A field of Ws2Mode fixes one such decision at
 // compile time; kModeDyn leaves it to the run-time test, which then compiles to exactly the generic kernel's code for that decision.
-// ws2_select_mode (mcpc_api.hip) returns a specialised mode only when every launched workgroup would have decided the same.
+// ws2_select_mode (mcpc_run.hip) returns a specialised mode only when every launched workgroup would have decided the same.
 constexpr int kModeDyn = -1;
 enum { WS2_UPD_SGD = 1, WS2_UPD_SGD_PHILOX = 2, WS2_UPD_ADAM = 3 };     // lean epilogues with the fused update: SGD, SGD + Philox kick, Adam without noise
 enum { WS2_SPILL_OFF = 0, WS2_SPILL_SYS = 1 };                          // no step of the launch accumulates / every step does, its stores at system scope

@@ -3,7 +3,10 @@
 
 A kernel's machine code must not depend on the translation unit it is compiled in.  For every `.amdhsa_kernel` name this takes the text
 from the kernel's label to its `.Lfunc_end`, without comments and with the function's index dropped from its `.LBB<n>_` labels (the index
-counts the functions of the unit), and the `.amdhsa_kernel ... .end_amdhsa_kernel` block as it stands.  It reports the two sets of names,
+counts the functions of the unit), and the `.amdhsa_kernel ... .end_amdhsa_kernel` block as it stands.  The number of a `.Lpost_getpc<n>`
+label is likewise counted from the kernel's first one, where the label is defined and where it is used: the compiler numbers the
+long-branch expansions through the whole unit, so a kernel that has some (mcpc_steps_u_kernel) gets other numbers when other kernels
+are compiled in front of it, around the same instructions.  It reports the two sets of names,
 names that occur more than once, and every kernel whose text or block differs; the exit status is 0 when there is nothing to report."""
 import re
 import sys
@@ -27,10 +30,11 @@ def kernels(path):
         block = "\n".join(x.strip() for x in lines[i:end + 1])
         start = max(s for s in label[name] if s < i)          # the kernel's code precedes its descriptor
         stop = next(j for j in range(start, len(lines)) if re.match(r"\.Lfunc_end\d+:", lines[j]))
-        text = []
+        text, getpc = [], {}
         for x in lines[start:stop]:
             x = re.sub(r"\s*;.*$", "", x).rstrip()
             x = re.sub(r"\.LBB\d+_", ".LBB_", x)
+            x = re.sub(r"\.Lpost_getpc(\d+)", lambda m: ".Lpost_getpc#%d" % getpc.setdefault(m.group(1), len(getpc)), x)
             if x:
                 text.append(x)
         out.setdefault(name, []).append(("\n".join(text), block))

@@ -14,7 +14,7 @@
 #include <string>
 #include <vector>
 
-#include "mcpc_plan.h"          // (sees no kernel: mcpc_types.h, mcpc_gemm_f16.h, mcpc_heb_forms.h, mcpc_host.h)
+#include "mcpc_plan.h"          // (sees no kernel: mcpc_types.h, mcpc_heb_forms.h, mcpc_host.h)
 
 using namespace mcpc;
 

@@ -3,6 +3,7 @@
 * a kernel exists once in the library -- no kernel name appears in two units (`make asm`: the units' device code side by side);
 * every entry point of include/mcpc.h that the binding resolves is exported by the linked library, whichever unit defines it;
 * the records unit (the stateless reducers) sees nothing of the engine, the planner or the step kernels;
+* the run unit (mcpc_run and its executor) sees no kernel header and reaches the step kernels through launchers only;
 * an edit recompiles the units that include the edited file, the build-info unit (so that the reported source hash is the tree's) and
   nothing else -- planned with `make -n -W <file>`, which modifies nothing."""
 import os
@@ -15,7 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "montecarlopredictivecoding_amd")
 CSRC = os.path.join(PKG, "csrc")
 OBJDIR = os.path.join(PKG, "build", "product")
-UNITS = ("mcpc_api", "mcpc_flush", "mcpc_records", "mcpc_build_info")
+STEP_UNITS = ("mcpc_steps_ws2", "mcpc_steps_ws2_spec", "mcpc_steps_u", "mcpc_steps_lw")
+UNITS = ("mcpc_api", "mcpc_run") + STEP_UNITS + ("mcpc_eval", "mcpc_flush", "mcpc_records", "mcpc_build_info")
 
 
 @pytest.fixture(scope="module")
@@ -59,6 +61,28 @@ def test_records_unit_stands_apart(built):
     assert not ours, ours
 
 
+def test_run_unit_sees_no_kernel_header(built):
+    dep = open(os.path.join(OBJDIR, "mcpc_run.d")).read()
+    seen = set(re.findall(r"(mcpc_\w+\.(?:h|inc))", dep))
+    assert {"mcpc_engine.h", "mcpc_step_forms.h", "mcpc_plan.h"} <= seen, "the depfile does not name the unit's own headers: the pattern is broken"
+    kernel_headers = {"mcpc_kernels.h", "mcpc_ws2_lean.h", "mcpc_ws2_fill.h", "mcpc_lw_tile.h", "mcpc_gemm_f16.h", "mcpc_step_math.h", "mcpc_engine_kernels.h",
+                      "mcpc_chain_energy.h", "mcpc_pred_err.h", "mcpc_ancestral.h", "mcpc_hebbian.h",                                    # evaluators, Hebbian flush
+                      "mcpc_moments.h", "mcpc_cov.h", "mcpc_hist.h", "mcpc_hist2d.h", "mcpc_acov.h", "mcpc_roll.h", "mcpc_probe.h", "mcpc_knn.h", "mcpc_loglik.h"}
+    for h in kernel_headers:
+        assert os.path.exists(os.path.join(CSRC, h)), f"{h} is no file of csrc/: the list is stale"
+    barred = {h for h in seen if h in kernel_headers or h.startswith("mcpc_steps_")}
+    assert not barred, f"mcpc_run.hip includes {sorted(barred)}"
+    # the object agrees: of the library's other units it needs host functions -- the launchers among them -- and not one kernel's stub
+    run = subprocess.run(["nm", "-u", "-C", os.path.join(OBJDIR, "mcpc_run.o")], capture_output=True, text=True, check=True)
+    ours = [line.split(None, 1)[1].strip() for line in run.stdout.splitlines() if "mcpc" in line]
+    launchers = ("mcpc::launch_ws2(", "mcpc::launch_u(", "mcpc::launch_barrier(", "mcpc::launch_lw_steps(", "mcpc::launch_lw_act(", "mcpc::launch_mu1(",
+                 "mcpc::flush_spill(")
+    for fn in launchers:
+        assert any(sym.startswith(fn) for sym in ours), (fn, ours)
+    stubs = [sym for sym in ours if "_kernel" in sym]
+    assert not stubs, stubs
+
+
 def planned(touched):
     """What `make` would do if `touched` were newer than everything: the units it recompiles, and whether it links."""
     run = subprocess.run(["make", "-C", CSRC, "-n", "-W", touched], capture_output=True, text=True, timeout=120)
@@ -71,6 +95,10 @@ def planned(touched):
 @pytest.mark.parametrize("touched, units", [
     ("mcpc_hist.h", {"mcpc_records", "mcpc_build_info"}),
     ("mcpc_hebbian.h", {"mcpc_flush", "mcpc_build_info"}),
+    ("mcpc_steps_u.h", {"mcpc_steps_u", "mcpc_build_info"}),
+    ("mcpc_steps_ws2_body.inc", {"mcpc_steps_ws2", "mcpc_steps_ws2_spec", "mcpc_build_info"}),
+    ("mcpc_chain_energy.h", {"mcpc_eval", "mcpc_build_info"}),
+    ("mcpc_run.hip", {"mcpc_run", "mcpc_build_info"}),
 ])
 def test_an_edit_recompiles_its_unit_and_the_build_info(built, touched, units):
     assert planned(touched) == (units, True)
@@ -78,7 +106,7 @@ def test_an_edit_recompiles_its_unit_and_the_build_info(built, touched, units):
 
 def test_a_step_kernel_edit_leaves_the_records_unit_alone(built):
     units, links = planned("mcpc_gemm_f16.h")
-    assert links and "mcpc_api" in units and "mcpc_build_info" in units and "mcpc_records" not in units, units
+    assert links and units == set(UNITS) - {"mcpc_run", "mcpc_records"}, units
 
 
 def test_nothing_to_do_when_nothing_changed(built):

@@ -1,5 +1,5 @@
 """The Hebbian flush against fp64 sums of the recorded states, on every plan `plan_flush` (csrc/mcpc_plan.h) can choose; `flush_spill`
-(csrc/mcpc_api.hip) executes the planned launches.
+(csrc/mcpc_flush.hip) executes the planned launches.
 
 A learning call records x_t on every step of its accumulation window; the fp64 sums of the same window are then built from the records
 (as tests/test_gpu_headline.py does):  dF/dW_j = -sum e_j^T f(x_{j-1}) for the latent Linears, +sum e_o^T f(x_L) for the

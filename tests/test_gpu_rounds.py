@@ -1,4 +1,4 @@
-"""The round schedule (csrc/mcpc_plan.h: plan_rounds, csrc/mcpc_api.hip: run_round_cycle): a shard of more 16-chain units than CUs runs as k launches
+"""The round schedule (csrc/mcpc_plan.h: plan_rounds, csrc/mcpc_run.hip: run_round_cycle): a shard of more 16-chain units than CUs runs as k launches
 per cycle, every unit in m of them, instead of ceil(U / CUs) hardware rounds.
 
 Chains are independent and every schedule runs the same per-chain arithmetic, so against

@@ -1,4 +1,4 @@
-"""A run does what its plan says (csrc/mcpc_plan.h: plan_run; csrc/mcpc_api.hip: mcpc_run executes the plan's items in order).
+"""A run does what its plan says (csrc/mcpc_plan.h: plan_run; csrc/mcpc_run.hip: mcpc_run executes the plan's items in order).
 
 With profiling on, mcpc_run brackets every launch of the step kernel with HIP events and counts the steps the launches cover
 (mcpc_last_step_kernel_ms); mcpc_last_step_kernel_name names the forms it launched.  Both must be what mcpc_debug_run_plan plans for

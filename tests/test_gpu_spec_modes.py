@@ -1,7 +1,7 @@
 """The specialised instantiations of the in-place step kernel against its generic one (csrc/mcpc_ws2_lean.h: Ws2Mode).
 
 Every case runs the same call on two engines -- the default, whose launches take a specialised instantiation where
-`ws2_select_mode` (csrc/mcpc_api.hip) finds that every workgroup would decide alike, and `tuning="spec=0"`, which keeps every
+`ws2_select_mode` (csrc/mcpc_run.hip) finds that every workgroup would decide alike, and `tuning="spec=0"`, which keeps every
 launch on the generic kernel -- from the same state and seed, and demands
 
 * bitwise equal final states, recorded states and read-out records, and flat gradient bucket (`torch.equal`): a mode removes

@@ -162,7 +162,7 @@ def _args(text, name):
 
 def test_header_source_and_binding_agree_on_the_signature():
     header = open(os.path.join(ROOT, "include", "mcpc.h")).read()
-    source = open(os.path.join(ROOT, "montecarlopredictivecoding_amd", "csrc", "mcpc_api.hip")).read()
+    source = open(os.path.join(ROOT, "montecarlopredictivecoding_amd", "csrc", "mcpc_eval.hip")).read()       # the unit of the evaluators
     assert re.search(r"#define\s+MCPC_ABI_VERSION\s+4\b", header) and _lib.ABI_VERSION == 4
     name = "mcpc_prediction_errors"
     h, s = _args(header, name), _args(source, name)
