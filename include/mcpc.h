@@ -542,6 +542,33 @@ int mcpc_loglik_accumulate(int device, const float* y, int64_t n_data, const flo
                            int64_t workspace_bytes, void* stream);
 int64_t mcpc_loglik_workspace_bytes(int64_t n_data, int64_t n_samp, int32_t width);
 
+/* The log-weight increment of annealed importance sampling, on the device (csrc/mcpc_ais.h): what turns the Langevin kernels into an
+ * estimate of the evidence.  x is device fp32 [rows][width], the last latent layer of `rows` chains (the layout of one record, or of
+ * mcpc_store_state's last tensor); W fp32 [n_out][width] (torch layout), the UNSCALED read-out; bias [n_out] or NULL (zeros); y fp32
+ * [rows][n_out], the target row of each chain; act an MCPC_ACT_*; logw device fp64 [rows].  All contiguous.  For every row r
+ *   o_u     = bias_u + sum_k f(x_rk) W_uk                                                              u < n_out
+ *   l(a)    = sum over u >= mask_start of   MCPC_LOSS_BERNOULLI: softplus(a o_u) - y_ru a o_u
+ *                                           MCPC_LOSS_GAUSSIAN:  (0.5 / loss_var) (a o_u - y_ru)^2
+ *   logw[r] = (accumulate ? logw[r] : 0) + c0 l(a0) - c1 l(a1)
+ * so that with f_k(x) = p(x) exp(-loss_k(x)) one call adds log f_k(x) - log f_{k-1}(x): the Bernoulli ladder that scales the read-out
+ * takes (a0, c0, a1, c1) = (beta_{k-1}, 1, beta_k, 1), the geometric Gaussian ladder (1, beta_{k-1}, 1, beta_k).  A side whose c is
+ * exactly 0 is not evaluated and contributes exactly 0.  No normalising constant is added: the caller owns them.
+ *   arithmetic    fp64 throughout: the contraction on the fp64 MFMA with the operands converted from fp32 on load, f (ReLU, tanh,
+ *                 identity) and the loss terms in fp64, softplus(z) = max(z, 0) + log1p(exp(-|z|)); every sum has one fixed order.
+ *   independence  a row's result depends on that row, W, bias and the scalars alone: not on `rows`, on the other rows or on the launch
+ *                 shape.  Two runs of the same call are bitwise equal.  No atomics, no workspace, nothing is allocated.
+ *   non-finite    a NaN or Inf stays in its own row.
+ * Against exact arithmetic a result stays within 2^-40 M_r, M_r = sum_u [ c0 |term0_u| + c1 |term1_u| + (|c0 a0 dl0/do_u| +
+ * |c1 a1 dl1/do_u|) (|bias_u| + sum_k |f(x_rk) W_uk|) ] (tests/ais_cases.py derives it).
+ * Stateless, asynchronous on `stream` (a hipStream_t), no engine needed, all offsets 64-bit.  rows = 0 launches nothing.
+ * MCPC_EINVAL, checked before any HIP call (nothing is launched then): width < 1, n_out < 1, rows outside 0..MCPC_AIS_MAX_ROWS,
+ * mask_start outside 0..n_out-1, an unknown act or loss_kind or MCPC_LOSS_NONE, MCPC_LOSS_GAUSSIAN with loss_var <= 0, a NaN scalar
+ * (loss_var, a0, c0, a1, c1), x, W, y or logw NULL with rows > 0. */
+#define MCPC_AIS_MAX_ROWS 2147483647LL
+int mcpc_ais_increment(int device, const float* x, int64_t rows, int32_t width, int32_t act, const float* W, const float* bias,
+                       int32_t n_out, const float* y, int32_t loss_kind, double loss_var, int32_t mask_start, double a0, double c0,
+                       double a1, double c1, double* logw, int32_t accumulate, void* stream);
+
 /* Per-chain energies of recorded states, evaluated on the device (the reference has them per datapoint: is_return_batchelement_loss,
  * PCLayer(is_keep_energy_per_datapoint=True), get_energies(is_per_datapoint=True); pc_trainer.py:776-836, pc_layer.py:250-262).
  * A ROW is one chain at one recorded step.  x_rec[l], l < n_latent: [n_rec][batch][n_l] fp32, as mcpc_run writes rec_x[l] (n_rec = 1

@@ -131,6 +131,9 @@ SYMBOLS = {
     "mcpc_loglik_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_double,
                                          C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "mcpc_loglik_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
+    "mcpc_ais_increment": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                     C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p,
+                                     C.c_int32, C.c_void_p]),
     "mcpc_chain_energies": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_int32,
                                       C.c_void_p, C.c_int32, C.c_void_p]),
     "mcpc_prediction_errors": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_int32,

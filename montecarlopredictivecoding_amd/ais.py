@@ -1,0 +1,250 @@
+"""Annealed importance sampling (Neal 2001) of the log marginal likelihood PER DATUM: the estimator behind ``PCTrainer.mcpc_ais``.
+
+Importance sampling from the prior (``likelihood.log_likelihood``) is degenerate: its effective sample size is about 1 on a 784-pixel
+read-out.  AIS walks every chain from an exact prior sample to the posterior over a ladder of distributions ``f_0 .. f_K`` with a few
+Langevin steps per rung, and the product of the ratios ``f_k(x_{k-1}) / f_{k-1}(x_{k-1})`` met on the way is an importance weight whose
+mean estimates ``Z_K / Z_0``.  Everything it needs is what the engine is fast at: ``Engine.sample_prior`` draws the start,
+``Engine.run`` makes the transitions, ``engine.ais_increment`` (csrc/mcpc_ais.h) adds the log-ratio per chain in fp64.
+
+The two ladders, both walked with what ``mcpc_run`` already takes:
+  Bernoulli  ``f_k(x) = p(x) exp(-BCE(beta_k o(x), y))``: rung k runs the ordinary Bernoulli loss on a read-out scaled by ``beta_k``
+             (a scratch copy, re-bound per rung).  At ``beta = 0`` the likelihood factor is the constant ``2^-n_active``.
+  Gaussian   ``f_k(x) = p(x) exp(-beta_k (0.5 / var) |o(x) - y|^2)``: the geometric ladder, rung k runs ``loss_var = var / beta_k``.
+             ``f_0`` is the prior; the likelihood's normaliser ``(2 pi var)^(-n_active / 2)`` is added at the end.
+
+This module holds the host logic (schedule, scalars per rung, chunking, the fold of log-weights into a ``LogLikelihood`` state) as
+functions that need no device, and ``run``, the loop itself.  No device code.
+"""
+import math
+from typing import List, Optional, Sequence, Tuple
+
+import torch
+
+from . import _lib as L
+from .likelihood import LogLikelihood, empty_state
+
+
+def schedule(stages: int = 64, power: float = 2.0, betas: Optional[Sequence[float]] = None) -> List[float]:
+    """The ladder ``beta_0 = 0 < beta_1 < ... < beta_K = 1``: ``(k / stages)^power`` for k = 0..stages, or ``betas`` as given, which
+    must be strictly increasing from exactly 0 to exactly 1.  Anything else is a ValueError."""
+    if betas is None:
+        if isinstance(stages, bool) or not isinstance(stages, int) or stages < 1:
+            raise ValueError(f"stages={stages!r}, must be an int of at least 1")
+        power = float(power)
+        if not (power > 0.0 and math.isfinite(power)):
+            raise ValueError(f"power={power!r}, must be positive and finite")
+        out = [(k / stages) ** power for k in range(stages + 1)]
+        out[0], out[-1] = 0.0, 1.0
+    else:
+        try:
+            out = [float(b) for b in betas]
+        except (TypeError, ValueError):
+            raise ValueError(f"betas must be a sequence of numbers, got {betas!r}") from None
+        if len(out) < 2:
+            raise ValueError(f"betas holds {len(out)} values, at least two (0 and 1) are needed")
+        if out[0] != 0.0 or out[-1] != 1.0:
+            raise ValueError(f"betas must start at 0 and end at 1, got {out[0]!r} .. {out[-1]!r}")
+    if any(not math.isfinite(b) for b in out) or any(not a < b for a, b in zip(out, out[1:])):
+        raise ValueError("betas must be finite and strictly increasing" + ("" if betas is not None else
+                                                                          f" (stages={stages}, power={power}: two rungs coincide)"))
+    return out
+
+
+def rung_scalars(loss_kind: int, beta_prev: float, beta_k: float) -> Tuple[float, float, float, float]:
+    """``(a0, c0, a1, c1)`` of ``ais_increment`` for the step from rung k-1 to rung k: ``c0 l(a0) - c1 l(a1) = log f_k - log f_{k-1}``."""
+    if loss_kind == L.LOSS_BERNOULLI:
+        return (float(beta_prev), 1.0, float(beta_k), 1.0)
+    if loss_kind == L.LOSS_GAUSSIAN:
+        return (1.0, float(beta_prev), 1.0, float(beta_k))
+    raise ValueError(f"loss_kind={loss_kind}: the ladder is defined for the Bernoulli and the Gaussian read-out")
+
+
+def rung_run(loss_kind: int, var: float, beta_k: float) -> Tuple[float, float]:
+    """``(read-out scale, loss_var)`` of the Langevin steps that target ``f_k``."""
+    if loss_kind == L.LOSS_BERNOULLI:
+        return float(beta_k), 1.0
+    return 1.0, float(var) / float(beta_k)
+
+
+def log_norm(loss_kind: int, n_active: int, var: float = 1.0) -> float:
+    """What is subtracted from a chain's log-weight: ``-log`` of the constant the ladder leaves out.  Bernoulli: ``f_0`` carries
+    ``exp(-BCE(0, y)) = 2^-n_active``, so ``Z_0 = 2^-n_active`` and ``log p = log mean w + log Z_0``; Gaussian: the density's
+    normaliser ``(2 pi var)^(-n_active / 2)``."""
+    if loss_kind == L.LOSS_BERNOULLI:
+        return n_active * math.log(2.0)
+    return 0.5 * n_active * math.log(2.0 * math.pi * float(var))
+
+
+def chunks(n_data: int, replicas: int, max_chains: int, chain_base: int = 0) -> List[Tuple[int, int, int]]:
+    """``[(first datum, data, global id of the first chain)]``: the call as chunks of at most ``max_chains // replicas`` data.  Chain
+    ``c`` of a chunk serves datum ``first + c // replicas``; its global id counts the chains of the whole call from ``chain_base``."""
+    for name, v in (("replicas", replicas), ("max_chains", max_chains)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"{name}={v!r}, must be an int of at least 1")
+    if isinstance(chain_base, bool) or not isinstance(chain_base, int) or chain_base < 0:
+        raise ValueError(f"chain_base={chain_base!r}, must be a non-negative int")
+    per = max_chains // replicas
+    if per < 1:
+        raise ValueError(f"max_chains={max_chains} holds not one datum's {replicas} replicas")
+    if chain_base + n_data * replicas > 1 << 32:
+        raise ValueError(f"chain_base={chain_base} with {n_data * replicas} chains: chain ids are 32 bits")
+    return [(d0, min(per, n_data - d0), chain_base + d0 * replicas) for d0 in range(0, n_data, per)]
+
+
+def engine_calls(n_data, replicas, max_chains, n_rungs, steps_per_stage, step_base=0, chain_base=0):
+    """Every engine call of ``run`` that consumes normals, in order: ``(what, sample_base or chain_base, step_base, chains)`` with
+    ``what`` "prior" (``Engine.sample_prior``) or "run" (``Engine.run`` of ``steps_per_stage`` steps).  The prior uses step
+    ``step_base``; the transitions after increment k use steps ``step_base + 1 + (k - 1) * steps_per_stage`` onwards: no normal twice."""
+    out = []
+    for _, n, g0 in chunks(n_data, replicas, max_chains, chain_base):
+        out.append(("prior", g0, step_base, n * replicas))
+        for k in range(1, n_rungs):
+            out.append(("run", g0, step_base + 1 + (k - 1) * steps_per_stage, n * replicas))
+    return out
+
+
+def fold(logw: torch.Tensor, replicas: int, const: float) -> torch.Tensor:
+    """``[n, 4]`` fp64 ``LogLikelihood`` states of n data from the log-weights ``logw`` ``[n * replicas]`` of their chains (datum i:
+    chains ``i * replicas ..``): ``nll_r = -(logw_r - const)``, then ``m = min nll``, ``s1 = sum e^-(nll - m)``, ``s2 = sum e^-2(nll -
+    m)``, ``cnt``, over the finite ones -- a replica whose log-weight is not finite is neither taken nor counted.  On the device of
+    ``logw``.  Element-wise operations and a halving tree of additions only: a datum's state does not depend on the other data."""
+    nll = -(logw.to(torch.float64).reshape(-1, int(replicas)) - float(const))
+    ok = torch.isfinite(nll)
+    n = nll.shape[0]
+    m = torch.where(ok, nll, torch.full_like(nll, math.inf)).min(dim=1).values if nll.shape[1] else torch.full((n,), math.inf)
+    live = m < math.inf
+    base = torch.where(live, m, torch.zeros_like(m)).unsqueeze(1)
+    e = torch.where(ok, torch.exp(-(torch.where(ok, nll, base) - base)), torch.zeros_like(nll))
+    width = 1
+    while width < nll.shape[1]:
+        width *= 2
+    pad = torch.zeros(n, width - nll.shape[1], dtype=torch.float64, device=nll.device)
+    s1, s2, cnt = (torch.cat([t, pad], dim=1) for t in (e, e * e, ok.to(torch.float64)))
+    while width > 1:
+        width //= 2
+        s1, s2, cnt = (t[:, :width] + t[:, width:2 * width] for t in (s1, s2, cnt))
+    st = torch.stack([m, s1[:, 0], s2[:, 0], cnt[:, 0]], dim=1)
+    return torch.where(live.unsqueeze(1), st, empty_state(n, nll.device))
+
+
+def check_counts(replicas, steps_per_stage, noise_var, seed, step_base):
+    for name, v, low in (("replicas", replicas, 1), ("steps_per_stage", steps_per_stage, 1), ("seed", seed, None), ("step_base", step_base, 0)):
+        if isinstance(v, bool) or not isinstance(v, int) or (low is not None and v < low):
+            raise ValueError(f"{name}={v!r}, must be an int" + ("" if low is None else f" of at least {low}"))
+    if not (float(noise_var) > 0.0 and math.isfinite(float(noise_var))):
+        raise ValueError(f"noise_var={noise_var!r}, must be positive and finite")
+
+
+def resolve_lr(lr, xopt, why=""):
+    """The Langevin step size: ``lr``, or the trainer's x optimiser's when that is plain SGD."""
+    if lr is None:
+        if xopt is None or xopt.kind != L.XOPT_SGD:
+            raise ValueError("lr: the trainer's x optimiser is not plain SGD ({}); its lr is no Langevin step size -- pass lr=".format(
+                why or "Adam"))
+        return float(xopt.lr)
+    lr = float(lr)
+    if not (lr > 0.0 and math.isfinite(lr)):
+        raise ValueError(f"lr={lr!r}, must be positive and finite")
+    return lr
+
+
+def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, power=2.0, betas=None, steps_per_stage=5, lr=None,
+        noise_var=2.0, seed=0, step_base=0, chain_base=0, max_chains=6000, return_logw=False):
+    """``PCTrainer.mcpc_ais`` (its docstring is the contract).  ``return_logw``: also the raw log-weights, fp64 ``[N * replicas]``."""
+    from . import engine as E
+    from .predictive_coding import recognise
+    loss_fn_kwargs = dict(loss_fn_kwargs or {})
+    if "_target" in loss_fn_kwargs:
+        raise ValueError("mcpc_ais: loss_fn_kwargs holds a _target; `data` is the target")
+    ladder = schedule(stages, power, betas)
+    check_counts(replicas, steps_per_stage, noise_var, seed, step_base)
+    net, why = recognise.describe_model(trainer._model)
+    if net is None:
+        raise NotImplementedError("mcpc_ais: outside what the HIP engine expresses ({})".format(why))
+    if net.n_out == 0:
+        raise NotImplementedError("mcpc_ais: the model ends in a PCLayer; the evidence is that of a read-out's data")
+    if loss_fn is None:
+        raise NotImplementedError("mcpc_ais: a read-out distribution is needed (bernoulli_fn, fe_fn or their masked forms)")
+    model_device = net.linears[0].weight.device
+    if not isinstance(data, torch.Tensor):
+        data = torch.tensor(data)                # a copy: the array may be read-only
+    if data.dim() != 2 or data.shape[1] != net.n_out:
+        raise ValueError(f"data: expected [N, {net.n_out}], got {tuple(data.shape)}")
+    n_data = int(data.shape[0])
+    # everything the call can refuse is refused here, before a device is asked for
+    kw = dict(loss_fn_kwargs, _target=torch.zeros(1, net.n_out, device=model_device))       # (the loss is recognised by its kind alone)
+    loss, why = recognise.describe_loss(loss_fn, kw, net.n_out, 1, model_device)
+    if loss is None:
+        raise NotImplementedError("mcpc_ais: outside what the HIP engine expresses ({})".format(why))
+    if loss.kind not in (L.LOSS_BERNOULLI, L.LOSS_GAUSSIAN):
+        raise NotImplementedError("mcpc_ais: the read-out is Bernoulli (bernoulli_fn) or Gaussian (fe_fn), masked or not")
+    if lr is None:
+        xopt, why = (None, "manual_optimizer_x_fn is set") if trainer._manual_optimizer_x_fn is not None else \
+            recognise.describe_x_optimizer(trainer._optimizer_x_fn, trainer._optimizer_x_kwargs)
+        lr = resolve_lr(None, xopt, why or "optimizer_x_fn is {}".format(getattr(trainer._optimizer_x_fn, "__name__", trainer._optimizer_x_fn)))
+    else:
+        lr = resolve_lr(lr, None)
+    chunks(n_data, replicas, max_chains, chain_base)
+    plan, why = trainer._plan(torch.zeros(1, net.n_in, device=model_device), loss_fn, kw, False, False, None, None, {}, {}, False, False)
+    if plan is None:
+        raise NotImplementedError("mcpc_ais: outside what the HIP engine expresses ({})".format(why))
+    net, loss = plan["net"], plan["loss"]
+    parts = chunks(n_data, replicas, max_chains, chain_base)
+    device = plan["device"]
+    n_active = net.n_out - loss.mask_start
+    const = log_norm(loss.kind, n_active, loss.var)
+    y_all = data.to(device=device, dtype=torch.float32).contiguous()
+    K = len(ladder) - 1
+    states, logws = [], []
+    engines = []
+    try:
+        with torch.cuda.device(device):
+            for d0, n, g0 in parts:
+                B = n * replicas
+                eng = trainer._engine_for(dict(plan, B=B))
+                if all(eng is not e for e in engines):
+                    engines.append(eng)
+                trainer._sync_params(eng, net, plan=plan)
+                weights, biases = list(eng._keep["W"]), list(eng._keep["b"])
+                W_L, b_L = weights[-1], biases[-1]
+                y = y_all[d0:d0 + n].repeat_interleave(replicas, dim=0).contiguous()
+                eng.bind_inputs(None)
+                eng.bind_target(y)
+                if loss.kind == L.LOSS_BERNOULLI:
+                    # the scaled read-out of the rung, a scratch copy the engine is bound to for the length of the chunk
+                    W_s, b_s = W_L.clone(), None if b_L is None else b_L.clone()
+                    eng._bound_sig = None
+                    eng.bind_params(weights[:-1] + [W_s], biases[:-1] + [b_s])         # (re-packed per rung below)
+                _, xs = eng.sample_prior(B, seed, step=step_base, sample_base=g0, latents=True, readout=None)
+                eng.load_state(xs)
+                logw = torch.zeros(B, dtype=torch.float64, device=device)
+                for k in range(1, K + 1):
+                    eng.store_state(xs)
+                    a0, c0, a1, c1 = rung_scalars(loss.kind, ladder[k - 1], ladder[k])
+                    E.ais_increment(xs[-1], W_L, b_L, y, net.acts[-1], loss.kind, loss.var, loss.mask_start, a0, c0, a1, c1, logw,
+                                    accumulate=True)
+                    if k == K:
+                        break
+                    scale, run_var = rung_run(loss.kind, loss.var, ladder[k])
+                    if loss.kind == L.LOSS_BERNOULLI:
+                        torch.mul(W_L, scale, out=W_s)
+                        if b_s is not None:
+                            torch.mul(b_L, scale, out=b_s)
+                        eng.params_changed()
+                    eng.run(steps_per_stage, loss_kind=loss.kind, loss_var=run_var, mask_start=loss.mask_start, xopt=L.XOPT_SGD, lr=lr,
+                            noise_mode=L.NOISE_PHILOX, noise_var=float(noise_var), seed=seed,
+                            step_base=step_base + 1 + (k - 1) * steps_per_stage, chain_base=g0)
+                eng.sync_check()
+                states.append(fold(logw, replicas, const))
+                if return_logw:
+                    logws.append(logw)
+    finally:
+        # the engines are cached (and shared with train_on_batch): each one holds the model's own read-out again
+        for eng in engines:
+            eng._bound_sig = None
+            trainer._sync_params(eng, net, force=True, plan=plan)
+    state = torch.cat(states, dim=0) if states else empty_state(0, device)
+    res = LogLikelihood(state=state.to(plan["model_device"]))
+    if return_logw:
+        return res, (torch.cat(logws) if logws else torch.zeros(0, dtype=torch.float64, device=device))
+    return res

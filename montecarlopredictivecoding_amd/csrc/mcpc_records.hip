@@ -1,6 +1,6 @@
 // libmcpc.so, the stateless reducers over recorded states: the entries of include/mcpc.h that take an `int device` and no engine --
 // moments, covariances, histograms (1-D and joint), lagged autocovariances, rolling windows, linear probes, nearest-neighbour
-// divergences, log marginal likelihoods -- with their kernels.  A translation unit of its own: it sees nothing of the step kernels,
+// divergences, log marginal likelihoods, annealed-importance-sampling increments -- with their kernels.  A translation unit of its own: it sees nothing of the step kernels,
 // the planner or the engine, and an edit to a reducer recompiles this unit alone.  What an entry refuses is read through
 // mcpc_last_error (mcpc_api.hip) like every other error of the library: mcpc_host.h.
 #include <hip/hip_runtime.h>
@@ -19,6 +19,7 @@
 #include "mcpc_probe.h"
 #include "mcpc_knn.h"
 #include "mcpc_loglik.h"
+#include "mcpc_ais.h"
 
 using namespace mcpc;
 
@@ -478,6 +479,41 @@ int mcpc_loglik_accumulate(int device, const float* y, int64_t n_data, const flo
     P.b = P.a + n_data;
     P.state = state;
     loglik_dispatch(g, P, stream);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+int mcpc_ais_increment(int device, const float* x, int64_t rows, int32_t width, int32_t act, const float* W, const float* bias,
+                       int32_t n_out, const float* y, int32_t loss_kind, double loss_var, int32_t mask_start, double a0, double c0,
+                       double a1, double c1, double* logw, int32_t accumulate, void* stream_) {
+    if (width < 1) return fail(MCPC_EINVAL, "ais: width=%d, must be at least 1", width);
+    if (n_out < 1) return fail(MCPC_EINVAL, "ais: n_out=%d, must be at least 1", n_out);
+    if (rows < 0 || rows > MCPC_AIS_MAX_ROWS)
+        return fail(MCPC_EINVAL, "ais: rows=%lld outside 0..%lld", (long long)rows, (long long)MCPC_AIS_MAX_ROWS);
+    if (mask_start < 0 || mask_start >= n_out) return fail(MCPC_EINVAL, "ais: mask_start=%d outside 0..%d", mask_start, n_out - 1);
+    if (act != MCPC_ACT_IDENTITY && act != MCPC_ACT_RELU && act != MCPC_ACT_TANH) return fail(MCPC_EINVAL, "ais: unknown act %d", act);
+    if (loss_kind != MCPC_LOSS_BERNOULLI && loss_kind != MCPC_LOSS_GAUSSIAN)
+        return fail(MCPC_EINVAL, "ais: loss_kind=%d, expected MCPC_LOSS_GAUSSIAN (%d) or MCPC_LOSS_BERNOULLI (%d)", loss_kind,
+                    MCPC_LOSS_GAUSSIAN, MCPC_LOSS_BERNOULLI);
+    if (loss_kind == MCPC_LOSS_GAUSSIAN && !(loss_var > 0.0)) return fail(MCPC_EINVAL, "ais: loss_var=%g, must be positive", loss_var);
+    if (std::isnan(loss_var) || std::isnan(a0) || std::isnan(c0) || std::isnan(a1) || std::isnan(c1))
+        return fail(MCPC_EINVAL, "ais: a scalar is NaN (loss_var=%g a0=%g c0=%g a1=%g c1=%g)", loss_var, a0, c0, a1, c1);
+    if (rows > 0 && !x) return fail(MCPC_EINVAL, "ais: x is null with rows=%lld", (long long)rows);
+    if (rows > 0 && !W) return fail(MCPC_EINVAL, "ais: W is null with rows=%lld", (long long)rows);
+    if (rows > 0 && !y) return fail(MCPC_EINVAL, "ais: y is null with rows=%lld", (long long)rows);
+    if (rows > 0 && !logw) return fail(MCPC_EINVAL, "ais: logw is null with rows=%lld", (long long)rows);
+    if (rows == 0) return MCPC_OK;                                // no row to write
+    HIP_TRY(hipSetDevice(device));
+    AisParams P{};
+    P.x = x; P.W = W; P.bias = bias; P.y = y; P.logw = logw; P.rows = rows;
+    P.width = width; P.n_out = n_out; P.mask_start = mask_start;
+    P.gauss = loss_kind == MCPC_LOSS_GAUSSIAN ? 1 : 0;
+    P.accumulate = accumulate ? 1 : 0;
+    P.tile_begin = mask_start / 16;
+    P.n_groups = ((n_out + 15) / 16 - P.tile_begin + kAisTiles - 1) / kAisTiles;
+    P.a0 = a0; P.c0 = c0; P.a1 = a1; P.c1 = c1;
+    P.half_inv_var = P.gauss ? 0.5 / loss_var : 0.0;
+    ais_dispatch(act, P, (hipStream_t)stream_);
     HIP_TRY(hipGetLastError());
     return MCPC_OK;
 }

@@ -990,3 +990,57 @@ def loglik_accumulate(y, out, loss, var, clamp, state, accumulate=False, workspa
     L.check(lib.mcpc_loglik_accumulate(device.index or 0, _ptr(y), n_data, _ptr(out), n_samp, width, _LOGLIK_LOSSES[loss],
                                        float(var) if loss == "gaussian" else 1.0, clamp, _ptr(state), 1 if accumulate else 0,
                                        _ptr(workspace), ws_bytes, stream))
+
+
+_AIS_ACTS = {"identity": L.ACT_IDENTITY, "relu": L.ACT_RELU, "tanh": L.ACT_TANH,
+             L.ACT_IDENTITY: L.ACT_IDENTITY, L.ACT_RELU: L.ACT_RELU, L.ACT_TANH: L.ACT_TANH}
+_AIS_LOSSES = {**_LOGLIK_LOSSES, L.LOSS_BERNOULLI: L.LOSS_BERNOULLI, L.LOSS_GAUSSIAN: L.LOSS_GAUSSIAN}
+
+
+def ais_increment(x, W, bias, y, act, loss, var, mask_start, a0, c0, a1, c1, logw, accumulate=True):
+    """Add the log-weight increment of one rung of annealed importance sampling to ``logw`` on the device (include/mcpc.h:
+    mcpc_ais_increment).  ``x``: contiguous fp32 ``[rows, width]``, the last latent layer of ``rows`` chains; ``W``: contiguous fp32
+    ``[n_out, width]`` (the layout of ``nn.Linear.weight``), the UNSCALED read-out; ``bias``: fp32 ``[n_out]`` or None for zeros;
+    ``y``: contiguous fp32 ``[rows, n_out]``, the target row of each chain; ``act``: "identity", "relu", "tanh" or an ``L.ACT_*``;
+    ``loss``: "bernoulli", "gaussian" or an ``L.LOSS_*`` (Gaussian: with the variance ``var``); ``logw``: contiguous fp64 ``[rows]``.
+    With ``o = f(x) W^T + bias`` and ``l(a)`` the loss of ``a o`` against ``y`` summed over the columns from ``mask_start`` on,
+    ``logw += c0 l(a0) - c1 l(a1)`` per row (``accumulate=False`` overwrites); a side whose ``c`` is exactly 0 is not evaluated.  fp64
+    throughout, the contraction on the fp64 MFMA.  A row's result depends on that row, ``W``, ``bias`` and the scalars alone, and two
+    runs of the same call are bitwise equal.  Everything on the device of ``x``.  On the current torch stream."""
+    lib = L.load()
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise TypeError("x: expected a torch.Tensor [rows, width]")
+    if not isinstance(W, torch.Tensor) or W.dim() != 2:
+        raise TypeError("W: expected a torch.Tensor [n_out, width]")
+    device = x.device
+    if device.type != "cuda":
+        raise ValueError(f"x: expected a tensor on a HIP device, got {device}")
+    if act not in _AIS_ACTS:
+        raise ValueError(f"act: expected 'identity', 'relu' or 'tanh', got {act!r}")
+    if loss not in _AIS_LOSSES:
+        raise ValueError(f"loss: expected 'bernoulli' or 'gaussian', got {loss!r}")
+    loss_kind = _AIS_LOSSES[loss]
+    if loss_kind == L.LOSS_GAUSSIAN and (var is None or not float(var) > 0.0):
+        raise ValueError(f"var: the Gaussian read-out needs a positive variance, got {var!r}")
+    rows, width = (int(s) for s in x.shape)
+    n_out = int(W.shape[0])
+    if width < 1 or n_out < 1:
+        raise ValueError(f"x has {width} columns and W {n_out} rows: expected at least one of each")
+    mask_start = int(mask_start)
+    if not 0 <= mask_start < n_out:
+        raise ValueError(f"mask_start={mask_start} outside 0..{n_out - 1}")
+    scalars = [float(v) for v in (a0, c0, a1, c1)]
+    if any(v != v for v in scalars):
+        raise ValueError(f"(a0, c0, a1, c1) = {tuple(scalars)}: a NaN")
+    _check_tensor(x, (rows, width), device, "x")
+    _check_tensor(W, (n_out, width), device, "W")
+    if bias is not None:
+        _check_tensor(bias, (n_out,), device, "bias")
+    _check_tensor(y, (rows, n_out), device, "y")
+    _check_tensor(logw, (rows,), device, "logw", torch.float64)
+    if rows == 0:                                  # an empty tensor has no address to hand over
+        return
+    stream = _current_stream(device)
+    L.check(lib.mcpc_ais_increment(device.index or 0, _ptr(x), rows, width, _AIS_ACTS[act], _ptr(W), _ptr(bias), n_out, _ptr(y), loss_kind,
+                                   float(var) if loss_kind == L.LOSS_GAUSSIAN else 1.0, mask_start, *scalars, _ptr(logw),
+                                   1 if accumulate else 0, stream))

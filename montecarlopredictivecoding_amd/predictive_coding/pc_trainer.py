@@ -1078,6 +1078,42 @@ class PCTrainer(object):
         to = plan["model_device"]
         return (None if out is None else out.to(to)), [None if x is None else x.to(to) for x in xs]
 
+    def mcpc_ais(self, data, loss_fn: typing.Callable, loss_fn_kwargs: dict = {}, *, replicas=64, stages=64, power=2.0, betas=None,
+                 steps_per_stage=5, lr=None, noise_var=2.0, seed=0, step_base=0, chain_base=0, max_chains=6000):
+        """The log marginal likelihood of every row of ``data`` ``[N, n_out]`` by annealed importance sampling (Neal 2001) on the device
+        (montecarlopredictivecoding_amd/ais.py): ``replicas`` chains per datum start from exact ancestral samples
+        (``Engine.sample_prior``), walk the ladder ``beta_0 = 0 .. beta_K = 1`` -- ``(k / stages)^power``, or ``betas``, strictly
+        increasing from 0 to 1 -- with ``steps_per_stage`` Langevin steps per rung (``Engine.run``: SGD with ``lr``, Philox noise of
+        ``noise_var``) and collect one log-weight each in fp64 (``engine.ais_increment``).  ``loss_fn``: ``bernoulli_fn`` (the rung
+        scales the read-out by ``beta_k``), ``fe_fn`` (the rung runs ``_var / beta_k``) or their masked forms, with ``_var`` / ``perc``
+        in ``loss_fn_kwargs`` as train_on_batch takes them; ``data`` is the target, no ``_target`` is passed.  ``lr=None`` takes the
+        trainer's x optimiser's, which must then be plain SGD (ValueError otherwise).  Chain ``c`` of the call has the global id
+        ``chain_base + c`` and uses the normals of ``(seed, step_base ..)``: the prior draw at ``step_base``, the transitions from
+        ``step_base + 1`` on, ``1 + (K - 1) * steps_per_stage`` steps in all.  At most ``max_chains`` chains run at once.
+
+        Returns ``likelihood.LogLikelihood`` over the data in order: ``.log_p``, ``.ess`` (of the ``replicas`` weights), ``.n_samples``
+        (a replica whose log-weight is not finite is not taken), ``.mean()``, ``.cat``; ``.merge`` of two calls with disjoint
+        ``chain_base`` ranges is the estimate over the union of their replicas.  The result is a function of the arguments and the
+        parameters alone: bit for bit the same from run to run and whatever ``max_chains`` is.
+
+        What it is: AIS with UNADJUSTED Langevin transitions is unbiased only as ``lr -> 0``.  At a finite ``lr`` the chains sample a
+        slightly wrong distribution at every rung and the estimate carries a bias of order ``lr`` -- negative in every case tried (an
+        under-estimate of log p).  ``.ess`` measures the spread of the weights, not that bias: halve ``lr`` (and double
+        ``steps_per_stage``) to see it.
+
+        The model's parameters, the PCLayers' x, every param.grad, the optimisers, the step counters and the cached engine's parameter
+        binding are what they were when the call returns, also when it raises.  A model or loss the fused loop does not express, or
+        a model without a read-out, raises NotImplementedError."""
+        from .. import ais as _ais
+        with _few_cpu_threads(self._model_is_on_cpu()):
+            return _ais.run(self, data, loss_fn, loss_fn_kwargs, replicas=replicas, stages=stages, power=power, betas=betas,
+                            steps_per_stage=steps_per_stage, lr=lr, noise_var=noise_var, seed=seed, step_base=step_base,
+                            chain_base=chain_base, max_chains=max_chains)
+
+    def _model_is_on_cpu(self) -> bool:
+        p = next(self._model.parameters(), None)
+        return p is not None and p.device.type != "cuda"
+
     def mcpc_state_probe(self, spec):
         """The probe of ``spec`` (a dict as ``mcpc_probe`` takes; ``begin`` and ``stride`` are not consulted) on the CURRENT x of its
         layer -- what a MAP call leaves -- through the kernel of the sampled probe (engine.probe_accumulate with one record): the

@@ -271,6 +271,33 @@ def get_marginal_likelihood_per_datum(gen_pc, config, dataloader, use_cuda, n_sa
     return state
 
 
+def get_marginal_likelihood_ais(gen_pc, config, dataloader, use_cuda, replicas=64, stages=64, steps_per_stage=5, seed=0, **kw):
+    """The log marginal likelihood per datum by annealed importance sampling on the device (``PCTrainer.mcpc_ais``): a
+    ``likelihood.LogLikelihood`` over the loader's data, in the loader's order.  Where ``get_marginal_likelihood_per_datum`` weighs
+    prior samples -- an effective sample size of about 1 on an image -- every datum here gets ``replicas`` chains that are annealed from
+    the prior to its posterior over ``stages`` rungs of ``steps_per_stage`` Langevin steps.  The trainer is the MCPC trainer of
+    ``config`` (``get_mcpc_trainer``: SGD on x with ``config["optimizer_x_kwargs_mcpc"]``, whose ``lr`` is the Langevin step size);
+    ``config["loss_fn"]`` / ``config["input_var"]`` name the read-out.  Batch ``b`` of the loader uses the chain ids that follow those
+    of the batches before it, so the result does not depend on the batch size.  ``kw``: further keywords of ``mcpc_ais`` (``power``,
+    ``betas``, ``lr``, ``noise_var``, ``step_base``, ``chain_base``, ``max_chains``)."""
+    from ..likelihood import LogLikelihood
+    from ..utils.model import bernoulli_fn, fe_fn
+    if config["loss_fn"] not in (bernoulli_fn, fe_fn):
+        raise NotImplementedError("get_marginal_likelihood_ais: the read-out is bernoulli_fn or fe_fn")
+    loss_kw = {"_var": config["input_var"]} if config["loss_fn"] is fe_fn else {}
+    gen_pc.train()
+    device = next(gen_pc.parameters()).device
+    trainer = get_mcpc_trainer(gen_pc, config, training=False)
+    chain_base = int(kw.pop("chain_base", 0))
+    parts = []
+    for data, _ in dataloader:
+        data = data.to(device).reshape(data.shape[0], -1)
+        parts.append(trainer.mcpc_ais(data, config["loss_fn"], loss_kw, replicas=replicas, stages=stages, steps_per_stage=steps_per_stage,
+                                      seed=seed, chain_base=chain_base, **kw))
+        chain_base += data.shape[0] * replicas
+    return LogLikelihood.cat(parts)
+
+
 def knn_kl_divergence(x, y):
     """The nearest-neighbour (Perez-Cruz) estimate of D(P || Q) between samples ``x`` of P and ``y`` of Q on the device: what the
     reference's ``KLdivergence(x, y)`` (:240-284) estimates, by exact brute force instead of two KD-trees queried with ``eps=.01``, so
