@@ -569,6 +569,49 @@ int mcpc_ais_increment(int device, const float* x, int64_t rows, int32_t width, 
                        int32_t n_out, const float* y, int32_t loss_kind, double loss_var, int32_t mask_start, double a0, double c0,
                        double a1, double c1, double* logw, int32_t accumulate, void* stream);
 
+/* The per-chain arithmetic of a Metropolis-adjusted Langevin step (MALA; csrc/mcpc_mala.h): a Langevin proposal followed by a
+ * Metropolis-Hastings decision leaves its target p(x) ~ exp(-F(x)) exactly invariant at any step size, where the unadjusted step of
+ * mcpc_run does so only as lr -> 0.  The gradient g = dF/dx and the energy E = F come from the engine (mcpc_run with update_x = 0 and
+ * xgrad set; the last column of mcpc_chain_energies); these two entries see them as arrays.  A STATE is n_layers contiguous fp32
+ * tensors [rows][widths[l]], 1 <= n_layers <= MCPC_MAX_LATENT, handed over as a host array of device pointers and a host array of
+ * widths (the layout of mcpc_store_state).  Row r is the chain with the global id chain_base + r.
+ *
+ * mcpc_mala_propose: x_out_l = (x_l - lr g_l) + s xi_l per element, in fp32, with lr and s = sqrt(noise_var * lr) rounded to fp32 as
+ * mcpc_run rounds them and xi_l the normals of (seed, step, layer l, chain_base + r): what mcpc_philox_normals returns and a fused
+ * Langevin step at the same (seed, step) consumes.  Four roundings, none contracted: fl(lr g), fl(x - .), fl(s xi), fl(. + .).
+ * x_out must not overlap x or g.
+ *
+ * mcpc_mala_accept, per chain r, with (x, g, E) the current state and (x_prop, g_prop, E_prop) the proposal of `step` and what the
+ * engine evaluated at it:
+ *   log_alpha = E[r] - E_prop[r] - ( sum_l |x_l - x'_l + lr g'_l|^2  -  sum_l |x'_l - x_l + lr g_l|^2 ) / (2 noise_var lr)
+ *   u         = ((w >> 8) + 1) * 2^-24,   w = word 0 of philox4x32_10(chain_base + r, (0xFF << 24) | 0, step lo, step hi; key seed)
+ *   accept    = log(u) < log_alpha                                      (fp64; a NaN log_alpha rejects)
+ * The second term is the log-ratio of the proposal densities, so any noise_var > 0 is valid, not only 2.  Layer index 0xFF lies outside
+ * every layer the normals and mcpc_sample_prior use: no Philox word is consumed twice.
+ *   arithmetic    fp64 from the fp32 inputs, every operation rounded separately, in one fixed order that holds the chain's own values
+ *                 only (csrc/mcpc_mala.h spells it out): a row's result does not depend on `rows` or on the other rows, and two runs
+ *                 are bitwise equal.  No atomics, no workspace, nothing is allocated.
+ *   in place      an accepted chain's rows of x, g and E are overwritten with those of x_prop, g_prop and E_prop; a rejected chain
+ *                 keeps its bits (it is not written).  A step thus costs ONE gradient and ONE energy evaluation, at the proposal.
+ *   non-finite    a NaN or Inf stays in its own chain; a chain whose log_alpha is NaN rejects.
+ *   optional      diag fp64 [rows][3] = (log_alpha, u, accepted as 0 / 1); n_accepted int32 [rows], incremented by 1 for an accepted
+ *                 chain; x_next, a state: the proposal of step + 1 from the selected (x, g), bitwise what mcpc_mala_propose would
+ *                 write (it saves a launch per step).  Each may be NULL.  x_next must not overlap any other argument.
+ * Against exact arithmetic log_alpha stays within 2^-41 M_r, M_r = |E| + |E'| + sum_u [(|x - x'| + lr |g'|)^2 + (|x' - x| + lr |g|)^2] /
+ * (2 noise_var lr), for up to 2038 units per chain (tests/mala_cases.py derives it).
+ * Both: stateless, asynchronous on `stream` (a hipStream_t), no engine needed, all offsets 64-bit, nothing is read or written beyond
+ * rows x widths[l].  rows = 0 launches nothing.  MCPC_EINVAL, checked before any HIP call (nothing is launched then): n_layers outside
+ * 1..MCPC_MAX_LATENT, rows outside 0..MCPC_MALA_MAX_ROWS, lr or noise_var not positive and finite, widths NULL or a width < 1, and
+ * with rows > 0 a NULL state array or a NULL tensor in it (x_next only when given), E or E_prop NULL. */
+#define MCPC_MALA_MAX_ROWS 2147483647LL
+int mcpc_mala_propose(int device, const float* const* x, const float* const* g, const int32_t* widths, int32_t n_layers, int64_t rows,
+                      double lr, double noise_var, uint64_t seed, uint64_t step, uint64_t chain_base, float* const* x_out,
+                      void* stream);
+int mcpc_mala_accept(int device, float* const* x, float* const* g, double* E, const float* const* x_prop, const float* const* g_prop,
+                     const double* E_prop, const int32_t* widths, int32_t n_layers, int64_t rows, double lr, double noise_var,
+                     uint64_t seed, uint64_t step, uint64_t chain_base, double* diag, int32_t* n_accepted, float* const* x_next,
+                     void* stream);
+
 /* Per-chain energies of recorded states, evaluated on the device (the reference has them per datapoint: is_return_batchelement_loss,
  * PCLayer(is_keep_energy_per_datapoint=True), get_energies(is_per_datapoint=True); pc_trainer.py:776-836, pc_layer.py:250-262).
  * A ROW is one chain at one recorded step.  x_rec[l], l < n_latent: [n_rec][batch][n_l] fp32, as mcpc_run writes rec_x[l] (n_rec = 1

@@ -134,6 +134,11 @@ SYMBOLS = {
     "mcpc_ais_increment": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p,
                                      C.c_int32, C.c_void_p]),
+    "mcpc_mala_propose": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_int64,
+                                    C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.c_void_p]),
+    "mcpc_mala_accept": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p),
+                                   C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.c_double, C.c_double,
+                                   C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
     "mcpc_chain_energies": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_int32,
                                       C.c_void_p, C.c_int32, C.c_void_p]),
     "mcpc_prediction_errors": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_int32,

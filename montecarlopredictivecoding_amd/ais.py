@@ -6,6 +6,11 @@ Langevin steps per rung, and the product of the ratios ``f_k(x_{k-1}) / f_{k-1}(
 mean estimates ``Z_K / Z_0``.  Everything it needs is what the engine is fast at: ``Engine.sample_prior`` draws the start,
 ``Engine.run`` makes the transitions, ``engine.ais_increment`` (csrc/mcpc_ais.h) adds the log-ratio per chain in fp64.
 
+The transitions are unadjusted Langevin steps (``adjust=None``: unbiased only as ``lr -> 0``) or Metropolis-adjusted ones
+(``adjust="mala"``): a proposal ``engine.mala_propose``, the engine's gradient (``Engine.run(1, update_x=False)``) and energy
+(``Engine.chain_energies``) at it, and the accept / reject decision ``engine.mala_accept`` (csrc/mcpc_mala.h).  Each adjusted
+transition leaves its rung's distribution exactly invariant, so ``exp(log p_hat)`` is unbiased at any step size.
+
 The two ladders, both walked with what ``mcpc_run`` already takes:
   Bernoulli  ``f_k(x) = p(x) exp(-BCE(beta_k o(x), y))``: rung k runs the ordinary Bernoulli loss on a read-out scaled by ``beta_k``
              (a scratch copy, re-bound per rung).  At ``beta = 0`` the likelihood factor is the constant ``2^-n_active``.
@@ -127,6 +132,13 @@ def fold(logw: torch.Tensor, replicas: int, const: float) -> torch.Tensor:
     return torch.where(live.unsqueeze(1), st, empty_state(n, nll.device))
 
 
+def check_adjust(adjust):
+    """``adjust`` as ``run`` takes it: None (unadjusted Langevin transitions) or "mala"; anything else is a ValueError."""
+    if adjust is not None and not (isinstance(adjust, str) and adjust == "mala"):
+        raise ValueError(f"adjust={adjust!r}, expected None or 'mala'")
+    return adjust
+
+
 def check_counts(replicas, steps_per_stage, noise_var, seed, step_base):
     for name, v, low in (("replicas", replicas, 1), ("steps_per_stage", steps_per_stage, 1), ("seed", seed, None), ("step_base", step_base, 0)):
         if isinstance(v, bool) or not isinstance(v, int) or (low is not None and v < low):
@@ -149,14 +161,16 @@ def resolve_lr(lr, xopt, why=""):
 
 
 def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, power=2.0, betas=None, steps_per_stage=5, lr=None,
-        noise_var=2.0, seed=0, step_base=0, chain_base=0, max_chains=6000, return_logw=False):
-    """``PCTrainer.mcpc_ais`` (its docstring is the contract).  ``return_logw``: also the raw log-weights, fp64 ``[N * replicas]``."""
+        noise_var=2.0, seed=0, step_base=0, chain_base=0, max_chains=6000, adjust=None, return_logw=False, return_accepted=False):
+    """``PCTrainer.mcpc_ais`` (its docstring is the contract).  ``return_logw``: also the raw log-weights, fp64 ``[N * replicas]``.
+    ``return_accepted``: also the accepted proposals per rung and chain, int32 ``[K - 1, N * replicas]`` (None when unadjusted)."""
     from . import engine as E
     from .predictive_coding import recognise
     loss_fn_kwargs = dict(loss_fn_kwargs or {})
     if "_target" in loss_fn_kwargs:
         raise ValueError("mcpc_ais: loss_fn_kwargs holds a _target; `data` is the target")
     ladder = schedule(stages, power, betas)
+    check_adjust(adjust)
     check_counts(replicas, steps_per_stage, noise_var, seed, step_base)
     net, why = recognise.describe_model(trainer._model)
     if net is None:
@@ -195,7 +209,7 @@ def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, 
     const = log_norm(loss.kind, n_active, loss.var)
     y_all = data.to(device=device, dtype=torch.float32).contiguous()
     K = len(ladder) - 1
-    states, logws = [], []
+    states, logws, accepts = [], [], []
     engines = []
     try:
         with torch.cuda.device(device):
@@ -218,7 +232,11 @@ def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, 
                 _, xs = eng.sample_prior(B, seed, step=step_base, sample_base=g0, latents=True, readout=None)
                 eng.load_state(xs)
                 logw = torch.zeros(B, dtype=torch.float64, device=device)
-                for k in range(1, K + 1):
+                if adjust == "mala":
+                    accepts.append(_mala_ladder(E, eng, xs, y, logw, net, loss, ladder, W_L, b_L,
+                                                (W_s, b_s) if loss.kind == L.LOSS_BERNOULLI else None, steps_per_stage, lr,
+                                                float(noise_var), seed, step_base, g0))
+                for k in range(1, K + 1) if adjust is None else ():              # the unadjusted ladder, as it was
                     eng.store_state(xs)
                     a0, c0, a1, c1 = rung_scalars(loss.kind, ladder[k - 1], ladder[k])
                     E.ais_increment(xs[-1], W_L, b_L, y, net.acts[-1], loss.kind, loss.var, loss.mask_start, a0, c0, a1, c1, logw,
@@ -245,6 +263,57 @@ def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, 
             trainer._sync_params(eng, net, force=True, plan=plan)
     state = torch.cat(states, dim=0) if states else empty_state(0, device)
     res = LogLikelihood(state=state.to(plan["model_device"]))
+    accepted = None
+    if adjust == "mala":
+        accepted = torch.cat(accepts, dim=1) if accepts else torch.zeros(K - 1, 0, dtype=torch.int32, device=device)
+        # the share of accepted proposals per rung over all chains of the call
+        trainer.mcpc_last_ais_acceptance = (accepted.sum(dim=1).to(torch.float64) / max(1, accepted.shape[1] * steps_per_stage)).to(
+            plan["model_device"])
+    else:
+        trainer.mcpc_last_ais_acceptance = None
+    out = (res,)
     if return_logw:
-        return res, (torch.cat(logws) if logws else torch.zeros(0, dtype=torch.float64, device=device))
-    return res
+        out += (torch.cat(logws) if logws else torch.zeros(0, dtype=torch.float64, device=device),)
+    if return_accepted:
+        out += (accepted,)
+    return out if len(out) > 1 else res
+
+
+def _mala_ladder(E, eng, xs, y, logw, net, loss, ladder, W_L, b_L, scaled, steps_per_stage, lr, noise_var, seed, step_base, g0):
+    """The ladder of one chunk with Metropolis-adjusted transitions: ``logw`` receives the log-weights, the return value is the number
+    of accepted proposals per rung and chain, int32 ``[K - 1, B]``.  The chunk's state lives in ``xs`` (the prior draw on entry), its
+    gradient ``g`` and its energy ``En``, all owned here; the engine only evaluates (``load_state``, then the gradient of ``run(1,
+    update_x=False)`` and the last column of ``chain_energies``), once per step, at the proposal.  ``scaled``: the Bernoulli ladder's
+    scratch read-out ``(W_s, b_s)`` the engine is bound to, else None.  Step t of rung k takes its normals and its uniform from
+    Philox step ``step_base + 1 + (k - 1) * steps_per_stage + t``: the one an unadjusted transition would use."""
+    K = len(ladder) - 1
+    accepted = torch.zeros(K - 1, xs[0].shape[0], dtype=torch.int32, device=xs[0].device)
+    spare = [[torch.empty_like(x) for x in xs] for _ in range(2)]         # two proposal buffers: accept reads one and fills the other
+
+    def evaluate(state, run_var):
+        eng.load_state(state)
+        g = eng.run(1, loss_kind=loss.kind, loss_var=run_var, mask_start=loss.mask_start, xopt=L.XOPT_SGD, lr=lr, update_x=False,
+                    step_base=0).xgrad
+        en = eng.chain_energies(None, state, loss_kind=loss.kind, loss_var=run_var, mask_start=loss.mask_start)
+        return g, en[0, :, -1].contiguous()
+
+    for k in range(1, K + 1):
+        a0, c0, a1, c1 = rung_scalars(loss.kind, ladder[k - 1], ladder[k])
+        E.ais_increment(xs[-1], W_L, b_L, y, net.acts[-1], loss.kind, loss.var, loss.mask_start, a0, c0, a1, c1, logw, accumulate=True)
+        if k == K:
+            break
+        scale, run_var = rung_run(loss.kind, loss.var, ladder[k])
+        if scaled is not None:
+            torch.mul(W_L, scale, out=scaled[0])
+            if scaled[1] is not None:
+                torch.mul(b_L, scale, out=scaled[1])
+            eng.params_changed()
+        g, En = evaluate(xs, run_var)
+        first = step_base + 1 + (k - 1) * steps_per_stage
+        xp = E.mala_propose(xs, g, lr, noise_var, seed, first, g0, out=spare[0])
+        for t in range(steps_per_stage):
+            gp, Ep = evaluate(xp, run_var)
+            nxt = spare[(t + 1) % 2] if t + 1 < steps_per_stage else None
+            E.mala_accept(xs, g, En, xp, gp, Ep, lr, noise_var, seed, first + t, g0, n_accepted=accepted[k - 1], x_next=nxt)
+            xp = nxt
+    return accepted

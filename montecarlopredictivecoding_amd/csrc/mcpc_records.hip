@@ -1,7 +1,7 @@
 // libmcpc.so, the stateless reducers over recorded states: the entries of include/mcpc.h that take an `int device` and no engine --
 // moments, covariances, histograms (1-D and joint), lagged autocovariances, rolling windows, linear probes, nearest-neighbour
-// divergences, log marginal likelihoods, annealed-importance-sampling increments -- with their kernels.  A translation unit of its own: it sees nothing of the step kernels,
-// the planner or the engine, and an edit to a reducer recompiles this unit alone.  What an entry refuses is read through
+// divergences, log marginal likelihoods, annealed-importance-sampling increments, Metropolis-adjusted Langevin proposals and
+// decisions -- with their kernels.  A translation unit of its own: it sees nothing of the step kernels, the planner or the engine, and an edit to a reducer recompiles this unit alone.  What an entry refuses is read through
 // mcpc_last_error (mcpc_api.hip) like every other error of the library: mcpc_host.h.
 #include <hip/hip_runtime.h>
 
@@ -20,6 +20,7 @@
 #include "mcpc_knn.h"
 #include "mcpc_loglik.h"
 #include "mcpc_ais.h"
+#include "mcpc_mala.h"
 
 using namespace mcpc;
 
@@ -514,6 +515,87 @@ int mcpc_ais_increment(int device, const float* x, int64_t rows, int32_t width, 
     P.a0 = a0; P.c0 = c0; P.a1 = a1; P.c1 = c1;
     P.half_inv_var = P.gauss ? 0.5 / loss_var : 0.0;
     ais_dispatch(act, P, (hipStream_t)stream_);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+namespace {
+// what mcpc_mala_propose and mcpc_mala_accept share: the counts, the two scalars, the widths; `who` opens every message
+int mala_check(const char* who, const int32_t* widths, int32_t n_layers, int64_t rows, double lr, double noise_var) {
+    if (n_layers < 1 || n_layers > MCPC_MAX_LATENT)
+        return fail(MCPC_EINVAL, "%s: n_layers=%d outside 1..%d", who, n_layers, MCPC_MAX_LATENT);
+    if (rows < 0 || rows > MCPC_MALA_MAX_ROWS)
+        return fail(MCPC_EINVAL, "%s: rows=%lld outside 0..%lld", who, (long long)rows, (long long)MCPC_MALA_MAX_ROWS);
+    if (!(lr > 0.0) || !std::isfinite(lr)) return fail(MCPC_EINVAL, "%s: lr=%g, must be positive and finite", who, lr);
+    if (!(noise_var > 0.0) || !std::isfinite(noise_var))
+        return fail(MCPC_EINVAL, "%s: noise_var=%g, must be positive and finite", who, noise_var);
+    if (!widths) return fail(MCPC_EINVAL, "%s: widths is null", who);
+    for (int l = 0; l < n_layers; ++l)
+        if (widths[l] < 1) return fail(MCPC_EINVAL, "%s: widths[%d]=%d, must be at least 1", who, l, widths[l]);
+    return 0;
+}
+int mala_check_ptrs(const char* who, const char* name, const float* const* p, int32_t n_layers) {
+    if (!p) return fail(MCPC_EINVAL, "%s: %s is null", who, name);
+    for (int l = 0; l < n_layers; ++l)
+        if (!p[l]) return fail(MCPC_EINVAL, "%s: %s[%d] is null", who, name, l);
+    return 0;
+}
+void mala_scalars(MalaParams& P, const int32_t* widths, int32_t n_layers, int64_t rows, double lr, double noise_var, uint64_t seed,
+                  uint64_t step, uint64_t chain_base) {
+    for (int l = 0; l < n_layers; ++l) P.n[l] = widths[l];
+    P.rows = rows; P.n_layers = n_layers;
+    P.lr = (float)lr;
+    P.s = (float)std::sqrt(noise_var * lr);                       // as mcpc_run rounds the step kernels' noise scale
+    P.lr_d = lr;
+    P.denom = (2.0 * noise_var) * lr;
+    P.seed = seed; P.step = step; P.chain_base = chain_base;
+}
+}  // namespace
+
+int mcpc_mala_propose(int device, const float* const* x, const float* const* g, const int32_t* widths, int32_t n_layers, int64_t rows,
+                      double lr, double noise_var, uint64_t seed, uint64_t step, uint64_t chain_base, float* const* x_out,
+                      void* stream_) {
+    if (const int rc = mala_check("mala_propose", widths, n_layers, rows, lr, noise_var)) return rc;
+    if (rows == 0) return MCPC_OK;                                // no row to write
+    if (const int rc = mala_check_ptrs("mala_propose", "x", x, n_layers)) return rc;
+    if (const int rc = mala_check_ptrs("mala_propose", "g", g, n_layers)) return rc;
+    if (const int rc = mala_check_ptrs("mala_propose", "x_out", x_out, n_layers)) return rc;
+    HIP_TRY(hipSetDevice(device));
+    MalaParams P{};
+    mala_scalars(P, widths, n_layers, rows, lr, noise_var, seed, step, chain_base);
+    for (int l = 0; l < n_layers; ++l) {
+        P.x[l] = const_cast<float*>(x[l]); P.g[l] = const_cast<float*>(g[l]); P.out[l] = x_out[l];
+    }
+    P.has_out = 1;
+    hipLaunchKernelGGL(mcpc_mala_propose_kernel, mala_grid(rows), dim3(64 * kMalaWaves), 0, (hipStream_t)stream_, P);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+int mcpc_mala_accept(int device, float* const* x, float* const* g, double* E, const float* const* x_prop, const float* const* g_prop,
+                     const double* E_prop, const int32_t* widths, int32_t n_layers, int64_t rows, double lr, double noise_var,
+                     uint64_t seed, uint64_t step, uint64_t chain_base, double* diag, int32_t* n_accepted, float* const* x_next,
+                     void* stream_) {
+    if (const int rc = mala_check("mala_accept", widths, n_layers, rows, lr, noise_var)) return rc;
+    if (rows == 0) return MCPC_OK;                                // no row to decide
+    if (const int rc = mala_check_ptrs("mala_accept", "x", x, n_layers)) return rc;
+    if (const int rc = mala_check_ptrs("mala_accept", "g", g, n_layers)) return rc;
+    if (const int rc = mala_check_ptrs("mala_accept", "x_prop", x_prop, n_layers)) return rc;
+    if (const int rc = mala_check_ptrs("mala_accept", "g_prop", g_prop, n_layers)) return rc;
+    if (x_next)
+        if (const int rc = mala_check_ptrs("mala_accept", "x_next", x_next, n_layers)) return rc;
+    if (!E) return fail(MCPC_EINVAL, "mala_accept: E is null with rows=%lld", (long long)rows);
+    if (!E_prop) return fail(MCPC_EINVAL, "mala_accept: E_prop is null with rows=%lld", (long long)rows);
+    HIP_TRY(hipSetDevice(device));
+    MalaParams P{};
+    mala_scalars(P, widths, n_layers, rows, lr, noise_var, seed, step, chain_base);
+    for (int l = 0; l < n_layers; ++l) {
+        P.x[l] = x[l]; P.g[l] = g[l]; P.xp[l] = x_prop[l]; P.gp[l] = g_prop[l];
+        if (x_next) P.out[l] = x_next[l];
+    }
+    P.E = E; P.Ep = E_prop; P.diag = diag; P.n_accepted = n_accepted;
+    P.has_out = x_next ? 1 : 0;
+    hipLaunchKernelGGL(mcpc_mala_accept_kernel, mala_grid(rows), dim3(64 * kMalaWaves), 0, (hipStream_t)stream_, P);
     HIP_TRY(hipGetLastError());
     return MCPC_OK;
 }

@@ -1044,3 +1044,91 @@ def ais_increment(x, W, bias, y, act, loss, var, mask_start, a0, c0, a1, c1, log
     L.check(lib.mcpc_ais_increment(device.index or 0, _ptr(x), rows, width, _AIS_ACTS[act], _ptr(W), _ptr(bias), n_out, _ptr(y), loss_kind,
                                    float(var) if loss_kind == L.LOSS_GAUSSIAN else 1.0, mask_start, *scalars, _ptr(logw),
                                    1 if accumulate else 0, stream))
+
+
+def _mala_shape(xs):
+    """(rows, widths, device) of a state as the MALA entries take it: a list of 1..MAX_LATENT fp32 ``[rows, n_l]`` tensors on one HIP
+    device."""
+    if not isinstance(xs, (list, tuple)) or not 1 <= len(xs) <= L.MAX_LATENT:
+        raise ValueError(f"xs: expected a list of 1..{L.MAX_LATENT} tensors, one per layer")
+    for l, t in enumerate(xs):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise TypeError(f"xs[{l}]: expected a torch.Tensor [rows, width]")
+        if t.shape[1] < 1:
+            raise ValueError(f"xs[{l}]: a layer of width 0")
+    device = xs[0].device
+    if device.type != "cuda":
+        raise ValueError(f"xs[0]: expected a tensor on a HIP device, got {device}")
+    return int(xs[0].shape[0]), [int(t.shape[1]) for t in xs], device
+
+
+def _mala_ptrs(tensors, name, rows, widths, device):
+    """The host array of device pointers of a state of that shape."""
+    if not isinstance(tensors, (list, tuple)) or len(tensors) != len(widths):
+        raise ValueError(f"{name}: expected a list of {len(widths)} tensors, one per layer")
+    arr = (C.c_void_p * len(widths))()
+    for l, t in enumerate(tensors):
+        _check_tensor(t, (rows, widths[l]), device, f"{name}[{l}]")
+        arr[l] = t.data_ptr()
+    return arr
+
+
+def _mala_scalars(lr, noise_var, seed, step, chain_base):
+    lr, noise_var = float(lr), float(noise_var)
+    for name, v in (("lr", lr), ("noise_var", noise_var)):
+        if not (v > 0.0 and v != float("inf")):
+            raise ValueError(f"{name}={v!r}, must be positive and finite")
+    return lr, noise_var, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, int(chain_base) & 0xFFFFFFFFFFFFFFFF
+
+
+def mala_propose(xs, gs, lr, noise_var, seed, step, chain_base=0, out=None):
+    """The Langevin proposal of a Metropolis-adjusted step on the device (include/mcpc.h: mcpc_mala_propose): per layer
+    ``out_l = (x_l - lr g_l) + sqrt(noise_var lr) xi_l`` in fp32, four separate roundings, with ``xi_l`` the normals of ``(seed, step,
+    layer l, chain_base + row)`` -- ``philox_normals`` of the same arguments, those a fused Langevin step at that ``(seed, step)``
+    consumes.  ``xs``, ``gs``: one contiguous fp32 ``[rows, n_l]`` tensor per layer (1..MAX_LATENT of them): a state and its gradient
+    (``Engine.run(1, update_x=False).xgrad``).  ``out``: tensors to fill (they must not overlap ``xs`` or ``gs``), or None for fresh
+    ones.  Returns ``out``.  On the current torch stream."""
+    lib = L.load()
+    rows, widths, device = _mala_shape(xs)
+    x_arr, g_arr = _mala_ptrs(xs, "xs", rows, widths, device), _mala_ptrs(gs, "gs", rows, widths, device)
+    lr, noise_var, seed, step, chain_base = _mala_scalars(lr, noise_var, seed, step, chain_base)
+    if out is None:
+        out = [torch.empty_like(x) for x in xs]
+    o_arr = _mala_ptrs(out, "out", rows, widths, device)
+    if rows == 0:                                  # an empty tensor has no address to hand over
+        return out
+    w_arr = (C.c_int32 * len(widths))(*widths)
+    L.check(lib.mcpc_mala_propose(device.index or 0, x_arr, g_arr, w_arr, len(widths), rows, lr, noise_var, seed, step, chain_base, o_arr,
+                                  _current_stream(device)))
+    return out
+
+
+def mala_accept(xs, gs, E, xps, gps, Ep, lr, noise_var, seed, step, chain_base=0, diag=None, n_accepted=None, x_next=None):
+    """The Metropolis-Hastings decision of a Metropolis-adjusted Langevin step on the device (include/mcpc.h: mcpc_mala_accept).
+    ``(xs, gs, E)``: the current state, its gradient and its energy (fp64 ``[rows]``, the last column of ``Engine.chain_energies``);
+    ``(xps, gps, Ep)``: the proposal ``mala_propose`` made at this ``(seed, step, chain_base)`` with this ``lr`` and ``noise_var``, and
+    the gradient and energy the engine evaluated at it.  Per chain ``log_alpha = E - E' - (|x - x' + lr g'|^2 - |x' - x + lr g|^2) /
+    (2 noise_var lr)`` in fp64 and ``accept = log(u) < log_alpha`` with ``u`` the chain's Philox uniform of ``(seed, step, layer
+    0xFF)``.  An accepted chain's rows of ``xs``, ``gs`` and ``E`` are overwritten IN PLACE with the proposal's; a rejected one keeps
+    its bits.  A row's result depends on that row alone and two runs are bitwise equal.  Optional: ``diag`` fp64 ``[rows, 3]`` receives
+    (log_alpha, u, accepted); ``n_accepted`` int32 ``[rows]`` is incremented for an accepted chain; ``x_next``, a state, receives the
+    proposal of ``step + 1`` from the selected ``(x, g)``, bitwise ``mala_propose``'s (it must not overlap another argument).  On the
+    current torch stream."""
+    lib = L.load()
+    rows, widths, device = _mala_shape(xs)
+    n = len(widths)
+    x_arr, g_arr = _mala_ptrs(xs, "xs", rows, widths, device), _mala_ptrs(gs, "gs", rows, widths, device)
+    xp_arr, gp_arr = _mala_ptrs(xps, "xps", rows, widths, device), _mala_ptrs(gps, "gps", rows, widths, device)
+    xn_arr = None if x_next is None else _mala_ptrs(x_next, "x_next", rows, widths, device)
+    _check_tensor(E, (rows,), device, "E", torch.float64)
+    _check_tensor(Ep, (rows,), device, "Ep", torch.float64)
+    if diag is not None:
+        _check_tensor(diag, (rows, 3), device, "diag", torch.float64)
+    if n_accepted is not None:
+        _check_tensor(n_accepted, (rows,), device, "n_accepted", torch.int32)
+    lr, noise_var, seed, step, chain_base = _mala_scalars(lr, noise_var, seed, step, chain_base)
+    if rows == 0:
+        return
+    w_arr = (C.c_int32 * n)(*widths)
+    L.check(lib.mcpc_mala_accept(device.index or 0, x_arr, g_arr, _ptr(E), xp_arr, gp_arr, _ptr(Ep), w_arr, n, rows, lr, noise_var, seed,
+                                 step, chain_base, _ptr(diag), _ptr(n_accepted), xn_arr, _current_stream(device)))

@@ -239,6 +239,8 @@ class PCTrainer(object):
         self.mcpc_chain_energies = None
         self.mcpc_last_chain_energies = None
         self.mcpc_chain_energies_max_rows = 0
+        # mcpc_ais(adjust="mala") leaves the share of accepted proposals per rung here (fp64 [K - 1]); None after an unadjusted call
+        self.mcpc_last_ais_acceptance = None
         # layers=all, outputs=None | "identity" | "sigmoid", pool=None | "chains" -> covariance.Covariance
         self.mcpc_covariance = None
         self.mcpc_last_covariance = None
@@ -1079,7 +1081,7 @@ class PCTrainer(object):
         return (None if out is None else out.to(to)), [None if x is None else x.to(to) for x in xs]
 
     def mcpc_ais(self, data, loss_fn: typing.Callable, loss_fn_kwargs: dict = {}, *, replicas=64, stages=64, power=2.0, betas=None,
-                 steps_per_stage=5, lr=None, noise_var=2.0, seed=0, step_base=0, chain_base=0, max_chains=6000):
+                 steps_per_stage=5, lr=None, noise_var=2.0, seed=0, step_base=0, chain_base=0, max_chains=6000, adjust=None):
         """The log marginal likelihood of every row of ``data`` ``[N, n_out]`` by annealed importance sampling (Neal 2001) on the device
         (montecarlopredictivecoding_amd/ais.py): ``replicas`` chains per datum start from exact ancestral samples
         (``Engine.sample_prior``), walk the ladder ``beta_0 = 0 .. beta_K = 1`` -- ``(k / stages)^power``, or ``betas``, strictly
@@ -1096,10 +1098,20 @@ class PCTrainer(object):
         ``chain_base`` ranges is the estimate over the union of their replicas.  The result is a function of the arguments and the
         parameters alone: bit for bit the same from run to run and whatever ``max_chains`` is.
 
-        What it is: AIS with UNADJUSTED Langevin transitions is unbiased only as ``lr -> 0``.  At a finite ``lr`` the chains sample a
-        slightly wrong distribution at every rung and the estimate carries a bias of order ``lr`` -- negative in every case tried (an
-        under-estimate of log p).  ``.ess`` measures the spread of the weights, not that bias: halve ``lr`` (and double
-        ``steps_per_stage``) to see it.
+        What it is: the transitions come in two modes.  ``adjust=None``: UNADJUSTED Langevin steps (``Engine.run``), the fast mode,
+        unbiased only as ``lr -> 0``.  At a finite ``lr`` the chains sample a slightly wrong distribution at every rung and the
+        estimate carries a bias of order ``lr`` -- negative in every case tried (an under-estimate of log p: 0.19 nats at ``lr = 0.05``
+        and 0.82 at 0.15 on the known-answer case of tests/ais_cases.py).  ``.ess`` measures the spread of the weights, not that bias:
+        halve ``lr`` (and double ``steps_per_stage``) to see it.  ``adjust="mala"``: every Langevin step becomes a proposal
+        (``engine.mala_propose``) that a Metropolis-Hastings decision accepts or rejects per chain (``engine.mala_accept``, fp64, with
+        the engine's gradient and per-chain energy at the proposal: one evaluation of each per step).  Every transition then leaves its
+        rung's distribution exactly invariant, ``exp(log p_hat)`` is unbiased at ANY ``lr`` and any ``noise_var > 0``, and the spread of
+        the weights -- which ``.ess`` does measure -- is the only error (0.02 and 0.01 nats on that case).  The normals are those the
+        unadjusted step would use; the uniform of a decision comes from the same ``(seed, step, chain)`` under a layer index of its
+        own.  The price is several small launches per step instead of one fused kernel per rung.  After an
+        adjusted call ``self.mcpc_last_ais_acceptance`` is an fp64 ``[K - 1]`` tensor, the share of accepted proposals per rung over
+        all chains of the call (it falls as ``lr`` grows; well below 0.5 says ``lr`` is too large for the chains to move); after an
+        unadjusted call it is None.  Any other ``adjust`` is a ValueError.  Both modes keep every promise above.
 
         The model's parameters, the PCLayers' x, every param.grad, the optimisers, the step counters and the cached engine's parameter
         binding are what they were when the call returns, also when it raises.  A model or loss the fused loop does not express, or
@@ -1108,7 +1120,7 @@ class PCTrainer(object):
         with _few_cpu_threads(self._model_is_on_cpu()):
             return _ais.run(self, data, loss_fn, loss_fn_kwargs, replicas=replicas, stages=stages, power=power, betas=betas,
                             steps_per_stage=steps_per_stage, lr=lr, noise_var=noise_var, seed=seed, step_base=step_base,
-                            chain_base=chain_base, max_chains=max_chains)
+                            chain_base=chain_base, max_chains=max_chains, adjust=adjust)
 
     def _model_is_on_cpu(self) -> bool:
         p = next(self._model.parameters(), None)
