@@ -18,14 +18,17 @@ The two ladders, both walked with what ``mcpc_run`` already takes:
              ``f_0`` is the prior; the likelihood's normaliser ``(2 pi var)^(-n_active / 2)`` is added at the end.
 
 This module holds the host logic (schedule, scalars per rung, chunking, the fold of log-weights into a ``LogLikelihood`` state) as
-functions that need no device, and ``run``, the loop itself.  No device code.
+functions that need no device, ``run``, the call, and ``_ladder``, the one loop over the rungs of a chunk that both kinds of
+transition share.  No device code.
 """
 import math
+from types import SimpleNamespace
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib as L
+from . import engine as E
 from .likelihood import LogLikelihood, empty_state
 
 
@@ -160,11 +163,69 @@ def resolve_lr(lr, xopt, why=""):
     return lr
 
 
+def _ladder(call, c):
+    """Walk one chunk up the ladder: ``c.logw`` receives the log-weights.  ``call`` holds what every chunk of a call shares: ``adjust``,
+    ``ladder``, ``steps_per_stage``, ``lr``, ``noise_var``, ``seed``, ``step_base`` as ``run`` takes them, the read-out's activation
+    ``act`` and its ``loss``.  ``c`` holds what the chunk owns: its engine ``eng``, the chains' state ``xs`` (the prior draw on entry),
+    their targets ``y``, ``logw``, the global id ``g0`` of the first chain, the model's own read-out ``W_L``, ``b_L`` and, on the
+    Bernoulli ladder, the scratch read-out ``scaled = (W_s, b_s)`` the engine is bound to (else None).
+
+    Rung k adds its increment at the state the transitions of rung k - 1 left, re-packs the scaled read-out, and makes
+    ``steps_per_stage`` transitions that target ``f_k``; step t of them takes its normals (and its uniform) from Philox step
+    ``step_base + 1 + (k - 1) * steps_per_stage + t``.  Unadjusted, the state lives in the engine, ``c.xs`` is read back before each
+    increment, and a rung is one ``Engine.run``.  Adjusted, the state lives in ``c.xs`` with its gradient ``g`` and energy ``En``, the
+    engine only evaluates (once per step, at the proposal), and the return value is the number of accepted proposals per rung and
+    chain, int32 ``[K - 1, B]`` (None when unadjusted)."""
+    eng, xs, loss, K, mala = c.eng, c.xs, call.loss, len(call.ladder) - 1, call.adjust == "mala"
+    run_kw = dict(loss_kind=loss.kind, mask_start=loss.mask_start, xopt=L.XOPT_SGD, lr=call.lr)
+    accepted = None
+    if mala:
+        accepted = torch.zeros(K - 1, xs[0].shape[0], dtype=torch.int32, device=xs[0].device)
+        spare = [[torch.empty_like(x) for x in xs] for _ in range(2)]     # two proposal buffers: accept reads one and fills the other
+
+    def evaluate(state, run_var):
+        """Gradient and energy of ``state`` under the rung's distribution: one launch each (``update_x=False`` moves nothing)."""
+        eng.load_state(state)
+        g = eng.run(1, loss_var=run_var, update_x=False, step_base=0, **run_kw).xgrad
+        en = eng.chain_energies(None, state, loss_kind=loss.kind, loss_var=run_var, mask_start=loss.mask_start)
+        return g, en[0, :, -1].contiguous()
+
+    def langevin(k, first, run_var):
+        eng.run(call.steps_per_stage, loss_var=run_var, noise_mode=L.NOISE_PHILOX, noise_var=call.noise_var, seed=call.seed,
+                step_base=first, chain_base=c.g0, **run_kw)
+
+    def metropolis(k, first, run_var):
+        g, En = evaluate(xs, run_var)
+        xp = E.mala_propose(xs, g, call.lr, call.noise_var, call.seed, first, c.g0, out=spare[0])
+        for t in range(call.steps_per_stage):
+            gp, Ep = evaluate(xp, run_var)
+            nxt = spare[(t + 1) % 2] if t + 1 < call.steps_per_stage else None
+            E.mala_accept(xs, g, En, xp, gp, Ep, call.lr, call.noise_var, call.seed, first + t, c.g0, n_accepted=accepted[k - 1],
+                          x_next=nxt)
+            xp = nxt
+
+    transitions = metropolis if mala else langevin
+    for k in range(1, K + 1):
+        if not mala:
+            eng.store_state(xs)
+        a0, c0, a1, c1 = rung_scalars(loss.kind, call.ladder[k - 1], call.ladder[k])
+        E.ais_increment(xs[-1], c.W_L, c.b_L, c.y, call.act, loss.kind, loss.var, loss.mask_start, a0, c0, a1, c1, c.logw, accumulate=True)
+        if k == K:
+            break
+        scale, run_var = rung_run(loss.kind, loss.var, call.ladder[k])
+        if c.scaled is not None:
+            torch.mul(c.W_L, scale, out=c.scaled[0])
+            if c.scaled[1] is not None:
+                torch.mul(c.b_L, scale, out=c.scaled[1])
+            eng.params_changed()
+        transitions(k, call.step_base + 1 + (k - 1) * call.steps_per_stage, run_var)
+    return accepted
+
+
 def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, power=2.0, betas=None, steps_per_stage=5, lr=None,
         noise_var=2.0, seed=0, step_base=0, chain_base=0, max_chains=6000, adjust=None, return_logw=False, return_accepted=False):
     """``PCTrainer.mcpc_ais`` (its docstring is the contract).  ``return_logw``: also the raw log-weights, fp64 ``[N * replicas]``.
     ``return_accepted``: also the accepted proposals per rung and chain, int32 ``[K - 1, N * replicas]`` (None when unadjusted)."""
-    from . import engine as E
     from .predictive_coding import recognise
     loss_fn_kwargs = dict(loss_fn_kwargs or {})
     if "_target" in loss_fn_kwargs:
@@ -198,17 +259,16 @@ def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, 
         lr = resolve_lr(None, xopt, why or "optimizer_x_fn is {}".format(getattr(trainer._optimizer_x_fn, "__name__", trainer._optimizer_x_fn)))
     else:
         lr = resolve_lr(lr, None)
-    chunks(n_data, replicas, max_chains, chain_base)
-    plan, why = trainer._plan(torch.zeros(1, net.n_in, device=model_device), loss_fn, kw, False, False, None, None, {}, {}, False, False)
-    if plan is None:
-        raise NotImplementedError("mcpc_ais: outside what the HIP engine expresses ({})".format(why))
-    net, loss = plan["net"], plan["loss"]
     parts = chunks(n_data, replicas, max_chains, chain_base)
+    plan = trainer._plan_or_raise("mcpc_ais", loss_fn, kw, model_alone=True)
+    net, loss = plan["net"], plan["loss"]
     device = plan["device"]
     n_active = net.n_out - loss.mask_start
     const = log_norm(loss.kind, n_active, loss.var)
     y_all = data.to(device=device, dtype=torch.float32).contiguous()
     K = len(ladder) - 1
+    call = SimpleNamespace(adjust=adjust, ladder=ladder, steps_per_stage=steps_per_stage, lr=lr, noise_var=float(noise_var), seed=seed,
+                           step_base=step_base, act=net.acts[-1], loss=loss)
     states, logws, accepts = [], [], []
     engines = []
     try:
@@ -219,39 +279,20 @@ def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, 
                 if all(eng is not e for e in engines):
                     engines.append(eng)
                 trainer._sync_params(eng, net, plan=plan)
-                weights, biases = list(eng._keep["W"]), list(eng._keep["b"])
+                weights, biases = eng.bound_params()
                 W_L, b_L = weights[-1], biases[-1]
                 y = y_all[d0:d0 + n].repeat_interleave(replicas, dim=0).contiguous()
                 eng.bind_inputs(None)
                 eng.bind_target(y)
+                scaled = None
                 if loss.kind == L.LOSS_BERNOULLI:
                     # the scaled read-out of the rung, a scratch copy the engine is bound to for the length of the chunk
-                    W_s, b_s = W_L.clone(), None if b_L is None else b_L.clone()
-                    eng._bound_sig = None
-                    eng.bind_params(weights[:-1] + [W_s], biases[:-1] + [b_s])         # (re-packed per rung below)
+                    scaled = (W_L.clone(), None if b_L is None else b_L.clone())
+                    eng.bind_params(weights[:-1] + [scaled[0]], biases[:-1] + [scaled[1]])      # (re-packed per rung by the ladder)
                 _, xs = eng.sample_prior(B, seed, step=step_base, sample_base=g0, latents=True, readout=None)
                 eng.load_state(xs)
                 logw = torch.zeros(B, dtype=torch.float64, device=device)
-                if adjust == "mala":
-                    accepts.append(_mala_ladder(E, eng, xs, y, logw, net, loss, ladder, W_L, b_L,
-                                                (W_s, b_s) if loss.kind == L.LOSS_BERNOULLI else None, steps_per_stage, lr,
-                                                float(noise_var), seed, step_base, g0))
-                for k in range(1, K + 1) if adjust is None else ():              # the unadjusted ladder, as it was
-                    eng.store_state(xs)
-                    a0, c0, a1, c1 = rung_scalars(loss.kind, ladder[k - 1], ladder[k])
-                    E.ais_increment(xs[-1], W_L, b_L, y, net.acts[-1], loss.kind, loss.var, loss.mask_start, a0, c0, a1, c1, logw,
-                                    accumulate=True)
-                    if k == K:
-                        break
-                    scale, run_var = rung_run(loss.kind, loss.var, ladder[k])
-                    if loss.kind == L.LOSS_BERNOULLI:
-                        torch.mul(W_L, scale, out=W_s)
-                        if b_s is not None:
-                            torch.mul(b_L, scale, out=b_s)
-                        eng.params_changed()
-                    eng.run(steps_per_stage, loss_kind=loss.kind, loss_var=run_var, mask_start=loss.mask_start, xopt=L.XOPT_SGD, lr=lr,
-                            noise_mode=L.NOISE_PHILOX, noise_var=float(noise_var), seed=seed,
-                            step_base=step_base + 1 + (k - 1) * steps_per_stage, chain_base=g0)
+                accepts.append(_ladder(call, SimpleNamespace(eng=eng, xs=xs, y=y, logw=logw, g0=g0, W_L=W_L, b_L=b_L, scaled=scaled)))
                 eng.sync_check()
                 states.append(fold(logw, replicas, const))
                 if return_logw:
@@ -259,8 +300,7 @@ def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, 
     finally:
         # the engines are cached (and shared with train_on_batch): each one holds the model's own read-out again
         for eng in engines:
-            eng._bound_sig = None
-            trainer._sync_params(eng, net, force=True, plan=plan)
+            trainer._rebind_own_params(eng, plan)
     state = torch.cat(states, dim=0) if states else empty_state(0, device)
     res = LogLikelihood(state=state.to(plan["model_device"]))
     accepted = None
@@ -277,43 +317,3 @@ def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, 
     if return_accepted:
         out += (accepted,)
     return out if len(out) > 1 else res
-
-
-def _mala_ladder(E, eng, xs, y, logw, net, loss, ladder, W_L, b_L, scaled, steps_per_stage, lr, noise_var, seed, step_base, g0):
-    """The ladder of one chunk with Metropolis-adjusted transitions: ``logw`` receives the log-weights, the return value is the number
-    of accepted proposals per rung and chain, int32 ``[K - 1, B]``.  The chunk's state lives in ``xs`` (the prior draw on entry), its
-    gradient ``g`` and its energy ``En``, all owned here; the engine only evaluates (``load_state``, then the gradient of ``run(1,
-    update_x=False)`` and the last column of ``chain_energies``), once per step, at the proposal.  ``scaled``: the Bernoulli ladder's
-    scratch read-out ``(W_s, b_s)`` the engine is bound to, else None.  Step t of rung k takes its normals and its uniform from
-    Philox step ``step_base + 1 + (k - 1) * steps_per_stage + t``: the one an unadjusted transition would use."""
-    K = len(ladder) - 1
-    accepted = torch.zeros(K - 1, xs[0].shape[0], dtype=torch.int32, device=xs[0].device)
-    spare = [[torch.empty_like(x) for x in xs] for _ in range(2)]         # two proposal buffers: accept reads one and fills the other
-
-    def evaluate(state, run_var):
-        eng.load_state(state)
-        g = eng.run(1, loss_kind=loss.kind, loss_var=run_var, mask_start=loss.mask_start, xopt=L.XOPT_SGD, lr=lr, update_x=False,
-                    step_base=0).xgrad
-        en = eng.chain_energies(None, state, loss_kind=loss.kind, loss_var=run_var, mask_start=loss.mask_start)
-        return g, en[0, :, -1].contiguous()
-
-    for k in range(1, K + 1):
-        a0, c0, a1, c1 = rung_scalars(loss.kind, ladder[k - 1], ladder[k])
-        E.ais_increment(xs[-1], W_L, b_L, y, net.acts[-1], loss.kind, loss.var, loss.mask_start, a0, c0, a1, c1, logw, accumulate=True)
-        if k == K:
-            break
-        scale, run_var = rung_run(loss.kind, loss.var, ladder[k])
-        if scaled is not None:
-            torch.mul(W_L, scale, out=scaled[0])
-            if scaled[1] is not None:
-                torch.mul(b_L, scale, out=scaled[1])
-            eng.params_changed()
-        g, En = evaluate(xs, run_var)
-        first = step_base + 1 + (k - 1) * steps_per_stage
-        xp = E.mala_propose(xs, g, lr, noise_var, seed, first, g0, out=spare[0])
-        for t in range(steps_per_stage):
-            gp, Ep = evaluate(xp, run_var)
-            nxt = spare[(t + 1) % 2] if t + 1 < steps_per_stage else None
-            E.mala_accept(xs, g, En, xp, gp, Ep, lr, noise_var, seed, first + t, g0, n_accepted=accepted[k - 1], x_next=nxt)
-            xp = nxt
-    return accepted

@@ -31,22 +31,28 @@ def _check_tensor(t: torch.Tensor, shape, device, name, dtype=torch.float32):
         raise ValueError(f"{name}: tensor must be contiguous")
 
 
-def _check_records(rec, rank=3, what="[records, B, width]"):
-    """A record buffer as an engine run fills it: a contiguous fp32 tensor of ``rank`` dimensions (None: one at least) on a HIP
-    device.  Returns (device, shape)."""
+def _record_window(rec, first, stride, n, rank=3, what="[records, B, width]", holds="rec holds"):
+    """What a stateless reducer checks before it looks at its own arguments.  ``rec`` is a record buffer as an engine run fills it: a
+    contiguous fp32 tensor of ``rank`` dimensions (None: one at least) on a HIP device.  The records ``first + k * stride``, k < n, lie
+    inside it (the library refuses negative ones itself).  Returns (device, shape, first, stride, n), the three as ints."""
     if not isinstance(rec, torch.Tensor) or (rec.dim() < 1 if rank is None else rec.dim() != rank):
         raise TypeError(f"rec: expected a torch.Tensor {what}")
     device = rec.device
     if device.type != "cuda":
         raise ValueError(f"rec: expected a tensor on a HIP device, got {device}")
     _check_tensor(rec, rec.shape, device, "rec")
-    return device, tuple(int(d) for d in rec.shape)
+    first, stride, n = int(first), int(stride), int(n)
+    if n > 0 and first >= 0 and stride >= 1 and first + (n - 1) * stride >= rec.shape[0]:
+        raise ValueError(f"{holds} {rec.shape[0]} records, the last one asked for is {first + (n - 1) * stride}")
+    return device, tuple(int(d) for d in rec.shape), first, stride, n
 
 
-def _check_last_record(records, first, stride, n, what="rec holds"):
-    """Records ``first + k * stride``, k < n, lie inside a buffer of ``records`` (the library refuses negative ones itself)."""
-    if n > 0 and first >= 0 and stride >= 1 and first + (n - 1) * stride >= records:
-        raise ValueError(f"{what} {records} records, the last one asked for is {first + (n - 1) * stride}")
+def _workspace_bytes(fn, *args) -> int:
+    """The figure of one of the library's ``mcpc_*_workspace_bytes``; a negative one is its error code."""
+    need = fn(*args)
+    if need < 0:
+        L.check(need)
+    return need
 
 
 def _check_workspace(workspace, device, need, align, asks):
@@ -115,6 +121,10 @@ class Engine:
         self._keep = {}          # borrowed tensors the library holds pointers to
         self.n_lin = self.L + (1 if self.n_out > 0 else 0)
         self.step_counter = 0    # Philox step offset, advances across runs
+        # what a facade that caches engines (PCTrainer) notes on them: a signature of the parameters it bound, which every
+        # bind_params forgets (None: whoever comes next binds afresh), and why the engine runs on the layer-wise kernels, if it does
+        self.bound_sig = None
+        self.wide_reason = None
 
     # ---- lifetime ------------------------------------------------------------------------------
     def close(self):
@@ -147,7 +157,12 @@ class Engine:
                 _check_tensor(b, (n_out,), self.device, f"bias[{j}]")
             L.check(self._lib.mcpc_bind_params(self._h, j, _ptr(W), _ptr(b)))
         self._keep["W"], self._keep["b"] = list(weights), list(biases)
+        self.bound_sig = None
         self.params_changed()
+
+    def bound_params(self):
+        """``(weights, biases)`` as the last ``bind_params`` took them: lists of the bound tensors, a bias None where there is none."""
+        return list(self._keep["W"]), list(self._keep["b"])
 
     def params_changed(self):
         L.check(self._lib.mcpc_params_changed(self._h, self._stream()))
@@ -530,6 +545,16 @@ _MOM_TRANSFORMS = {None: L.MOM_IDENTITY, "identity": L.MOM_IDENTITY, "sigmoid": 
                    L.MOM_IDENTITY: L.MOM_IDENTITY, L.MOM_SIGMOID: L.MOM_SIGMOID}
 
 
+def _transform(t, what="transform", pair=False):
+    """The library's code of the transform ``t`` of a reducer; ``pair``: ``t`` holds the two of hist2d_accumulate's axes, and both
+    codes are returned.  Any other name is the reducers' ValueError."""
+    names = tuple(t) if pair else (t,)
+    if (pair and len(names) != 2) or any(x not in _MOM_TRANSFORMS for x in names):
+        raise ValueError(f"{what}: expected {'two of ' if pair else ''}'identity' or 'sigmoid', got {names if pair else t!r}")
+    codes = [_MOM_TRANSFORMS[x] for x in names]
+    return codes if pair else codes[0]
+
+
 def moments_accumulate(rec, first, stride, n, sum, sumsq=None, transform="identity", accumulate=True):
     """Add records ``rec[first + k * stride]``, k < n, and their squares to the fp64 accumulators ``sum`` / ``sumsq`` on the device
     (include/mcpc.h: mcpc_moments_accumulate), in ascending order of k, one thread per element: the sums are bitwise those of a
@@ -537,14 +562,11 @@ def moments_accumulate(rec, first, stride, n, sum, sumsq=None, transform="identi
     records it; ``sum`` / ``sumsq``: contiguous fp64 of ``rec[0].numel()`` elements (``sumsq`` may be None).  ``transform``:
     "identity", or "sigmoid" for the read-out's Bernoulli mean.  ``accumulate=False`` overwrites.  On the current torch stream."""
     lib = L.load()
-    if transform not in _MOM_TRANSFORMS:
-        raise ValueError(f"transform: expected 'identity' or 'sigmoid', got {transform!r}")
-    device, shape = _check_records(rec, rank=None, what="[records, ...]")
+    xf = _transform(transform)
+    device, shape, first, stride, n = _record_window(rec, first, stride, n, rank=None, what="[records, ...]")
     row = 1
     for d in shape[1:]:
         row *= d
-    first, stride, n = int(first), int(stride), int(n)
-    _check_last_record(shape[0], first, stride, n)
     for t, name in ((sum, "sum"), (sumsq, "sumsq")):
         if t is None and name == "sumsq":
             continue
@@ -554,18 +576,14 @@ def moments_accumulate(rec, first, stride, n, sum, sumsq=None, transform="identi
             raise ValueError(f"{name}: expected {row} elements (one per element of a record), got {t.numel()}")
         _check_tensor(t, t.shape, device, name, torch.float64)
     stream = _current_stream(device)
-    L.check(lib.mcpc_moments_accumulate(device.index or 0, _ptr(rec), row, first, stride, n, _MOM_TRANSFORMS[transform],
+    L.check(lib.mcpc_moments_accumulate(device.index or 0, _ptr(rec), row, first, stride, n, xf,
                                         _ptr(sum), _ptr(sumsq), 1 if accumulate else 0, stream))
 
 
 def cov_workspace_bytes(B, widths, pool=True) -> int:
     """Bytes of device workspace ``cov_accumulate`` needs for ``B`` chains and blocks of these widths (0 unless pooled)."""
-    lib = L.load()
     w = (C.c_int32 * len(widths))(*[int(x) for x in widths])
-    need = lib.mcpc_cov_workspace_bytes(int(B), w, len(widths), 1 if pool else 0)
-    if need < 0:
-        L.check(need)
-    return need
+    return _workspace_bytes(L.load().mcpc_cov_workspace_bytes, int(B), w, len(widths), 1 if pool else 0)
 
 
 def cov_accumulate(recs, first, stride, n, outer, transforms=None, pool=False, accumulate=True, workspace=None):
@@ -586,9 +604,7 @@ def cov_accumulate(recs, first, stride, n, outer, transforms=None, pool=False, a
     transforms = [None] * len(recs) if transforms is None else list(transforms)
     if len(transforms) != len(recs):
         raise ValueError(f"transforms: expected one per block ({len(recs)}), got {len(transforms)}")
-    for t in transforms:
-        if t not in _MOM_TRANSFORMS:
-            raise ValueError(f"transforms: expected 'identity' or 'sigmoid', got {t!r}")
+    xf = (C.c_int32 * len(recs))(*[_transform(t, "transforms") for t in transforms])
     for j, r in enumerate(recs):
         if not isinstance(r, torch.Tensor) or r.dim() != 3:
             raise TypeError(f"recs[{j}]: expected a torch.Tensor [records, B, width]")
@@ -600,20 +616,16 @@ def cov_accumulate(recs, first, stride, n, outer, transforms=None, pool=False, a
         _check_tensor(r, (R, B, r.shape[2]), device, f"recs[{j}]")
     widths = [int(r.shape[2]) for r in recs]
     D = sum(widths)
-    first, stride, n = int(first), int(stride), int(n)
-    _check_last_record(R, first, stride, n, what="recs hold")
+    _, _, first, stride, n = _record_window(recs[0], first, stride, n, holds="recs hold")
     if not isinstance(outer, torch.Tensor):
         raise TypeError(f"outer: expected a torch.Tensor, got {type(outer)}")
     _check_tensor(outer, (D, D) if pool else (B, D, D), device, "outer", torch.float64)
     w = (C.c_int32 * len(recs))(*widths)
-    need = lib.mcpc_cov_workspace_bytes(B, w, len(recs), 1 if pool else 0)
-    if need < 0:
-        L.check(need)
+    need = _workspace_bytes(lib.mcpc_cov_workspace_bytes, B, w, len(recs), 1 if pool else 0)
     ws_bytes = 0
     if pool:
         workspace, ws_bytes = _check_workspace(workspace, device, need, 8, "cov_workspace_bytes")
     ptrs = (C.c_void_p * len(recs))(*[r.data_ptr() for r in recs])
-    xf = (C.c_int32 * len(recs))(*[_MOM_TRANSFORMS[t] for t in transforms])
     stream = _current_stream(device)
     L.check(lib.mcpc_cov_accumulate(device.index or 0, ptrs, w, xf, len(recs), B, first, stride, n, 1 if pool else 0, _ptr(outer),
                                     1 if accumulate else 0, _ptr(workspace) if pool else None, ws_bytes, stream))
@@ -628,11 +640,8 @@ def hist_accumulate(rec, first, stride, n, edges, counts, transform="identity", 
     edges does.  ``transform``: "identity", or "sigmoid" for the read-out's Bernoulli mean.  ``accumulate=False`` overwrites.  Counts are
     integers: exact, however the records are chunked over calls.  On the current torch stream."""
     lib = L.load()
-    if transform not in _MOM_TRANSFORMS:
-        raise ValueError(f"transform: expected 'identity' or 'sigmoid', got {transform!r}")
-    device, (R, B, width) = _check_records(rec)
-    first, stride, n = int(first), int(stride), int(n)
-    _check_last_record(R, first, stride, n)
+    xf = _transform(transform)
+    device, (R, B, width), first, stride, n = _record_window(rec, first, stride, n)
     e = torch.as_tensor(edges)
     if e.device.type != "cpu" or e.dtype != torch.float32 or e.dim() != 1:
         raise TypeError("edges: expected a 1-D fp32 CPU tensor or array")
@@ -644,7 +653,7 @@ def hist_accumulate(rec, first, stride, n, edges, counts, transform="identity", 
         raise TypeError(f"counts: expected a torch.Tensor, got {type(counts)}")
     _check_tensor(counts, (width, n_bins + 3) if pool else (B, width, n_bins + 3), device, "counts", torch.int64)
     stream = _current_stream(device)
-    L.check(lib.mcpc_hist_accumulate(device.index or 0, _ptr(rec), B, width, first, stride, n, _MOM_TRANSFORMS[transform],
+    L.check(lib.mcpc_hist_accumulate(device.index or 0, _ptr(rec), B, width, first, stride, n, xf,
                                      C.cast(e.data_ptr(), C.POINTER(C.c_float)), n_bins, 1 if pool else 0, _ptr(counts),
                                      1 if accumulate else 0, stream))
 
@@ -659,11 +668,9 @@ def acov_accumulate(rec, first, stride, n, max_lag, n_seen, lagged, sum, window,
     read-out's Bernoulli mean.  Every accumulator is bitwise a sequential fp64 loop over the stream, however it is chunked over calls.
     On the current torch stream."""
     lib = L.load()
-    if transform not in _MOM_TRANSFORMS:
-        raise ValueError(f"transform: expected 'identity' or 'sigmoid', got {transform!r}")
-    device, (R, B, width) = _check_records(rec)
-    first, stride, n, max_lag, n_seen = int(first), int(stride), int(n), int(max_lag), int(n_seen)
-    _check_last_record(R, first, stride, n)
+    xf = _transform(transform)
+    device, (R, B, width), first, stride, n = _record_window(rec, first, stride, n)
+    max_lag, n_seen = int(max_lag), int(n_seen)
     if not 0 <= max_lag <= L.ACOV_MAX_LAG:
         raise ValueError(f"max_lag={max_lag}, expected 0..{L.ACOV_MAX_LAG}")
     _check_tensor(lagged, (B, width, max_lag + 1), device, "lagged", torch.float64)
@@ -671,18 +678,14 @@ def acov_accumulate(rec, first, stride, n, max_lag, n_seen, lagged, sum, window,
     _check_tensor(window, (max_lag, B, width), device, "window")
     _check_tensor(head, (max_lag, B, width), device, "head")
     stream = _current_stream(device)
-    L.check(lib.mcpc_acov_accumulate(device.index or 0, _ptr(rec), B, width, first, stride, n, _MOM_TRANSFORMS[transform], max_lag,
+    L.check(lib.mcpc_acov_accumulate(device.index or 0, _ptr(rec), B, width, first, stride, n, xf, max_lag,
                                      n_seen, _ptr(lagged), _ptr(sum), _ptr(window), _ptr(head), stream))
 
 
 def roll_workspace_bytes(B, width, n) -> int:
     """Bytes of device workspace ``roll_accumulate`` needs for the pooled rows of a chunk of ``n`` samples of ``B`` chains x ``width``
     units (include/mcpc.h: mcpc_roll_workspace_bytes)."""
-    lib = L.load()
-    need = lib.mcpc_roll_workspace_bytes(int(B), int(width), int(n))
-    if need < 0:
-        L.check(need)
-    return need
+    return _workspace_bytes(L.load().mcpc_roll_workspace_bytes, int(B), int(width), int(n))
 
 
 def roll_rows(n_seen, n, window, every=1) -> int:
@@ -709,11 +712,9 @@ def roll_accumulate(rec, first, stride, n, window, every, n_seen, s1, s2, hist, 
     for this call.  ``transform``: "identity", or "sigmoid" for the read-out's Bernoulli mean.  Returns the rows emitted.  On the
     current torch stream."""
     lib = L.load()
-    if transform not in _MOM_TRANSFORMS:
-        raise ValueError(f"transform: expected 'identity' or 'sigmoid', got {transform!r}")
-    device, (R, B, width) = _check_records(rec)
-    first, stride, n, window, every, n_seen = int(first), int(stride), int(n), int(window), int(every), int(n_seen)
-    _check_last_record(R, first, stride, n)
+    xf = _transform(transform)
+    device, (R, B, width), first, stride, n = _record_window(rec, first, stride, n)
+    window, every, n_seen = int(window), int(every), int(n_seen)
     if window < 2:
         raise ValueError(f"window={window}, expected at least 2")
     if every < 1:
@@ -740,7 +741,7 @@ def roll_accumulate(rec, first, stride, n, window, every, n_seen, s1, s2, hist, 
         # that emits no row writes no output)
         return None if t is None else C.c_void_p(t.data_ptr() or s1.data_ptr())
     stream = _current_stream(device)
-    L.check(lib.mcpc_roll_accumulate(device.index or 0, _ptr(rec), B, width, first, stride, n, _MOM_TRANSFORMS[transform], window, every,
+    L.check(lib.mcpc_roll_accumulate(device.index or 0, _ptr(rec), B, width, first, stride, n, xf, window, every,
                                      n_seen, _ptr(s1), _ptr(s2), _ptr(hist), out_ptr(out_elem), out_ptr(out_pool),
                                      _ptr(workspace) if out_pool is not None else None, stream))
     return rows
@@ -761,9 +762,7 @@ def probe_accumulate(rec, first, stride, n, W, bias, link, psum, psumsq, votes, 
     lib = L.load()
     if link not in _PROBE_LINKS:
         raise ValueError(f"link: expected 'identity', 'sigmoid' or 'softmax', got {link!r}")
-    device, (R, B, width) = _check_records(rec)
-    first, stride, n = int(first), int(stride), int(n)
-    _check_last_record(R, first, stride, n)
+    device, (R, B, width), first, stride, n = _record_window(rec, first, stride, n)
     if not isinstance(W, torch.Tensor) or W.dim() != 2:
         raise TypeError("W: expected a torch.Tensor [C, width]")
     n_classes = int(W.shape[0])
@@ -796,9 +795,7 @@ def probe_records(rec, first, stride, n, W, bias, link, out=None):
     lib = L.load()
     if link not in _PROBE_LINKS:
         raise ValueError(f"link: expected 'identity', 'sigmoid' or 'softmax', got {link!r}")
-    device, (R, B, width) = _check_records(rec)
-    first, stride, n = int(first), int(stride), int(n)
-    _check_last_record(R, first, stride, n)
+    device, (R, B, width), first, stride, n = _record_window(rec, first, stride, n)
     if not isinstance(W, torch.Tensor) or W.dim() != 2:
         raise TypeError("W: expected a torch.Tensor [C, width]")
     n_classes = int(W.shape[0])
@@ -840,16 +837,12 @@ def hist2d_accumulate(rec_x, rec_y, first, stride, n, pairs, edges_x, edges_y, c
     decided as ``hist_accumulate`` decides it.  ``transforms``: per axis "identity" or "sigmoid".  ``accumulate=False`` overwrites.
     Counts are integers: exact, however the records are chunked over calls and the pairs are ordered.  On the current torch stream."""
     lib = L.load()
-    transforms = tuple(transforms)
-    if len(transforms) != 2 or any(t not in _MOM_TRANSFORMS for t in transforms):
-        raise ValueError(f"transforms: expected two of 'identity' or 'sigmoid', got {transforms!r}")
-    device, (R, B, wx) = _check_records(rec_x)
+    xf = _transform(transforms, "transforms", pair=True)
+    device, (R, B, wx), first, stride, n = _record_window(rec_x, first, stride, n)
     if not isinstance(rec_y, torch.Tensor) or rec_y.dim() != 3:
         raise TypeError("rec_y: expected a torch.Tensor [records, B, width]")
     _check_tensor(rec_y, (R, B, rec_y.shape[2]), device, "rec_y")
     wy = int(rec_y.shape[2])
-    first, stride, n = int(first), int(stride), int(n)
-    _check_last_record(R, first, stride, n)
     pairs = [(int(a), int(b)) for a, b in pairs]
     if not pairs:
         raise ValueError("pairs: expected at least one (x column, y column)")
@@ -865,7 +858,6 @@ def hist2d_accumulate(rec_x, rec_y, first, stride, n, pairs, edges_x, edges_y, c
     grid = (len(pairs), nx + 3, ny + 3)
     _check_tensor(counts, grid if pool else (B,) + grid, device, "counts", torch.int64)
     stream = _current_stream(device)
-    xf = [_MOM_TRANSFORMS[t] for t in transforms]
     fptr = C.POINTER(C.c_float)
 
     def call(some, into):
@@ -890,11 +882,7 @@ def hist2d_accumulate(rec_x, rec_y, first, stride, n, pairs, edges_x, edges_y, c
 
 def knn_workspace_bytes(nq, nr, d, k) -> int:
     """Bytes of device workspace ``knn_accumulate`` needs for ``nq`` queries into ``nr`` reference rows of ``d`` coordinates, ``k`` kept."""
-    lib = L.load()
-    need = lib.mcpc_knn_workspace_bytes(int(nq), int(nr), int(d), int(k))
-    if need < 0:
-        L.check(need)
-    return need
+    return _workspace_bytes(L.load().mcpc_knn_workspace_bytes, int(nq), int(nr), int(d), int(k))
 
 
 def knn_accumulate(q, ref, k, best, accumulate=False, workspace=None):
@@ -924,9 +912,7 @@ def knn_accumulate(q, ref, k, best, accumulate=False, workspace=None):
     _check_tensor(q, (nq, d), device, "q")
     _check_tensor(ref, (nr, d), device, "ref")
     _check_tensor(best, (nq, k), device, "best")
-    need = lib.mcpc_knn_workspace_bytes(nq, nr, d, k)
-    if need < 0:
-        L.check(need)
+    need = _workspace_bytes(lib.mcpc_knn_workspace_bytes, nq, nr, d, k)
     workspace, ws_bytes = _check_workspace(workspace, device, need, 4, "knn_workspace_bytes")
     stream = _current_stream(device)
     L.check(lib.mcpc_knn_accumulate(device.index or 0, _ptr(q), nq, _ptr(ref), nr, d, k, _ptr(best), 1 if accumulate else 0,
@@ -939,11 +925,7 @@ _SAMPLE_READOUTS = {None: L.SAMPLE_HIDDEN, "hidden": L.SAMPLE_HIDDEN, "mean": L.
 
 def loglik_workspace_bytes(n_data, n_samp, width) -> int:
     """Bytes of device workspace ``loglik_accumulate`` needs for ``n_data`` data against ``n_samp`` samples of ``width`` columns."""
-    lib = L.load()
-    need = lib.mcpc_loglik_workspace_bytes(int(n_data), int(n_samp), int(width))
-    if need < 0:
-        L.check(need)
-    return need
+    return _workspace_bytes(L.load().mcpc_loglik_workspace_bytes, int(n_data), int(n_samp), int(width))
 
 
 def loglik_accumulate(y, out, loss, var, clamp, state, accumulate=False, workspace=None):
@@ -982,9 +964,7 @@ def loglik_accumulate(y, out, loss, var, clamp, state, accumulate=False, workspa
     _check_tensor(y, (n_data, width), device, "y")
     _check_tensor(out, (n_samp, width), device, "out")
     _check_tensor(state, (n_data, 4), device, "state", torch.float64)
-    need = lib.mcpc_loglik_workspace_bytes(n_data, n_samp, width)
-    if need < 0:
-        L.check(need)
+    need = _workspace_bytes(lib.mcpc_loglik_workspace_bytes, n_data, n_samp, width)
     workspace, ws_bytes = _check_workspace(workspace, device, need, 8, "loglik_workspace_bytes")
     stream = _current_stream(device)
     L.check(lib.mcpc_loglik_accumulate(device.index or 0, _ptr(y), n_data, _ptr(out), n_samp, width, _LOGLIK_LOSSES[loss],

@@ -56,7 +56,7 @@ from .utils import slow_down_warning
 _PHILOX_STEPS = [0]
 # engines are keyed by (network shape, batch, device, tuning) and shared between trainers -- the scripts build a PC and an
 # MCPC trainer over the same nn.Sequential, and figure_4 / table_1 run several models of one architecture side by side.
-# WHICH parameters an engine is bound to is therefore tracked on the engine (``_bound_sig``), never on a trainer.  The
+# WHICH parameters an engine is bound to is therefore tracked on the engine (``bound_sig``), never on a trainer.  The
 # cache is a small LRU: every distinct (shape, batch) -- e.g. the ragged last batch of a data loader -- owns device
 # memory, evicted engines are closed.
 _ENGINES = collections.OrderedDict()
@@ -488,9 +488,11 @@ class PCTrainer(object):
         if is_return_results_every_t:
             slow_down_warning("PCTrainer.train_on_batch", "is_return_results_every_t", "False")
 
-        plan, why_not_fused = self._plan(inputs, loss_fn, loss_fn_kwargs, is_unwrap_inputs, is_optimize_inputs,
-                                         callback_after_backward, callback_after_t, callback_after_t_kwargs,
-                                         backward_kwargs, is_clear_energy_after_use, is_return_batchelement_loss)
+        plan, why_not_fused = self._plan(
+            inputs, loss_fn, loss_fn_kwargs, is_unwrap_inputs=is_unwrap_inputs, is_optimize_inputs=is_optimize_inputs,
+            callback_after_backward=callback_after_backward, callback_after_t=callback_after_t,
+            callback_after_t_kwargs=callback_after_t_kwargs, backward_kwargs=backward_kwargs,
+            is_clear_energy_after_use=is_clear_energy_after_use, is_return_batchelement_loss=is_return_batchelement_loss)
         # the statistics asked of this call (ring.REQUESTS): validated into the plan, or refused where the fused loop does not run
         ring.validate(self, plan, self._T, runs_on=None if plan is not None else "on the generic torch loop ({})".format(why_not_fused))
         if plan is None:
@@ -546,10 +548,11 @@ class PCTrainer(object):
                                       is_checking_after_callback_after_t=is_checking_after_callback_after_t, **common)
 
     # ---- recognition ------------------------------------------------------------------------------------
-    def _plan(self, inputs, loss_fn, loss_fn_kwargs, is_unwrap_inputs, is_optimize_inputs, callback_after_backward,
-              callback_after_t, callback_after_t_kwargs, backward_kwargs, is_clear_energy_after_use,
-              is_return_batchelement_loss):
-        """Returns (plan dict, "") or (None, reason: the call runs on the generic loop).  plan['mode'] is 'fused' or 'stepwise'."""
+    def _plan(self, inputs, loss_fn, loss_fn_kwargs, is_unwrap_inputs=False, is_optimize_inputs=False, callback_after_backward=None,
+              callback_after_t=None, callback_after_t_kwargs={}, backward_kwargs={}, is_clear_energy_after_use=False,
+              is_return_batchelement_loss=False):
+        """Returns (plan dict, "") or (None, reason: the call runs on the generic loop).  plan['mode'] is 'fused' or 'stepwise'.  The
+        keywords are train_on_batch's; their defaults are what an evaluation call (mcpc_state_energies, mcpc_ais ...) plans with."""
         net, why = recognise.describe_model(self._model)
         if net is None:
             return None, why
@@ -621,6 +624,22 @@ class PCTrainer(object):
         plan["why_stepwise"] = "; ".join(reasons)
         return plan, ""
 
+    def _plan_or_raise(self, who, loss_fn, loss_fn_kwargs, inputs=None, model_alone=False):
+        """The plan of the evaluation call ``who``, or the NotImplementedError that names why the engine does not express it.
+        ``model_alone``: a call that reads the model and no batch (mcpc_sample_prior, mcpc_ais) plans with a ``[1, n_in]`` zero input
+        and, when a loss is given without one, a ``[1, n_out]`` zero ``_target`` (the loss is recognised by its kind alone)."""
+        if model_alone:
+            net, _ = recognise.describe_model(self._model)
+            if net is not None:                  # (a model that is not recognised: _plan names the reason before it looks at inputs)
+                model_device = net.linears[0].weight.device
+                inputs = torch.zeros(1, net.n_in, device=model_device)
+                if loss_fn is not None and "_target" not in loss_fn_kwargs:
+                    loss_fn_kwargs = dict(loss_fn_kwargs, _target=torch.zeros(1, net.n_out, device=model_device))
+        plan, why = self._plan(inputs, loss_fn, loss_fn_kwargs)
+        if plan is None:
+            raise NotImplementedError("{}: outside what the HIP engine expresses ({})".format(who, why))
+        return plan
+
     # ---- engine plumbing ----------------------------------------------------------------------------------
     def _engine_for(self, plan) -> Engine:
         net, B, device = plan["net"], plan["B"], plan["device"]
@@ -629,7 +648,6 @@ class PCTrainer(object):
         if eng is None:
             try:
                 eng = Engine(net.sizes, net.acts, net.n_in, net.n_out, B, device=device, ecoef=net.ecoef)
-                eng._wide_reason = None
             except L.MCPCError as exc:
                 if exc.code != _MCPC_ENOMEM:
                     raise
@@ -637,20 +655,19 @@ class PCTrainer(object):
                 # serve it -- whatever MCPC_TUNING pins keeps governing the LDS kernels wherever those serve
                 tuning = ",".join(s for s in (os.environ.get("MCPC_TUNING"), "wide=1") if s)
                 eng = Engine(net.sizes, net.acts, net.n_in, net.n_out, B, device=device, ecoef=net.ecoef, tuning=tuning)
-                eng._wide_reason = str(exc)
-            eng._bound_sig = None
+                eng.wide_reason = str(exc)
             _ENGINES[key] = eng
             while len(_ENGINES) > _ENGINE_CACHE_SIZE:
                 _, old = _ENGINES.popitem(last=False)
                 old.close()
         else:
             _ENGINES.move_to_end(key)
-        if getattr(eng, "_wide_reason", None) and not getattr(self, "_wide_announced", False):
+        if eng.wide_reason and not getattr(self, "_wide_announced", False):
             self._wide_announced = True         # leaving the fast path is loud, once per trainer
             warnings.warn(
                 "In PCTrainer.train_on_batch, the network does not fit the LDS-resident step kernels ({}): the call runs on the "
                 "layer-wise kernels (mcpc_lw_fwd_kernel + mcpc_lw_bwd_kernel: state, activations and errors of all chains in "
-                "global memory, two launches per step).  {}".format(eng._wide_reason, _WIDE_COST), category=RuntimeWarning)
+                "global memory, two launches per step).  {}".format(eng.wide_reason, _WIDE_COST), category=RuntimeWarning)
         return eng
 
     def _announce_staging(self, plan):
@@ -674,11 +691,12 @@ class PCTrainer(object):
 
     def _sync_params(self, eng: Engine, net, force=False, plan=None):
         """(Re)bind + re-pack the Linear parameters when their storage or contents changed."""
-        sig = tuple((lin.weight.data_ptr(), lin.weight._version,
-                     None if lin.bias is None else (lin.bias.data_ptr(), lin.bias._version)) for lin in net.linears)
+        def signature():
+            return tuple((lin.weight.data_ptr(), lin.weight._version,
+                          None if lin.bias is None else (lin.bias.data_ptr(), lin.bias._version)) for lin in net.linears)
         # the signature lives on the ENGINE: two models of one architecture share it, and a trainer whose own weights did
         # not change must still rebind after another trainer ran on the engine
-        if force or sig != eng._bound_sig:
+        if force or signature() != eng.bound_sig:
             for lin in net.linears:
                 if not lin.weight.is_contiguous():
                     lin.weight.data = lin.weight.data.contiguous()
@@ -691,9 +709,53 @@ class PCTrainer(object):
                 eng.bind_params([lin.weight.data for lin in net.linears],
                                 [None if lin.bias is None else lin.bias.data for lin in net.linears])
             # (contiguous() above may have replaced storage: take the signature after binding)
-            eng._bound_sig = tuple((lin.weight.data_ptr(), lin.weight._version,
-                                    None if lin.bias is None else (lin.bias.data_ptr(), lin.bias._version))
-                                   for lin in net.linears)
+            eng.bound_sig = signature()
+
+    def _rebind_own_params(self, eng: Engine, plan):
+        """The engine holds the model's own parameters again, bound and re-packed whatever it was bound to: after optimizer_p has
+        stepped them, and after mcpc_ais has run the engine on a scaled copy of the read-out."""
+        eng.bound_sig = None
+        self._sync_params(eng, plan["net"], force=True, plan=plan)
+
+    def _bind_target(self, eng: Engine, plan, loss):
+        """Bind the loss's target, if it has one, as the engine takes it: fp32, contiguous, on the engine's device."""
+        tgt = loss.target
+        if tgt is not None:
+            if tgt.dtype != torch.float32 or not tgt.is_contiguous() or tgt.device != plan["device"]:
+                tgt = tgt.to(device=plan["device"], dtype=torch.float32).contiguous()
+            eng.bind_target(tgt)
+
+    def _engine_inputs(self, plan, inputs):
+        """What the engine is handed for the call's ``inputs``: None for zeros (one host synchronisation), else the tensor on its device."""
+        return None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous())
+
+    def _current_xs(self, who, plan):
+        """The PCLayers' current x, as the evaluation call ``who`` reads it: float32 ``[B, n_l]`` each, or a RuntimeError."""
+        net, xs = plan["net"], []
+        for l, layer in enumerate(net.pc_layers):
+            x = layer.get_x()
+            if x is None or tuple(x.shape) != (plan["B"], net.sizes[l]) or x.dtype != torch.float32:
+                raise RuntimeError("{}: PCLayer {} holds no float32 x of shape {}; run a call first".format(
+                    who, l, (plan["B"], net.sizes[l])))
+            xs.append(x)
+        return xs
+
+    def _evaluate_state(self, who, inputs, loss_fn, loss_fn_kwargs, evaluator, **evaluator_kw):
+        """The front of mcpc_state_energies and mcpc_state_errors: plan or refuse, read the PCLayers' current x, bring the engine's
+        parameters and target up to date, then ``evaluator`` (Engine.chain_energies or Engine.prediction_errors) on the staged inputs
+        and x as one record, with the loss's keywords and ``evaluator_kw``.  Returns (plan, what the evaluator returned), synchronised."""
+        plan = self._plan_or_raise(who, loss_fn, loss_fn_kwargs, inputs)
+        loss = plan["loss"]
+        xs = self._current_xs(who, plan)
+        eng = self._engine_for(plan)
+        with _few_cpu_threads(plan["staged"]):
+            self._sync_params(eng, plan["net"], plan=plan)
+            self._bind_target(eng, plan, loss)
+            res = evaluator(eng, self._engine_inputs(plan, inputs), [self._on_engine(plan, x.data.contiguous()) for x in xs],
+                            loss_kind=loss.kind, loss_var=loss.var, mask_start=loss.mask_start,
+                            max_rows=self.mcpc_chain_energies_max_rows, **evaluator_kw)
+            eng.sync_check()
+        return plan, res
 
     def _initial_state(self, plan, inputs, is_sample_x_at_batch_start):
         """Draw / validate x exactly as the first forward of the reference does (pc_trainer.py:717-733,
@@ -822,12 +884,9 @@ class PCTrainer(object):
             self.recreate_optimize_p()
         self._announce_staging(plan)
         self._sync_params(eng, net, plan=plan)
-        eng.bind_inputs(None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous()))
-        if loss.target is not None:
-            tgt = loss.target
-            if tgt.dtype != torch.float32 or not tgt.is_contiguous() or tgt.device != plan["device"]:
-                tgt = tgt.to(device=plan["device"], dtype=torch.float32).contiguous()
-            eng.bind_target(tgt)
+        inputs_eng = self._engine_inputs(plan, inputs)
+        eng.bind_inputs(inputs_eng)
+        self._bind_target(eng, plan, loss)
         xs_eng = [self._on_engine(plan, x.data) for x in xs]          # the script's own tensors, or their device copies when staged
         eng.load_state(xs_eng)
 
@@ -861,8 +920,7 @@ class PCTrainer(object):
         self.last_record_slices = 0
         if any(row.key in plan for row in ring.REQUESTS):
             # statistics of the call: it runs as slices whatever its size, and the records they ask for are reduced on the device
-            call = ring.Call(trainer=self, eng=eng, net=net, model_device=plan["model_device"],
-                             inputs=None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous()),
+            call = ring.Call(trainer=self, eng=eng, net=net, model_device=plan["model_device"], inputs=inputs_eng,
                              loss_kw=dict(loss_kind=loss.kind, loss_var=loss.var, mask_start=loss.mask_start))
             res = self._run_fused_sliced(eng, net, plan, T, run_kw, acc_reset, rec_layers, host_step_bytes,
                                          is_return_outputs and net.n_out > 0, every_t=is_return_results_every_t,
@@ -887,7 +945,7 @@ class PCTrainer(object):
                 self._optimizer_x.state[x] = {"step": torch.tensor(float(T)), "exp_avg": m_.to(x.device), "exp_avg_sq": v_.to(x.device)}
         if do_update:
             self._apply_p_step(plan, eng, net, len(self._accumulate_p_at))
-            self._sync_params(eng, net, force=True, plan=plan)
+            self._rebind_own_params(eng, plan)
         elif self.mcpc_materialize_unused_grads:
             for j, lin in enumerate(net.linears):
                 self._add_param_grads(plan, eng, j, lin, accumulate=start is None)
@@ -986,31 +1044,8 @@ class PCTrainer(object):
         n = 1: ``loss [1, B]``, ``energy [1, B, L]``, ``overall [1, B]``, fp64 on the model's device.  ``inputs``, ``loss_fn`` and
         ``loss_fn_kwargs`` as in train_on_batch; a model or loss the fused loop does not express raises NotImplementedError."""
         from ..chain_energies import from_table
-        plan, why = self._plan(inputs, loss_fn, loss_fn_kwargs, False, False, None, None, {}, {}, False, False)
-        if plan is None:
-            raise NotImplementedError("mcpc_state_energies: outside what the HIP engine expresses ({})".format(why))
-        net, loss = plan["net"], plan["loss"]
-        xs = []
-        for l, layer in enumerate(net.pc_layers):
-            x = layer.get_x()
-            if x is None or tuple(x.shape) != (plan["B"], net.sizes[l]) or x.dtype != torch.float32:
-                raise RuntimeError("mcpc_state_energies: PCLayer {} holds no float32 x of shape {}; run a call first".format(
-                    l, (plan["B"], net.sizes[l])))
-            xs.append(x)
-        eng = self._engine_for(plan)
-        with _few_cpu_threads(plan["staged"]):
-            self._sync_params(eng, net, plan=plan)
-            if loss.target is not None:
-                tgt = loss.target
-                if tgt.dtype != torch.float32 or not tgt.is_contiguous() or tgt.device != plan["device"]:
-                    tgt = tgt.to(device=plan["device"], dtype=torch.float32).contiguous()
-                eng.bind_target(tgt)
-            table = eng.chain_energies(None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous()),
-                                       [self._on_engine(plan, x.data.contiguous()) for x in xs],
-                                       loss_kind=loss.kind, loss_var=loss.var, mask_start=loss.mask_start,
-                                       max_rows=self.mcpc_chain_energies_max_rows)
-            eng.sync_check()
-        return from_table(table, len(net.sizes), self._energy_coefficient, [], plan["model_device"])
+        plan, table = self._evaluate_state("mcpc_state_energies", inputs, loss_fn, loss_fn_kwargs, Engine.chain_energies)
+        return from_table(table, len(plan["net"].sizes), self._energy_coefficient, [], plan["model_device"])
 
     def mcpc_state_errors(self, inputs, loss_fn: typing.Callable = None, loss_fn_kwargs: dict = {}, layers=None, quantity="error",
                           outputs=None):
@@ -1019,30 +1054,8 @@ class PCTrainer(object):
         (None = all), ``quantity`` and ``outputs`` as in Engine.prediction_errors.  Returns a dict of fp32 ``[B, n_l]`` tensors on the
         model's device by name: "e<l>" / "mu<l>", "eout" / "out".  ``inputs``, ``loss_fn`` and ``loss_fn_kwargs`` as in
         train_on_batch; a model or loss the fused loop does not express raises NotImplementedError."""
-        plan, why = self._plan(inputs, loss_fn, loss_fn_kwargs, False, False, None, None, {}, {}, False, False)
-        if plan is None:
-            raise NotImplementedError("mcpc_state_errors: outside what the HIP engine expresses ({})".format(why))
-        net, loss = plan["net"], plan["loss"]
-        xs = []
-        for l, layer in enumerate(net.pc_layers):
-            x = layer.get_x()
-            if x is None or tuple(x.shape) != (plan["B"], net.sizes[l]) or x.dtype != torch.float32:
-                raise RuntimeError("mcpc_state_errors: PCLayer {} holds no float32 x of shape {}; run a call first".format(
-                    l, (plan["B"], net.sizes[l])))
-            xs.append(x)
-        eng = self._engine_for(plan)
-        with _few_cpu_threads(plan["staged"]):
-            self._sync_params(eng, net, plan=plan)
-            if loss.target is not None:
-                tgt = loss.target
-                if tgt.dtype != torch.float32 or not tgt.is_contiguous() or tgt.device != plan["device"]:
-                    tgt = tgt.to(device=plan["device"], dtype=torch.float32).contiguous()
-                eng.bind_target(tgt)
-            res = eng.prediction_errors(None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous()),
-                                        [self._on_engine(plan, x.data.contiguous()) for x in xs], layers=layers, quantity=quantity,
-                                        outputs=outputs, loss_kind=loss.kind, loss_var=loss.var, mask_start=loss.mask_start,
-                                        max_rows=self.mcpc_chain_energies_max_rows)
-            eng.sync_check()
+        plan, res = self._evaluate_state("mcpc_state_errors", inputs, loss_fn, loss_fn_kwargs, Engine.prediction_errors,
+                                         layers=layers, quantity=quantity, outputs=outputs)
         return {k: v[0].to(plan["model_device"]) for k, v in res.items()}
 
     def mcpc_sample_prior(self, n, seed=0, step=0, sample_base=0, loss_fn: typing.Callable = None, loss_fn_kwargs: dict = {},
@@ -1054,16 +1067,7 @@ class PCTrainer(object):
         ``latents``: False, True or layer indices.  Returns ``(out or None, [x_l or None])``, fp32 ``[n, width]`` on the model's device.
         The engine is one the trainer's calls already made for this model where there is one, else a small one.  A model or loss the
         fused loop does not express raises NotImplementedError."""
-        net, why = recognise.describe_model(self._model)
-        if net is None:
-            raise NotImplementedError("mcpc_sample_prior: outside what the HIP engine expresses ({})".format(why))
-        model_device = net.linears[0].weight.device
-        kw = dict(loss_fn_kwargs)
-        if loss_fn is not None and "_target" not in kw:
-            kw["_target"] = torch.zeros(1, net.n_out, device=model_device)      # (the loss is recognised by its kind alone)
-        plan, why = self._plan(torch.zeros(1, net.n_in, device=model_device), loss_fn, kw, False, False, None, None, {}, {}, False, False)
-        if plan is None:
-            raise NotImplementedError("mcpc_sample_prior: outside what the HIP engine expresses ({})".format(why))
+        plan = self._plan_or_raise("mcpc_sample_prior", loss_fn, loss_fn_kwargs, model_alone=True)
         net, loss = plan["net"], plan["loss"]
         # an engine of this model whatever its batch (a sample does not depend on it), most recently used first
         tuning = os.environ.get("MCPC_TUNING")
@@ -1168,9 +1172,8 @@ class PCTrainer(object):
         if is_reset_optimizer_p_at_batch_start:
             self.recreate_optimize_p()
         self._announce_staging(plan)
-        eng.bind_inputs(None if not bool(inputs.any()) else self._on_engine(plan, inputs.contiguous()))
-        if loss.target is not None:
-            eng.bind_target(loss.target.to(device=plan["device"], dtype=torch.float32).contiguous())
+        eng.bind_inputs(self._engine_inputs(plan, inputs))
+        self._bind_target(eng, plan, loss)
         results = {"loss": [], "energy": [], "overall": []}
         if is_return_outputs:
             results["outputs"] = []

@@ -1,7 +1,8 @@
 """The host logic of annealed importance sampling (montecarlopredictivecoding_amd/ais.py; PCTrainer.mcpc_ais): the ladder, the scalars
-per rung, the normalising constants, the chunking and its chain ids, the fold of log-weights into a LogLikelihood state, everything the
-call refuses -- and the algorithm itself, on the NumPy restatement of tests/ais_cases.py against an exact value.  No device."""
+per rung, the normalising constants, the chunking and its chain ids, the calls the ladder of one chunk makes on its engine in both
+modes, the fold of log-weights into a LogLikelihood state, everything the call refuses -- and the algorithm itself, on the NumPy restatement of tests/ais_cases.py against an exact value.  No device."""
 import math
+import types
 
 import numpy as np
 import pytest
@@ -110,6 +111,98 @@ def test_two_chunkings_consume_the_same_normals_and_none_twice():
         assert _words(ais.engine_calls(max_chains=max_chains, **kw), 4) == words
     parts = ais.engine_calls(max_chains=32, **kw)
     assert [c[:3] for c in parts if c[0] == "prior"] == [("prior", 40, 100), ("prior", 72, 100), ("prior", 104, 100)]
+
+
+# ---- the ladder of one chunk: every call it makes, in order ---------------------------------------------------------------------------
+class LadderRecorder:
+    """Stands in for the engine of one chunk and for engine.ais_increment / mala_propose / mala_accept.  Every call is noted as
+    ``(name, Philox step, chain_base, update_x, x_next given)``, None where the call has no such argument (``run`` carries its step
+    count in the name; a ``run`` that is not told ``update_x`` updates).  No device, no library."""
+
+    def __init__(self, batch, sizes):
+        self.batch, self.sizes, self.calls = batch, sizes, []
+
+    def note(self, name, step=None, chain_base=None, update_x=None, x_next=None):
+        self.calls.append((name, step, chain_base, update_x, x_next))
+
+    def store_state(self, xs):
+        self.note("store_state")
+
+    def load_state(self, xs):
+        self.note("load_state")
+
+    def params_changed(self):
+        self.note("params_changed")
+
+    def run(self, T, **kw):
+        self.note(f"run({T})", kw["step_base"], kw.get("chain_base"), kw.get("update_x", True))
+        return types.SimpleNamespace(xgrad=[torch.zeros(self.batch, n) for n in self.sizes])
+
+    def chain_energies(self, inputs, xs, **kw):
+        self.note("chain_energies")
+        return torch.zeros(1, self.batch, len(self.sizes) + 2, dtype=torch.float64)
+
+    def ais_increment(self, x, W, bias, y, act, loss, var, mask_start, a0, c0, a1, c1, logw, accumulate=True):
+        self.note("ais_increment")
+
+    def mala_propose(self, xs, gs, lr, noise_var, seed, step, chain_base=0, out=None):
+        self.note("mala_propose", step, chain_base)
+        return out
+
+    def mala_accept(self, xs, gs, E, xps, gps, Ep, lr, noise_var, seed, step, chain_base=0, diag=None, n_accepted=None, x_next=None):
+        self.note("mala_accept", step, chain_base, None, x_next is not None)
+
+
+# K = 3 rungs of 2 steps, step_base = 100, the chunk's first chain 40.  The lists were recorded with LadderRecorder over the two separate
+# ladders this loop replaced (an inline one for the unadjusted transitions, a function for the adjusted ones), not over the code under test.
+_EVALUATE = [("load_state", None, None, None, None), ("run(1)", 0, None, False, None), ("chain_energies", None, None, None, None)]
+LADDER_CALLS = {
+    None: [
+        ("store_state", None, None, None, None), ("ais_increment", None, None, None, None),
+        ("params_changed", None, None, None, None), ("run(2)", 101, 40, True, None),
+        ("store_state", None, None, None, None), ("ais_increment", None, None, None, None),
+        ("params_changed", None, None, None, None), ("run(2)", 103, 40, True, None),
+        ("store_state", None, None, None, None), ("ais_increment", None, None, None, None)],
+    "mala": [
+        ("ais_increment", None, None, None, None), ("params_changed", None, None, None, None),
+        *_EVALUATE, ("mala_propose", 101, 40, None, None),
+        *_EVALUATE, ("mala_accept", 101, 40, None, True),
+        *_EVALUATE, ("mala_accept", 102, 40, None, False),
+        ("ais_increment", None, None, None, None), ("params_changed", None, None, None, None),
+        *_EVALUATE, ("mala_propose", 103, 40, None, None),
+        *_EVALUATE, ("mala_accept", 103, 40, None, True),
+        *_EVALUATE, ("mala_accept", 104, 40, None, False),
+        ("ais_increment", None, None, None, None)],
+}       # the Bernoulli read-out's calls; the Gaussian ladder re-packs nothing: the same without params_changed
+
+
+def ladder_chunk(rec, loss_kind, adjust):
+    """The arguments of ``ais._ladder`` for one chunk of 5 chains on a 4-6 net with 3 outputs, driven by ``rec``."""
+    g = torch.Generator().manual_seed(3)
+    W_L, b_L = torch.randn(3, 6, generator=g), torch.randn(3, generator=g)
+    call = types.SimpleNamespace(adjust=adjust, ladder=ais.schedule(3), steps_per_stage=2, lr=0.05, noise_var=2.0, seed=7, step_base=100,
+                                 act=L.ACT_TANH, loss=types.SimpleNamespace(kind=loss_kind, var=0.7, mask_start=1))
+    chunk = types.SimpleNamespace(eng=rec, xs=[torch.zeros(5, n) for n in rec.sizes], y=torch.zeros(5, 3),
+                                  logw=torch.zeros(5, dtype=torch.float64), g0=40, W_L=W_L, b_L=b_L,
+                                  scaled=(W_L.clone(), b_L.clone()) if loss_kind == L.LOSS_BERNOULLI else None)
+    return call, chunk
+
+
+@pytest.mark.parametrize("adjust", [None, "mala"])
+@pytest.mark.parametrize("loss_kind", [L.LOSS_BERNOULLI, L.LOSS_GAUSSIAN])
+def test_the_ladder_of_a_chunk_makes_these_calls_in_this_order(monkeypatch, loss_kind, adjust):
+    from montecarlopredictivecoding_amd import engine as E
+    rec = LadderRecorder(5, [4, 6])
+    for name in ("ais_increment", "mala_propose", "mala_accept"):
+        monkeypatch.setattr(E, name, getattr(rec, name))
+    call, chunk = ladder_chunk(rec, loss_kind, adjust)
+    accepted = ais._ladder(call, chunk)
+    want = [c for c in LADDER_CALLS[adjust] if loss_kind == L.LOSS_BERNOULLI or c[0] != "params_changed"]
+    assert rec.calls == want, "\n".join(f"{g} | {w}" for g, w in zip(rec.calls, want))
+    assert (accepted is None) if adjust is None else (tuple(accepted.shape) == (2, 5) and accepted.dtype == torch.int32)
+    if loss_kind == L.LOSS_BERNOULLI:
+        # the last re-pack is that of rung K - 1: the engine is left on the read-out scaled by beta_2
+        assert torch.equal(chunk.scaled[0], chunk.W_L * call.ladder[2]) and torch.equal(chunk.scaled[1], chunk.b_L * call.ladder[2])
 
 
 # ---- the fold -------------------------------------------------------------------------------------------------------------------------

@@ -67,11 +67,26 @@ def _state(tr, model, res):
 
 
 # ---- 5. a fused Langevin call ---------------------------------------------------------------------------------------
-def test_fused_call_leaves_the_trace_and_nothing_else_moves():
+@pytest.mark.parametrize("nonzero_inputs", [False, True])
+def test_fused_call_leaves_the_trace_and_nothing_else_moves(nonzero_inputs):
     um, model, data, inputs = _net(DEV)
-    tr, res = _call(um, model, data, inputs, SPEC)
+    if nonzero_inputs:
+        # the engine is handed the inputs themselves, not None: one tensor serves the step kernels and the evaluator of the ring
+        inputs = torch.randn(B, SIZES[0], generator=torch.Generator().manual_seed(12)).to(DEV)
+    tr, res = _call(um, model, data, inputs, SPEC, is_return_xs=True)
     assert tr.last_call_mode == "fused"
     ce = tr.mcpc_last_chain_energies
+    # the last recorded row (step T - 1 holds x before that step's update) is mcpc_state_energies of the state it recorded, bit for bit
+    left = [x.detach().clone() for x in tr.get_model_xs()]
+    for x, rec in zip(tr.get_model_xs(), res["xs"][STEPS[-1]]):
+        x.data.copy_(rec)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        st = tr.mcpc_state_energies(inputs=inputs, loss_fn=um.bernoulli_fn, loss_fn_kwargs={"_target": data, "_var": None})
+    for p, q in ((st.loss[0], ce.loss[-1]), (st.energy[0], ce.energy[-1]), (st.overall[0], ce.overall[-1])):
+        assert np.array_equal(_bits(p), _bits(q))
+    for x, was in zip(tr.get_model_xs(), left):
+        x.data.copy_(was)
     assert ce.steps == STEPS
     assert ce.loss.shape == (4, B) and ce.energy.shape == (4, B, 3) and ce.overall.shape == (4, B)
     for t in (ce.loss, ce.energy, ce.overall):

@@ -128,5 +128,5 @@ def test_inputs_on_another_device_than_the_model_are_not_fused():
     cfg = dict(input_size=5, hidden_size=16, hidden2_size=16, output_size=20, activation_fn="relu")
     m = um.get_model(cfg, False)
     tr = pc.PCTrainer(m, T=3, update_p_at="never", plot_progress_at=[])
-    plan, why = tr._plan(torch.zeros(4, 5, device=DEV), None, {}, False, False, None, None, {}, {}, False, False)
+    plan, why = tr._plan(torch.zeros(4, 5, device=DEV), None, {})
     assert plan is None and "inputs on cuda" in why

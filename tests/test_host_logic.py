@@ -167,7 +167,7 @@ def test_unsupported_configurations_name_their_reason():
             warnings.simplefilter("ignore")
             with pytest.raises(L.MCPCLibraryError, match="no CPU path"):
                 tr.train_on_batch(inputs=torch.zeros(2, 3), is_log_progress=False)
-    plan, why = tr._plan(torch.zeros(2, 3), None, {}, False, False, None, None, {}, {}, False, False)
+    plan, why = tr._plan(torch.zeros(2, 3), None, {})
     assert plan is None and "S/M masks" in why
     tr2 = pc.PCTrainer(um.get_model(CFG, False), T=4)          # plot_progress_at defaults to 'all'
     with warnings.catch_warnings():
