@@ -612,6 +612,43 @@ int mcpc_mala_accept(int device, float* const* x, float* const* g, double* E, co
                      uint64_t seed, uint64_t step, uint64_t chain_base, double* diag, int32_t* n_accepted, float* const* x_next,
                      void* stream);
 
+/* Resampling the replicas of annealed importance sampling (csrc/mcpc_smc.h): between two rungs, a datum whose R weights have
+ * degenerated draws R ancestors among its own replicas, which turns AIS into a sequential Monte Carlo sampler (Del Moral, Doucet &
+ * Jasra 2006).  Datum i owns rows i R .. i R + R - 1 (R = replicas); row r is the chain with the global id chain_base + r.
+ *
+ * mcpc_smc_ancestors, per datum i, in fp64, every operation rounded separately and nothing contracted into an fma:
+ *   ok_j = isfinite(logw_j), cnt = #ok, m = max_ok logw_j;    e_j = ok_j ? exp(logw_j - m) : 0
+ *   c_j = c_{j-1} + e_j,  q_j = q_{j-1} + e_j e_j             in replica order, sequentially (one lane walks them: np.cumsum)
+ *   S = c_{R-1},  ess = (S S) / q_{R-1};                       resample = ess < threshold * (double)R   (a NaN does not resample)
+ *   u = (w >> 8) * 2^-24 + 2^-25,   w = word 0 of philox4x32_10(chain_base + i R, (0xFE << 24) | 0, step lo, step hi; key seed)
+ *   p_s = (((double)s + u) / (double)R) S,   a_s = #{j : c_j <= p_s} clamped to the last j with e_j > 0       (systematic resampling)
+ *   ancestors[i R + s] = i R + a_s,   logw[i R + s] = m + log(S / cnt) for all R slots: the log of the mean weight over the finite
+ *   replicas.  u is exact and inside (0, 1).  Layer index 0xFE lies outside every layer the normals (0 .. MCPC_MAX_LATENT - 1),
+ *   mcpc_sample_prior (0 .. MCPC_MAX_LATENT) and mcpc_mala_accept (0xFF) use: no Philox word is consumed twice.
+ *   not resampled a datum with ess >= threshold R, or with cnt = 0 (its ess is NaN), gets identity ancestors and its logw is NOT written.
+ *   independence  a datum's result depends on its own R log-weights, threshold, seed, step and chain_base + i R alone: not on
+ *                 n_data, the other data or the launch shape; two runs are bitwise equal.  No atomics, no workspace.
+ *   non-finite    a NaN or Inf log-weight has weight 0: it is never an ancestor and never leaves its datum.
+ *   optional      diag fp64 [n_data][4] = (ess, resampled as 0 / 1, u, m + log(S / cnt)); with cnt = 0: (NaN, 0, u, NaN).  May be NULL.
+ *   One workgroup per datum, replicas doubles of LDS (32 KiB at the cap).  0 <= threshold <= 1: 0 never resamples, 1 always does
+ *   unless the weights are exactly equal (ess = R is not below R).
+ *   MCPC_EINVAL, checked before any HIP call: replicas outside 1..MCPC_SMC_MAX_REPLICAS, n_data < 0 or n_data * replicas above
+ *   MCPC_SMC_MAX_ROWS, threshold outside [0, 1] or NaN, and with n_data > 0 logw or ancestors NULL.  n_data = 0 launches nothing.
+ *
+ * mcpc_smc_gather, out of place: x_out_l[r] = x_l[ancestors[r]], bitwise, for every layer l of a STATE (as the MALA entries take it:
+ * host arrays of device pointers and of widths) in one launch, one wave per destination row.  An index outside 0 .. rows - 1 is
+ * never dereferenced: that row copies itself and, when n_bad (one int32 on the device) is given, n_bad is incremented by 1 for it --
+ * the counter exists for exactly this purpose.  x_out must not overlap x.  Nothing is read or written beyond rows x widths[l].
+ *   MCPC_EINVAL, checked before any HIP call: n_layers outside 1..MCPC_MAX_LATENT, rows outside 0..MCPC_SMC_MAX_ROWS, widths NULL or
+ *   a width < 1, and with rows > 0 a NULL state array or a NULL tensor in it, ancestors NULL.  rows = 0 launches nothing.
+ * Both: stateless, asynchronous on `stream` (a hipStream_t), no engine needed, all offsets 64-bit. */
+#define MCPC_SMC_MAX_REPLICAS 4096
+#define MCPC_SMC_MAX_ROWS 2147483647LL
+int mcpc_smc_ancestors(int device, double* logw, int64_t n_data, int32_t replicas, double threshold, uint64_t seed, uint64_t step,
+                       uint64_t chain_base, int32_t* ancestors, double* diag, void* stream);
+int mcpc_smc_gather(int device, const float* const* x, const int32_t* widths, int32_t n_layers, int64_t rows, const int32_t* ancestors,
+                    float* const* x_out, int32_t* n_bad, void* stream);
+
 /* Per-chain energies of recorded states, evaluated on the device (the reference has them per datapoint: is_return_batchelement_loss,
  * PCLayer(is_keep_energy_per_datapoint=True), get_energies(is_per_datapoint=True); pc_trainer.py:776-836, pc_layer.py:250-262).
  * A ROW is one chain at one recorded step.  x_rec[l], l < n_latent: [n_rec][batch][n_l] fp32, as mcpc_run writes rec_x[l] (n_rec = 1

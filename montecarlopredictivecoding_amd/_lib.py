@@ -25,6 +25,7 @@ PROBE_MAX_CLASSES = 64
 PROBE_IDENTITY, PROBE_SIGMOID, PROBE_SOFTMAX = 0, 1, 2
 KNN_MAX_DIM, KNN_MAX_K = 32, 4
 SAMPLE_HIDDEN, SAMPLE_MEAN, SAMPLE_DRAW = 0, 1, 2
+SMC_MAX_REPLICAS = 4096
 
 # MCPC_LIB: developer override to load a diagnostic build (e.g. libmcpc_stamps.so) or a `make variant` A/B library; a library that
 # reports exp=1 (built with a timing-experiment switch: wrong results on purpose) is refused unless MCPC_ALLOW_EXP=1
@@ -139,6 +140,10 @@ SYMBOLS = {
     "mcpc_mala_accept": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p),
                                    C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.c_double, C.c_double,
                                    C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
+    "mcpc_smc_ancestors": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "mcpc_smc_gather": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.c_void_p,
+                                  C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
     "mcpc_chain_energies": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_int32,
                                       C.c_void_p, C.c_int32, C.c_void_p]),
     "mcpc_prediction_errors": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_int32,

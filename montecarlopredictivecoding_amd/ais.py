@@ -11,6 +11,11 @@ The transitions are unadjusted Langevin steps (``adjust=None``: unbiased only as
 (``Engine.chain_energies``) at it, and the accept / reject decision ``engine.mala_accept`` (csrc/mcpc_mala.h).  Each adjusted
 transition leaves its rung's distribution exactly invariant, so ``exp(log p_hat)`` is unbiased at any step size.
 
+The replicas of a datum may be RESAMPLED between rungs (``resample="systematic"``): when the effective sample size of a datum's
+weights falls below ``ess_threshold * replicas``, ``engine.smc_ancestors`` draws the ancestors and resets the log-weights to the log
+of their mean, and ``engine.smc_gather`` moves the state (csrc/mcpc_smc.h).  That is the sequential Monte Carlo sampler of Del
+Moral, Doucet & Jasra (2006) on the same ladder, with either kind of transition.
+
 The two ladders, both walked with what ``mcpc_run`` already takes:
   Bernoulli  ``f_k(x) = p(x) exp(-BCE(beta_k o(x), y))``: rung k runs the ordinary Bernoulli loss on a read-out scaled by ``beta_k``
              (a scratch copy, re-bound per rung).  At ``beta = 0`` the likelihood factor is the constant ``2^-n_active``.
@@ -142,6 +147,19 @@ def check_adjust(adjust):
     return adjust
 
 
+def check_resample(resample, ess_threshold, replicas):
+    """``(resample, ess_threshold as a float)`` as ``run`` takes them: ``resample`` None or "systematic", ``ess_threshold`` a number
+    in [0, 1], and at most ``SMC_MAX_REPLICAS`` replicas when resampling (one workgroup walks a datum's weights); anything else is a
+    ValueError."""
+    if resample is not None and not (isinstance(resample, str) and resample == "systematic"):
+        raise ValueError(f"resample={resample!r}, expected None or 'systematic'")
+    if isinstance(ess_threshold, bool) or not isinstance(ess_threshold, (int, float)) or not 0.0 <= float(ess_threshold) <= 1.0:
+        raise ValueError(f"ess_threshold={ess_threshold!r}, must be a number in [0, 1]")
+    if resample is not None and isinstance(replicas, int) and replicas > L.SMC_MAX_REPLICAS:
+        raise ValueError(f"replicas={replicas} with resample={resample!r}: at most {L.SMC_MAX_REPLICAS} replicas of a datum are resampled")
+    return resample, float(ess_threshold)
+
+
 def check_counts(replicas, steps_per_stage, noise_var, seed, step_base):
     for name, v, low in (("replicas", replicas, 1), ("steps_per_stage", steps_per_stage, 1), ("seed", seed, None), ("step_base", step_base, 0)):
         if isinstance(v, bool) or not isinstance(v, int) or (low is not None and v < low):
@@ -175,10 +193,19 @@ def _ladder(call, c):
     ``step_base + 1 + (k - 1) * steps_per_stage + t``.  Unadjusted, the state lives in the engine, ``c.xs`` is read back before each
     increment, and a rung is one ``Engine.run``.  Adjusted, the state lives in ``c.xs`` with its gradient ``g`` and energy ``En``, the
     engine only evaluates (once per step, at the proposal), and the return value is the number of accepted proposals per rung and
-    chain, int32 ``[K - 1, B]`` (None when unadjusted)."""
+    chain, int32 ``[K - 1, B]`` (None when unadjusted).
+
+    With ``call.resample``, rung k < K resamples between its increment and its transitions: ``engine.smc_ancestors`` decides per datum
+    from ``c.logw`` (the uniform is that of the rung's first Philox step, under a layer index of its own) and ``engine.smc_gather``
+    moves all latent layers.  Unadjusted, the gathered state is loaded back into the engine; adjusted, ``c.xs`` is replaced -- the
+    gradient and the energy are re-evaluated at the start of every rung, so nothing stale survives.  ``c.smc_diag`` fp64
+    ``[K - 1, n, 4]`` and ``c.ancestors`` int32 ``[K - 1, B]`` (rows of the chunk) receive the trace."""
     eng, xs, loss, K, mala = c.eng, c.xs, call.loss, len(call.ladder) - 1, call.adjust == "mala"
     run_kw = dict(loss_kind=loss.kind, mask_start=loss.mask_start, xopt=L.XOPT_SGD, lr=call.lr)
     accepted = None
+    resample = getattr(call, "resample", None) is not None
+    if resample:
+        gathered = [torch.empty_like(x) for x in xs]
     if mala:
         accepted = torch.zeros(K - 1, xs[0].shape[0], dtype=torch.int32, device=xs[0].device)
         spare = [[torch.empty_like(x) for x in xs] for _ in range(2)]     # two proposal buffers: accept reads one and fills the other
@@ -212,6 +239,15 @@ def _ladder(call, c):
         E.ais_increment(xs[-1], c.W_L, c.b_L, c.y, call.act, loss.kind, loss.var, loss.mask_start, a0, c0, a1, c1, c.logw, accumulate=True)
         if k == K:
             break
+        if resample:
+            E.smc_ancestors(c.logw, call.replicas, call.ess_threshold, call.seed, call.step_base + 1 + (k - 1) * call.steps_per_stage,
+                            c.g0, ancestors=c.ancestors[k - 1], diag=c.smc_diag[k - 1])
+            E.smc_gather(xs, c.ancestors[k - 1], out=gathered)
+            if mala:
+                xs, gathered = gathered, xs                                # (the closures above read this binding)
+                c.xs = xs
+            else:
+                eng.load_state(gathered)
         scale, run_var = rung_run(loss.kind, loss.var, call.ladder[k])
         if c.scaled is not None:
             torch.mul(c.W_L, scale, out=c.scaled[0])
@@ -223,15 +259,20 @@ def _ladder(call, c):
 
 
 def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, power=2.0, betas=None, steps_per_stage=5, lr=None,
-        noise_var=2.0, seed=0, step_base=0, chain_base=0, max_chains=6000, adjust=None, return_logw=False, return_accepted=False):
+        noise_var=2.0, seed=0, step_base=0, chain_base=0, max_chains=6000, adjust=None, resample=None, ess_threshold=0.5,
+        return_logw=False, return_accepted=False, return_ancestors=False):
     """``PCTrainer.mcpc_ais`` (its docstring is the contract).  ``return_logw``: also the raw log-weights, fp64 ``[N * replicas]``.
-    ``return_accepted``: also the accepted proposals per rung and chain, int32 ``[K - 1, N * replicas]`` (None when unadjusted)."""
+    ``return_accepted``: also the accepted proposals per rung and chain, int32 ``[K - 1, N * replicas]`` (None when unadjusted).
+    ``return_ancestors``: also the ancestor of every chain at every rung, int32 ``[K - 1, N * replicas]``, as indices into the chains
+    of the call (None without resampling; the identity where a datum did not resample)."""
     from .predictive_coding import recognise
     loss_fn_kwargs = dict(loss_fn_kwargs or {})
     if "_target" in loss_fn_kwargs:
         raise ValueError("mcpc_ais: loss_fn_kwargs holds a _target; `data` is the target")
     ladder = schedule(stages, power, betas)
     check_adjust(adjust)
+    trainer.mcpc_last_ais_resampling = None          # a call that raises leaves no trace behind
+    resample, ess_threshold = check_resample(resample, ess_threshold, replicas)
     check_counts(replicas, steps_per_stage, noise_var, seed, step_base)
     net, why = recognise.describe_model(trainer._model)
     if net is None:
@@ -268,8 +309,9 @@ def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, 
     y_all = data.to(device=device, dtype=torch.float32).contiguous()
     K = len(ladder) - 1
     call = SimpleNamespace(adjust=adjust, ladder=ladder, steps_per_stage=steps_per_stage, lr=lr, noise_var=float(noise_var), seed=seed,
-                           step_base=step_base, act=net.acts[-1], loss=loss)
-    states, logws, accepts = [], [], []
+                           step_base=step_base, act=net.acts[-1], loss=loss, resample=resample, ess_threshold=ess_threshold,
+                           replicas=replicas)
+    states, logws, accepts, diags, ancestors = [], [], [], [], []
     engines = []
     try:
         with torch.cuda.device(device):
@@ -292,11 +334,18 @@ def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, 
                 _, xs = eng.sample_prior(B, seed, step=step_base, sample_base=g0, latents=True, readout=None)
                 eng.load_state(xs)
                 logw = torch.zeros(B, dtype=torch.float64, device=device)
-                accepts.append(_ladder(call, SimpleNamespace(eng=eng, xs=xs, y=y, logw=logw, g0=g0, W_L=W_L, b_L=b_L, scaled=scaled)))
+                chunk = SimpleNamespace(eng=eng, xs=xs, y=y, logw=logw, g0=g0, W_L=W_L, b_L=b_L, scaled=scaled)
+                if resample is not None:
+                    chunk.smc_diag = torch.zeros(K - 1, n, 4, dtype=torch.float64, device=device)
+                    chunk.ancestors = torch.empty(K - 1, B, dtype=torch.int32, device=device)
+                accepts.append(_ladder(call, chunk))
                 eng.sync_check()
                 states.append(fold(logw, replicas, const))
                 if return_logw:
                     logws.append(logw)
+                if resample is not None:
+                    diags.append(chunk.smc_diag)
+                    ancestors.append(chunk.ancestors + d0 * replicas)       # rows of the chunk -> chains of the call
     finally:
         # the engines are cached (and shared with train_on_batch): each one holds the model's own read-out again
         for eng in engines:
@@ -311,9 +360,21 @@ def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, 
             plan["model_device"])
     else:
         trainer.mcpc_last_ais_acceptance = None
+    anc = None
+    if resample is not None:
+        diag = torch.cat(diags, dim=1) if diags else torch.zeros(K - 1, 0, 4, dtype=torch.float64, device=device)
+        anc = torch.cat(ancestors, dim=1) if ancestors else torch.zeros(K - 1, 0, dtype=torch.int32, device=device)
+        resampled = diag[:, :, 1] != 0.0
+        to = plan["model_device"]
+        # the ESS of every datum BEFORE its rung's resampling, what was resampled, and the share of the data resampled per rung
+        trainer.mcpc_last_ais_resampling = SimpleNamespace(
+            ess=diag[:, :, 0].contiguous().to(to), resampled=resampled.to(to),
+            share=(resampled.sum(dim=1).to(torch.float64) / max(1, resampled.shape[1])).to(to))
     out = (res,)
     if return_logw:
         out += (torch.cat(logws) if logws else torch.zeros(0, dtype=torch.float64, device=device),)
     if return_accepted:
         out += (accepted,)
+    if return_ancestors:
+        out += (anc,)
     return out if len(out) > 1 else res

@@ -1,7 +1,7 @@
 // libmcpc.so, the stateless reducers over recorded states: the entries of include/mcpc.h that take an `int device` and no engine --
 // moments, covariances, histograms (1-D and joint), lagged autocovariances, rolling windows, linear probes, nearest-neighbour
 // divergences, log marginal likelihoods, annealed-importance-sampling increments, Metropolis-adjusted Langevin proposals and
-// decisions -- with their kernels.  A translation unit of its own: it sees nothing of the step kernels, the planner or the engine, and an edit to a reducer recompiles this unit alone.  What an entry refuses is read through
+// decisions, resampling ancestors and their gather -- with their kernels.  A translation unit of its own: it sees nothing of the step kernels, the planner or the engine, and an edit to a reducer recompiles this unit alone.  What an entry refuses is read through
 // mcpc_last_error (mcpc_api.hip) like every other error of the library: mcpc_host.h.
 #include <hip/hip_runtime.h>
 
@@ -21,6 +21,7 @@
 #include "mcpc_loglik.h"
 #include "mcpc_ais.h"
 #include "mcpc_mala.h"
+#include "mcpc_smc.h"
 
 using namespace mcpc;
 
@@ -596,6 +597,50 @@ int mcpc_mala_accept(int device, float* const* x, float* const* g, double* E, co
     P.E = E; P.Ep = E_prop; P.diag = diag; P.n_accepted = n_accepted;
     P.has_out = x_next ? 1 : 0;
     hipLaunchKernelGGL(mcpc_mala_accept_kernel, mala_grid(rows), dim3(64 * kMalaWaves), 0, (hipStream_t)stream_, P);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+int mcpc_smc_ancestors(int device, double* logw, int64_t n_data, int32_t replicas, double threshold, uint64_t seed, uint64_t step,
+                       uint64_t chain_base, int32_t* ancestors, double* diag, void* stream_) {
+    if (replicas < 1 || replicas > MCPC_SMC_MAX_REPLICAS)
+        return fail(MCPC_EINVAL, "smc_ancestors: replicas=%d outside 1..%d", replicas, MCPC_SMC_MAX_REPLICAS);
+    if (n_data < 0 || n_data > MCPC_SMC_MAX_ROWS / replicas)
+        return fail(MCPC_EINVAL, "smc_ancestors: n_data=%lld with replicas=%d: rows outside 0..%lld", (long long)n_data, replicas,
+                    (long long)MCPC_SMC_MAX_ROWS);
+    if (!(threshold >= 0.0 && threshold <= 1.0))
+        return fail(MCPC_EINVAL, "smc_ancestors: threshold=%g outside [0, 1]", threshold);
+    if (n_data == 0) return MCPC_OK;                              // no datum to resample
+    if (!logw) return fail(MCPC_EINVAL, "smc_ancestors: logw is null with n_data=%lld", (long long)n_data);
+    if (!ancestors) return fail(MCPC_EINVAL, "smc_ancestors: ancestors is null with n_data=%lld", (long long)n_data);
+    HIP_TRY(hipSetDevice(device));
+    SmcParams P{};
+    P.logw = logw; P.ancestors = ancestors; P.diag = diag; P.n_data = n_data; P.replicas = replicas; P.threshold = threshold;
+    P.seed = seed; P.step = step; P.chain_base = chain_base;
+    hipLaunchKernelGGL(mcpc_smc_ancestors_kernel, dim3((unsigned)n_data), dim3(kSmcLanes), (size_t)replicas * sizeof(double),
+                       (hipStream_t)stream_, P);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+int mcpc_smc_gather(int device, const float* const* x, const int32_t* widths, int32_t n_layers, int64_t rows, const int32_t* ancestors,
+                    float* const* x_out, int32_t* n_bad, void* stream_) {
+    if (n_layers < 1 || n_layers > MCPC_MAX_LATENT)
+        return fail(MCPC_EINVAL, "smc_gather: n_layers=%d outside 1..%d", n_layers, MCPC_MAX_LATENT);
+    if (rows < 0 || rows > MCPC_SMC_MAX_ROWS)
+        return fail(MCPC_EINVAL, "smc_gather: rows=%lld outside 0..%lld", (long long)rows, (long long)MCPC_SMC_MAX_ROWS);
+    if (!widths) return fail(MCPC_EINVAL, "smc_gather: widths is null");
+    for (int l = 0; l < n_layers; ++l)
+        if (widths[l] < 1) return fail(MCPC_EINVAL, "smc_gather: widths[%d]=%d, must be at least 1", l, widths[l]);
+    if (rows == 0) return MCPC_OK;                                // no row to write
+    if (const int rc = mala_check_ptrs("smc_gather", "x", x, n_layers)) return rc;
+    if (const int rc = mala_check_ptrs("smc_gather", "x_out", x_out, n_layers)) return rc;
+    if (!ancestors) return fail(MCPC_EINVAL, "smc_gather: ancestors is null with rows=%lld", (long long)rows);
+    HIP_TRY(hipSetDevice(device));
+    SmcGatherParams P{};
+    for (int l = 0; l < n_layers; ++l) { P.x[l] = x[l]; P.out[l] = x_out[l]; P.n[l] = widths[l]; }
+    P.ancestors = ancestors; P.n_bad = n_bad; P.rows = rows; P.n_layers = n_layers;
+    hipLaunchKernelGGL(mcpc_smc_gather_kernel, smc_gather_grid(rows), dim3(64 * kSmcWaves), 0, (hipStream_t)stream_, P);
     HIP_TRY(hipGetLastError());
     return MCPC_OK;
 }

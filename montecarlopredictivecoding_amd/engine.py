@@ -1112,3 +1112,63 @@ def mala_accept(xs, gs, E, xps, gps, Ep, lr, noise_var, seed, step, chain_base=0
     w_arr = (C.c_int32 * n)(*widths)
     L.check(lib.mcpc_mala_accept(device.index or 0, x_arr, g_arr, _ptr(E), xp_arr, gp_arr, _ptr(Ep), w_arr, n, rows, lr, noise_var, seed,
                                  step, chain_base, _ptr(diag), _ptr(n_accepted), xn_arr, _current_stream(device)))
+
+
+def smc_ancestors(logw, replicas, threshold, seed, step, chain_base=0, ancestors=None, diag=None):
+    """The resampling decision and the ancestors of every datum of a chunk on the device (include/mcpc.h: mcpc_smc_ancestors).
+    ``logw``: fp64 ``[n_data * replicas]``, datum i owning rows ``i * replicas ..``.  Per datum, in fp64 and sequentially in replica
+    order, ``ess = (sum e)^2 / sum e^2`` with ``e_j = exp(logw_j - max)`` over the finite log-weights; when ``ess < threshold *
+    replicas`` the datum draws ``replicas`` ancestors by systematic resampling with the Philox uniform of ``(seed, step, layer 0xFE,
+    chain_base + i * replicas)`` and ALL its log-weights are overwritten IN PLACE with the log of the mean weight; otherwise it gets
+    identity ancestors and its log-weights are not written.  ``threshold`` in [0, 1], ``replicas`` in 1..SMC_MAX_REPLICAS.  A datum's
+    result depends on its own log-weights and scalars alone and two runs are bitwise equal.  Optional: ``ancestors`` int32 ``[n_data
+    * replicas]`` to fill (else a fresh one), ``diag`` fp64 ``[n_data, 4]`` receives (ess, resampled, u, log mean weight).  Returns
+    ``ancestors`` (row indices into the chunk).  On the current torch stream."""
+    lib = L.load()
+    if not isinstance(logw, torch.Tensor) or logw.dim() != 1:
+        raise TypeError("logw: expected a torch.Tensor [n_data * replicas]")
+    device = logw.device
+    if device.type != "cuda":
+        raise ValueError(f"logw: expected a tensor on a HIP device, got {device}")
+    if isinstance(replicas, bool) or not isinstance(replicas, int) or not 1 <= replicas <= L.SMC_MAX_REPLICAS:
+        raise ValueError(f"replicas={replicas!r}, must be an int in 1..{L.SMC_MAX_REPLICAS}")
+    threshold = float(threshold)
+    if not 0.0 <= threshold <= 1.0:
+        raise ValueError(f"threshold={threshold!r} outside [0, 1]")
+    rows = int(logw.shape[0])
+    if rows % replicas:
+        raise ValueError(f"logw holds {rows} rows, no multiple of replicas={replicas}")
+    _check_tensor(logw, (rows,), device, "logw", torch.float64)
+    if ancestors is None:
+        ancestors = torch.empty(rows, dtype=torch.int32, device=device)
+    _check_tensor(ancestors, (rows,), device, "ancestors", torch.int32)
+    if diag is not None:
+        _check_tensor(diag, (rows // replicas, 4), device, "diag", torch.float64)
+    if rows == 0:                                  # an empty tensor has no address to hand over
+        return ancestors
+    mask = 0xFFFFFFFFFFFFFFFF
+    L.check(lib.mcpc_smc_ancestors(device.index or 0, _ptr(logw), rows // replicas, replicas, threshold, int(seed) & mask, int(step) & mask,
+                                   int(chain_base) & mask, _ptr(ancestors), _ptr(diag), _current_stream(device)))
+    return ancestors
+
+
+def smc_gather(xs, ancestors, out=None, n_bad=None):
+    """``out_l[r] = xs_l[ancestors[r]]`` for every layer of a state in one launch (include/mcpc.h: mcpc_smc_gather), bitwise and out of
+    place.  ``xs``: one contiguous fp32 ``[rows, n_l]`` tensor per layer (1..MAX_LATENT of them); ``ancestors``: int32 ``[rows]``.  An
+    index outside ``0..rows - 1`` is never dereferenced: that row copies itself and ``n_bad`` (int32 ``[1]``, optional) is incremented.
+    ``out``: tensors to fill (they must not overlap ``xs``), or None for fresh ones.  Returns ``out``.  On the current torch stream."""
+    lib = L.load()
+    rows, widths, device = _mala_shape(xs)
+    x_arr = _mala_ptrs(xs, "xs", rows, widths, device)
+    _check_tensor(ancestors, (rows,), device, "ancestors", torch.int32)
+    if out is None:
+        out = [torch.empty_like(x) for x in xs]
+    o_arr = _mala_ptrs(out, "out", rows, widths, device)
+    if n_bad is not None:
+        _check_tensor(n_bad, (1,), device, "n_bad", torch.int32)
+    if rows == 0:
+        return out
+    w_arr = (C.c_int32 * len(widths))(*widths)
+    L.check(lib.mcpc_smc_gather(device.index or 0, x_arr, w_arr, len(widths), rows, _ptr(ancestors), o_arr, _ptr(n_bad),
+                                _current_stream(device)))
+    return out

@@ -241,6 +241,9 @@ class PCTrainer(object):
         self.mcpc_chain_energies_max_rows = 0
         # mcpc_ais(adjust="mala") leaves the share of accepted proposals per rung here (fp64 [K - 1]); None after an unadjusted call
         self.mcpc_last_ais_acceptance = None
+        # mcpc_ais(resample="systematic") leaves its trace here: .ess fp64 [K - 1, N] (before resampling), .resampled bool [K - 1, N],
+        # .share fp64 [K - 1]; None after a call without resampling
+        self.mcpc_last_ais_resampling = None
         # layers=all, outputs=None | "identity" | "sigmoid", pool=None | "chains" -> covariance.Covariance
         self.mcpc_covariance = None
         self.mcpc_last_covariance = None
@@ -1085,7 +1088,8 @@ class PCTrainer(object):
         return (None if out is None else out.to(to)), [None if x is None else x.to(to) for x in xs]
 
     def mcpc_ais(self, data, loss_fn: typing.Callable, loss_fn_kwargs: dict = {}, *, replicas=64, stages=64, power=2.0, betas=None,
-                 steps_per_stage=5, lr=None, noise_var=2.0, seed=0, step_base=0, chain_base=0, max_chains=6000, adjust=None):
+                 steps_per_stage=5, lr=None, noise_var=2.0, seed=0, step_base=0, chain_base=0, max_chains=6000, adjust=None,
+                 resample=None, ess_threshold=0.5):
         """The log marginal likelihood of every row of ``data`` ``[N, n_out]`` by annealed importance sampling (Neal 2001) on the device
         (montecarlopredictivecoding_amd/ais.py): ``replicas`` chains per datum start from exact ancestral samples
         (``Engine.sample_prior``), walk the ladder ``beta_0 = 0 .. beta_K = 1`` -- ``(k / stages)^power``, or ``betas``, strictly
@@ -1117,6 +1121,23 @@ class PCTrainer(object):
         all chains of the call (it falls as ``lr`` grows; well below 0.5 says ``lr`` is too large for the chains to move); after an
         unadjusted call it is None.  Any other ``adjust`` is a ValueError.  Both modes keep every promise above.
 
+        ``resample="systematic"`` resamples the replicas of a datum between rungs, after the increment and before the transitions,
+        whenever the effective sample size of its weights is below ``ess_threshold * replicas`` (``engine.smc_ancestors``,
+        ``engine.smc_gather``): the sequential Monte Carlo sampler of Del Moral, Doucet & Jasra (2006), with either kind of
+        transition.  ``resample=None`` is the call without the keyword, bit for bit.  An unknown ``resample``, an ``ess_threshold``
+        outside [0, 1] or more than 4096 ``replicas`` when resampling is a ValueError.  After a resampling call
+        ``self.mcpc_last_ais_resampling`` holds ``.ess`` (fp64 ``[K - 1, N]``, taken before resampling), ``.resampled`` (bool
+        ``[K - 1, N]``) and ``.share`` (``[K - 1]``); otherwise it is None.
+        - The returned ``.ess`` is that of the weights since the last resampling; the honest diagnostic is the trace in
+          ``mcpc_last_ais_resampling.ess``.
+        - ``ess_threshold=1.0`` resamples at every rung; equal weights resample to the identity, so this is the fixed-schedule SMC
+          sampler, and its ``exp(log p_hat)`` is unbiased under exact (``adjust="mala"``) transitions.
+        - A weight-triggered schedule is consistent in ``replicas``; the closed-form case of tests/smc_cases.py measures what it does
+          at finite ``replicas``.
+        - ``.merge`` of two calls with disjoint ``chain_base`` averages two independent estimates; with resampling this is no longer
+          the call over the union.
+        - The result is still bitwise independent of ``max_chains``, because a datum's replicas are never split over chunks.
+
         The model's parameters, the PCLayers' x, every param.grad, the optimisers, the step counters and the cached engine's parameter
         binding are what they were when the call returns, also when it raises.  A model or loss the fused loop does not express, or
         a model without a read-out, raises NotImplementedError."""
@@ -1124,7 +1145,8 @@ class PCTrainer(object):
         with _few_cpu_threads(self._model_is_on_cpu()):
             return _ais.run(self, data, loss_fn, loss_fn_kwargs, replicas=replicas, stages=stages, power=power, betas=betas,
                             steps_per_stage=steps_per_stage, lr=lr, noise_var=noise_var, seed=seed, step_base=step_base,
-                            chain_base=chain_base, max_chains=max_chains, adjust=adjust)
+                            chain_base=chain_base, max_chains=max_chains, adjust=adjust, resample=resample,
+                            ess_threshold=ess_threshold)
 
     def _model_is_on_cpu(self) -> bool:
         p = next(self._model.parameters(), None)
