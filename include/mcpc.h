@@ -612,6 +612,52 @@ int mcpc_mala_accept(int device, float* const* x, float* const* g, double* E, co
                      uint64_t seed, uint64_t step, uint64_t chain_base, double* diag, int32_t* n_accepted, float* const* x_next,
                      void* stream);
 
+/* The per-chain arithmetic of a Hamiltonian Monte Carlo transition of L leapfrog steps (csrc/mcpc_hmc.h): one directed trajectory of
+ * the unit-mass Hamiltonian H(x, p) = F(x) + |p|^2 / 2 with ONE Metropolis decision at its end, in place of L random-walk MALA steps
+ * (Duane et al. 1987; Neal 2011).  States, gradients, energies, widths and chain ids are those of the MALA entries above.  The step
+ * size is eps = sqrt(2 lr): the host forms eps = (float)sqrt(2.0 * lr) in double and rounds it once, h = 0.5f * eps is exact.  L = 1
+ * in this parameterisation is the MALA proposal and decision at noise_var = 2.  All fp32 element arithmetic is rounded operation by
+ * operation, none contracted into an fma.  A trajectory from (x, g, E) at `step`:
+ *
+ * mcpc_hmc_begin, once:        p = xi                    q_out = fl(p - fl(h g))          x_out = fl(x + fl(eps q_out))
+ *                              K0[r] = 0.5 * sum_u (double)p_u (double)p_u
+ *   with xi the normals of (seed, step, layer l, chain_base + r): the very normals mcpc_mala_propose takes.  q_out, x_out and K0 must
+ *   not overlap x or g.
+ * mcpc_hmc_leap, L - 1 times:  q = fl(q - fl(eps g_t))   x_t = fl(x_t + fl(eps q))        in place, g_t the gradient at x_t as it
+ *   stands before the call.  No random numbers; step, seed and chain_base are not taken.
+ * mcpc_hmc_accept, once, with g_t and E_t the gradient and the energy at the trajectory's end x_t:
+ *                              p' = fl(q - fl(h g_t))    K1 = 0.5 * sum_u (double)p'_u (double)p'_u
+ *   log_alpha = (E[r] - E_t[r]) + (K0[r] - K1)                          (two differences and one sum, each rounded)
+ *   u         = ((w >> 8) + 1) * 2^-24,   w = word 0 of philox4x32_10(chain_base + r, (0xFD << 24) | 0, step lo, step hi; key seed)
+ *   accept    = log(u) < log_alpha                                      (fp64; a NaN log_alpha rejects)
+ *   Layer index 0xFD is unused elsewhere: the normals and mcpc_sample_prior take 0 .. MCPC_MAX_LATENT, mcpc_smc_ancestors 0xFE and
+ *   mcpc_mala_accept 0xFF, so no Philox word is consumed twice.
+ *   sums          each lane of the chain's wave adds its squares in ascending order (layers, groups of four units, units of a group),
+ *                 the 64 lanes are summed by the xor butterfly 32..1, exactly as mcpc_mala_accept sums, then one product by 0.5.  A
+ *                 row's result depends on that row alone and two runs are bitwise equal.  No atomics, no LDS, no workspace.
+ *   in place      an accepted chain's rows of x, g and E are overwritten with those of x_t, g_t and E_t; a rejected chain keeps its
+ *                 bits (it is not written).  x_t, g_t, q and K0 are never written.  A transition thus costs L gradient evaluations and
+ *                 ONE energy evaluation, at the end point.
+ *   non-finite    a NaN or Inf stays in its own chain; a chain whose log_alpha is NaN rejects.
+ *   optional      diag fp64 [rows][3] = (log_alpha, u, accepted as 0 / 1); n_accepted int32 [rows], incremented by 1 for an accepted
+ *                 chain.  Each may be NULL.
+ * Against exact arithmetic on the same fp32 p, p' the device's and a fp64 restatement's K0 and log_alpha differ by at most 2^-41 K0 and
+ * 2^-41 M_r, M_r = |E| + |E_t| + K0 + K1, for up to 2038 units per chain: the squares are exact, a sum of N of them in any order errs
+ * by at most (N - 1) 2^-53 of itself, and three more roundings form log_alpha (tests/hmc_cases.py derives it).
+ * All three: stateless, asynchronous on `stream` (a hipStream_t), no engine needed, all offsets 64-bit, nothing is read or written
+ * beyond rows x widths[l].  rows = 0 launches nothing.  MCPC_EINVAL, checked before any HIP call (nothing is launched then): n_layers
+ * outside 1..MCPC_MAX_LATENT, rows outside 0..MCPC_HMC_MAX_ROWS, lr not positive and finite, widths NULL or a width < 1, and with
+ * rows > 0 a NULL state array or a NULL tensor in it, E, E_t or K0 NULL. */
+#define MCPC_HMC_MAX_ROWS 2147483647LL
+int mcpc_hmc_begin(int device, const float* const* x, const float* const* g, const int32_t* widths, int32_t n_layers, int64_t rows,
+                   double lr, uint64_t seed, uint64_t step, uint64_t chain_base, float* const* q_out, float* const* x_out, double* K0,
+                   void* stream);
+int mcpc_hmc_leap(int device, float* const* x_t, float* const* q, const float* const* g_t, const int32_t* widths, int32_t n_layers,
+                  int64_t rows, double lr, void* stream);
+int mcpc_hmc_accept(int device, float* const* x, float* const* g, double* E, const float* const* x_t, const float* const* g_t,
+                    const double* E_t, const float* const* q, const double* K0, const int32_t* widths, int32_t n_layers, int64_t rows,
+                    double lr, uint64_t seed, uint64_t step, uint64_t chain_base, double* diag, int32_t* n_accepted, void* stream);
+
 /* Resampling the replicas of annealed importance sampling (csrc/mcpc_smc.h): between two rungs, a datum whose R weights have
  * degenerated draws R ancestors among its own replicas, which turns AIS into a sequential Monte Carlo sampler (Del Moral, Doucet &
  * Jasra 2006).  Datum i owns rows i R .. i R + R - 1 (R = replicas); row r is the chain with the global id chain_base + r.

@@ -140,6 +140,14 @@ SYMBOLS = {
     "mcpc_mala_accept": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p),
                                    C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.c_double, C.c_double,
                                    C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
+    "mcpc_hmc_begin": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_int64,
+                                 C.c_double, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p,
+                                 C.c_void_p]),
+    "mcpc_hmc_leap": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
+                                C.c_int32, C.c_int64, C.c_double, C.c_void_p]),
+    "mcpc_hmc_accept": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p),
+                                  C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_int32), C.c_int32,
+                                  C.c_int64, C.c_double, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcpc_smc_ancestors": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "mcpc_smc_gather": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.c_void_p,

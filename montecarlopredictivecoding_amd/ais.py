@@ -9,7 +9,10 @@ mean estimates ``Z_K / Z_0``.  Everything it needs is what the engine is fast at
 The transitions are unadjusted Langevin steps (``adjust=None``: unbiased only as ``lr -> 0``) or Metropolis-adjusted ones
 (``adjust="mala"``): a proposal ``engine.mala_propose``, the engine's gradient (``Engine.run(1, update_x=False)``) and energy
 (``Engine.chain_energies``) at it, and the accept / reject decision ``engine.mala_accept`` (csrc/mcpc_mala.h).  Each adjusted
-transition leaves its rung's distribution exactly invariant, so ``exp(log p_hat)`` is unbiased at any step size.
+transition leaves its rung's distribution exactly invariant, so ``exp(log p_hat)`` is unbiased at any step size.  With ``leapfrog=L >=
+2`` an adjusted transition is a Hamiltonian trajectory of L leapfrog steps of size ``sqrt(2 lr)`` with one decision at its end
+(``engine.hmc_begin``, ``engine.hmc_leap``, ``engine.hmc_accept``, csrc/mcpc_hmc.h): the same L gradient evaluations spent on one
+directed move instead of L random-walk steps, and ONE energy evaluation instead of L.  ``leapfrog=1`` is the MALA step itself.
 
 The replicas of a datum may be RESAMPLED between rungs (``resample="systematic"``): when the effective sample size of a datum's
 weights falls below ``ess_threshold * replicas``, ``engine.smc_ancestors`` draws the ancestors and resets the log-weights to the log
@@ -107,7 +110,9 @@ def chunks(n_data: int, replicas: int, max_chains: int, chain_base: int = 0) -> 
 def engine_calls(n_data, replicas, max_chains, n_rungs, steps_per_stage, step_base=0, chain_base=0):
     """Every engine call of ``run`` that consumes normals, in order: ``(what, sample_base or chain_base, step_base, chains)`` with
     ``what`` "prior" (``Engine.sample_prior``) or "run" (``Engine.run`` of ``steps_per_stage`` steps).  The prior uses step
-    ``step_base``; the transitions after increment k use steps ``step_base + 1 + (k - 1) * steps_per_stage`` onwards: no normal twice."""
+    ``step_base``; the transitions after increment k use steps ``step_base + 1 + (k - 1) * steps_per_stage`` onwards: no normal twice.
+    It accounts for Philox steps, not launches: a transition takes ONE step whatever ``leapfrog`` is (its normals are the trajectory's
+    momentum), so ``leapfrog`` does not enter."""
     out = []
     for _, n, g0 in chunks(n_data, replicas, max_chains, chain_base):
         out.append(("prior", g0, step_base, n * replicas))
@@ -145,6 +150,19 @@ def check_adjust(adjust):
     if adjust is not None and not (isinstance(adjust, str) and adjust == "mala"):
         raise ValueError(f"adjust={adjust!r}, expected None or 'mala'")
     return adjust
+
+
+def check_leapfrog(leapfrog, adjust=None, noise_var=2.0):
+    """``leapfrog`` as ``run`` takes it: an int of at least 1.  More than one leapfrog step needs the decision at the trajectory's end
+    (``adjust="mala"``) and ``noise_var == 2.0`` (a unit-mass Hamiltonian has no other noise scale: its one-step trajectory is the
+    Langevin proposal at ``noise_var = 2``); anything else is a ValueError."""
+    if isinstance(leapfrog, bool) or not isinstance(leapfrog, int) or leapfrog < 1:
+        raise ValueError(f"leapfrog={leapfrog!r}, must be an int of at least 1")
+    if leapfrog > 1 and adjust is None:
+        raise ValueError(f"leapfrog={leapfrog} with adjust=None: a trajectory is accepted or rejected at its end, pass adjust='mala'")
+    if leapfrog > 1 and not (isinstance(noise_var, (int, float)) and not isinstance(noise_var, bool) and float(noise_var) == 2.0):
+        raise ValueError(f"leapfrog={leapfrog} with noise_var={noise_var!r}: a unit-mass Hamiltonian has noise_var = 2 alone")
+    return leapfrog
 
 
 def check_resample(resample, ess_threshold, replicas):
@@ -186,14 +204,17 @@ def _ladder(call, c):
     ``ladder``, ``steps_per_stage``, ``lr``, ``noise_var``, ``seed``, ``step_base`` as ``run`` takes them, the read-out's activation
     ``act`` and its ``loss``.  ``c`` holds what the chunk owns: its engine ``eng``, the chains' state ``xs`` (the prior draw on entry),
     their targets ``y``, ``logw``, the global id ``g0`` of the first chain, the model's own read-out ``W_L``, ``b_L`` and, on the
-    Bernoulli ladder, the scratch read-out ``scaled = (W_s, b_s)`` the engine is bound to (else None).
+    Bernoulli ladder, the scratch read-out ``scaled = (W_s, b_s)`` the engine is bound to (else None).  ``call.leapfrog`` (1 when
+    absent) is the number of leapfrog steps of an adjusted transition.
 
     Rung k adds its increment at the state the transitions of rung k - 1 left, re-packs the scaled read-out, and makes
     ``steps_per_stage`` transitions that target ``f_k``; step t of them takes its normals (and its uniform) from Philox step
     ``step_base + 1 + (k - 1) * steps_per_stage + t``.  Unadjusted, the state lives in the engine, ``c.xs`` is read back before each
     increment, and a rung is one ``Engine.run``.  Adjusted, the state lives in ``c.xs`` with its gradient ``g`` and energy ``En``, the
     engine only evaluates (once per step, at the proposal), and the return value is the number of accepted proposals per rung and
-    chain, int32 ``[K - 1, B]`` (None when unadjusted).
+    chain, int32 ``[K - 1, B]`` (None when unadjusted).  With ``leapfrog = L >= 2`` a transition is ``hmc_begin``, L - 1 times a
+    gradient at the trajectory's point (no energy there) and ``hmc_leap``, then gradient and energy at its end and ``hmc_accept``: the
+    trajectory's position, momentum and initial kinetic energy live in three buffers allocated once per chunk.
 
     With ``call.resample``, rung k < K resamples between its increment and its transitions: ``engine.smc_ancestors`` decides per datum
     from ``c.logw`` (the uniform is that of the rung's first Philox step, under a layer index of its own) and ``engine.smc_gather``
@@ -209,11 +230,19 @@ def _ladder(call, c):
     if mala:
         accepted = torch.zeros(K - 1, xs[0].shape[0], dtype=torch.int32, device=xs[0].device)
         spare = [[torch.empty_like(x) for x in xs] for _ in range(2)]     # two proposal buffers: accept reads one and fills the other
+    leapfrog = getattr(call, "leapfrog", 1)
+    if leapfrog > 1:
+        xt, q = spare                                                     # the trajectory's position and half-step momentum
+        K0 = torch.empty(xs[0].shape[0], dtype=torch.float64, device=xs[0].device)
+
+    def gradient(state, run_var):
+        """Gradient of ``state`` under the rung's distribution (``update_x=False`` moves nothing)."""
+        eng.load_state(state)
+        return eng.run(1, loss_var=run_var, update_x=False, step_base=0, **run_kw).xgrad
 
     def evaluate(state, run_var):
-        """Gradient and energy of ``state`` under the rung's distribution: one launch each (``update_x=False`` moves nothing)."""
-        eng.load_state(state)
-        g = eng.run(1, loss_var=run_var, update_x=False, step_base=0, **run_kw).xgrad
+        """Gradient and energy of ``state`` under the rung's distribution: one launch each."""
+        g = gradient(state, run_var)
         en = eng.chain_energies(None, state, loss_kind=loss.kind, loss_var=run_var, mask_start=loss.mask_start)
         return g, en[0, :, -1].contiguous()
 
@@ -231,7 +260,16 @@ def _ladder(call, c):
                           x_next=nxt)
             xp = nxt
 
-    transitions = metropolis if mala else langevin
+    def hamiltonian(k, first, run_var):
+        g, En = evaluate(xs, run_var)
+        for t in range(call.steps_per_stage):
+            E.hmc_begin(xs, g, call.lr, call.seed, first + t, c.g0, q_out=q, x_out=xt, K0=K0)
+            for _ in range(leapfrog - 1):                                  # interior points: the gradient alone
+                E.hmc_leap(xt, q, gradient(xt, run_var), call.lr)
+            gt, Et = evaluate(xt, run_var)
+            E.hmc_accept(xs, g, En, xt, gt, Et, q, K0, call.lr, call.seed, first + t, c.g0, n_accepted=accepted[k - 1])
+
+    transitions = (hamiltonian if leapfrog > 1 else metropolis) if mala else langevin
     for k in range(1, K + 1):
         if not mala:
             eng.store_state(xs)
@@ -260,9 +298,10 @@ def _ladder(call, c):
 
 def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, power=2.0, betas=None, steps_per_stage=5, lr=None,
         noise_var=2.0, seed=0, step_base=0, chain_base=0, max_chains=6000, adjust=None, resample=None, ess_threshold=0.5,
-        return_logw=False, return_accepted=False, return_ancestors=False):
+        leapfrog=1, return_logw=False, return_accepted=False, return_ancestors=False):
     """``PCTrainer.mcpc_ais`` (its docstring is the contract).  ``return_logw``: also the raw log-weights, fp64 ``[N * replicas]``.
-    ``return_accepted``: also the accepted proposals per rung and chain, int32 ``[K - 1, N * replicas]`` (None when unadjusted).
+    ``return_accepted``: also the accepted proposals (trajectories when ``leapfrog > 1``) per rung and chain, int32 ``[K - 1, N *
+    replicas]`` (None when unadjusted).
     ``return_ancestors``: also the ancestor of every chain at every rung, int32 ``[K - 1, N * replicas]``, as indices into the chains
     of the call (None without resampling; the identity where a datum did not resample)."""
     from .predictive_coding import recognise
@@ -274,6 +313,7 @@ def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, 
     trainer.mcpc_last_ais_resampling = None          # a call that raises leaves no trace behind
     resample, ess_threshold = check_resample(resample, ess_threshold, replicas)
     check_counts(replicas, steps_per_stage, noise_var, seed, step_base)
+    check_leapfrog(leapfrog, adjust, noise_var)
     net, why = recognise.describe_model(trainer._model)
     if net is None:
         raise NotImplementedError("mcpc_ais: outside what the HIP engine expresses ({})".format(why))
@@ -310,7 +350,7 @@ def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, 
     K = len(ladder) - 1
     call = SimpleNamespace(adjust=adjust, ladder=ladder, steps_per_stage=steps_per_stage, lr=lr, noise_var=float(noise_var), seed=seed,
                            step_base=step_base, act=net.acts[-1], loss=loss, resample=resample, ess_threshold=ess_threshold,
-                           replicas=replicas)
+                           replicas=replicas, leapfrog=leapfrog)
     states, logws, accepts, diags, ancestors = [], [], [], [], []
     engines = []
     try:

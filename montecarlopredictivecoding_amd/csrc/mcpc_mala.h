@@ -20,7 +20,7 @@
 //     accept = log(u) < log_alpha                                   (fp64 log; a NaN log_alpha compares false: the chain rejects)
 // That order involves the chain's own values only: a row's result does not depend on `rows` or on the other rows, and two runs are
 // bitwise equal.  No atomics, no LDS, no workspace.  Layer 0xFF is outside every layer the normals and mcpc_sample_prior use
-// (layers 0 .. MCPC_MAX_LATENT), so no Philox word is consumed twice.
+// (layers 0 .. MCPC_MAX_LATENT), so no Philox word is consumed twice (mcpc_smc.h takes 0xFE, mcpc_hmc.h 0xFD).
 // An accepted chain's x, g and E are overwritten with x', g', E' (each lane copies the units it read); a rejected chain is not
 // written.  x_next, when asked for, is PROPOSE at step + 1 from the selected (x, g), formed from the registers the copy holds.
 //

@@ -21,6 +21,7 @@
 #include "mcpc_loglik.h"
 #include "mcpc_ais.h"
 #include "mcpc_mala.h"
+#include "mcpc_hmc.h"
 #include "mcpc_smc.h"
 
 using namespace mcpc;
@@ -597,6 +598,86 @@ int mcpc_mala_accept(int device, float* const* x, float* const* g, double* E, co
     P.E = E; P.Ep = E_prop; P.diag = diag; P.n_accepted = n_accepted;
     P.has_out = x_next ? 1 : 0;
     hipLaunchKernelGGL(mcpc_mala_accept_kernel, mala_grid(rows), dim3(64 * kMalaWaves), 0, (hipStream_t)stream_, P);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+namespace {
+// what the three mcpc_hmc entries share: MALA's checks (a unit-mass Hamiltonian has no noise scale: 2 stands in), then the scalars
+int hmc_check(const char* who, const int32_t* widths, int32_t n_layers, int64_t rows, double lr) {
+    if (rows > MCPC_HMC_MAX_ROWS)
+        return fail(MCPC_EINVAL, "%s: rows=%lld outside 0..%lld", who, (long long)rows, (long long)MCPC_HMC_MAX_ROWS);
+    return mala_check(who, widths, n_layers, rows, lr, 2.0);
+}
+void hmc_scalars(HmcParams& P, const int32_t* widths, int32_t n_layers, int64_t rows, double lr, uint64_t seed, uint64_t step,
+                 uint64_t chain_base) {
+    for (int l = 0; l < n_layers; ++l) P.n[l] = widths[l];
+    P.rows = rows; P.n_layers = n_layers;
+    P.eps = (float)std::sqrt(2.0 * lr);                           // formed in double, rounded once
+    P.h = 0.5f * P.eps;                                           // exact
+    P.seed = seed; P.step = step; P.chain_base = chain_base;
+}
+}  // namespace
+
+int mcpc_hmc_begin(int device, const float* const* x, const float* const* g, const int32_t* widths, int32_t n_layers, int64_t rows,
+                   double lr, uint64_t seed, uint64_t step, uint64_t chain_base, float* const* q_out, float* const* x_out, double* K0,
+                   void* stream_) {
+    if (const int rc = hmc_check("hmc_begin", widths, n_layers, rows, lr)) return rc;
+    if (rows == 0) return MCPC_OK;                                // no row to write
+    if (const int rc = mala_check_ptrs("hmc_begin", "x", x, n_layers)) return rc;
+    if (const int rc = mala_check_ptrs("hmc_begin", "g", g, n_layers)) return rc;
+    if (const int rc = mala_check_ptrs("hmc_begin", "q_out", q_out, n_layers)) return rc;
+    if (const int rc = mala_check_ptrs("hmc_begin", "x_out", x_out, n_layers)) return rc;
+    if (!K0) return fail(MCPC_EINVAL, "hmc_begin: K0 is null with rows=%lld", (long long)rows);
+    HIP_TRY(hipSetDevice(device));
+    HmcParams P{};
+    hmc_scalars(P, widths, n_layers, rows, lr, seed, step, chain_base);
+    for (int l = 0; l < n_layers; ++l) {
+        P.x[l] = const_cast<float*>(x[l]); P.g[l] = const_cast<float*>(g[l]); P.q[l] = q_out[l]; P.xt[l] = x_out[l];
+    }
+    P.K0 = K0;
+    hipLaunchKernelGGL(mcpc_hmc_begin_kernel, mala_grid(rows), dim3(64 * kMalaWaves), 0, (hipStream_t)stream_, P);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+int mcpc_hmc_leap(int device, float* const* x_t, float* const* q, const float* const* g_t, const int32_t* widths, int32_t n_layers,
+                  int64_t rows, double lr, void* stream_) {
+    if (const int rc = hmc_check("hmc_leap", widths, n_layers, rows, lr)) return rc;
+    if (rows == 0) return MCPC_OK;                                // no row to move
+    if (const int rc = mala_check_ptrs("hmc_leap", "x_t", x_t, n_layers)) return rc;
+    if (const int rc = mala_check_ptrs("hmc_leap", "q", q, n_layers)) return rc;
+    if (const int rc = mala_check_ptrs("hmc_leap", "g_t", g_t, n_layers)) return rc;
+    HIP_TRY(hipSetDevice(device));
+    HmcParams P{};
+    hmc_scalars(P, widths, n_layers, rows, lr, 0, 0, 0);
+    for (int l = 0; l < n_layers; ++l) { P.xt[l] = x_t[l]; P.q[l] = q[l]; P.gt[l] = g_t[l]; }
+    hipLaunchKernelGGL(mcpc_hmc_leap_kernel, mala_grid(rows), dim3(64 * kMalaWaves), 0, (hipStream_t)stream_, P);
+    HIP_TRY(hipGetLastError());
+    return MCPC_OK;
+}
+
+int mcpc_hmc_accept(int device, float* const* x, float* const* g, double* E, const float* const* x_t, const float* const* g_t,
+                    const double* E_t, const float* const* q, const double* K0, const int32_t* widths, int32_t n_layers, int64_t rows,
+                    double lr, uint64_t seed, uint64_t step, uint64_t chain_base, double* diag, int32_t* n_accepted, void* stream_) {
+    if (const int rc = hmc_check("hmc_accept", widths, n_layers, rows, lr)) return rc;
+    if (rows == 0) return MCPC_OK;                                // no row to decide
+    if (const int rc = mala_check_ptrs("hmc_accept", "x", x, n_layers)) return rc;
+    if (const int rc = mala_check_ptrs("hmc_accept", "g", g, n_layers)) return rc;
+    if (const int rc = mala_check_ptrs("hmc_accept", "x_t", x_t, n_layers)) return rc;
+    if (const int rc = mala_check_ptrs("hmc_accept", "g_t", g_t, n_layers)) return rc;
+    if (const int rc = mala_check_ptrs("hmc_accept", "q", q, n_layers)) return rc;
+    if (!E) return fail(MCPC_EINVAL, "hmc_accept: E is null with rows=%lld", (long long)rows);
+    if (!E_t) return fail(MCPC_EINVAL, "hmc_accept: E_t is null with rows=%lld", (long long)rows);
+    if (!K0) return fail(MCPC_EINVAL, "hmc_accept: K0 is null with rows=%lld", (long long)rows);
+    HIP_TRY(hipSetDevice(device));
+    HmcParams P{};
+    hmc_scalars(P, widths, n_layers, rows, lr, seed, step, chain_base);
+    for (int l = 0; l < n_layers; ++l) {
+        P.x[l] = x[l]; P.g[l] = g[l]; P.xt[l] = const_cast<float*>(x_t[l]); P.gt[l] = g_t[l]; P.q[l] = const_cast<float*>(q[l]);
+    }
+    P.E = E; P.Et = E_t; P.K0 = const_cast<double*>(K0); P.diag = diag; P.n_accepted = n_accepted;
+    hipLaunchKernelGGL(mcpc_hmc_accept_kernel, mala_grid(rows), dim3(64 * kMalaWaves), 0, (hipStream_t)stream_, P);
     HIP_TRY(hipGetLastError());
     return MCPC_OK;
 }

@@ -16,7 +16,8 @@
 // u is exact in fp64 and inside (0, 1).  A datum that does not resample gets identity ancestors and its logw is NOT written.
 // Layer 0xFE is outside every layer another consumer of the Philox stream uses: the normals of the step kernels and of
 // mcpc_mala_propose take layers 0 .. MCPC_MAX_LATENT - 1, mcpc_sample_prior layers 0 .. MCPC_MAX_LATENT (the read-out's draw), and the
-// uniform of mcpc_mala_accept layer 0xFF (mcpc_mala.h), so no Philox word is consumed twice.
+// uniform of mcpc_mala_accept layer 0xFF (mcpc_mala.h) and that of mcpc_hmc_accept layer 0xFD (mcpc_hmc.h), so no Philox word is
+// consumed twice.
 //
 // One workgroup of 256 lanes serves one datum.  The exps run in parallel into LDS (R doubles: 32 KiB at MCPC_SMC_MAX_REPLICAS = 4096);
 // m and cnt are a maximum and an integer count, which no order of evaluation changes; lane 0 then walks the two sums, overwriting e_j

@@ -1114,6 +1114,81 @@ def mala_accept(xs, gs, E, xps, gps, Ep, lr, noise_var, seed, step, chain_base=0
                                  step, chain_base, _ptr(diag), _ptr(n_accepted), xn_arr, _current_stream(device)))
 
 
+def hmc_begin(xs, gs, lr, seed, step, chain_base=0, q_out=None, x_out=None, K0=None):
+    """The first leapfrog step of a Hamiltonian trajectory on the device (include/mcpc.h: mcpc_hmc_begin): per layer, with ``eps =
+    sqrt(2 lr)`` rounded to fp32 once and ``h = eps / 2``, ``p = xi_l``, ``q_l = p - h g_l``, ``x_out_l = x_l + eps q_l`` in fp32, every
+    operation rounded separately, with ``xi_l`` the normals of ``(seed, step, layer l, chain_base + row)`` -- ``philox_normals`` of
+    the same arguments, those ``mala_propose`` takes.  ``K0`` fp64 ``[rows]`` receives the kinetic energy ``0.5 |p|^2`` per chain.
+    ``xs``, ``gs``: one contiguous fp32 ``[rows, n_l]`` tensor per layer (1..MAX_LATENT of them): a state and its gradient
+    (``Engine.run(1, update_x=False).xgrad``).  ``q_out``, ``x_out``, ``K0``: tensors to fill (they must not overlap ``xs`` or ``gs``),
+    or None for fresh ones.  Returns ``(q_out, x_out, K0)``.  On the current torch stream."""
+    lib = L.load()
+    rows, widths, device = _mala_shape(xs)
+    x_arr, g_arr = _mala_ptrs(xs, "xs", rows, widths, device), _mala_ptrs(gs, "gs", rows, widths, device)
+    lr, _, seed, step, chain_base = _mala_scalars(lr, 2.0, seed, step, chain_base)
+    if q_out is None:
+        q_out = [torch.empty_like(x) for x in xs]
+    if x_out is None:
+        x_out = [torch.empty_like(x) for x in xs]
+    if K0 is None:
+        K0 = torch.empty(rows, dtype=torch.float64, device=device)
+    q_arr, o_arr = _mala_ptrs(q_out, "q_out", rows, widths, device), _mala_ptrs(x_out, "x_out", rows, widths, device)
+    _check_tensor(K0, (rows,), device, "K0", torch.float64)
+    if rows == 0:                                  # an empty tensor has no address to hand over
+        return q_out, x_out, K0
+    w_arr = (C.c_int32 * len(widths))(*widths)
+    L.check(lib.mcpc_hmc_begin(device.index or 0, x_arr, g_arr, w_arr, len(widths), rows, lr, seed, step, chain_base, q_arr, o_arr,
+                               _ptr(K0), _current_stream(device)))
+    return q_out, x_out, K0
+
+
+def hmc_leap(xts, qs, gts, lr):
+    """An interior leapfrog step of a Hamiltonian trajectory on the device (include/mcpc.h: mcpc_hmc_leap), IN PLACE on the
+    trajectory's position ``xts`` and half-step momentum ``qs``: ``q_l = q_l - eps g_t,l``, then ``x_t,l = x_t,l + eps q_l`` with
+    ``eps = sqrt(2 lr)``, in fp32, every operation rounded separately.  ``gts``: the gradient at ``xts`` as it stands before the call.
+    No random numbers.  On the current torch stream."""
+    lib = L.load()
+    rows, widths, device = _mala_shape(xts)
+    x_arr, q_arr = _mala_ptrs(xts, "xts", rows, widths, device), _mala_ptrs(qs, "qs", rows, widths, device)
+    g_arr = _mala_ptrs(gts, "gts", rows, widths, device)
+    lr = _mala_scalars(lr, 2.0, 0, 0, 0)[0]
+    if rows == 0:
+        return
+    w_arr = (C.c_int32 * len(widths))(*widths)
+    L.check(lib.mcpc_hmc_leap(device.index or 0, x_arr, q_arr, g_arr, w_arr, len(widths), rows, lr, _current_stream(device)))
+
+
+def hmc_accept(xs, gs, E, xts, gts, Et, qs, K0, lr, seed, step, chain_base=0, diag=None, n_accepted=None):
+    """The Metropolis decision at the end of a Hamiltonian trajectory on the device (include/mcpc.h: mcpc_hmc_accept).  ``(xs, gs,
+    E)``: the current state, its gradient and its energy (fp64 ``[rows]``, the last column of ``Engine.chain_energies``); ``(xts, gts,
+    Et)``: the trajectory's end and the gradient and energy the engine evaluated at it; ``qs``, ``K0``: the half-step momentum and
+    the initial kinetic energy that ``hmc_begin`` at this ``(seed, step, chain_base)`` and ``lr`` started and ``hmc_leap`` carried.
+    Per chain ``p' = q - (eps / 2) g_t`` in fp32, ``log_alpha = (E - E_t) + (K0 - 0.5 |p'|^2)`` in fp64 and ``accept = log(u) <
+    log_alpha`` with ``u`` the chain's Philox uniform of ``(seed, step, layer 0xFD)``.  An accepted chain's rows of ``xs``, ``gs`` and
+    ``E`` are overwritten IN PLACE with the end point's; a rejected one keeps its bits.  ``xts``, ``gts``, ``qs`` and ``K0`` are never
+    written.  A row's result depends on that row alone and two runs are bitwise equal.  Optional: ``diag`` fp64 ``[rows, 3]`` receives
+    (log_alpha, u, accepted); ``n_accepted`` int32 ``[rows]`` is incremented for an accepted chain.  On the current torch stream."""
+    lib = L.load()
+    rows, widths, device = _mala_shape(xs)
+    n = len(widths)
+    x_arr, g_arr = _mala_ptrs(xs, "xs", rows, widths, device), _mala_ptrs(gs, "gs", rows, widths, device)
+    xt_arr, gt_arr = _mala_ptrs(xts, "xts", rows, widths, device), _mala_ptrs(gts, "gts", rows, widths, device)
+    q_arr = _mala_ptrs(qs, "qs", rows, widths, device)
+    _check_tensor(E, (rows,), device, "E", torch.float64)
+    _check_tensor(Et, (rows,), device, "Et", torch.float64)
+    _check_tensor(K0, (rows,), device, "K0", torch.float64)
+    if diag is not None:
+        _check_tensor(diag, (rows, 3), device, "diag", torch.float64)
+    if n_accepted is not None:
+        _check_tensor(n_accepted, (rows,), device, "n_accepted", torch.int32)
+    lr, _, seed, step, chain_base = _mala_scalars(lr, 2.0, seed, step, chain_base)
+    if rows == 0:
+        return
+    w_arr = (C.c_int32 * n)(*widths)
+    L.check(lib.mcpc_hmc_accept(device.index or 0, x_arr, g_arr, _ptr(E), xt_arr, gt_arr, _ptr(Et), q_arr, _ptr(K0), w_arr, n, rows, lr,
+                                seed, step, chain_base, _ptr(diag), _ptr(n_accepted), _current_stream(device)))
+
+
 def smc_ancestors(logw, replicas, threshold, seed, step, chain_base=0, ancestors=None, diag=None):
     """The resampling decision and the ancestors of every datum of a chunk on the device (include/mcpc.h: mcpc_smc_ancestors).
     ``logw``: fp64 ``[n_data * replicas]``, datum i owning rows ``i * replicas ..``.  Per datum, in fp64 and sequentially in replica
