@@ -1006,7 +1006,10 @@ class PCTrainer(object):
         for t0, n in bounds:
             half = n_slices & 1
             last = t0 + n == T
-            view = ring.RingView(x=ring_x[half], out=out_full[t0:t0 + n] if out_direct else ring_o[half])
+            # every block of a view holds the slice's n rows: a reducer that takes several blocks in one call (cov_accumulate,
+            # hist2d_accumulate) needs them equally long, and the read-out's rows, written straight into out_full, are n already
+            view = ring.RingView(x=[None if t is None else t[:n] for t in ring_x[half]],
+                                 out=out_full[t0:t0 + n] if out_direct else None if ring_o[half] is None else ring_o[half][:n])
             if drained[half] is not None:
                 main.wait_event(drained[half])
             eng.run(T, t_begin=t0, n_steps=n, adam_step0=t0, energies_out=energies,

@@ -43,7 +43,7 @@ class Call:
 @dataclass
 class RingView:
     """One filled half of the ring."""
-    x: list                                      # per latent layer the [S, B, n_l] block, None for a layer not in the ring
+    x: list                                      # per latent layer the [n, B, n_l] rows of this slice, None for a layer not in the ring
     out: Optional[torch.Tensor]                  # the read-out's rows of this slice, from row 0
 
 
