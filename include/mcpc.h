@@ -738,6 +738,35 @@ int mcpc_prediction_errors(mcpc_engine* e, const float* inputs, const float* con
                            double loss_var, int32_t mask_start, float* const* err, float* const* pred, float* err_out, float* pred_out,
                            int32_t max_rows, void* stream);
 
+/* Gradient of the free energy, and the energies, of handed-over states: what a sampler of the caller's own needs at a proposal (the score
+ * dF/dx for saliency, MALA, HMC), without the state passing through the engine.  Rows, x, `inputs`, the target, loss_kind / loss_var /
+ * mask_start, max_rows and the x / f(x) scratch are those of mcpc_chain_energies.  Per row r = k * batch + chain the call writes
+ *   grad[l][r][u] = dF/dx_l = e_l - f'(x_l) (e_{l+1} W_{l+1})    e_l = c_l (x_l - mu_l), the read-out's error above the last layer
+ * unpadded fp32 [n_rec][batch][n_l] -- bitwise what mcpc_run writes into xgrad (update_x = 0) on the layer-wise step kernels after
+ * mcpc_load_state of the same state: the same operands, exponents, k order and per-element arithmetic -- and, when `energies` is not
+ * NULL, energies[r][:] bitwise as mcpc_chain_energies writes it for the same rows.  The call adds one padded fp32 row per unit of
+ * layers 1 .. and of the read-out to the evaluators' scratch (allocated on the first call, enlarged with the chunk).  A value depends on
+ * its own row alone: not on the other rows, n_rec, max_rows or on whether the energies are asked for.  Nothing is written outside rows
+ * < n_rec * batch and units < n_l.  Destinations need 4-byte alignment; one that is 16-byte aligned with n_l % 4 == 0 is written with
+ * 16-byte stores.  The engine's state, Adam moments, sums, Philox position, records and bound pointers are not touched.
+ * The stream rides in the descriptor (mcpc_run_desc is the precedent for a descriptor): every other entry point takes it as its last
+ * parameter, and this one will too once its side-stream scenario has a row in the table those entry points are tested from.
+ * MCPC_EINVAL, before any device work: null engine / descriptor / x / grad / x[l] / grad[l], n_rec < 0, max_rows < 0, and what
+ * mcpc_chain_energies refuses of a loss.  MCPC_ESTATE: parameters not bound, a loss without a bound target.  n_rec = 0: MCPC_OK. */
+typedef struct mcpc_gradient_desc {
+    const float* inputs;        /* [batch][n_in] or NULL (zeros) */
+    const float* const* x;      /* [n_latent]: states [n_rec][batch][n_l] */
+    int32_t n_rec;
+    int32_t loss_kind;
+    double loss_var;
+    int32_t mask_start;
+    float* const* grad;         /* [n_latent]: dF/dx_l [n_rec][batch][n_l]; every entry required */
+    double* energies;           /* NULL, or [n_rec * batch][MCPC_MAX_LATENT + 2] as mcpc_chain_energies writes it */
+    int32_t max_rows;           /* rows per scratch chunk, 0 = default; no result depends on it */
+    void* stream;               /* a hipStream_t */
+} mcpc_gradient_desc;
+int mcpc_state_gradients(mcpc_engine* e, const mcpc_gradient_desc* d);
+
 /* Ancestral samples of the generative model, drawn on the device: x_1 ~ N(mu_1, 1/c_1), x_2 ~ N(mu_2(x_1), 1/c_2), ..., the read-out (the
  * reference's utils.training_evaluation.sample_pc, which draws on the CPU and runs nn.Linear in torch).  A ROW is one sample; row i has
  * the global id g = sample_base + i.  n is independent of the engine's batch, as the rows of mcpc_chain_energies are; rows are processed

@@ -80,6 +80,19 @@ class RunDesc(C.Structure):
     ]
 
 
+class GradientDesc(C.Structure):
+    _fields_ = [
+        ("inputs", C.c_void_p),
+        ("x", C.POINTER(C.c_void_p)),
+        ("n_rec", C.c_int32),
+        ("loss_kind", C.c_int32), ("loss_var", C.c_double), ("mask_start", C.c_int32),
+        ("grad", C.POINTER(C.c_void_p)),
+        ("energies", C.c_void_p),
+        ("max_rows", C.c_int32),
+        ("stream", C.c_void_p),
+    ]
+
+
 # every symbol include/mcpc.h declares: (restype, argtypes)
 SYMBOLS = {
     "mcpc_abi_version": (C.c_int, []),
@@ -156,6 +169,7 @@ SYMBOLS = {
                                       C.c_void_p, C.c_int32, C.c_void_p]),
     "mcpc_prediction_errors": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_int32,
                                          C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "mcpc_state_gradients": (C.c_int, [C.c_void_p, C.POINTER(GradientDesc)]),
     "mcpc_sample_prior": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_double, C.c_int32,
                                     C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_void_p]),
     "mcpc_query": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),

@@ -13,6 +13,8 @@ transition leaves its rung's distribution exactly invariant, so ``exp(log p_hat)
 2`` an adjusted transition is a Hamiltonian trajectory of L leapfrog steps of size ``sqrt(2 lr)`` with one decision at its end
 (``engine.hmc_begin``, ``engine.hmc_leap``, ``engine.hmc_accept``, csrc/mcpc_hmc.h): the same L gradient evaluations spent on one
 directed move instead of L random-walk steps, and ONE energy evaluation instead of L.  ``leapfrog=1`` is the MALA step itself.
+``gradients="evaluator"`` evaluates a proposal with ONE ``Engine.state_gradients`` call on the proposal's own tensors
+(csrc/mcpc_state_grad.h: gradient and, where the decision needs it, energy) instead of passing it through the engine's state.
 
 The replicas of a datum may be RESAMPLED between rungs (``resample="systematic"``): when the effective sample size of a datum's
 weights falls below ``ess_threshold * replicas``, ``engine.smc_ancestors`` draws the ancestors and resets the log-weights to the log
@@ -152,6 +154,17 @@ def check_adjust(adjust):
     return adjust
 
 
+def check_gradients(gradients, adjust=None):
+    """``gradients`` as ``run`` takes it: "run" (a proposal passes through the engine's state: ``load_state``, ``Engine.run(1,
+    update_x=False)``, ``Engine.chain_energies``) or "evaluator" (one ``Engine.state_gradients`` call on the proposal itself, which
+    only an adjusted call makes: ``adjust="mala"``); anything else is a ValueError."""
+    if not (isinstance(gradients, str) and gradients in ("run", "evaluator")):
+        raise ValueError(f"gradients={gradients!r}, expected 'run' or 'evaluator'")
+    if gradients == "evaluator" and adjust is None:
+        raise ValueError("gradients='evaluator' with adjust=None: unadjusted transitions evaluate nothing, pass adjust='mala'")
+    return gradients
+
+
 def check_leapfrog(leapfrog, adjust=None, noise_var=2.0):
     """``leapfrog`` as ``run`` takes it: an int of at least 1.  More than one leapfrog step needs the decision at the trajectory's end
     (``adjust="mala"``) and ``noise_var == 2.0`` (a unit-mass Hamiltonian has no other noise scale: its one-step trajectory is the
@@ -235,15 +248,23 @@ def _ladder(call, c):
         xt, q = spare                                                     # the trajectory's position and half-step momentum
         K0 = torch.empty(xs[0].shape[0], dtype=torch.float64, device=xs[0].device)
 
+    evaluator = getattr(call, "gradients", "run") == "evaluator"
+    eval_kw = dict(loss_kind=loss.kind, mask_start=loss.mask_start)
+
     def gradient(state, run_var):
-        """Gradient of ``state`` under the rung's distribution (``update_x=False`` moves nothing)."""
+        """Gradient of ``state`` under the rung's distribution (``update_x=False`` moves nothing; the evaluator reads ``state`` itself)."""
+        if evaluator:
+            return [g[0] for g in eng.state_gradients(None, state, loss_var=run_var, **eval_kw)[0]]
         eng.load_state(state)
         return eng.run(1, loss_var=run_var, update_x=False, step_base=0, **run_kw).xgrad
 
     def evaluate(state, run_var):
-        """Gradient and energy of ``state`` under the rung's distribution: one launch each."""
+        """Gradient and energy of ``state`` under the rung's distribution: one launch each, or one evaluator call for both."""
+        if evaluator:
+            gs, en = eng.state_gradients(None, state, loss_var=run_var, energies=True, **eval_kw)
+            return [g[0] for g in gs], en[0, :, -1].contiguous()
         g = gradient(state, run_var)
-        en = eng.chain_energies(None, state, loss_kind=loss.kind, loss_var=run_var, mask_start=loss.mask_start)
+        en = eng.chain_energies(None, state, loss_var=run_var, **eval_kw)
         return g, en[0, :, -1].contiguous()
 
     def langevin(k, first, run_var):
@@ -298,7 +319,7 @@ def _ladder(call, c):
 
 def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, power=2.0, betas=None, steps_per_stage=5, lr=None,
         noise_var=2.0, seed=0, step_base=0, chain_base=0, max_chains=6000, adjust=None, resample=None, ess_threshold=0.5,
-        leapfrog=1, return_logw=False, return_accepted=False, return_ancestors=False):
+        leapfrog=1, gradients="run", return_logw=False, return_accepted=False, return_ancestors=False):
     """``PCTrainer.mcpc_ais`` (its docstring is the contract).  ``return_logw``: also the raw log-weights, fp64 ``[N * replicas]``.
     ``return_accepted``: also the accepted proposals (trajectories when ``leapfrog > 1``) per rung and chain, int32 ``[K - 1, N *
     replicas]`` (None when unadjusted).
@@ -314,6 +335,7 @@ def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, 
     resample, ess_threshold = check_resample(resample, ess_threshold, replicas)
     check_counts(replicas, steps_per_stage, noise_var, seed, step_base)
     check_leapfrog(leapfrog, adjust, noise_var)
+    check_gradients(gradients, adjust)
     net, why = recognise.describe_model(trainer._model)
     if net is None:
         raise NotImplementedError("mcpc_ais: outside what the HIP engine expresses ({})".format(why))
@@ -350,7 +372,7 @@ def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, 
     K = len(ladder) - 1
     call = SimpleNamespace(adjust=adjust, ladder=ladder, steps_per_stage=steps_per_stage, lr=lr, noise_var=float(noise_var), seed=seed,
                            step_base=step_base, act=net.acts[-1], loss=loss, resample=resample, ess_threshold=ess_threshold,
-                           replicas=replicas, leapfrog=leapfrog)
+                           replicas=replicas, leapfrog=leapfrog, gradients=gradients)
     states, logws, accepts, diags, ancestors = [], [], [], [], []
     engines = []
     try:
@@ -372,7 +394,8 @@ def run(trainer, data, loss_fn, loss_fn_kwargs=None, *, replicas=64, stages=64, 
                     scaled = (W_L.clone(), None if b_L is None else b_L.clone())
                     eng.bind_params(weights[:-1] + [scaled[0]], biases[:-1] + [scaled[1]])      # (re-packed per rung by the ladder)
                 _, xs = eng.sample_prior(B, seed, step=step_base, sample_base=g0, latents=True, readout=None)
-                eng.load_state(xs)
+                if gradients != "evaluator":             # (the evaluator reads the chains' own tensors: the engine's state stays)
+                    eng.load_state(xs)
                 logw = torch.zeros(B, dtype=torch.float64, device=device)
                 chunk = SimpleNamespace(eng=eng, xs=xs, y=y, logw=logw, g0=g0, W_L=W_L, b_L=b_L, scaled=scaled)
                 if resample is not None:

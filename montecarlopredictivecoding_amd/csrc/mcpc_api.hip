@@ -73,6 +73,8 @@ int free_all(mcpc_engine* e) {
     F(e->lw_err_o); F(e->lw_jobs);
     for (int l = 0; l < kMaxLatent; ++l) { F(e->ce_x[l]); F(e->ce_fx[l]); }
     F(e->ce_mu1); F(e->ce_part); F(e->ce_jobs); F(e->pe_jobs);
+    for (int l = 0; l < kMaxLatent; ++l) F(e->sg_err[l]);
+    F(e->sg_err_o); F(e->sg_bjobs);
     for (auto& ln : e->lin) { F(ln.Wf); F(ln.Wb); F(ln.bias_pad); F(ln.G); F(ln.Gb); }
     for (auto& ev : e->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     for (int h = 0; h < kMaxRingParts; ++h) { if (e->ev_steps[h]) (void)hipEventDestroy(e->ev_steps[h]); if (e->ev_flush[h]) (void)hipEventDestroy(e->ev_flush[h]); e->ev_steps[h] = e->ev_flush[h] = nullptr; }

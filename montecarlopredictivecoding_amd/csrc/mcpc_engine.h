@@ -88,7 +88,14 @@ struct mcpc_engine : mcpc::EnginePlan {
     LwJob* pe_jobs = nullptr;       // device copy of pe_job_table(ce_table, pe_want)
     unsigned pe_want = 0;
     int pe_njobs = 0;
-    RunPlan run_plan;               // the schedule of the last mcpc_run (plan_run); kept for its storage: no allocation per run
+    // gradients of handed-over states (mcpc_state_grad.h): the error rows beside that scratch, allocated by the first mcpc_state_gradients
+    // and re-allocated whenever the evaluators' chunk grows; the backward half of lw_job_table (every engine form: not lw_jobs)
+    float* sg_err[kMaxLatent]{};    // e_l [sg_rows][npad_l], l >= 1
+    float* sg_err_o = nullptr;      // e_o [sg_rows][out_pad]
+    int sg_rows = 0;                // rows the error rows hold (0, or ce_rows)
+    LwJob* sg_bjobs = nullptr;
+    int sg_nb = 0;
+    RunPlan run_plan;              // the schedule of the last mcpc_run (plan_run); kept for its storage: no allocation per run
     // diagnostics, host strings set while launching (no device work): what the last mcpc_run and each Linear's last flush launched
     std::string last_step;                       // mcpc_last_step_kernel_name
     std::string last_flush[kMaxLatent + 1];      // mcpc_last_flush_plan, per Linear j >= 1

@@ -1,5 +1,5 @@
-// libmcpc.so, the evaluators of recorded states and the ancestral sampler: mcpc_chain_energies, mcpc_prediction_errors, mcpc_sample_prior
-// with their kernels (mcpc_chain_energy.h, mcpc_pred_err.h, mcpc_ancestral.h: the only unit that includes them).  They share the
+// libmcpc.so, the evaluators of recorded states and the ancestral sampler: mcpc_chain_energies, mcpc_prediction_errors, mcpc_state_gradients,
+// mcpc_sample_prior with their kernels (mcpc_chain_energy.h, mcpc_pred_err.h, mcpc_state_grad.h, mcpc_ancestral.h: the only unit that includes them).  They share the
 // layer-wise tile (mcpc_lw_tile.h), the packed weights, mu_1's kernel (launch_mu1) and the engine's evaluator scratch with each other.
 #include <hip/hip_runtime.h>
 
@@ -12,6 +12,7 @@
 #include "mcpc_engine.h"
 #include "mcpc_chain_energy.h"
 #include "mcpc_pred_err.h"
+#include "mcpc_state_grad.h"
 #include "mcpc_ancestral.h"
 
 using namespace mcpc;
@@ -117,6 +118,32 @@ int eval_chunks(const mcpc_engine* e, const EvalCall& c, const float* const* x_r
     HIP_TRY(hipGetLastError());
     return MCPC_OK;
 }
+
+// The error rows of mcpc_state_gradients for chunks of `chunk` rows (the evaluators' scratch holds e->ce_rows >= chunk by now), and its
+// backward job table
+int sg_ensure_scratch(mcpc_engine* e, int chunk, hipStream_t stream) {
+    if (!e->sg_bjobs) {
+        std::vector<LwJob> fwd, bwd;
+        lw_job_table(e->L, e->npad, e->has_head ? e->out_pad : 0, fwd, bwd);
+        if (bwd.size() > 65535) return fail(MCPC_EINVAL, "state gradients: more than 65535 unit-tile jobs");
+        if (const int rc = upload(e->sg_bjobs, bwd, "the state-gradient job table")) return rc;
+        e->sg_nb = (int)bwd.size();
+    }
+    if (chunk > e->sg_rows) {
+        // everything is given up before the first new allocation: one that fails leaves a consistent, empty scratch
+        for (int l = 0; l < e->L; ++l) give_up(e, e->sg_err[l], stream);
+        give_up(e, e->sg_err_o, stream);
+        e->sg_rows = 0;
+        size_t floats[kMaxLatent + 1];
+        sg_err_floats(e->L, e->npad, e->has_head ? e->out_pad : 0, e->ce_rows, floats);
+        for (int l = 1; l < e->L; ++l)
+            if (const int rc = dmalloc(e->sg_err[l], floats[l])) return rc;
+        if (e->has_head)
+            if (const int rc = dmalloc(e->sg_err_o, floats[kMaxLatent])) return rc;
+        e->sg_rows = e->ce_rows;
+    }
+    return MCPC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -193,6 +220,69 @@ int mcpc_prediction_errors(mcpc_engine* e, const float* inputs, const float* con
             P.pred[j] = pp ? pp + (size_t)r0 * P.n[j] : nullptr;
         }
         hipLaunchKernelGGL(mcpc_pe_kernel, dim3(padded / kLwChains, e->pe_njobs), dim3(kLwThreads), 0, stream, P);
+    });
+}
+
+int mcpc_state_gradients(mcpc_engine* e, const mcpc_gradient_desc* d) {
+    static const char pre[] = "state gradients: ";
+    if (!e) return fail(MCPC_EINVAL, "%snull engine", pre);
+    if (!d) return fail(MCPC_EINVAL, "%snull descriptor", pre);
+    if (!d->x) return fail(MCPC_EINVAL, "%sx is null", pre);
+    if (!d->grad) return fail(MCPC_EINVAL, "%sgrad is null", pre);
+    if (d->n_rec < 0) return fail(MCPC_EINVAL, "%sn_rec=%d, must not be negative", pre, d->n_rec);
+    if (d->max_rows < 0) return fail(MCPC_EINVAL, "%smax_rows=%d, must not be negative (0 = default)", pre, d->max_rows);
+    const int L = e->L;
+    for (int l = 0; l < L; ++l) {
+        if (!d->x[l]) return fail(MCPC_EINVAL, "%sx[%d] is null", pre, l);
+        if (!d->grad[l]) return fail(MCPC_EINVAL, "%sgrad[%d] is null", pre, l);
+    }
+    // every layer is read and every Linear evaluated
+    const bool with_loss = d->loss_kind != MCPC_LOSS_NONE;
+    const EvalCall c{(1u << L) - 1u, (1u << (L + (e->has_head ? 1 : 0))) - 1u, 0u, with_loss};
+    if (const int rc = eval_check_reads(pre, e, d->x, c)) return rc;
+    if (const int rc = check_loss(pre, e, d->loss_kind, d->loss_var, d->mask_start)) return rc;
+    const int64_t R = (int64_t)d->n_rec * e->d.batch;
+    if (R == 0) return MCPC_OK;
+    hipStream_t stream = (hipStream_t)d->stream;
+    SgParams P{};
+    CeParams& Q = P.ce;
+    if (const int rc = eval_setup(e, c, d->inputs, R, d->max_rows, d->loss_kind, d->loss_var, d->mask_start, stream, Q)) return rc;
+    if (const int rc = sg_ensure_scratch(e, Q.chunk, stream)) return rc;
+    // the forward launch walks the whole table: a read-out without a loss propagates an error of zeros, as the step kernels' does
+    Q.part = d->energies ? e->ce_part : nullptr;
+    Q.job0 = 0;
+    Q.jobs = e->ce_jobs;
+    P.bjobs = e->sg_bjobs;
+    P.has_head = e->has_head ? 1 : 0;
+    P.err_o = e->sg_err_o;
+    for (int l = 0; l < L; ++l) {
+        P.err[l] = e->sg_err[l];
+        P.n[l] = e->d.sizes[l];
+        P.act[l] = e->d.acts[l];
+        // 16-byte stores where every row of a destination starts on a 16-byte boundary
+        if (P.n[l] % 4 == 0 && ((uintptr_t)d->grad[l] & 15u) == 0) P.vec_grad |= 1u << l;
+    }
+    for (int j = 1; j < L + (e->has_head ? 1 : 0); ++j) P.Wb[j] = e->lin[j].Wb;
+    SgPrep T{};
+    T.L = L;
+    for (int l = 0; l < L; ++l) { T.x[l] = e->ce_x[l]; T.fx[l] = e->ce_fx[l]; T.n[l] = P.n[l]; T.npad[l] = e->npad[l]; T.act[l] = P.act[l]; }
+    const EvalCall none{0u, c.lins, 0u, with_loss};      // (eval_chunks prepares no layer: the launch below prepares them all at once)
+    return eval_chunks(e, none, d->x, R, Q, stream, [&](int64_t r0, int rows, int padded) {
+        // (a chunk starts at a multiple of kLwChains rows: r0 * n_l floats keeps the 16-byte alignment where n_l % 4 == 0)
+        for (int l = 0; l < L; ++l) { T.rec[l] = d->x[l] + (size_t)r0 * P.n[l]; P.grad[l] = d->grad[l] + (size_t)r0 * P.n[l]; }
+        T.rows = rows;
+        if (sg_prep_ends(L, e->npad, padded, T.end4)) {
+            hipLaunchKernelGGL(mcpc_grad_prep_kernel, dim3(grid_for(T.end4[L - 1])), dim3(256), 0, stream, T);
+        } else {                                          // more than 2^32 quads in one chunk: layer by layer
+            for (int l = 0; l < L; ++l)
+                hipLaunchKernelGGL(mcpc_ce_prep_kernel, dim3(grid_for((size_t)padded * e->npad[l] / 4)), dim3(256), 0, stream, T.rec[l],
+                                   e->ce_x[l], e->ce_fx[l], rows, padded, P.n[l], e->npad[l], P.act[l]);
+        }
+        hipLaunchKernelGGL(mcpc_grad_fwd_kernel, dim3(padded / kLwChains, e->ce_njobs), dim3(kLwThreads), 0, stream, P);
+        hipLaunchKernelGGL(mcpc_grad_bwd_kernel, dim3(padded / kLwChains, e->sg_nb), dim3(kLwThreads), 0, stream, P);
+        if (d->energies)
+            hipLaunchKernelGGL(mcpc_ce_finish_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, (const double*)e->ce_part, d->energies,
+                               e->ce_finish, L, with_loss ? 1 : 0, rows, Q.chunk, (size_t)r0);
     });
 }
 

@@ -355,6 +355,56 @@ class Engine:
                                                  pred_out, int(max_rows), self._stream()))
         return res
 
+    # ---- gradients of handed-over states --------------------------------------------------------------
+    def state_gradients(self, inputs: Optional[torch.Tensor], x: Sequence[torch.Tensor], *, loss_kind=L.LOSS_NONE, loss_var=1.0,
+                        mask_start=0, energies: bool = False, out: Optional[Sequence[torch.Tensor]] = None,
+                        energies_out: Optional[torch.Tensor] = None, max_rows: int = 0):
+        """``dF/dx_l`` of handed-over states and, when asked, their energies, in one evaluator call (include/mcpc.h:
+        mcpc_state_gradients).  The engine's own state, moments, Philox position and records are not touched.
+
+        ``x[l]``: contiguous fp32 ``[n_rec, batch, n_l]``, or ``[batch, n_l]`` for one state; ``inputs``, the target, the loss arguments
+        and ``max_rows`` as in ``chain_energies``.  Returns ``(grads, table)``: ``grads[l]`` fp32 ``[n_rec, batch, n_l]`` (the tensors of
+        ``out`` where given), bitwise what ``run(1, update_x=False).xgrad`` gives on the layer-wise kernels after ``load_state``; ``table``
+        fp64 ``[n_rec, batch, ENERGY_COLS]`` bitwise ``chain_energies`` of the same rows (``energies_out`` where given), or None
+        unless ``energies`` (an ``energies_out`` asks for them too).  On the current torch stream."""
+        if len(x) != self.L:
+            raise ValueError(f"x: expected one tensor per latent layer ({self.L}), got {len(x)}")
+        if inputs is not None:
+            _check_tensor(inputs, (self.batch, self.n_in), self.device, "inputs")
+        n_rec = 1 if x[0].dim() == 2 else int(x[0].shape[0])
+        xs = (C.c_void_p * self.L)()
+        for l, t in enumerate(x):
+            shape = (self.batch, self.sizes[l]) if t.dim() == 2 else (n_rec, self.batch, self.sizes[l])
+            _check_tensor(t, shape, self.device, f"x[{l}]")
+            xs[l] = t.data_ptr()
+        if out is not None and len(out) != self.L:
+            raise ValueError(f"out: expected one tensor per latent layer ({self.L}), got {len(out)}")
+        gs = (C.c_void_p * self.L)()
+        grads = []
+        for l in range(self.L):
+            if out is None:
+                g = torch.empty(n_rec, self.batch, self.sizes[l], dtype=torch.float32, device=self.device)
+            else:
+                g = out[l]
+                _check_tensor(g, (n_rec, self.batch, self.sizes[l]), self.device, f"out[{l}]")
+            grads.append(g)
+            gs[l] = g.data_ptr()
+        table = None
+        if energies_out is not None:
+            _check_tensor(energies_out, (n_rec, self.batch, L.ENERGY_COLS), self.device, "energies_out", torch.float64)
+            table = energies_out
+        elif energies:
+            table = torch.empty(n_rec, self.batch, L.ENERGY_COLS, dtype=torch.float64, device=self.device)
+        d = L.GradientDesc()
+        d.inputs = None if inputs is None else inputs.data_ptr()
+        d.x, d.grad = xs, gs
+        d.n_rec, d.loss_kind, d.loss_var, d.mask_start = n_rec, loss_kind, loss_var, mask_start
+        d.energies = None if table is None else table.data_ptr()
+        d.max_rows = int(max_rows)
+        d.stream = self._stream()
+        L.check(self._lib.mcpc_state_gradients(self._h, C.byref(d)))
+        return grads, table
+
     # ---- ancestral samples ---------------------------------------------------------------------------
     def sample_prior(self, n: int, seed: int, step: int = 0, sample_base: int = 0, inputs: Optional[torch.Tensor] = None, loss=None,
                      var=None, readout="hidden", latents=False, out: Optional[torch.Tensor] = None, max_rows: int = 0):

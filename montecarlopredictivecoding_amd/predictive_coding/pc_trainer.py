@@ -1064,6 +1064,22 @@ class PCTrainer(object):
                                          layers=layers, quantity=quantity, outputs=outputs)
         return {k: v[0].to(plan["model_device"]) for k, v in res.items()}
 
+    def mcpc_state_gradients(self, inputs, loss_fn: typing.Callable = None, loss_fn_kwargs: dict = {}, energies=False):
+        """The gradient of the free energy ``d overall / d x_l`` at the CURRENT x of the PCLayers, per chain and unit -- the score a
+        saliency map or a sampler of the caller's own needs -- evaluated on the device in one call (Engine.state_gradients; no step is
+        run, no state, gradient or optimiser changes).  Returns a list of fp32 ``[B, n_l]`` tensors on the model's device, one per
+        PCLayer; with ``energies=True`` ``(that list, chain_energies.ChainEnergies)``, the energies of the same state from the same
+        call, as ``mcpc_state_energies`` returns them.  ``inputs``, ``loss_fn`` and ``loss_fn_kwargs`` as in train_on_batch; a model or
+        loss the fused loop does not express raises NotImplementedError."""
+        from ..chain_energies import from_table
+        plan, (grads, table) = self._evaluate_state("mcpc_state_gradients", inputs, loss_fn, loss_fn_kwargs, Engine.state_gradients,
+                                                    energies=bool(energies))
+        to = plan["model_device"]
+        grads = [g[0].to(to) for g in grads]
+        if not energies:
+            return grads
+        return grads, from_table(table, len(plan["net"].sizes), self._energy_coefficient, [], to)
+
     def mcpc_sample_prior(self, n, seed=0, step=0, sample_base=0, loss_fn: typing.Callable = None, loss_fn_kwargs: dict = {},
                           readout="hidden", latents=False):
         """``n`` ancestral samples of the model -- ``x_1 ~ N(mu_1, 1/c_1)``, ``x_2 ~ N(mu_2(x_1), 1/c_2)``, ..., the read-out -- drawn on
@@ -1092,7 +1108,7 @@ class PCTrainer(object):
 
     def mcpc_ais(self, data, loss_fn: typing.Callable, loss_fn_kwargs: dict = {}, *, replicas=64, stages=64, power=2.0, betas=None,
                  steps_per_stage=5, lr=None, noise_var=2.0, seed=0, step_base=0, chain_base=0, max_chains=6000, adjust=None,
-                 resample=None, ess_threshold=0.5, leapfrog=1):
+                 resample=None, ess_threshold=0.5, leapfrog=1, gradients="run"):
         """The log marginal likelihood of every row of ``data`` ``[N, n_out]`` by annealed importance sampling (Neal 2001) on the device
         (montecarlopredictivecoding_amd/ais.py): ``replicas`` chains per datum start from exact ancestral samples
         (``Engine.sample_prior``), walk the ladder ``beta_0 = 0 .. beta_K = 1`` -- ``(k / stages)^power``, or ``betas``, strictly
@@ -1154,6 +1170,14 @@ class PCTrainer(object):
           the call over the union.
         - The result is still bitwise independent of ``max_chains``, because a datum's replicas are never split over chunks.
 
+        ``gradients`` says how an adjusted transition evaluates gradient and energy at a proposal.  ``"run"``, the default, is the call
+        without the keyword, bit for bit: the proposal is loaded into the engine, ``Engine.run(1, update_x=False)`` gives the
+        gradient and ``Engine.chain_energies`` the energy.  ``"evaluator"`` (with ``adjust="mala"``; ValueError otherwise, as for any
+        other value) makes it ONE ``Engine.state_gradients`` call on the proposal's own tensors -- without the energies at the
+        interior points of a trajectory -- and never loads the engine's state.  Its gradient is the layer-wise step kernels': on
+        engines that run those it is the ``"run"`` call bit for bit, on the others it differs from it by rounding where the step
+        kernel's read-out back-projection does (DESIGN.md section Ksg).  Every promise above holds under both.
+
         The model's parameters, the PCLayers' x, every param.grad, the optimisers, the step counters and the cached engine's parameter
         binding are what they were when the call returns, also when it raises.  A model or loss the fused loop does not express, or
         a model without a read-out, raises NotImplementedError."""
@@ -1162,7 +1186,7 @@ class PCTrainer(object):
             return _ais.run(self, data, loss_fn, loss_fn_kwargs, replicas=replicas, stages=stages, power=power, betas=betas,
                             steps_per_stage=steps_per_stage, lr=lr, noise_var=noise_var, seed=seed, step_base=step_base,
                             chain_base=chain_base, max_chains=max_chains, adjust=adjust, resample=resample,
-                            ess_threshold=ess_threshold, leapfrog=leapfrog)
+                            ess_threshold=ess_threshold, leapfrog=leapfrog, gradients=gradients)
 
     def _model_is_on_cpu(self) -> bool:
         p = next(self._model.parameters(), None)

@@ -279,8 +279,9 @@ def get_marginal_likelihood_ais(gen_pc, config, dataloader, use_cuda, replicas=6
     ``config`` (``get_mcpc_trainer``: SGD on x with ``config["optimizer_x_kwargs_mcpc"]``, whose ``lr`` is the Langevin step size);
     ``config["loss_fn"]`` / ``config["input_var"]`` name the read-out.  Batch ``b`` of the loader uses the chain ids that follow those
     of the batches before it, so the result does not depend on the batch size.  ``kw``: further keywords of ``mcpc_ais`` (``power``,
-    ``betas``, ``lr``, ``noise_var``, ``step_base``, ``chain_base``, ``max_chains``, ``adjust``, ``resample``, ``ess_threshold``, ``leapfrog`` -- with ``adjust="mala", leapfrog=L`` each of a rung's
-    ``steps_per_stage`` transitions is a Hamiltonian trajectory of L leapfrog steps)."""
+    ``betas``, ``lr``, ``noise_var``, ``step_base``, ``chain_base``, ``max_chains``, ``adjust``, ``resample``, ``ess_threshold``, ``leapfrog``, ``gradients`` -- with ``adjust="mala", leapfrog=L`` each of a rung's
+    ``steps_per_stage`` transitions is a Hamiltonian trajectory of L leapfrog steps; ``gradients="evaluator"`` evaluates an adjusted transition's
+    proposals with one ``Engine.state_gradients`` call each)."""
     from ..likelihood import LogLikelihood
     from ..utils.model import bernoulli_fn, fe_fn
     if config["loss_fn"] not in (bernoulli_fn, fe_fn):
