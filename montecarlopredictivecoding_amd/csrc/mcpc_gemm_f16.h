@@ -4,7 +4,7 @@
 // with three bf16 pieces per operand and six v_mfma_f32_16x16x32_bf16 per 32-deep block ("bf16x6": 24 significant bits per operand).  This
 // core uses TWO fp16 pieces per operand (11 + 11 = 22 significant bits) and THREE v_mfma_f32_16x16x32_f16 (four in GEMMs with K <= 64) --
 // same issue rate per instruction, half the instructions, two fragment planes instead of three (4 B per weight instead of 6 through the
-// CU's vector-memory path) and a split of 24 instead of 47 VALU instructions per 8 values:
+// CU's vector-memory path) and a split of 16 instead of 47 VALU instructions per 8 values (28 until the second piece was rounded once):
 //      a b  ~  [a_m b_m] + (a_m b_h + a_h b_m) + a_h b_h,        a = (a_h + a_m) 2^-sa,  b = (b_h + b_m) 2^-sb.
 // fp16 has 5 exponent bits, so both operands are SCALED BY POWERS OF TWO (exact) before the split: the weights of a Linear by one
 // exponent chosen when they are packed (max |W| -> [2^14, 2^15)), the B operand PER CHAIN ROW by an exponent taken from the row's own
@@ -22,7 +22,8 @@
 //     32-deep block kb, plane p, lane (m = lane & 15, g = lane >> 4) holds W[16 ut + m][32 kb + 8 g .. + 7] 2^sa as 8 fp16 = 16 B:
 //     one block of one tile = 2 x 1 KiB contiguous, two global_load_dwordx4 per wave.
 //   B operand (activations / errors): stays fp32 in LDS rows [chain][k]; lane (c, g) reads k = 32 kb + 8 g .. + 7 as two ds_read_b128,
-//     multiplies by its chain's 2^sb and splits (v_pk_mul_f32, v_cvt_pk_f16_f32, 2 v_cvt_f32_f16, v_pk_fma_f32, v_cvt_pk_f16_f32 per pair).
+//     multiplies by its chain's 2^sb and splits (per pair: v_pk_mul_f32 -- or two v_mul_f32 where the compiler un-packs it --,
+//     v_cvt_pk_f16_f32, v_fma_mixlo_f16, v_fma_mixhi_f16: split2_pair; the loop's listing is in profiles/gemm_diet_asm.txt).
 //   C: the fp32 accumulator tile of the 16x16 MFMAs (lane (c, q): units 4q..4q+3 of chain c) -- the lane's chain is the one whose
 //     row it scaled, so the un-scaling factor is a per-lane scalar.
 // The read-out's back-projection accumulates over SEVERAL GEMMs (one per chunk of read-out units) in the same accumulators: they stay
@@ -43,28 +44,71 @@ namespace mcpc {
 struct frag_t { u32x4 h, m; };          // one k-block of one tile as seen by a lane
 
 __device__ __forceinline__ frag_t frag_zero() { frag_t f; f.h = f.m = u32x4{0u, 0u, 0u, 0u}; return f; }
-__device__ __forceinline__ frag_t load_frag(const gu32x4* A, int off, int lane) {
+// The two planes of one (tile, k-block): 1 KiB each, lane l at byte voff = 16 (off + l) of a wave-uniform base.  The loads are to take the
+// `saddr` form -- global_load_dwordx4 v, v_off, s[base:base+1] offset:imm: a scalar base, ONE 32-bit VGPR offset, no VALU address
+// arithmetic -- which instruction selection finds only when it sees the offset's zero-extension in the block of the load.  Left to
+// itself the compiler widens the offsets (or base + offset) to 64-bit VGPR pairs once, in front of the k loop, and adds the scalar k
+// advance to the pairs with v_lshl_add_u64 / v_add_co_u32 + v_addc_co_u32 in every block.  The empty asm is no instruction: it only makes the
+// 32-bit offset a value defined where it is used (in place, so that no copy of it is kept), and the widening stays behind it.
+// voff is a 32-bit byte offset: the packed weights of an engine span less than 4 GiB and no caller passes a negative `off` (absent
+// fragments are asked for at offset 0 of `dummy`); gemm_fixed's lane offsets have always assumed the same.
+//
+// DIET (the last template parameter of everything below that has it): true = the forms described here and at split2_pair -- the
+// specialised in-place kernels, the unified-wave kernel, the barrier kernel, the flush, the pack kernels.  false = the code as it was
+// before them, instruction for instruction: 64-bit lane addresses and the second piece rounded twice.  The GENERIC in-place kernel and
+// the layer-wise tile (mcpc_lw_tile.h: K1w and the evaluators) stay on it because they measured SLOWER with the new forms
+// (profiles/gemm_diet_ab.txt: + 0.5-1.7 % and + 2-3 %; in the layer-wise k loop the register allocator then rotates six accumulator tiles
+// through 24 v_accvgpr moves per k-block).  Both forms compute the same bits (tests/test_split_mix_host.py, tests/test_gpu_split_bitwise.py).
+typedef const char __attribute__((address_space(1)))* gbytes_t;
+template <bool DIET = true>
+__device__ __forceinline__ frag_t load_frag_at(gbytes_t base, uint32_t& voff) {
+    if constexpr (DIET) asm volatile("" : "+v"(voff));
     frag_t f;
-    f.h = A[off + lane]; f.m = A[off + 64 + lane];
+    f.h = *(const gu32x4*)(base + voff); f.m = *(const gu32x4*)(base + voff + 1024u);
     return f;
+}
+template <bool DIET = true>
+__device__ __forceinline__ frag_t load_frag(const gu32x4* A, int off, int lane) {
+    if constexpr (DIET) {
+        uint32_t voff = (uint32_t)(off + lane) * 16u;
+        return load_frag_at<true>((gbytes_t)A, voff);
+    } else {
+        frag_t f;
+        f.h = A[off + lane]; f.m = A[off + 64 + lane];
+        return f;
+    }
 }
 
 // x 2^sb = h + m for a pair of values (h, m fp16; exact to 22 significant bits while m stays a normal fp16)
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+template <bool DIET = true>
 __device__ __forceinline__ void split2_pair(f32x2 x, float s, unsigned& h, unsigned& m) {
     const f32x2 xs = x * s;                                             // exact: s is a power of two
     const f16x2 hh = __builtin_convertvector(xs, f16x2);                // v_cvt_pk_f16_f32 (round to nearest even)
-    const f32x2 r = xs - __builtin_convertvector(hh, f32x2);            // exact: the residual has at most 13 significant bits
+    if constexpr (!DIET) {                                              // the form before: the residual rounded to fp32, then to fp16
+        const f32x2 r = xs - __builtin_convertvector(hh, f32x2);        // exact: the residual has at most 13 significant bits
+        h = __builtin_bit_cast(unsigned, hh);
+        m = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
+        return;
+    }
+    // The residual x s - h, per component as ONE fma that reads the fp16 h and rounds to fp16: v_fma_mixlo_f16 / v_fma_mixhi_f16.  It is
+    // exact in fp32 (a multiple of ulp(x s), no larger than |x s|: at most 13 significant bits), so rounding it once to fp16 gives the bits
+    // that rounding to fp32 and then to fp16 gave (tests/test_split_mix_host.py) -- as long as x s itself is a finite fp32 or x is not
+    // finite: a finite x whose x s overflows fp32 has h = Inf either way and m = -Inf here where the two-step form had Inf - Inf = NaN.
+    f16x2 mm;
+    mm.x = (_Float16)__builtin_fmaf(x.x, s, -(float)hh.x);
+    mm.y = (_Float16)__builtin_fmaf(x.y, s, -(float)hh.y);
     h = __builtin_bit_cast(unsigned, hh);
-    m = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
+    m = __builtin_bit_cast(unsigned, mm);
 }
+template <bool DIET = true>
 __device__ __forceinline__ frag_t split8(f32x4 x0, f32x4 x1, float s) {
     unsigned h[4], m[4];
-    split2_pair(f32x2{x0.x, x0.y}, s, h[0], m[0]);
-    split2_pair(f32x2{x0.z, x0.w}, s, h[1], m[1]);
-    split2_pair(f32x2{x1.x, x1.y}, s, h[2], m[2]);
-    split2_pair(f32x2{x1.z, x1.w}, s, h[3], m[3]);
+    split2_pair<DIET>(f32x2{x0.x, x0.y}, s, h[0], m[0]);
+    split2_pair<DIET>(f32x2{x0.z, x0.w}, s, h[1], m[1]);
+    split2_pair<DIET>(f32x2{x1.x, x1.y}, s, h[2], m[2]);
+    split2_pair<DIET>(f32x2{x1.z, x1.w}, s, h[3], m[3]);
     frag_t f;
     f.h = u32x4{h[0], h[1], h[2], h[3]}; f.m = u32x4{m[0], m[1], m[2], m[3]};
     return f;
@@ -72,10 +116,10 @@ __device__ __forceinline__ frag_t split8(f32x4 x0, f32x4 x1, float s) {
 // the B planes of one k-block as a lane reads them: split here from fp32 (x 2^sb = h + m), or -- PS, unified-wave kernel -- already split by
 // the operand's producer (mcpc_ws2_lean.h: lean_headf writes a Bernoulli read-out's error that way: the same split2_pair with the same
 // exponent, once per value instead of once per k-block, wave and GEMM): the 32 bytes then hold [h0..h7][m0..m7]
-template <bool PS>
+template <bool PS, bool DIET = true>
 __device__ __forceinline__ frag_t b_planes(f32x4 x0, f32x4 x1, float s) {
     if constexpr (PS) { frag_t f; f.h = __builtin_bit_cast(u32x4, x0); f.m = __builtin_bit_cast(u32x4, x1); (void)s; return f; }
-    else return split8(x0, x1, s);
+    else return split8<DIET>(x0, x1, s);
 }
 __device__ __forceinline__ f32x4 mfma4(u32x4 a, u32x4 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
@@ -124,7 +168,7 @@ struct GemmScale { int a_exp; int mode; int fixed_b; int run; int short_k; int s
 #ifdef MCPC_EXP_NOSPLIT    // timing experiment only (wrong results): the B planes of block 0 serve every block (no LDS reads, no split)
 #define MCPC_EXP_SPLIT8(a_, b_) bs
 #else
-#define MCPC_EXP_SPLIT8(a_, b_) b_planes<PS>(a_, b_, bscale)
+#define MCPC_EXP_SPLIT8(a_, b_) b_planes<PS, DIET>(a_, b_, bscale)
 #endif
 // acc += W-tiles . B over nkb blocks.  On entry `pre` holds block 0 of every tile, requested by the caller's prefetch (one table
 // entry early); on return it is free.
@@ -141,7 +185,7 @@ struct GemmScale { int a_exp; int mode; int fixed_b; int run; int short_k; int s
 // 2.6e-8 with it; fp32 MFMA chain 1.0e-7 / 2.1e-8).  From K = 96 on the term changes neither figure (profiles/r05_f16x4_study.txt) and longer
 // GEMMs run THREE MFMAs per product.
 // (kShortK itself is the planner's too: mcpc_types.h)
-template <int NT, int NTT, int NW, bool MM, bool PS = false>
+template <int NT, int NTT, int NW, bool MM, bool PS = false, bool DIET = true>
 __device__ __forceinline__ void gemm_fixed(f32x4 (&acc)[NTT], const gu32x4* __restrict__ A, const int (&aoff)[NTT], int nkb, int kw,
                                            const float* B, int ldb, int lane, frag_t (&pre)[NTT], const float* zeros, int b_exp) {
     constexpr int N0 = NT < 2 ? NT : 2, N1 = NT - N0;            // tiles of group 0 / group 1
@@ -154,11 +198,12 @@ __device__ __forceinline__ void gemm_fixed(f32x4 (&acc)[NTT], const gu32x4* __re
 #else
     const float* const bp_last = (uint32_t)(kKB * (nkb - 1) + 8 * g) < (uint32_t)kw ? bp + (nkb - 1) * kKB : zeros;
 #endif
-    // wave-uniform base + a 32-bit per-lane byte offset that never changes during the GEMM (no VALU address arithmetic per load)
+    // wave-uniform base (a pair of SGPRs, stepped by the scalar ALU) + a 32-bit per-lane byte offset that never changes during the GEMM:
+    // no VALU address arithmetic per load (load_frag_at)
     uint32_t voff[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) voff[t] = (uint32_t)(aoff[t] + lane) * 16u;
-    const char __attribute__((address_space(1)))* const Ab = (const char __attribute__((address_space(1)))*)A;
+    const gbytes_t Ab = (gbytes_t)A;
     f32x4 bC[2];
     frag_t bs;
     frag_t s0[2], s1[2], s2[2];                                   // the three half-sets
@@ -173,11 +218,8 @@ __device__ __forceinline__ void gemm_fixed(f32x4 (&acc)[NTT], const gu32x4* __re
 #define MCPC_LOAD_HALF(s_, G_, k_)                                                                  \
     do {                                                                                            \
         const int kc_ = (k_) < last ? (k_) : last;                                                  \
-        const char __attribute__((address_space(1)))* const Ak_ = Ab + (size_t)MCPC_KSEL(kc_) * (kFragBlock * 16u); \
-        _Pragma("unroll") for (int i = 0; i < ((G_) ? N1 : N0); ++i) {                              \
-            s_[i].h = *(const gu32x4*)(Ak_ + voff[2 * (G_) + i]);                                   \
-            s_[i].m = *(const gu32x4*)(Ak_ + voff[2 * (G_) + i] + 1024u);                           \
-        }                                                                                           \
+        const gbytes_t Ak_ = Ab + (size_t)MCPC_KSEL(kc_) * (kFragBlock * 16u);                      \
+        _Pragma("unroll") for (int i = 0; i < ((G_) ? N1 : N0); ++i) s_[i] = load_frag_at<DIET>(Ak_, voff[2 * (G_) + i]); \
     } while (0)
     // the four products of group G_ out of half-set s_, small terms first; consecutive MFMAs alternate between the group's (at most
     // two) accumulators
@@ -192,7 +234,7 @@ __device__ __forceinline__ void gemm_fixed(f32x4 (&acc)[NTT], const gu32x4* __re
     do { if constexpr (MM) { MCPC_M4(s_, G_, m, m); }                                               \
          MCPC_M4(s_, G_, m, h); MCPC_M4(s_, G_, h, m); MCPC_M4(s_, G_, h, h); } while (0)
 #endif
-#define MCPC_SPLIT1() bs = b_planes<PS>(bC[0], bC[1], bscale)
+#define MCPC_SPLIT1() bs = b_planes<PS, DIET>(bC[0], bC[1], bscale)
     // One k-block: the chain tile's planes are read by both sub-steps, so the next block's split goes into a second copy beside
     // (k, G1) and is moved over at the end of the block (8 v_mov)
 #define MCPC_BLOCK1(sa_, sb_, sc_, k_)                                                              \
@@ -210,7 +252,7 @@ __device__ __forceinline__ void gemm_fixed(f32x4 (&acc)[NTT], const gu32x4* __re
     } while (0)
 #define MCPC_BLOCK(sa_, sb_, sc_, k_) MCPC_BLOCK1(sa_, sb_, sc_, k_)
     // The LAST block of a GEMM requests, reads and splits nothing: there is no next block.  (Until round 5 every block ran MCPC_BLOCK1 with
-    // its requests clamped to the last block: 8 fragment loads, 2 LDS reads and a 24-instruction split per GEMM for nothing -- ~400 of the
+    // its requests clamped to the last block: 8 fragment loads, 2 LDS reads and a split (then 24 instructions) per GEMM for nothing -- ~400 of the
     // ~2000 cycles a table entry costs a GEMM wave beyond its k-blocks, 13 entries per step.)
 #define MCPC_BLOCK_LAST(sa_, sb_)                                                                   \
     do {                                                                                            \
@@ -279,7 +321,7 @@ __device__ __forceinline__ void gemm_deep(f32x4 (&acc)[NTT], const gu32x4* __res
     uint32_t voff[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) voff[t] = (uint32_t)(aoff[t] + lane) * 16u;
-    const char __attribute__((address_space(1)))* const Ab = (const char __attribute__((address_space(1)))*)A;
+    const gbytes_t Ab = (gbytes_t)A;
     const int last = nkb - 1;
     frag_t f[W][NT];
 #pragma unroll
@@ -301,11 +343,11 @@ __device__ __forceinline__ void gemm_deep(f32x4 (&acc)[NTT], const gu32x4* __res
          MCPC_DM(j_, m, h); MCPC_DM(j_, h, m); MCPC_DM(j_, h, h); } while (0)
 #define MCPC_DREFILL(j_, k_)                                                                        \
     do {                                                                                            \
-        const char __attribute__((address_space(1)))* const Ak_ = Ab + (size_t)MCPC_KSEL(k_) * (kFragBlock * 16u); \
-        _Pragma("unroll") for (int i = 0; i < NT; ++i) {                                            \
-            f[j_][i].h = *(const gu32x4*)(Ak_ + voff[i]);                                           \
-            f[j_][i].m = *(const gu32x4*)(Ak_ + voff[i] + 1024u);                                   \
-        }                                                                                           \
+        gbytes_t Ak_ = Ab + (size_t)MCPC_KSEL(k_) * (kFragBlock * 16u);                             \
+        /* a scalar base of its own per refill: with ONE base for the W blocks in flight the far ones (8 KiB with one tile) lie beyond */ \
+        /* the load's 13-bit immediate and the compiler goes back to 64-bit VALU sums for them */   \
+        asm volatile("" : "+s"(Ak_));                                                               \
+        _Pragma("unroll") for (int i = 0; i < NT; ++i) f[j_][i] = load_frag_at(Ak_, voff[i]);       \
     } while (0)
     MCPC_DLOAD_B(0);
     const float bscale = pow2i(b_exp);
@@ -376,20 +418,20 @@ __device__ __forceinline__ void gemm_unscale(f32x4 (&acc)[NTT], int a_exp, int b
 }
 
 // nt (wave-uniform, 1..NTT) selects a straight-line instantiation: no per-tile branches in the loop
-template <int N, int NTT, int NW, bool MM>
+template <int N, int NTT, int NW, bool MM, bool DIET>
 __device__ __forceinline__ void gemm_dispatch(f32x4 (&acc)[NTT], const gu32x4* __restrict__ A, const int (&aoff)[NTT], int nt, int nkb, int kw,
                                               const float* B, int ldb, int lane, frag_t (&pre0)[NTT], const float* zeros, int b_exp) {
     if constexpr (N >= NTT) {
-        gemm_fixed<NTT, NTT, NW, MM>(acc, A, aoff, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
+        gemm_fixed<NTT, NTT, NW, MM, false, DIET>(acc, A, aoff, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
     } else {
-        if (nt == N) gemm_fixed<N, NTT, NW, MM>(acc, A, aoff, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
-        else gemm_dispatch<N + 1, NTT, NW, MM>(acc, A, aoff, nt, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
+        if (nt == N) gemm_fixed<N, NTT, NW, MM, false, DIET>(acc, A, aoff, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
+        else gemm_dispatch<N + 1, NTT, NW, MM, DIET>(acc, A, aoff, nt, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
     }
 }
 // kw: valid k width of the B rows (a multiple of 16, 32 (nkb - 1) < kw <= 32 nkb); zeros: 16 floats of LDS that stay zero for the launch.
 // gs: see GemmScale.  GS_FRESH: acc must be zero on entry and holds the true sums on return.  GS_ACCUM: acc carries earlier chunks in units
 // of 2^(a_exp + gs.run) and stays scaled; gs.run is updated (a smaller exponent rescales acc first: exact).
-template <int NTT, int NW>
+template <int NTT, int NW, bool DIET = true>
 __device__ __forceinline__ void gemm_tiles(f32x4 (&acc)[NTT], const void* A, const int (&aoff)[NTT], int nt, int nkb, int kw,
                                            const float* B, int ldb, int lane, frag_t (&pre0)[NTT], const float* zeros, GemmScale& gs) {
 #ifdef MCPC_EXP_NOROWEXP    // timing experiment only (wrong results): no pre-pass over the row, a constant exponent
@@ -410,8 +452,8 @@ __device__ __forceinline__ void gemm_tiles(f32x4 (&acc)[NTT], const void* A, con
         gs.run = b_exp;
     }
     const bool mm = gs.short_k >= 0 ? gs.short_k != 0 : nkb <= kShortK;
-    if (mm && nkb <= kShortK) gemm_dispatch<1, NTT, NW, true>(acc, (const gu32x4*)A, aoff, nt, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
-    else gemm_dispatch<1, NTT, NW, false>(acc, (const gu32x4*)A, aoff, nt, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
+    if (mm && nkb <= kShortK) gemm_dispatch<1, NTT, NW, true, DIET>(acc, (const gu32x4*)A, aoff, nt, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
+    else gemm_dispatch<1, NTT, NW, false, DIET>(acc, (const gu32x4*)A, aoff, nt, nkb, kw, B, ldb, lane, pre0, zeros, b_exp);
     if (gs.mode == GS_FRESH) gemm_unscale<NTT>(acc, gs.a_exp, b_exp);
 }
 

@@ -58,7 +58,7 @@ __device__ __forceinline__ void lw_gemm(f32x4 (&acc)[kLwUTW][kLwCTT], const gu32
     } while (0)
 #define LW_STAGE_WRITE(buf_)                                                                        \
     do {                                                                                            \
-        const frag_t f_ = split8(s0, s1, bscale);                                                   \
+        const frag_t f_ = split8<false>(s0, s1, bscale);      /* DIET = false: mcpc_gemm_f16.h */                                                   \
         float* const dst_ = stage + (buf_) * (kLwChains * kLwLd) + srow * kLwLd + 8 * sg;           \
         *reinterpret_cast<u32x4*>(dst_) = f_.h; *reinterpret_cast<u32x4*>(dst_ + 4) = f_.m;         \
     } while (0)

@@ -103,7 +103,8 @@ __device__ __forceinline__ int ws2_need(int base, int n_ent, int p, int dep) {
 // Branch-free: all four tile slots always issue both loads; unused slots repeat slot 0 (L1 hits) and entries without
 // a GEMM read `dummy` (any 2 KiB of valid global memory).  With the loads under `if (i < nt)` hipcc joined every
 // branch behind `s_waitcnt vmcnt(0)`: four serial L2 round trips (~1 k cycles) per table entry.
-template <int NT>
+// DIET: mcpc_gemm_f16.h (false: the generic kernel's loads, as they were)
+template <bool DIET, int NT>
 __device__ __forceinline__ void ws2_prefetch(const KPhase& ph, int k, int lane, const void* dummy, int& nt_out, int (&aoff)[NT],
                                              frag_t (&pre0)[NT]) {
     const int kk = (k + ph.rot) & (kWs2Pairs - 1);
@@ -118,7 +119,7 @@ __device__ __forceinline__ void ws2_prefetch(const KPhase& ph, int k, int lane, 
         const int ii = i < nt ? i : 0;
         const int off = valid ? (ph.tile0 + kk + kWs2Pairs * ii) * ph.a_tile_stride + ph.a_off0 : 0;
         aoff[i] = off;
-        pre0[i] = load_frag(A, off, lane);
+        pre0[i] = load_frag<DIET>(A, off, lane);
     }
 }
 

@@ -66,7 +66,7 @@
         frag_t pre0[NTW];
 #pragma unroll
         for (int i = 0; i < NTW; ++i) { pre0[i] = frag_zero(); aoff[i] = 0; }
-        ws2_prefetch(ph_next, k, lane, P.dummy, nt_next, aoff, pre0);
+        ws2_prefetch<!M::generic>(ph_next, k, lane, P.dummy, nt_next, aoff, pre0);
         STAMP_DECL
 #ifdef MCPC_STAMPS
         const unsigned long long clk_m0 = mcpc_stamp(), clk_r0 = wall_clock64();
@@ -111,7 +111,7 @@
                             const int fixed_b = hb_word ? rowexp_read(rx, ph.b_row, c) : hb_exp;
                             GemmScale gs{load_wexp(P.wexp, ph.a_lin), GS_ACCUM, fixed_b, accb_run,
                                          P.head.npad <= kShortK * kKB ? 1 : 0, (hb_exp == kScaleAuto && !hb_word) ? 1 : 0};
-                            gemm_tiles<NTW, NW>(accb, ph.A, aoff, nt, ph.nkb, ph.kw, lds + ph.b_lds, ph.ldb, lane, pre0, lds + P.lds_zero, gs);
+                            gemm_tiles<NTW, NW, !M::generic>(accb, ph.A, aoff, nt, ph.nkb, ph.kw, lds + ph.b_lds, ph.ldb, lane, pre0, lds + P.lds_zero, gs);
                             accb_run = gs.run; accb_aexp = gs.a_exp;
                         }
                         STAMP(2);
@@ -127,13 +127,13 @@
                             const bool has_word = rowexp && ph.b_row >= 0;
                             const int fixed_b = has_word ? rowexp_read(rx, ph.b_row, c) : kScaleAuto;
                             GemmScale gs{load_wexp(P.wexp, ph.a_lin), GS_FRESH, fixed_b, kRunNone, -1, has_word ? 0 : 1};
-                            gemm_tiles<NTW, NW>(acc, ph.A, aoff, nt, ph.nkb, ph.kw, lds + ph.b_lds, ph.ldb, lane, pre0, lds + P.lds_zero, gs);
+                            gemm_tiles<NTW, NW, !M::generic>(acc, ph.A, aoff, nt, ph.nkb, ph.kw, lds + ph.b_lds, ph.ldb, lane, pre0, lds + P.lds_zero, gs);
                         }
                         STAMP(3);
                     }
                 }
                 // the one prefetch site: fragments of the next entry travel while this block is handed over
-                ws2_prefetch(ph_next, k, lane, P.dummy, nt_next, aoff, pre0);   // (past the last entry: the old descriptor again)
+                ws2_prefetch<!M::generic>(ph_next, k, lane, P.dummy, nt_next, aoff, pre0);   // (past the last entry: the old descriptor again)
                 STAMP(4);
                 if (stores) {
                     // write-after-read: the rows this block goes to may still be read by GEMMs (dep_g) or epilogues (dep_se)
